@@ -1,6 +1,15 @@
 """bench.py — training samples/s of the CDAE hot path on MI355X (BASELINE.json metric).
 
-    python bench.py [--gpus N] [--steps K] [--warmup W] [--workload synth-10m|ml-1m|ml-100k] [--batch B]
+    python bench.py [--gpus N] [--steps K] [--warmup W] [--workload synth-10m|ml-1m|ml-100k] [--batch B] [--dump-outputs DIR] [--full]
+
+A plain run sets up, warms up, times the K steps, writes its outputs if --dump-outputs is given and prints the line: `value` (samples/s),
+`ms_per_step`, the timed window and the configuration.  Everything else — the roofline and per-kernel phase figures, the HBM copy rate,
+the CPU baselines, the HR@10 run, the `configs` block (BASELINE configurations 2, 3, 5) and the spread over several windows — is
+measured only with --full.
+
+--dump-outputs DIR: after the timed steps, the model's parameters as the last timed step left them (what a caller of the training step
+receives) as DIR/<name>.npy in float32; a table larger than 15 MiB is represented by a fixed, seeded sample of its rows (the same
+rows in every run of the same arguments), so two builds can be compared output for output.
 
 A "step" is one pass of the hot path over one batch of B (u, i, y) triples per GPU: gather + hidden layer + sampled output unit + BCE +
 backward + sparse-Adagrad update (drx_cdae_step_sparse_prepared).  Every step trains on a FRESH batch drawn by the device PointSampler
@@ -8,9 +17,10 @@ backward + sparse-Adagrad update (drx_cdae_step_sparse_prepared).  Every step tr
 both depend only on the data, never on the parameters — so the timed region is the whole training loop including sampling.  All inputs
 live in HBM; nothing crosses PCIe in the timed region except the 8-byte touch count the sampler posts to a pinned mailbox per step.
 
-Timing: W warm-up steps, then `--windows` (default 5) back-to-back windows of EXACTLY K steps, each bracketed by barrier +
-synchronize on both sides and reduced by MAX over ranks; `value` and `ms_per_step` come from the MEDIAN window, `window_ms_min/max`
-give the spread (a 20-step window is 8 ms: one shot cannot tell 5 % from noise).
+Timing: W warm-up steps, then `--windows` back-to-back windows of EXACTLY K steps (default: one in a plain run, so that K is the
+number of timed steps; five with --full), each bracketed by barrier + synchronize on both sides and reduced by MAX over ranks; `value`
+and `ms_per_step` come from the MEDIAN window, `window_ms_min/max` give the spread (a 20-step window is 8 ms: one shot cannot tell 5 %
+from noise).
 
 N GPUs (one process per GPU, RCCL over xGMI).  `python bench.py --gpus N` starts the N ranks itself when WORLD_SIZE is not set (no
 GPU call is made by the starting process); under `python -m torch.distributed.run --nproc-per-node N bench.py --gpus N` every worker
@@ -56,7 +66,12 @@ def parse(argv=None):
     ap.add_argument('--gpus', type=int, default=1)
     ap.add_argument('--steps', type=int, default=200)
     ap.add_argument('--warmup', type=int, default=20)
-    ap.add_argument('--windows', type=int, default=5, help='back-to-back timed windows of --steps steps; value = median window')
+    ap.add_argument('--windows', type=int, default=None, help='back-to-back timed windows of --steps steps; value = median window '
+                    '(default 1; 5 with --full)')
+    ap.add_argument('--full', action='store_true', help='also measure everything beside the headline: roofline and phase figures, HBM copy '
+                    'rate, CPU baselines, HR@10, the configs block, five timed windows')
+    ap.add_argument('--dump-outputs', default=None, metavar='DIR', help='after the timed steps, write the parameters the last timed step '
+                    'left (a fixed, seeded sample of rows of the large tables) as DIR/<name>.npy, float32')
     ap.add_argument('--workload', default='synth-10m', choices=['synth-10m', 'ml-1m', 'ml-100k'])
     ap.add_argument('--batch', type=int, default=65536, help='triples per GPU per step')
     ap.add_argument('--n-batches', type=int, default=8, help='batches sampled at setup (R estimate, CPU baseline; cycled with --presampled)')
@@ -67,7 +82,7 @@ def parse(argv=None):
     ap.add_argument('--cpu-triples', type=int, default=1024)
     ap.add_argument('--no-hr', action='store_true', help='skip the HR@10 sanity run (ml-100k-shaped set, reference mode)')
     ap.add_argument('--no-configs', action='store_true', help='skip the `configs` block (BASELINE configurations 2, 3, 5)')
-    ap.add_argument('--force-configs', action='store_true', help='emit the `configs` block whatever the main workload is (tests)')
+    ap.add_argument('--force-configs', action='store_true', help='with --full: emit the `configs` block whatever the main workload is (tests)')
     ap.add_argument('--no-overlap', action='store_true', help='build the touch list inline instead of ahead on a side stream')
     ap.add_argument('--prep-cus', type=int, default=-1, help='CUs of every XCD the run-ahead streams (sampler, list preparation) are confined to '
                     '(drx_stream_create_cu_slice); 0: the whole chip, high priority; default: engine.PREP_CUS_PER_XCD')
@@ -101,7 +116,10 @@ def parse(argv=None):
     ap.add_argument('--launch-selftest', action='store_true', help='children only rendezvous over gloo and all-reduce on the CPU (tests the launcher)')
     ap.add_argument('--layout-timeout-s', type=float, default=900.0, help='a layout whose children run longer is killed and reported as an error')
     ap.add_argument('--child-layout', default=None, choices=['columns', 'rows', 'selftest'], help=argparse.SUPPRESS)
-    return ap.parse_args(argv)
+    args = ap.parse_args(argv)
+    if args.windows is None:
+        args.windows = 5 if args.full else 1
+    return args
 
 
 # ------------------------------------------------------------------------------------------------------------------------------
@@ -556,7 +574,9 @@ class Windows:
         auto = max(8, self.steps // 2) if self.steps <= 64 else 16
         self.every = max(1, int(os.environ.get('DRX_BENCH_EVENTS_EVERY', auto)))
         total = self.steps * self.windows
-        self.evs = [[torch.cuda.Event(enable_timing=True) for _ in range(n_events)] if i % self.every == 0 else None for i in range(total)]
+        # (n_events 0: no step carries events — a plain run, whose line has no phase figures)
+        self.evs = [[torch.cuda.Event(enable_timing=True) for _ in range(n_events)] if n_events and i % self.every == 0 else None
+                    for i in range(total)]
         for es in self.evs:
             for e in (es or []):
                 e.record()
@@ -610,6 +630,24 @@ def rccl_ranks(dist, dev, world, debug_gloo):
     return int(t.item())
 
 
+DUMP_TABLE_BYTES = 15 << 20          # --dump-outputs: at most this much of every table (four of them at most 60 MiB: under 64 MB in all)
+
+
+def dump_outputs(path, eng):
+    """--dump-outputs: the parameters the last timed step left — the training step returns nothing else to its caller — as float32
+    .npy files (the first k columns; padding dropped).  A table larger than DUMP_TABLE_BYTES is represented by a sorted sample of its
+    rows (file name `<table>_sampled`), drawn with a fixed seed from its shape alone: runs with the same arguments name the same rows."""
+    os.makedirs(path, exist_ok=True)
+    torch.cuda.synchronize()
+    k = eng.k
+    for name, t in (('W', eng.W[:, :k]), ('W2T', eng.W2T[:, :k]), ('V', eng.V[:, :k]), ('b', eng.b[:k]), ('b2', eng.b2)):
+        row_bytes = 4 * (t.shape[1] if t.dim() == 2 else 1)
+        if t.shape[0] * row_bytes > DUMP_TABLE_BYTES:
+            pick = np.sort(np.random.default_rng(12345).choice(t.shape[0], size=DUMP_TABLE_BYTES // row_bytes, replace=False))
+            t, name = t[torch.as_tensor(pick, device=t.device)], name + '_sampled'
+        np.save(os.path.join(path, name + '.npy'), t.float().cpu().numpy())
+
+
 def run_columns(args, rank, world, dev, dist, debug_gloo, rccl1):
     """Column-sharded layout (dist.ColumnShardedCdae): the job's global batch (B per GPU x N GPUs) is drawn identically on every
     rank, each rank trains its K/N columns of every table on all of it; one all-reduce of B_global floats per step."""
@@ -625,12 +663,13 @@ def run_columns(args, rank, world, dev, dist, debug_gloo, rccl1):
     model = ColumnShardedCdae(U, N, K, rank, world, dev, indptr, indices, seed=10, lr=1e-3 if args.optimizer == 'adam' else LR, reg=REG,
                               optimizer=args.optimizer, q=Q, cpu_staging=debug_gloo, force_collectives=rccl1)
     eng = model.engine
-    uid, iid, y, keep_off = eng.sample_device(Bg, NEG_RATIO, 1000, n_items=N)
-    rows_per_sample = kept_count(keep_off, 1000, Q) / Bg + 2.0
-    f_solo = 0.0
-    for col in (uid.long(), iid.long()):
-        _, inv, cnt = torch.unique(col, return_inverse=True, return_counts=True)
-        f_solo += float((cnt[inv] == 1).float().mean().item())
+    rows_per_sample, f_solo = None, 0.0
+    if args.full:               # R and the sole-toucher rows of one batch: the line's model bytes (a plain run draws no extra batch)
+        uid, iid, y, keep_off = eng.sample_device(Bg, NEG_RATIO, 1000, n_items=N)
+        rows_per_sample = kept_count(keep_off, 1000, Q) / Bg + 2.0
+        for col in (uid.long(), iid.long()):
+            _, inv, cnt = torch.unique(col, return_inverse=True, return_counts=True)
+            f_solo += float((cnt[inv] == 1).float().mean().item())
     setup_s = time.time() - t_setup
     seed_of = lambda s: 5000 + 7919 * s                                                              # same seeds on every rank
     emu = int(os.environ.get('DRX_BENCH_EMULATE_RANKS', 0))
@@ -673,7 +712,7 @@ def run_columns(args, rank, world, dev, dist, debug_gloo, rccl1):
     pipe = model.pipeline(Bg, NEG_RATIO, seed_of, seed_of)
     for _ in range(args.warmup):
         pipe.run_step()
-    win = Windows(args.steps, args.windows, 7, world, dist, dev)
+    win = Windows(args.steps, args.windows, 7 if args.full else 0, world, dist, dev)
 
     def step_fn(i, es, last):
         if es is not None:
@@ -682,10 +721,25 @@ def run_columns(args, rank, world, dev, dist, debug_gloo, rccl1):
         else:
             pipe.run_step()
     win.run(step_fn)
+    kl = model.k_hi - model.k_lo
+    if rank == 0 and args.dump_outputs and (args.layout == 'columns' or args.force_columns):     # (with both layouts: the row layout's)
+        dump_outputs(args.dump_outputs, eng)
+    if not args.full:
+        n_ranks = rccl_ranks(dist, dev, world, debug_gloo)
+        if rank != 0:
+            return None
+        out = {'metric': 'training samples/sec (user-item pairs)', 'unit': 'samples/s', 'n_gpus': world, 'steps': args.steps, 'warmup': args.warmup,
+               'higher_is_better': True, 'scaling': 'weak', 'vs_baseline': None, 'dtype': 'f32', 'data': 'synthetic', 'rccl_ranks': n_ranks,
+               'config': {'workload': f'CDAE hidden_factors={K} sampled-output sparse-{"Adam (lazy)" if args.optimizer == "adam" else "Adagrad"} on '
+                                      f'{args.workload}-shaped synthetic ({U} users x {N} items, {nnz} positives), corruption {Q}, neg_ratio {NEG_RATIO}',
+                          'batch_per_gpu': args.batch, 'global_batch': Bg,
+                          'sharding': f'columns: every rank holds all rows x {kl} of {K} columns and trains on the whole global batch'},
+               'setup_s': round(setup_s, 1)}
+        out.update(win.fields(Bg))
+        return out
     ph, n_timed = win.phase_means(6)
     names = ['k_kshard_fwd+allreduce(dot)', 'k_kshard_rest', 'touch_sort(overlapped on side stream)', 'k_seg_reduce_planned(+bias partials)',
              'k_span_planned(short | long spans | bias update)', '(unused)']
-    kl = model.k_hi - model.k_lo
     S_opt = 2.0 if args.optimizer == 'adam' else 1.0
     alg_upd = Bg * 4.0 * kl * (rows_per_sample - f_solo) * (2.0 + 2.0 * S_opt)      # this rank's columns of the global batch
     alg_fwd = Bg * 4.0 * kl * rows_per_sample
@@ -759,9 +813,13 @@ def run_direct(args, rank, world, dev, dist, debug_gloo=False, rccl1=False):
         eng = stepper.engine
 
     micro = max(1, args.micro)       # > 1: micro-batches whose exchanges overlap each other's compute (measured at world 1: the split costs more than it hides)
+    overlap = not args.no_overlap
+    # a fresh device-sampled batch every step (single GPU: SampledPipeline; row layout: DeviceBatchSource) never reads the pre-sampled
+    # batches: a plain run of those paths draws none (they serve the R estimate, the row statistics and the CPU baseline of --full)
+    fresh_path = overlap and not args.presampled and (stepper is None or (micro == 1 and not debug_gloo))
     # ---- pre-sampled batches, resident in HBM -------------------------------------------------------------
     batches, structs, kept_tot = [], [], 0
-    for i in range(args.n_batches):
+    for i in range(args.n_batches if (args.full or not fresh_path) else 0):
         seed = 1000 + 7919 * i + 104729 * rank
         uid, iid, y, keep_off = eng.sample_device(B, NEG_RATIO, seed, n_items=N)
         torch.cuda.synchronize()
@@ -783,12 +841,11 @@ def run_direct(args, rank, world, dev, dist, debug_gloo=False, rccl1=False):
         else:
             bt, alive = eng.make_batch(uid, iid, y, keep_off=keep_off, q=Q, mask_seed=seed, n_touch_slots=n_slots)
             structs.append((bt, alive))
-    rows_per_sample = kept_tot / (args.n_batches * B) + 2.0          # R: kept W rows + V row + W2T row
+    rows_per_sample = kept_tot / (args.n_batches * B) + 2.0 if batches else None          # R: kept W rows + V row + W2T row
     setup_s = time.time() - t_setup
     _trace('setup done')
 
     # The touch list of a batch (sorted row keys) does not depend on the parameters: it is prepared ahead on a side stream
-    overlap = not args.no_overlap
     main = torch.cuda.current_stream()
     from drecpy_amd.engine import run_ahead_stream
     side = run_ahead_stream(dev, 0) if overlap else None            # (the process-wide pool: probed for a hardware queue of its own)
@@ -869,10 +926,40 @@ def run_direct(args, rank, world, dev, dist, debug_gloo=False, rccl1=False):
     for s in range(args.warmup):
         run_step(s)
     _trace('warm-up queued')
-    win = Windows(args.steps, args.windows, 6, world, dist, dev)
+    win = Windows(args.steps, args.windows, 6 if args.full else 0, world, dist, dev)
     win.run(lambda i, es, last: run_step(args.warmup + i, events=es, last=last))
     _trace('windows done')
     n_ranks = rccl_ranks(dist, dev, world, debug_gloo) if dist is not None else 1
+    if rank == 0 and args.dump_outputs:
+        dump_outputs(args.dump_outputs, eng)
+    config = {'workload': f'CDAE hidden_factors={K} sampled-output sparse-{dict(adam="Adam (lazy)", adagrad="Adagrad", rowwise_adagrad="row-wise Adagrad")[args.optimizer if stepper is None else "adagrad"]} on {args.workload}-shaped synthetic '
+                          f'({U} users x {N} items, {nnz_local * world if world > 1 else nnz_local} positives), '
+                          f'corruption {Q}, neg_ratio {NEG_RATIO}',
+              'batch_per_gpu': B, 'global_batch': B * world, 'rows_per_sample': None if rows_per_sample is None else round(rows_per_sample, 3),
+              'sole_toucher_rows_per_sample': None,
+              'touch_list': ('keys exchanged one batch ahead, counts two (dist.ShardedPipeline)' if pipe is not None else 'prepared ahead on a side stream') if overlap else 'inline',
+              'batches': 'fresh device-sampled batch every step (sampler running ahead on the side stream)' if (fresh or (pipe is not None and fresh_sharded))
+              else f'{args.n_batches} pre-sampled batches cycled',
+              'micro_batches': (micro if stepper is not None else None),
+              'exchange_chunks': (stepper.chunks if stepper is not None else None),
+              'transport': (type(stepper.xfer).__name__ if stepper is not None else None),
+              'exchanges_issued_by': (('library (drx_shard_phase_*)' if (stepper.phases and max(1, args.micro) == 1) else 'dist.py, call by call')
+                                      if stepper is not None else None),
+              'sharding': ('single GPU' if stepper is None else
+                           'row-sharded code path at world 1, ' + ('every row sent through the communicator (--no-self-bypass: all rows "remote", the link '
+                                                                   'replaced by a device copy)' if args.no_self_bypass else
+                                                                   'own rows bypass the collectives (at world 1: all of them; the exchanges are empty)')) if world == 1
+              else f'rows: users (V rows, histories, samples) sharded x{world} by range, item rows sharded by range; all-to-all(v) of rows and gradient '
+                   f'rows (one float buffer per direction; a rank\'s own rows bypass them), bias gradient in the sentinel rows of the gradient exchange'}
+    if not args.full:
+        if rank != 0:
+            return None
+        out = {'metric': 'training samples/sec (user-item pairs)', 'unit': 'samples/s', 'n_gpus': world, 'steps': args.steps, 'warmup': args.warmup,
+               'higher_is_better': True, 'scaling': 'weak', 'vs_baseline': None, 'dtype': 'f32', 'data': 'synthetic', 'rccl_ranks': n_ranks,
+               'config': config, 'setup_s': round(setup_s, 1),
+               'host_issue_ms_per_step': ([round(1e3 * t / total_steps, 4) for t in pipe.host_s + [stepper.wait_s]] if pipe is not None else None)}
+        out.update(win.fields(world * B))
+        return out
     ph, n_timed = win.phase_means(5)
     step_s = win.median / args.steps
     # SURVEY 8d's per-occurrence model (kept as model_*): forward reads 4K*R per sample; the update reads and writes parameter + S
@@ -956,31 +1043,14 @@ def run_direct(args, rank, world, dev, dist, debug_gloo=False, rccl1=False):
         'metric': 'training samples/sec (user-item pairs)', 'unit': 'samples/s',
         'n_gpus': world, 'steps': args.steps, 'warmup': args.warmup,
         'higher_is_better': True, 'scaling': 'weak', 'vs_baseline': None, 'dtype': 'f32', 'data': 'synthetic', 'rccl_ranks': n_ranks,
-        'config': {'workload': f'CDAE hidden_factors={K} sampled-output sparse-{dict(adam="Adam (lazy)", adagrad="Adagrad", rowwise_adagrad="row-wise Adagrad")[args.optimizer if stepper is None else "adagrad"]} on {args.workload}-shaped synthetic '
-                               f'({U} users x {N} items, {nnz_local * world if world > 1 else nnz_local} positives), '
-                               f'corruption {Q}, neg_ratio {NEG_RATIO}',
-                   'batch_per_gpu': B, 'global_batch': B * world, 'rows_per_sample': round(rows_per_sample, 3),
-                   'sole_toucher_rows_per_sample': round(f_solo, 3),
-                   'touch_list': ('keys exchanged one batch ahead, counts two (dist.ShardedPipeline)' if pipe is not None else 'prepared ahead on a side stream') if overlap else 'inline',
-                   'batches': 'fresh device-sampled batch every step (sampler running ahead on the side stream)' if (fresh or (pipe is not None and fresh_sharded))
-                   else f'{args.n_batches} pre-sampled batches cycled',
-                   'micro_batches': (micro if stepper is not None else None),
-                   'exchange_chunks': (stepper.chunks if stepper is not None else None),
-                   'transport': (type(stepper.xfer).__name__ if stepper is not None else None),
-                   'exchanges_issued_by': (('library (drx_shard_phase_*)' if (stepper.phases and max(1, args.micro) == 1) else 'dist.py, call by call')
-                                           if stepper is not None else None),
-                   'sharding': ('single GPU' if stepper is None else
-                                'row-sharded code path at world 1, ' + ('every row sent through the communicator (--no-self-bypass: all rows "remote", the link '
-                                                                        'replaced by a device copy)' if args.no_self_bypass else
-                                                                        'own rows bypass the collectives (at world 1: all of them; the exchanges are empty)')) if world == 1
-                   else f'rows: users (V rows, histories, samples) sharded x{world} by range, item rows sharded by range; all-to-all(v) of rows and gradient '
-                        f'rows (one float buffer per direction; a rank\'s own rows bypass them), bias gradient in the sentinel rows of the gradient exchange'},
+        'config': config,
         'roofline': None,
         'phases_ms': {n: float(v) for n, v in zip(names, ph)},
         'setup_s': round(setup_s, 1),
         'host_issue_ms_per_step': ([round(1e3 * t / total_steps, 4) for t in pipe.host_s + [stepper.wait_s]] if pipe is not None else None),
     }
     out.update(win.fields(world * B))
+    out['config']['sole_toucher_rows_per_sample'] = round(f_solo, 3)
     if stepper is None and len(ph) >= 4:
         # (i) end to end incl. the sampler = `value` (a fresh batch is drawn and prepared on the device for every step, beside
         # the training kernels); (ii) the training launches alone, HIP events around each of them on the timed steps that carry events
@@ -1089,7 +1159,7 @@ def run_direct(args, rank, world, dev, dist, debug_gloo=False, rccl1=False):
                            'avg_launch_ms': float(dom_ms), 'timed_launches': n_timed, 'hbm_copy_achievable': copy_gbs,
                            'definition': 'row-sharded path: only the per-occurrence model (SURVEY 8d) is evaluated here'}
     out['cpu_baseline'] = out['cpu_baseline_all_cores'] = None
-    if world == 1 and not args.no_cpu_baseline:
+    if world == 1 and not args.no_cpu_baseline:          # (only with --full: a plain run returned above)
         from bench_cpu import cpu_baseline
         uid, iid, y, keep_off, seed = batches[0]
         one, many = cpu_baseline(eng, indptr, indices, (uid, iid, y, keep_off), seed, Q, LR, REG, q_threshold, budget_s=args.cpu_budget_s,
@@ -1126,7 +1196,7 @@ def worker_main(args):
         out = run_columns(args, rank, world, dev, dist, debug_gloo, rccl1)
     else:
         out = run_direct(args, rank, world, dev, dist, debug_gloo, rccl1)
-    if rank == 0 and world == 1 and not args.force_columns and not args.force_sharded:
+    if rank == 0 and world == 1 and args.full and not args.force_columns and not args.force_sharded:
         out['hr_at_10'] = hr_at_10(dev, with_cpu=not args.no_cpu_baseline) if (not args.no_hr and not args.users) else None
         out['cpu_baseline_reference_mode'] = (out['hr_at_10'] or {}).get('cpu_baseline_reference_mode')
         if args.force_configs or (not args.no_configs and not args.users and args.workload == 'synth-10m' and K == 128):

@@ -246,7 +246,7 @@ def configs_block(dev, run_direct, base_args, with_cpu=True):
     try:
         a = copy.copy(base_args)
         a.workload, a.steps, a.warmup, a.windows, a.users = 'ml-1m', 30, 5, 3, 0
-        a.no_hr, a.no_configs = True, True
+        a.no_hr, a.no_configs, a.dump_outputs = True, True, None      # (the main workload's outputs are the ones --dump-outputs wrote)
         a.cpu_budget_s, a.cpu_triples, a.no_all_cores = 5.0, 128, True
         a.no_cpu_baseline = not with_cpu
         r = run_direct(a, 0, 1, dev, None)

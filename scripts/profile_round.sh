@@ -9,7 +9,7 @@ ROOT=$(pwd)
 OUT=$ROOT/gpurun_out/$TAG
 mkdir -p $OUT
 export TMPDIR=/tmp
-python bench.py > $OUT/bench.json 2> $OUT/bench.err
+python bench.py --full > $OUT/bench.json 2> $OUT/bench.err
 cd /tmp
 timeout -k 5 300 rocprofv3 --kernel-trace --stats --output-format csv -d $OUT/kt -o kt -- python3 $ROOT/bench.py --steps 200 --warmup 10 --windows 2 --no-cpu-baseline --no-hr --no-configs > $OUT/kt_bench.json 2> $OUT/kt.err
 timeout -k 5 120 rocprofv3 --pmc FETCH_SIZE --output-format csv -d $OUT/pmc_fetch -o f -- python3 $ROOT/bench.py --steps 6 --warmup 2 --windows 1 --no-cpu-baseline --no-hr --no-configs > /dev/null 2> $OUT/pmc_fetch.err
@@ -32,7 +32,7 @@ python profiles/pmc_summary.py $(find $OUT/pmc_fetch_ml1m -name '*counter_collec
 python profiles/pmc_l2.py $(find $OUT/pmc_l2_ml1m -name '*counter_collection.csv' | head -1) $OUT/pmc_l2_hit_rate_ml1m.json
 python profiles/pmc_make_traffic.py $OUT/pmc_traffic_raw_ml1m.json $OUT/pmc_traffic_ml-1m.json $TAG ml-1m 65536 adagrad $OUT/pmc_l2_hit_rate_ml1m.json
 cp $OUT/pmc_traffic_ml-1m.json profiles/pmc_traffic_ml-1m.json
-python bench.py > $OUT/bench_with_traffic.json 2>> $OUT/bench.err     # the line as the driver will see it, quoting the PMC passes just taken
+python bench.py --full > $OUT/bench_with_traffic.json 2>> $OUT/bench.err     # the --full line, quoting the PMC passes just taken
 grep -h "drx::" $(find $OUT/kt -name '*kernel_stats.csv' | head -1) | head -40 > $OUT/kernel_stats_drx.csv
 cp $(find $OUT/kt -name '*kernel_stats.csv' | head -1) $OUT/kernel_stats.csv
 # keep only the small summaries

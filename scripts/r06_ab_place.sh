@@ -4,7 +4,7 @@ set -u
 TAG=${1:-r06f}
 OUT=gpurun_out/$TAG
 mkdir -p $OUT
-COMMON="--steps 200 --warmup 20 --windows 3 --no-cpu-baseline --no-hr --no-configs"
+COMMON="--full --steps 200 --warmup 20 --windows 3 --no-cpu-baseline --no-hr --no-configs"
 for i in 1 2; do
   python bench.py $COMMON > $OUT/placed_$i.json 2> $OUT/placed_$i.err
   DRX_HOST_SANITIZER_LIB=drecpy_amd/csrc/build/libdrx_noplace.so python bench.py $COMMON > $OUT/noplace_$i.json 2> $OUT/noplace_$i.err

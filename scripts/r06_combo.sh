@@ -6,7 +6,7 @@ OUT=gpurun_out/$TAG
 mkdir -p $OUT
 bash scripts/r06_ab_place.sh $TAG/ab > $OUT/ab.log 2>&1; tail -8 $OUT/ab.log
 timeout -k 5 900 python -m pytest "tests/test_gpu_fullsize.py::test_one_full_size_step_matches_the_oracle_on_compacted_tables" tests/test_gpu_kshard.py tests/test_gpu_shard.py -q -m gpu > $OUT/pytest.log 2>&1; tail -5 $OUT/pytest.log
-COMMON="--steps 100 --warmup 10 --windows 3 --no-cpu-baseline --no-hr --no-configs"
+COMMON="--full --steps 100 --warmup 10 --windows 3 --no-cpu-baseline --no-hr --no-configs"
 for C in 1 2 4; do
   DRX_BENCH_RCCL1=1 timeout -k 5 300 python bench.py $COMMON --force-sharded --no-self-bypass --chunks $C > $OUT/remote_c$C.json 2> $OUT/remote_c$C.err
 done

@@ -4,7 +4,7 @@ set -u
 TAG=${1:-r06cc}
 OUT=gpurun_out/$TAG
 mkdir -p $OUT
-COMMON="--steps 300 --warmup 30 --windows 3 --no-cpu-baseline --no-hr --no-configs --batch 1024 --users 400000"
+COMMON="--full --steps 300 --warmup 30 --windows 3 --no-cpu-baseline --no-hr --no-configs --batch 1024 --users 400000"
 for C in 2; do
   for M in thread nothread; do
     F=""; [ $M = nothread ] && F="--no-comm-thread"
@@ -13,7 +13,7 @@ for C in 2; do
 done
 for i in 1 2; do for C in 1 2; do for M in thread nothread; do
   F=""; [ $M = nothread ] && F="--no-comm-thread"
-  DRX_BENCH_RCCL1=1 timeout -k 5 300 python bench.py --steps 100 --warmup 10 --windows 3 --no-cpu-baseline --no-hr --no-configs --force-sharded --no-self-bypass --chunks $C $F > $OUT/full_c${C}_${M}_$i.json 2> $OUT/full_c${C}_${M}_$i.err
+  DRX_BENCH_RCCL1=1 timeout -k 5 300 python bench.py --full --steps 100 --warmup 10 --windows 3 --no-cpu-baseline --no-hr --no-configs --force-sharded --no-self-bypass --chunks $C $F > $OUT/full_c${C}_${M}_$i.json 2> $OUT/full_c${C}_${M}_$i.err
 done; done; done
 python - <<PY
 import json, glob, os

@@ -4,7 +4,7 @@ TAG=${1:-r06bc}
 OUT=gpurun_out/$TAG
 mkdir -p $OUT
 timeout -k 5 900 python -m pytest tests/test_gpu_fit.py tests/test_gpu_cdae.py tests/test_gpu_kshard.py -q -m gpu -x > $OUT/pytest.log 2>&1; grep -n "passed\|failed" $OUT/pytest.log | tail -2
-COMMON="--no-cpu-baseline --no-hr --no-configs"
+COMMON="--full --no-cpu-baseline --no-hr --no-configs"
 for i in 1 2 3; do
   for K in 20 200; do
     python bench.py $COMMON --steps $K --warmup 5 > $OUT/k${K}_$i.json 2> $OUT/k${K}_$i.err

@@ -5,7 +5,7 @@ TAG=${1:-r06ac}
 OUT=gpurun_out/$TAG
 mkdir -p $OUT
 timeout -k 5 1200 python -m pytest tests/test_gpu_shard.py -q -m gpu -x > $OUT/pytest.log 2>&1; tail -8 $OUT/pytest.log
-COMMON="--steps 100 --warmup 10 --windows 3 --no-cpu-baseline --no-hr --no-configs"
+COMMON="--full --steps 100 --warmup 10 --windows 3 --no-cpu-baseline --no-hr --no-configs"
 for C in 1 2 4; do
   DRX_BENCH_RCCL1=1 timeout -k 5 300 python bench.py $COMMON --force-sharded --no-self-bypass --chunks $C > $OUT/remote_c${C}_phases.json 2> $OUT/remote_c${C}_phases.err
   DRX_BENCH_RCCL1=1 timeout -k 5 300 python bench.py $COMMON --force-sharded --no-self-bypass --chunks $C --no-phases > $OUT/remote_c${C}_python.json 2> $OUT/remote_c${C}_python.err

@@ -5,7 +5,7 @@ set -u
 TAG=${1:-r06a}
 OUT=gpurun_out/$TAG
 mkdir -p $OUT
-COMMON="--steps 100 --warmup 10 --windows 3 --no-cpu-baseline --no-hr --no-configs"
+COMMON="--full --steps 100 --warmup 10 --windows 3 --no-cpu-baseline --no-hr --no-configs"
 for B in 65536 131072 262144; do
   python bench.py $COMMON --batch $B > $OUT/single_B$B.json 2> $OUT/single_B$B.err
   for M in 1 2 4; do

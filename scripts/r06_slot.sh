@@ -4,7 +4,7 @@ TAG=${1:-r06cg}
 OUT=gpurun_out/$TAG
 mkdir -p $OUT
 for i in 1 2 3 4; do for C in 1 2; do
-  DRX_BENCH_RCCL1=1 timeout -k 5 300 python bench.py --steps 100 --warmup 10 --windows 3 --no-cpu-baseline --no-hr --no-configs --force-sharded --no-self-bypass --chunks $C > $OUT/remote_c${C}_$i.json 2> $OUT/remote_c${C}_$i.err
+  DRX_BENCH_RCCL1=1 timeout -k 5 300 python bench.py --full --steps 100 --warmup 10 --windows 3 --no-cpu-baseline --no-hr --no-configs --force-sharded --no-self-bypass --chunks $C > $OUT/remote_c${C}_$i.json 2> $OUT/remote_c${C}_$i.err
 done; done
 python - <<PY
 import json, glob, os

@@ -4,7 +4,7 @@ set -u
 TAG=${1:-r06l}
 OUT=gpurun_out/$TAG
 mkdir -p $OUT
-COMMON="--steps 200 --warmup 20 --windows 3 --no-cpu-baseline --no-hr --no-configs"
+COMMON="--full --steps 200 --warmup 20 --windows 3 --no-cpu-baseline --no-hr --no-configs"
 for i in 1 2; do
   python bench.py $COMMON > $OUT/default_$i.json 2> $OUT/default_$i.err
   for v in ipt4 t256 t1024 ipt16; do

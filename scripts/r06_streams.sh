@@ -13,7 +13,7 @@ for K in 6 10; do DRX_STREAM_PROBE=0 python scripts/r06_stream_parity.py $K -1 u
 } > $OUT/streams.log 2>&1
 cat $OUT/streams.log
 timeout -k 5 1500 python -m pytest tests/test_gpu_caser.py tests/test_gpu_dmf.py tests/test_gpu_shard.py tests/test_gpu_fit.py -q -m gpu -x > $OUT/pytest.log 2>&1; tail -3 $OUT/pytest.log
-timeout -k 5 600 python bench.py --steps 200 --warmup 20 --no-cpu-baseline > $OUT/bench.json 2> $OUT/bench.err
+timeout -k 5 600 python bench.py --full --steps 200 --warmup 20 --no-cpu-baseline > $OUT/bench.json 2> $OUT/bench.err
 python - <<PY
 import json
 d = json.loads([l for l in open('$OUT/bench.json') if l.startswith('{')][-1])

@@ -1,5 +1,5 @@
 """The one JSON line bench.py prints (the driver's contract): fields, types and internal consistency, on a short run of the small
-workload (a child process; the 10M x 1M default is what the driver itself times)."""
+workload (a child process; the 10M x 1M default is what the driver itself times) — with --full, and as a plain run with its outputs."""
 import json
 import os
 import subprocess
@@ -12,9 +12,10 @@ ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 
 
 def test_bench_line_has_the_contracted_fields():
+    """--full: everything measured beside the headline."""
     out = subprocess.run([sys.executable, os.path.join(ROOT, 'bench.py'), '--workload', 'ml-100k', '--batch', '4096', '--steps', '20',
-                          '--warmup', '5', '--no-hr', '--force-configs', '--cpu-budget-s', '3'], cwd=ROOT, capture_output=True, text=True,
-                         timeout=900)
+                          '--warmup', '5', '--full', '--no-hr', '--force-configs', '--cpu-budget-s', '3'], cwd=ROOT, capture_output=True,
+                         text=True, timeout=900)
     assert out.returncode == 0, out.stderr[-2000:]
     lines = [l for l in out.stdout.splitlines() if l.startswith('{')]
     assert len(lines) == 1, out.stdout[-2000:]
@@ -97,3 +98,34 @@ def test_bench_line_has_the_contracted_fields():
         assert cb['kind'] == 'port' and cb['cores'] == 1 and cb['value'] > 0 and cb['unit'] == unit and cb['sample']
     c5d = g['cfg5_caser_ml1m']['Caser_B4096_device_sampler']
     assert c5d['sampler'].startswith('device') and 0 < c5d['fit_steady_ms_per_step'] < c5['fit_steady_ms_per_step']
+
+
+def _plain_run(dump_dir):
+    out = subprocess.run([sys.executable, os.path.join(ROOT, 'bench.py'), '--workload', 'ml-100k', '--batch', '4096', '--steps', '20',
+                          '--warmup', '5', '--dump-outputs', str(dump_dir)], cwd=ROOT, capture_output=True, text=True, timeout=600)
+    assert out.returncode == 0, out.stderr[-2000:]
+    lines = [l for l in out.stdout.splitlines() if l.startswith('{')]
+    assert len(lines) == 1, out.stdout[-2000:]
+    return json.loads(lines[0])
+
+
+def test_plain_run_times_exactly_its_steps_and_dumps_the_same_outputs_every_time(tmp_path):
+    """A plain run: ONE window of exactly --steps timed steps, the headline fields and nothing measured beside them; --dump-outputs
+    writes the parameters the last timed step left (float32, under 64 MB), the same in two runs of the same arguments."""
+    import numpy as np
+    lines = [_plain_run(tmp_path / run) for run in ('a', 'b')]
+    for d in lines:
+        assert d['metric'].startswith('training samples/sec') and d['unit'] == 'samples/s' and d['higher_is_better'] is True
+        assert d['dtype'] == 'f32' and d['n_gpus'] == 1 and d['steps'] == 20 and d['warmup'] == 5
+        assert d['windows'] == 1 and len(d['window_ms']) == 1 and abs(d['window_ms'][0] - 20 * d['ms_per_step']) < 1e-3
+        assert abs(d['value'] - 4096 / (d['ms_per_step'] * 1e-3)) / d['value'] < 1e-6
+        for k in ('roofline', 'phases_ms', 'device_only', 'cpu_baseline', 'hr_at_10', 'configs'):
+            assert k not in d, k
+    names = sorted(p.name for p in (tmp_path / 'a').iterdir())
+    assert names == ['V.npy', 'W.npy', 'W2T.npy', 'b.npy', 'b2.npy'], names          # (ml-100k: every table whole)
+    shapes = {'V.npy': (943, 128), 'W.npy': (1682, 128), 'W2T.npy': (1682, 128), 'b.npy': (128,), 'b2.npy': (1682,)}
+    assert sum((tmp_path / 'a' / n).stat().st_size for n in names) < 64e6
+    for n in names:
+        a, b = np.load(tmp_path / 'a' / n), np.load(tmp_path / 'b' / n)
+        assert a.dtype == np.float32 and a.shape == shapes[n] and np.isfinite(a).all()
+        assert np.array_equal(a, b), (n, float(np.abs(a - b).max()))
