@@ -38,6 +38,10 @@ class Batch(C.Structure):
                 ('n_touch_slots', C.c_int32), ('flags', C.c_uint32)]
 
 
+class HotHead(C.Structure):                             # include/drx.h DrxHotHead
+    _fields_ = [('H', C.c_int32), ('slot', C.c_void_p), ('item', C.c_void_p)]
+
+
 class ListGroups(C.Structure):
     _fields_ = [('indptr', C.c_void_p), ('seq_ids', C.c_void_p), ('held_indptr', C.c_void_p), ('held', C.c_void_p),
                 ('group_value', C.c_void_p), ('eligible', C.c_void_p), ('n_groups', C.c_int32), ('n_eligible', C.c_int32),
@@ -147,6 +151,14 @@ SIGNATURES = {
     'drx_cdae_step_sparse_prepared': (C.c_int, [C.POINTER(CdaeParams), C.POINTER(Optim), C.POINTER(History),
                                                 C.POINTER(Batch), C.c_int32, C.c_void_p, C.c_size_t, C.c_void_p,
                                                 C.c_size_t, C.c_void_p, C.POINTER(C.c_void_p), C.c_void_p]),
+    'drx_cdae_prep_bytes_hot': (C.c_size_t, [C.POINTER(CdaeParams), C.c_int32, C.c_int32, C.c_int32]),
+    'drx_cdae_scratch_bytes_hot': (C.c_size_t, [C.POINTER(CdaeParams), C.c_int32, C.c_int32, C.c_int32]),
+    'drx_cdae_sparse_prepare_hot': (C.c_int, [C.POINTER(CdaeParams), C.POINTER(History), C.POINTER(Batch), C.POINTER(HotHead),
+                                              C.c_void_p, C.c_size_t, C.c_void_p]),
+    'drx_cdae_step_sparse_hot': (C.c_int, [C.POINTER(CdaeParams), C.POINTER(Optim), C.POINTER(History), C.POINTER(Batch),
+                                           C.POINTER(HotHead), C.c_int32, C.c_void_p, C.c_size_t, C.c_void_p, C.c_size_t,
+                                           C.c_void_p, C.POINTER(C.c_void_p), C.c_void_p]),
+    'drx_cdae_prep_forget': (None, [C.c_void_p]),
     'drx_point_sample_scratch_bytes': (C.c_size_t, [C.c_int32]),
     'drx_list_sample_device': (C.c_int, [C.POINTER(ListGroups), C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_uint64, C.c_void_p, C.c_void_p,
                                          C.c_void_p, C.c_void_p]),

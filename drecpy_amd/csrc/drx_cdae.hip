@@ -15,6 +15,8 @@
 #include "drx_prep.hpp"
 #include "drx_segstream.hpp"
 #include <type_traits>
+#include <mutex>
+#include <unordered_map>
 
 #ifndef DRX_GATHER_ROWS
 #define DRX_GATHER_ROWS 8
@@ -1075,6 +1077,148 @@ struct BiasFinalExtra {
 };
 
 // ------------------------------------------------------------------------------------------------
+// The HOT HEAD (include/drx.h DrxHotHead): the W rows of the H hottest items take no part in the touch list; their gradients are the
+// dense product (1/(1-q)) * M^T * dz1 of the batch's transposed 0/1 kept-mask M [H, B] (k_sparse_touches) with dz1 [B, ld], read once
+// as a stream instead of one random row gather per touch.  Two stages riding in the launches the step already has:
+//   partials: extra workgroups of k_seg_reduce_stream — one WAVE per (slice of kHotSlice samples, 32 hot rows, 32 columns): a 32 x 32
+//             tile of P[s] = M_slice^T * dz1_slice on v_mfma_f32_32x32x16_bf16.  dz1 is split exactly into hi + mid + lo bf16 (8
+//             significant bits each: 24 = the fp32 significand), so three MFMAs per k-step sum the fp32 values; a 0/1 A operand is
+//             exact in bf16; accumulation is fp32.  16 accumulators per lane: the launch keeps its 64-VGPR budget;
+//   finish:   extra workgroups of k_span_planned — one per hot row: the slices' partials summed in a fixed order, the row's Adagrad
+//             update as the segment path's (DirectPolicyAdagrad::stream_update); rows no sample kept are not touched.
+// ------------------------------------------------------------------------------------------------
+constexpr int kHotSlice = 512;       // samples per partial (P: [B / kHotSlice, H, ld] floats)
+// rows of 64 / 128 floats only: with rows of 256 the reduction's partial workgroups need 72 registers (56 + 16 accumulators), above the
+// 64 that keep that launch at 8 waves per SIMD
+constexpr int kHotMaxG = 32;
+
+struct HotArgs {
+  const float *dz1;             // [B, ld]
+  const uint32_t *mask;         // [H, Bw] (drx_prep.hpp PrepBufs::hmask)
+  float *part;                  // [S, H, ld]
+  uint32_t *any;                // [S, H / 32]: bit r of word (s, hb) = hot row 32 hb + r has a kept sample in slice s
+  const int32_t *item;          // [H]
+  float scale;                  // 1 / (1 - q)
+  int B, H, Bw, S, first;       // first: the launch's first workgroup of this stage
+};
+
+static inline int hot_slices(int B) { return (B + kHotSlice - 1) / kHotSlice; }
+
+typedef __bf16 hot_bf16x8 __attribute__((ext_vector_type(8)));
+typedef float hot_f32x16 __attribute__((ext_vector_type(16)));
+typedef uint32_t hot_u32x4 __attribute__((ext_vector_type(4)));
+
+// NT: threads of the launch it rides in (k_seg_reduce_stream<LD>: (kSegBlock / (LD / 4)) waves)
+template <int LD, int NT>
+struct HotPartialExtra {
+  HotArgs A;
+  __device__ __forceinline__ void operator()(float *) const {
+    constexpr int CT = LD / 32, NW = NT / 64;
+    const int lane = threadIdx.x & 63, wv = (int)(threadIdx.x >> 6);
+    const int hbs = A.H / 32;
+    const int task = ((int)blockIdx.x - A.first) * NW + wv;        // column tile fastest: the waves of a workgroup share a slice's rows
+    if (task >= A.S * hbs * CT) return;
+    const int ct = task % CT, hb = (task / CT) % hbs, s = task / (CT * hbs);
+    const int r = lane & 31, hh = lane >> 5;                       // A[row r][k = 8 hh + j], B[k = 8 hh + j][col r]
+    const uint32_t *const mrow = A.mask + (size_t)(hb * 32 + r) * A.Bw;
+    const float *const col = A.dz1 + ct * 32 + r;
+    hot_f32x16 acc;
+#pragma unroll
+    for (int i = 0; i < 16; ++i) acc[i] = 0.f;
+    uint32_t seen = 0u;
+    const int b_begin = s * kHotSlice, b_end = min(A.B, b_begin + kHotSlice);
+    for (int b0 = b_begin; b0 < b_end; b0 += 32) {                // one mask word: two k-steps of 16 samples
+      const uint32_t word = mrow[b0 >> 5];                         // (bits of samples >= B are never set)
+      seen |= word;
+#pragma unroll
+      for (int t = 0; t < 2; ++t) {
+        const uint32_t bits = (word >> (16 * t + 8 * hh)) & 0xFFu;
+        if (__ballot(bits != 0u) == 0ull) continue;                // no sample of these 16 kept a row of these 32
+        const int kb = b0 + 16 * t + 8 * hh;
+        float x[8];
+#pragma unroll
+        for (int j = 0; j < 8; ++j) x[j] = kb + j < A.B ? col[(size_t)(kb + j) * LD] : 0.f;
+        hot_u32x4 a, bh, bm, bl;
+#pragma unroll
+        for (int i = 0; i < 4; ++i) {
+          a[i] = ((bits >> (2 * i)) & 1u) * 0x3F80u | ((bits >> (2 * i + 1)) & 1u) * 0x3F800000u;      // bf16 1.0 or 0
+          uint32_t hv[2], mv[2], lv[2];
+#pragma unroll
+          for (int e = 0; e < 2; ++e) {                            // v = hi + mid + lo exactly (truncations; the rests are exact)
+            const float v = x[2 * i + e];
+            hv[e] = __float_as_uint(v) & 0xFFFF0000u;
+            const float r1 = v - __uint_as_float(hv[e]);
+            mv[e] = __float_as_uint(r1) & 0xFFFF0000u;
+            lv[e] = __float_as_uint(r1 - __uint_as_float(mv[e])) & 0xFFFF0000u;
+          }
+          bh[i] = (hv[0] >> 16) | hv[1];
+          bm[i] = (mv[0] >> 16) | mv[1];
+          bl[i] = (lv[0] >> 16) | lv[1];
+        }
+        const hot_bf16x8 av = __builtin_bit_cast(hot_bf16x8, a);
+        acc = __builtin_amdgcn_mfma_f32_32x32x16_bf16(av, __builtin_bit_cast(hot_bf16x8, bh), acc, 0, 0, 0);
+        acc = __builtin_amdgcn_mfma_f32_32x32x16_bf16(av, __builtin_bit_cast(hot_bf16x8, bm), acc, 0, 0, 0);
+        acc = __builtin_amdgcn_mfma_f32_32x32x16_bf16(av, __builtin_bit_cast(hot_bf16x8, bl), acc, 0, 0, 0);
+      }
+    }
+    // D: column r, row (i & 3) + 8 (i >> 2) + 4 hh of register i
+    float *const out = A.part + ((size_t)s * A.H + hb * 32) * LD + ct * 32 + r;
+#pragma unroll
+    for (int i = 0; i < 16; ++i) out[(size_t)((i & 3) + 8 * (i >> 2) + 4 * hh) * LD] = acc[i];
+    const uint32_t rows_seen = (uint32_t)__ballot(seen != 0u);    // (lanes r and r + 32 read the same row)
+    if (ct == 0 && lane == 0) A.any[(size_t)s * hbs + hb] = rows_seen;
+  }
+};
+
+// one workgroup of kFixBlock threads per hot row: NQ = kFixBlock / LD groups each sum a run of consecutive slices in slice order, the
+// runs are added in group order (a fixed order: bit-reproducible), then the row's Adagrad update
+template <int LD, class Policy>
+struct HotFinishExtra {
+  HotArgs A;
+  Policy pol;
+  __device__ __forceinline__ void operator()(float *lds) const {
+    constexpr int NT = kFixBlock, NQ = NT / LD;
+    static_assert(NQ >= 1 && NT % LD == 0, "a row per workgroup");
+    const int h = (int)blockIdx.x - A.first;
+    if (h >= A.H) return;
+    const uint32_t bit = 1u << (h & 31);
+    bool touched = false;
+    for (int s = (int)threadIdx.x; s < A.S; s += NT) touched |= (A.any[(size_t)s * (A.H / 32) + (h >> 5)] & bit) != 0u;
+    if (!__syncthreads_or(touched)) return;                        // no sample kept this row: it stays bit-equal
+    const int c = (int)threadIdx.x % LD, q = (int)threadIdx.x / LD;
+    const int per = (A.S + NQ - 1) / NQ, s0 = q * per, s1 = min(A.S, s0 + per);
+    float sum = 0.f;
+#pragma unroll 8
+    for (int s = s0; s < s1; ++s) sum += A.part[((size_t)s * A.H + h) * LD + c];
+    lds[q * LD + c] = sum;
+    __syncthreads();
+    if (q == 0) {
+      float t = lds[c];
+#pragma unroll
+      for (int k = 1; k < NQ; ++k) t += lds[k * LD + c];
+      const StreamArrays SA = pol.stream_arrays();
+      const size_t off = (size_t)A.item[h] * LD + c;
+      float pv = SA.table[0][off], av = SA.slot[0][off];
+      pol.stream_update(fmaf(pol.stream_decay(), pv, A.scale * t), pv, av);
+      SA.table[0][off] = pv;
+      SA.slot[0][off] = av;
+    }
+  }
+};
+
+// two kinds of extra workgroups in one launch: [.., n1) the first, the rest the second
+template <class E1, class E2>
+struct ExtraPair {
+  E1 e1;
+  int n1;
+  E2 e2;
+  __device__ __forceinline__ void operator()(float *lds) const {
+    if ((int)blockIdx.x < n1) e1(lds);
+    else e2(lds);
+  }
+};
+
+// ------------------------------------------------------------------------------------------------
 // scratch layouts (shared by the sizing entry point and the step functions)
 // ------------------------------------------------------------------------------------------------
 constexpr int kSmallBatch = 1024;    // at or below: one workgroup per batch row in the hidden-layer gather
@@ -1158,6 +1302,33 @@ static SparseBufs sparse_layout(Carver &cv, const DrxCdaeParams &P, int B, int n
   }
   S.bpart = cv.take<float>((size_t)S.n_bpart * (P.ld + 1));     // partial rows + per-block loss partials
   return S;
+}
+
+// Which prepared buffers carry a hot head, and of how many rows: the preparation's record, kept on the HOST — a step entry is queued
+// while the preparation may still be running on another stream, and reading a word of the device buffer would wait for that stream
+// (the pipeline's run-ahead would be gone).  Keyed by the buffer's address: every preparation into an address rewrites its entry (a plain
+// one drops it), drx_cdae_prep_forget drops it when the caller releases the buffer.  A step given another H than its list's is refused.
+static std::mutex g_hot_mu;
+static std::unordered_map<const void *, int> g_hot_of;
+static void hot_record(const void *prepared, int H) {
+  std::lock_guard<std::mutex> lk(g_hot_mu);
+  if (H > 0) g_hot_of[prepared] = H;
+  else g_hot_of.erase(prepared);
+}
+static int hot_recorded(const void *prepared) {
+  std::lock_guard<std::mutex> lk(g_hot_mu);
+  const auto it = g_hot_of.find(prepared);
+  return it == g_hot_of.end() ? 0 : it->second;
+}
+
+// the hot head's partials and row flags (behind the step's other buffers: a step without a head keeps its layout)
+struct HotBufs { float *part; uint32_t *any; };
+static HotBufs hot_layout(Carver &cv, const DrxCdaeParams &P, int B, int H) {
+  HotBufs HB{nullptr, nullptr};
+  if (H <= 0) return HB;
+  HB.part = cv.take<float>((size_t)hot_slices(B) * H * P.ld);
+  HB.any = cv.take<uint32_t>((size_t)hot_slices(B) * (H / 32));
+  return HB;
 }
 
 static int check_params(const DrxCdaeParams *p) {
@@ -1662,7 +1833,7 @@ int drx_cdae_fit_dense(const DrxCdaeParams *p, const DrxOptim *opt, const DrxHis
 static int step_sparse_impl(const DrxCdaeParams *p, const DrxOptim *opt, const DrxHistory *hist, const DrxBatch *bt,
                             int32_t loss_kind, const void *prepared, size_t prepared_bytes, void *scratch, size_t scratch_bytes,
                             float *loss_out, void *const *events, void *stream, const float *ks_h = nullptr,
-                            const float *ks_dot = nullptr) {
+                            const float *ks_dot = nullptr, const DrxHotHead *hot = nullptr) {
   int rc = check_params(p);
   if (rc) return rc;
   rc = check_batch(hist, bt);
@@ -1672,15 +1843,18 @@ static int step_sparse_impl(const DrxCdaeParams *p, const DrxOptim *opt, const D
     if (!opt->s1[i] || (opt->kind == DRX_OPT_ADAM && !opt->s2[i])) return DRX_EINVAL;
   if ((uint64_t)2 * p->n_items + p->n_users + 1 >= 0xFFFFFFFFull) return DRX_EINVAL;
   hipStream_t st = (hipStream_t)stream;
+  const int H = hot ? hot->H : 0;
+  if (prepared && hot_recorded(prepared) != H) return DRX_EINVAL;     // (a list prepared with another head, or none)
   Carver cv(scratch, scratch_bytes);
   SparseBufs S = sparse_layout(cv, *p, bt->B, bt->n_touch_slots);
+  const HotBufs HB = hot_layout(cv, *p, bt->B, H);
   PrepBufs R{};
   if (prepared) {
     Carver cp(const_cast<void *>(prepared), prepared_bytes);
-    R = prep_layout(cp, *p, bt->B, bt->n_touch_slots);
+    R = prep_layout(cp, *p, bt->B, bt->n_touch_slots, H);
     if (!cp.ok()) return DRX_ESCRATCH;
   } else {
-    R = prep_layout(cv, *p, bt->B, bt->n_touch_slots);
+    R = prep_layout(cv, *p, bt->B, bt->n_touch_slots, H);
   }
   if (!cv.ok()) return DRX_ESCRATCH;
   const float scale = 1.0f / (1.0f - bt->q);
@@ -1710,6 +1884,15 @@ static int step_sparse_impl(const DrxCdaeParams *p, const DrxOptim *opt, const D
   S.witem = share ? R.witem : nullptr;
   S.worder = share ? R.worder : nullptr;
   S.n_items = share ? R.n_du : nullptr;
+  if (H > 0) {
+    // the head exists on the streamed reduction's path alone (the single-GPU Adagrad step over short segments, ld = 64 / 128 / 256)
+    const Geom gm = pick_geom(p->ld);
+    const bool streamed_path = kStreamDepth > 0 && gm.J == 1 && gm.G >= 16 && gm.G <= kHotMaxG && p->ld == 4 * gm.G && !long_segments && !share &&
+                               opt->kind == DRX_OPT_ADAGRAD && bt->B < (1 << kStreamIndexBits) &&
+                               p->n_items < (1 << kStreamIndexBits) && p->n_users < (1 << kStreamIndexBits);
+    if (!streamed_path || ks_h) return DRX_EINVAL;
+  }
+  HotArgs HA{S.dz1, R.hmask, HB.part, HB.any, hot ? hot->item : nullptr, scale, bt->B, H, R.Bw, hot_slices(bt->B), 0};
   const long long mean_hist = bt->n_touch_slots / (long long)bt->B;
   const bool per_wg = mean_hist > wg_long || (bt->B <= 8192 && mean_hist > 16);
   BiasArgs BA{S.dz1, S.bpart, S.lossb, loss_out, bt->B, n_bpart, rows_per_block};
@@ -1729,9 +1912,26 @@ static int step_sparse_impl(const DrxCdaeParams *p, const DrxOptim *opt, const D
       if (!long_segments && p->ld == 4 * G && bt->B < (1 << kStreamIndexBits) && p->n_items < (1 << kStreamIndexBits) &&           \
           p->n_users < (1 << kStreamIndexBits)) { \
         BiasPartialExtra<G, J, cpb * 64> bpxs{p->ld, BA};                                                              \
-        const dim3 sgrid(n_bpart + (S.n_chunks + cpb - 1) / cpb);                                        \
-        hipLaunchKernelGGL((k_seg_reduce_stream<4 * G, kStreamDepth, POLT, BiasPartialExtra<G, J, cpb * 64>>), sgrid, dim3(cpb * 64), \
-                           seg_stream_lds_bytes(p->ld, kStreamDepth), st, SB, PB, R.plan, polk, n_bpart, bpxs);        \
+        bool hot_launched = false;                                                                                     \
+        if constexpr (G <= kHotMaxG) {                                                                                 \
+        if (H > 0) {                                                                                                   \
+          /* + the hot head's partials: one wave per (slice, 32 hot rows, 32 columns) */                               \
+          HotArgs hpa = HA;                                                                                            \
+          hpa.first = n_bpart;                                                                                         \
+          const int n_hot = (HA.S * (H / 32) * G / 8 + cpb - 1) / cpb;                                                 \
+          using PX = ExtraPair<BiasPartialExtra<G, J, cpb * 64>, HotPartialExtra<4 * G, cpb * 64>>;                   \
+          const dim3 sgrid(n_bpart + n_hot + (S.n_chunks + cpb - 1) / cpb);                                            \
+          hipLaunchKernelGGL((k_seg_reduce_stream<4 * G, kStreamDepth, POLT, PX>), sgrid, dim3(cpb * 64),              \
+                             seg_stream_lds_bytes(p->ld, kStreamDepth), st, SB, PB, R.plan, polk, n_bpart + n_hot,      \
+                             PX{bpxs, n_bpart, HotPartialExtra<4 * G, cpb * 64>{hpa}});                                \
+          hot_launched = true;                                                                                         \
+        }                                                                                                              \
+        }                                                                                                              \
+        if (!hot_launched) {                                                                                           \
+          const dim3 sgrid(n_bpart + (S.n_chunks + cpb - 1) / cpb);                                                    \
+          hipLaunchKernelGGL((k_seg_reduce_stream<4 * G, kStreamDepth, POLT, BiasPartialExtra<G, J, cpb * 64>>), sgrid, dim3(cpb * 64), \
+                             seg_stream_lds_bytes(p->ld, kStreamDepth), st, SB, PB, R.plan, polk, n_bpart, bpxs);      \
+        }                                                                                                              \
         streamed = true;                                                                                               \
       }                                                                                                                \
     }                                                                                                                  \
@@ -1743,11 +1943,26 @@ static int step_sparse_impl(const DrxCdaeParams *p, const DrxOptim *opt, const D
       hipLaunchKernelGGL((k_seg_reduce_planned<G, J, POLT, false, BiasPartialExtra<G, J>>), rgrid, dim3(kSegBlock), lds_r, st, SB, PB,    \
                          R.plan, polk, n_bpart, bpx);                                                                  \
     EV(3);                                                                                                             \
-    if (lds_b > 48 * 1024)                                                                                             \
-      DRX_HIP(hipFuncSetAttribute((const void *)k_span_planned<G, J, POLT, BiasFinalExtra<G, J>>,                     \
-                                  hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_b));                            \
-    hipLaunchKernelGGL((k_span_planned<G, J, POLT, BiasFinalExtra<G, J>>), dim3(kLongBlocks + kShortBlocks + 1),                  \
-                       dim3(kFixBlock), lds_b, st, SB, PB, R.plan, polk, kLongBlocks, kShortBlocks, bfx);                 \
+    bool finished_hot = false;                                                                                         \
+    if constexpr (kStreamDepth > 0 && J == 1 && G >= 16 && G <= kHotMaxG && std::is_same<POLT, DirectPolicyAdagrad>::value) { \
+      if (H > 0) {                                                                                                     \
+        /* + the hot head's finish: one workgroup per hot row behind the hidden bias's */                              \
+        HotArgs hfa = HA;                                                                                              \
+        hfa.first = kLongBlocks + kShortBlocks + 1;                                                                    \
+        using FX = ExtraPair<BiasFinalExtra<G, J>, HotFinishExtra<4 * G, POLT>>;                                      \
+        hipLaunchKernelGGL((k_span_planned<G, J, POLT, FX>), dim3(kLongBlocks + kShortBlocks + 1 + H), dim3(kFixBlock), lds_b, st, \
+                           SB, PB, R.plan, polk, kLongBlocks, kShortBlocks,                                            \
+                           FX{bfx, kLongBlocks + kShortBlocks + 1, HotFinishExtra<4 * G, POLT>{hfa, polk}});          \
+        finished_hot = true;                                                                                           \
+      }                                                                                                                \
+    }                                                                                                                  \
+    if (!finished_hot) {                                                                                               \
+      if (lds_b > 48 * 1024)                                                                                           \
+        DRX_HIP(hipFuncSetAttribute((const void *)k_span_planned<G, J, POLT, BiasFinalExtra<G, J>>,                   \
+                                    hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_b));                          \
+      hipLaunchKernelGGL((k_span_planned<G, J, POLT, BiasFinalExtra<G, J>>), dim3(kLongBlocks + kShortBlocks + 1),                \
+                         dim3(kFixBlock), lds_b, st, SB, PB, R.plan, polk, kLongBlocks, kShortBlocks, bfx);               \
+    }                                                                                                                  \
     EV(4);                                                                                                             \
     EV(5);                                                                                                             \
   }
@@ -1782,7 +1997,7 @@ static int step_sparse_impl(const DrxCdaeParams *p, const DrxOptim *opt, const D
                          scale, qthr, loss_kind, S);                                                                   \
     EV(1);                                                                                                             \
     if (!prepared) {                                                                                                   \
-      rc = prepare_impl(p, hist, bt, R, st);                                                                           \
+      rc = prepare_impl(p, hist, bt, R, st, false, TouchPresence{nullptr, WireGeo{1, 0, 1}}, hot ? hot->slot : nullptr); \
       if (rc) return rc;                                                                                               \
     }                                                                                                                  \
     EV(2);                                                                                                             \
@@ -1813,6 +2028,7 @@ int drx_cdae_sparse_prepare(const DrxCdaeParams *p, const DrxHistory *hist, cons
   Carver cp(prepared, prepared_bytes);
   PrepBufs R = prep_layout(cp, *p, bt->B, bt->n_touch_slots);
   if (!cp.ok()) return DRX_ESCRATCH;
+  hot_record(prepared, 0);                                           // (a list without a head from now on)
   rc = prepare_impl(p, hist, bt, R, (hipStream_t)stream, true);      // touches, sort, span plan + sole-toucher marks (+ launch order)
   if (rc) return rc;
   if (p->ld <= 16) order_by_degree(bt, R, (hipStream_t)stream, true);
@@ -1883,6 +2099,7 @@ int drx_cdae_sparse_prepare_part(const DrxCdaeParams *p, const DrxHistory *hist,
 
 int drx_cdae_sparse_prepare_assemble(const DrxCdaeParams *p, const DrxBatch *bt, const void *all_parts, int32_t parts, void *prepared,
                                      size_t prepared_bytes, int32_t *overflow_out, void *stream) {
+  if (prepared) hot_record(prepared, 0);
   int rc = check_params(p);
   if (rc) return rc;
   if (!bt || bt->B < 1 || !all_parts || !prepared || !overflow_out || parts < 1 || parts > DRX_MAX_WORLD) return DRX_EINVAL;
@@ -1967,6 +2184,62 @@ int drx_cdae_step_sparse_timed(const DrxCdaeParams *p, const DrxOptim *opt, cons
                                void *stream) {
   if (!events) return DRX_EINVAL;
   return step_sparse_impl(p, opt, hist, bt, loss_kind, nullptr, 0, scratch, scratch_bytes, loss_out, events, stream);
+}
+
+// ---- the hot head (include/drx.h DrxHotHead) ----------------------------------------------------------------------------------
+static int hot_rows(const DrxCdaeParams *p, int32_t H) {
+  if (!p || H < 0 || H > DRX_MAX_HOT || H % 32 || H > p->n_items) return -1;
+  return H;
+}
+
+static bool hot_ok(const DrxCdaeParams *p, const DrxHotHead *hot) {
+  return hot && hot_rows(p, hot->H) >= 0 && (hot->H == 0 || (hot->slot && hot->item && p->ld <= 4 * kHotMaxG));
+}
+
+size_t drx_cdae_prep_bytes_hot(const DrxCdaeParams *p, int32_t B, int32_t n_touch_slots, int32_t H) {
+  if (!p || B < 1 || n_touch_slots < 0 || hot_rows(p, H) < 0) return 0;
+  Carver c(nullptr, 0);
+  (void)prep_layout(c, *p, B, n_touch_slots, H);
+  return align_up(c.off, 256) + 256;
+}
+
+size_t drx_cdae_scratch_bytes_hot(const DrxCdaeParams *p, int32_t B, int32_t n_touch_slots, int32_t H) {
+  if (!p || B < 1 || n_touch_slots < 0 || hot_rows(p, H) < 0) return 0;
+  Carver c(nullptr, 0);
+  (void)sparse_layout(c, *p, B, n_touch_slots);
+  (void)hot_layout(c, *p, B, H);
+  (void)prep_layout(c, *p, B, n_touch_slots, H);
+  return align_up(c.off, 256) + 256;
+}
+
+int drx_cdae_sparse_prepare_hot(const DrxCdaeParams *p, const DrxHistory *hist, const DrxBatch *bt, const DrxHotHead *hot,
+                                void *prepared, size_t prepared_bytes, void *stream) {
+  int rc = check_params(p);
+  if (rc) return rc;
+  rc = check_batch(hist, bt);
+  if (rc || !prepared || !bt->iid || !bt->keep_off || !hot_ok(p, hot)) return DRX_EINVAL;
+  Carver cp(prepared, prepared_bytes);
+  PrepBufs R = prep_layout(cp, *p, bt->B, bt->n_touch_slots, hot->H);
+  if (!cp.ok()) return DRX_ESCRATCH;
+  hot_record(prepared, 0);
+  rc = prepare_impl(p, hist, bt, R, (hipStream_t)stream, true, TouchPresence{nullptr, WireGeo{1, 0, 1}}, hot->slot);
+  if (rc) return rc;
+  hot_record(prepared, hot->H);
+  if (p->ld <= 16) order_by_degree(bt, R, (hipStream_t)stream, true);
+  DRX_LAUNCH_CHECK();
+  return DRX_OK;
+}
+
+int drx_cdae_step_sparse_hot(const DrxCdaeParams *p, const DrxOptim *opt, const DrxHistory *hist, const DrxBatch *bt,
+                             const DrxHotHead *hot, int32_t loss_kind, const void *prepared, size_t prepared_bytes, void *scratch,
+                             size_t scratch_bytes, float *loss_out, void *const *events, void *stream) {
+  if (!hot_ok(p, hot)) return DRX_EINVAL;
+  return step_sparse_impl(p, opt, hist, bt, loss_kind, prepared, prepared_bytes, scratch, scratch_bytes, loss_out, events, stream,
+                          nullptr, nullptr, hot);
+}
+
+void drx_cdae_prep_forget(const void *prepared) {
+  if (prepared) hot_record(prepared, 0);
 }
 
 }  // extern "C"

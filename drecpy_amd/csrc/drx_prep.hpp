@@ -43,10 +43,20 @@ struct TouchPresence {
   __device__ __forceinline__ uint32_t wire(int item, int is_out) const { return G.wire(item, is_out); }
 };
 
+// The hot head (include/drx.h DrxHotHead): a kept entry of a hot item leaves the list and sets its sample's bit in the transposed mask
+// M[slot][b / 32].  A workgroup's 16 samples are exactly one 16-bit half of a mask word: it gathers its halves of all H rows in LDS
+// (the ORs commute) and STORES them, zeros included — no atomics to global memory (one per hot touch made this kernel 47 -> 81 us and
+// slowed the forward kernel beside it by 18 us), no clearing beforehand; the last workgroup also zeroes the half behind the batch.
+struct HotMark {
+  const int16_t *slot;          // [n_items] or nullptr: no head
+  uint32_t *mask;               // [H, Bw]
+  int H, Bw;
+};
+
 static __global__ __launch_bounds__(kBlock) void k_sparse_touches(int n_items, DrxHistory H, DrxBatch bt, uint32_t qthr, uint32_t *keys,
                                                            uint32_t *vals, int T, uint8_t *solo, uint32_t *zero_a,
                                                            int n_zero_a, uint32_t *zero_b, int n_zero_b, uint32_t *zero_c, int n_zero_c,
-                                                           TouchPresence pres) {
+                                                           TouchPresence pres, HotMark hot) {
   constexpr int G = 16;
   const int lane = threadIdx.x % G;
   const int b = blockIdx.x * (kBlock / G) + threadIdx.x / G;
@@ -54,7 +64,12 @@ static __global__ __launch_bounds__(kBlock) void k_sparse_touches(int n_items, D
   for (int w = blockIdx.x * kBlock + threadIdx.x; w < n_zero_a; w += gridDim.x * kBlock) zero_a[w] = 0u;
   for (int w = blockIdx.x * kBlock + threadIdx.x; w < n_zero_b; w += gridDim.x * kBlock) zero_b[w] = 0u;
   for (int w = blockIdx.x * kBlock + threadIdx.x; w < n_zero_c; w += gridDim.x * kBlock) zero_c[w] = 0u;      // (the sort's counters and tile words)
-  if (b >= bt.B) return;
+  __shared__ uint32_t hm[DRX_MAX_HOT];
+  if (hot.slot) {                                                  // (workgroup-uniform)
+    for (int i = threadIdx.x; i < hot.H; i += kBlock) hm[i] = 0u;
+    __syncthreads();
+  }
+  if (b < bt.B) {
   if (solo && lane == 0) { solo[b] = 0; solo[bt.B + b] = 0; }
   if (b == bt.B - 1)
     for (int j = bt.keep_off[bt.B] + 2 * bt.B + lane; j < T; j += G) { keys[j] = DRX_KEY_NONE; vals[j] = 0; }
@@ -66,8 +81,10 @@ static __global__ __launch_bounds__(kBlock) void k_sparse_touches(int n_items, D
     const uint32_t jj = (uint32_t)(j - s);
     const bool kf = kp ? (kp[jj] != 0) : (hash_u32(bt.mask_seed, (uint32_t)b, jj) >= qthr);
     const int item = H.indices[j];
-    keys[base + jj] = kf ? (uint32_t)item : DRX_KEY_NONE;
+    const int hs = hot.slot && kf ? (int)hot.slot[item] : -1;
+    keys[base + jj] = kf && hs < 0 ? (uint32_t)item : DRX_KEY_NONE;
     vals[base + jj] = (uint32_t)b;
+    if (hs >= 0) atomicOr(&hm[hs], 1u << (b & 15));
     if (pres.present && kf) pres.present[pres.wire(item, 0)] = 1;
   }
   if (lane == 0) {
@@ -75,6 +92,17 @@ static __global__ __launch_bounds__(kBlock) void k_sparse_touches(int n_items, D
     keys[base + deg] = (uint32_t)(n_items + bt.iid[b]);       vals[base + deg] = (uint32_t)b;
     if (pres.present) pres.present[pres.wire(bt.iid[b], 1)] = 1;
     keys[base + deg + 1] = (uint32_t)(2 * n_items) + (uint32_t)u;       vals[base + deg + 1] = (uint32_t)b;
+  }
+  }
+  if (hot.slot) {
+    __syncthreads();
+    uint16_t *const m16 = reinterpret_cast<uint16_t *>(hot.mask);      // half-word blockIdx.x of row i (little-endian: samples 16 blockIdx.x ..)
+    const size_t row = 2 * (size_t)hot.Bw;
+    const bool tail = blockIdx.x + 1 == gridDim.x && blockIdx.x + 1 < row;
+    for (int i = threadIdx.x; i < hot.H; i += kBlock) {
+      m16[(size_t)i * row + blockIdx.x] = (uint16_t)hm[i];
+      if (tail) m16[(size_t)i * row + blockIdx.x + 1] = 0;
+    }
   }
 }
 
@@ -277,12 +305,15 @@ struct PrepBufs {
   int n_chunks;
   size_t result_bytes;
   int T, bits;
+  // the hot head (behind everything else: a list without one keeps its layout): H rows of Bw mask words
+  uint32_t *hmask;
+  int H, Bw;
 };
 
 // more than 8 touches per table row on average: rows collect long runs of touches (MovieLens shapes)
 static inline bool long_segments(int T, const DrxCdaeParams &P) { return (int64_t)T > 8 * ((int64_t)2 * P.n_items + P.n_users); }
 
-static PrepBufs prep_layout(Carver &cv, const DrxCdaeParams &P, int B, int n_touch_slots) {
+static PrepBufs prep_layout(Carver &cv, const DrxCdaeParams &P, int B, int n_touch_slots, int H = 0) {
   PrepBufs R{};
   R.T = n_touch_slots + 2 * B;
   R.bits = bits_for((uint64_t)2 * P.n_items + P.n_users + 1);
@@ -320,6 +351,9 @@ static PrepBufs prep_layout(Carver &cv, const DrxCdaeParams &P, int B, int n_tou
   R.sort_bytes = sort_pairs_temp_bytes(R.T, R.bits);
   R.sort_temp = cv.take<char>(R.sort_bytes);
   R.order_work = cv.take<unsigned int>(512);
+  R.H = H;
+  R.Bw = (B + 31) / 32;
+  R.hmask = H > 0 ? cv.take<uint32_t>((size_t)H * R.Bw) : nullptr;
   return R;
 }
 
@@ -655,8 +689,11 @@ static int prepare_transposed(const DrxCdaeParams *p, const DrxHistory *hist, co
 }
 
 static int prepare_impl(const DrxCdaeParams *p, const DrxHistory *hist, const DrxBatch *bt, const PrepBufs &R, hipStream_t st,
-                        bool with_marks = false, TouchPresence pres = TouchPresence{nullptr, WireGeo{1, 0, 1}}) {
+                        bool with_marks = false, TouchPresence pres = TouchPresence{nullptr, WireGeo{1, 0, 1}},
+                        const int16_t *hot_slot = nullptr) {
   const int gpb = kBlock / 16;
+  // (the head exists on lists of short segments only: the transposed preparation below never builds one)
+  if (R.H > 0 && (!hot_slot || pres.present || long_segments(R.T, *p))) return DRX_EINVAL;
   if (hist->t_rank && hist->t_users && hist->t_pos && hist->t_items && !pres.present && long_segments(R.T, *p)) {
     const int32_t *row_end = nullptr;
     const int rc = prepare_transposed(p, hist, bt, R, st, with_marks, &row_end);
@@ -683,7 +720,7 @@ static int prepare_impl(const DrxCdaeParams *p, const DrxHistory *hist, const Dr
   sort_pairs_zero_region(R.sort_temp, (size_t)R.T, R.bits, &sort_zero, &sort_zero_words);
   hipLaunchKernelGGL(k_sparse_touches, dim3((bt->B + gpb - 1) / gpb), dim3(kBlock), 0, st, p->n_items, *hist, *bt,
                      q_threshold(bt->q), R.keys, R.vals, R.T, R.solo_v, R.plan.cnt, plan_zero_words(R), R.order_work, 512,
-                     sort_zero, (int)sort_zero_words, pres);
+                     sort_zero, (int)sort_zero_words, pres, HotMark{R.H > 0 ? hot_slot : nullptr, R.hmask, R.H, R.Bw});
   // the launch order (see k_degree_counts): its counts ride in the sort's first launch, its scatter in the plan + marks launch below
   const bool fused_order = with_marks && p->ld > 16;
   const SortRider rider{fused_order ? bt->keep_off : nullptr, bt->B, R.order_work};

@@ -9,6 +9,7 @@ import math
 
 import os
 import time
+import weakref
 
 import numpy as np
 import torch
@@ -25,7 +26,20 @@ def _round_up(x, m):
     return (x + m - 1) // m * m
 
 
+def _forget_prepared(addr):
+    try:
+        lib().drx_cdae_prep_forget(addr)
+    except Exception:           # (interpreter shutdown)
+        pass
+
+
 class CdaeEngine:
+    # the hot head of the sampled Adagrad step (include/drx.h DrxHotHead): the HOT_ROWS items of highest training-set degree, on
+    # catalogues of at least HOT_MIN_ITEMS_PER_ROW * HOT_ROWS items and batches of at least HOT_MIN_BATCH triples, rows of 64 / 128
+    # floats.  The environment variable DRX_HOT_ROWS (0 or a multiple of 32 up to 1024) overrides HOT_ROWS.
+    HOT_ROWS, HOT_MIN_ITEMS_PER_ROW, HOT_MIN_BATCH = 64, 16, 8192
+    HOT_LDS = (64, 128)
+
     def __init__(self, n_users, n_items, k, device='cuda:0'):
         if not torch.cuda.is_available():
             raise _lib.DrxError('drecpy_amd needs a ROCm GPU (MI355X); there is no CPU fallback.')
@@ -47,6 +61,8 @@ class CdaeEngine:
         self._scratch = None
         self._dense_scratch, self._dense_scratch_B, self._dense_clean = None, None, False
         self._loss = torch.zeros(2, **z)
+        self.hot_rows, self.hot_min_batch = 0, self.HOT_MIN_BATCH
+        self._hot_slot = self._hot_item = None
 
     # ---- parameters -------------------------------------------------------------------------
     def tables(self):
@@ -159,6 +175,56 @@ class CdaeEngine:
             self._hist_t = (rank, rows[order].to(torch.int32).contiguous(), pos[order].to(torch.int32).contiguous(),
                             idx[order].to(torch.int32).contiguous())
             self._hist = History(ptr(self.hist_indptr), ptr(self.hist_indices), ptr(rank), nnz, *[ptr(t) for t in self._hist_t[1:]])
+        H = self.default_hot_rows()
+        self._set_hot(H if 0 < H <= self.n_items // self.HOT_MIN_ITEMS_PER_ROW else 0)
+
+    @classmethod
+    def default_hot_rows(cls):
+        v = os.environ.get('DRX_HOT_ROWS')
+        if v is None:
+            return cls.HOT_ROWS
+        H = int(v)
+        if H < 0 or H % 32 or H > 1024:
+            raise _lib.DrxError(f'DRX_HOT_ROWS={v}: the hot head has 0 rows or a multiple of 32 up to 1024')
+        return H
+
+    @staticmethod
+    def hot_set(indices, n_items, H):
+        """The H items of highest degree in the history entries `indices` (ties: the lower item id first), as an int32 tensor."""
+        deg = torch.bincount(indices.long(), minlength=n_items)[:n_items]
+        order = torch.sort(deg, descending=True, stable=True).indices          # (stable: equal degrees keep ascending ids)
+        return order[:H].to(torch.int32).contiguous()
+
+    def _set_hot(self, H):
+        if H < 0 or H % 32 or H > 1024 or H > self.n_items:
+            raise _lib.DrxError(f'a hot head of {H} rows: 0 or a multiple of 32 up to 1024 and the number of items')
+        self.hot_rows = int(H)
+        if self.hot_rows <= 0:
+            self._hot_slot = self._hot_item = None
+            return
+        nnz = int(self.hist_indptr[-1].item())
+        self._hot_item = self.hot_set(self.hist_indices[:nnz], self.n_items, self.hot_rows)
+        self._hot_slot = torch.full((self.n_items,), -1, dtype=torch.int16, device=self.device)
+        self._hot_slot[self._hot_item.long()] = torch.arange(self.hot_rows, dtype=torch.int16, device=self.device)
+
+    def set_hot_rows(self, H, min_batch=None):
+        """Sets the hot head's size (a multiple of 32; 0: none) — the default is set by set_history — and, optionally, the least batch
+        it is used at."""
+        self._set_hot(H)
+        if min_batch is not None:
+            self.hot_min_batch = int(min_batch)
+
+    def _hot_for(self, bt):
+        """H of the hot head a batch is prepared / trained with by the single-GPU sampled step (0: none)."""
+        if self.hot_rows <= 0 or bt.B < self.hot_min_batch or self.ld not in self.HOT_LDS:
+            return 0
+        if getattr(self, 'opt_kind', None) != _lib.OPT_ADAGRAD:
+            return 0
+        T = bt.n_touch_slots + 2 * bt.B                 # lists of short segments only (drx_prep.hpp long_segments)
+        return self.hot_rows if T <= 8 * (2 * self.n_items + self.n_users) else 0
+
+    def _hot_head(self, H):
+        return _lib.HotHead(H, ptr(self._hot_slot) if H else None, ptr(self._hot_item) if H else None)
 
     # ---- optimizer --------------------------------------------------------------------------
     def init_optimizer(self, kind, lr, reg_rate, beta1=ADAM_B1, beta2=ADAM_B2, eps=None, initial_accumulator=ADAGRAD_INIT):
@@ -345,10 +411,11 @@ class CdaeEngine:
                    int(n_touch_slots), self._batch_flags(n_touch_slots))
         return bt, (uid, iid, y, keep_off, keep)
 
-    def _ensure_scratch(self, B, n_touch_slots, dense=False):
+    def _ensure_scratch(self, B, n_touch_slots, dense=False, hot=0):
         if dense:
             return self._ensure_dense_scratch(B)
-        need = lib().drx_cdae_scratch_bytes(C.byref(self._params), B, n_touch_slots, 0)
+        need = lib().drx_cdae_scratch_bytes_hot(C.byref(self._params), B, n_touch_slots, hot) if hot else \
+            lib().drx_cdae_scratch_bytes(C.byref(self._params), B, n_touch_slots, 0)
         if self._scratch is None or self._scratch.numel() < need:
             self._scratch = None
             self._scratch = torch.empty(int(need * 1.1) + 1024, dtype=torch.uint8, device=self.device)
@@ -434,9 +501,10 @@ class CdaeEngine:
         t.record_stream(torch.cuda.default_stream(self.device))
         t.record_stream(torch.cuda.current_stream(self.device))
 
-    def prep_buffer(self, bt, out=None):
-        """A buffer large enough for the prepared touch list of `bt` (`out` itself when it is)."""
-        need = lib().drx_cdae_prep_bytes(C.byref(self._params), bt.B, bt.n_touch_slots)
+    def prep_buffer(self, bt, out=None, hot=0):
+        """A buffer large enough for the prepared touch list of `bt` (`out` itself when it is); hot: with a head of that many rows."""
+        need = lib().drx_cdae_prep_bytes_hot(C.byref(self._params), bt.B, bt.n_touch_slots, hot) if hot else \
+            lib().drx_cdae_prep_bytes(C.byref(self._params), bt.B, bt.n_touch_slots)
         if out is None or out.numel() < need:
             out = None
             out = torch.empty(int(need * 1.03) + 4096, dtype=torch.uint8, device=self.device)
@@ -446,12 +514,24 @@ class CdaeEngine:
         """Leading bytes of a prepared buffer that a step reads (include/drx.h, drx_cdae_prep_result_bytes)."""
         return int(lib().drx_cdae_prep_result_bytes(C.byref(self._params), bt.B, bt.n_touch_slots))
 
-    def prepare_sparse(self, bt, out=None):
+    def prepare_sparse(self, bt, out=None, hot=False):
         """Builds and sorts the touch list of a batch (drx_cdae_sparse_prepare) on the CURRENT stream.  The list does not
-        depend on the parameters, so this may run on a side stream for batch t+1 while batch t trains."""
-        out = self.prep_buffer(bt, out)
-        check(lib().drx_cdae_sparse_prepare(C.byref(self._params), C.byref(self._hist), C.byref(bt), ptr(out), out.numel(),
-                                            stream_ptr(self.device)), 'drx_cdae_sparse_prepare')
+        depend on the parameters, so this may run on a side stream for batch t+1 while batch t trains.
+        hot=True: for this engine's own single-GPU step — with the hot head where it applies (_hot_for).  The buffer's H is recorded
+        (by the library; `_drx_hot` here) and step_sparse() trains it with that H: any other step refuses the list (DRX_EINVAL)."""
+        H = self._hot_for(bt) if hot else 0
+        out = self.prep_buffer(bt, out, H)
+        if H:
+            check(lib().drx_cdae_sparse_prepare_hot(C.byref(self._params), C.byref(self._hist), C.byref(bt), C.byref(self._hot_head(H)),
+                                                    ptr(out), out.numel(), stream_ptr(self.device)), 'drx_cdae_sparse_prepare_hot')
+        else:
+            check(lib().drx_cdae_sparse_prepare(C.byref(self._params), C.byref(self._hist), C.byref(bt), ptr(out), out.numel(),
+                                                stream_ptr(self.device)), 'drx_cdae_sparse_prepare')
+        out._drx_hot = H
+        if H and not getattr(out, '_drx_forget', None):
+            # the library records the buffer's head by its address (include/drx.h): dropped when the buffer is released, before the
+            # allocator can hand the address to another buffer
+            out._drx_forget = weakref.finalize(out, _forget_prepared, out.data_ptr())
         return out
 
     def prepare_part(self, bt, part, parts, slot=None):
@@ -503,17 +583,27 @@ class CdaeEngine:
                                                      stream_ptr(self.device)), 'drx_cdae_kshard_forward_prepared')
         return h, d
 
-    def step_sparse(self, step, bt, loss='bce', want_loss=False, events=None, prepared=None, kshard=None):
+    def step_sparse(self, step, bt, loss='bce', want_loss=False, events=None, prepared=None, kshard=None, hot=False):
         """One sampled-output step (sparse Adagrad / lazy Adam on touched rows).
         events: optional list of 6 recorded-once torch.cuda.Event(enable_timing=True); their raw hipEvent_t are
         re-recorded by the library around each phase (include/drx.h, drx_cdae_step_sparse_timed).
-        prepared: buffer returned by prepare_sparse() for this batch (else the touch list is built inline)."""
+        prepared: buffer returned by prepare_sparse() for this batch (else the touch list is built inline); it is trained with the hot
+        head it was prepared with.  hot=True (inline lists): with the hot head where it applies (_hot_for)."""
         a = self.adam_alpha(self.lr, step + 1, self.beta1, self.beta2)
         o = self._optim([a] * 5)
-        sc = self._ensure_scratch(bt.B, bt.n_touch_slots)
+        H = int(getattr(prepared, '_drx_hot', 0)) if prepared is not None else (self._hot_for(bt) if hot else 0)
+        sc = self._ensure_scratch(bt.B, bt.n_touch_slots, hot=H)
         lk = _lib.LOSS_BCE if loss == 'bce' else _lib.LOSS_MSE
         lo = ptr(self._loss) if want_loss else None
         arr = (C.c_void_p * len(events))(*[e.cuda_event for e in events]) if events is not None else None
+        if H:
+            if kshard is not None:
+                raise _lib.DrxError('the column-sharded step takes no hot head')
+            check(lib().drx_cdae_step_sparse_hot(C.byref(self._params), C.byref(o), C.byref(self._hist), C.byref(bt),
+                                                 C.byref(self._hot_head(H)), lk, ptr(prepared) if prepared is not None else None,
+                                                 prepared.numel() if prepared is not None else 0, ptr(sc), sc.numel(), lo, arr,
+                                                 stream_ptr(self.device)), 'drx_cdae_step_sparse_hot')
+            return self._loss if want_loss else None
         if kshard is not None:            # column-sharded step: (h, all-reduced dot products) replace the forward half
             h, dot_total = kshard
             check(lib().drx_cdae_kshard_step(C.byref(self._params), C.byref(o), C.byref(self._hist), C.byref(bt), lk, ptr(h),
@@ -885,8 +975,8 @@ class SampledPipeline:
         with _on_stream(self.sides[s % len(self.sides)], self.main):
             if self.prepare_fn is not None:
                 self.prep[k] = self.prepare_fn(s, bt, old)
-            else:
-                self.prep[k] = self.eng.prepare_sparse(bt, old)
+            else:            # (the hot head only for the engine's own single-GPU step: a step_fn of another layout takes none)
+                self.prep[k] = self.eng.prepare_sparse(bt, old, hot=self.step_fn is None)
         if old is not None and self.prep[k].data_ptr() != old.data_ptr():
             # the list grew into a new buffer.  The old one was allocated on the side stream, so the allocator would hand its memory to
             # the next side-stream allocation at once — but its last reader is a training step on the MAIN stream that, when the host

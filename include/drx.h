@@ -198,6 +198,33 @@ int drx_cdae_step_sparse_prepared(const DrxCdaeParams *p, const DrxOptim *opt, c
                                   int32_t loss_kind, const void *prepared, size_t prepared_bytes, void *scratch,
                                   size_t scratch_bytes, float *loss_out, void *const *events, void *stream);
 
+/* HOT HEAD of the single-GPU sampled Adagrad step (lists of short segments, ld = 64 / 128 / 256): the kept history entries of the H
+ * hottest items leave the touch list (DRX_KEY_NONE, like dropped ones) and set bit b of a transposed 0/1 mask M[h][b / 32] instead;
+ * their W rows' gradients are then (1/(1-q)) * M^T * dz1, computed on the matrix cores beside the segmented reduction.  slot[n_items]:
+ * the hot slot of an item (-1: cold); item[H]: the item of each slot (device arrays).  H = 0 is no head: the functions below are then
+ * the plain ones (drx_cdae_prep_bytes, drx_cdae_sparse_prepare, drx_cdae_step_sparse(_prepared)).  A step given H > 0 on any other path
+ * (Adam, row-wise Adagrad, long segments, ld = 256, the column-sharded step) returns DRX_EINVAL.  The prepared buffer carries the mask
+ * behind the plain layout.  The library records, by the buffer's address, the H every preparation into a buffer used (the plain ones: 0)
+ * — on the host, so that a step queued while its list is still being prepared need not wait for it — and every step on a prepared list
+ * (drx_cdae_step_sparse_prepared, drx_cdae_kshard_step, drx_cdae_step_sparse_hot) returns DRX_EINVAL unless it is given that H.  A copy
+ * of a list into another buffer carries no record (it reads as H = 0).  drx_cdae_prep_forget drops the record of a buffer that is
+ * released. */
+typedef struct DrxHotHead {
+  int32_t H;                    /* multiple of 32, <= DRX_MAX_HOT */
+  const int16_t *slot;
+  const int32_t *item;
+} DrxHotHead;
+#define DRX_MAX_HOT 1024
+size_t drx_cdae_prep_bytes_hot(const DrxCdaeParams *p, int32_t B, int32_t n_touch_slots, int32_t H);
+size_t drx_cdae_scratch_bytes_hot(const DrxCdaeParams *p, int32_t B, int32_t n_touch_slots, int32_t H);
+int drx_cdae_sparse_prepare_hot(const DrxCdaeParams *p, const DrxHistory *hist, const DrxBatch *bt, const DrxHotHead *hot,
+                                void *prepared, size_t prepared_bytes, void *stream);
+/* prepared == NULL: the list (and the mask) built inline, in the scratch */
+int drx_cdae_step_sparse_hot(const DrxCdaeParams *p, const DrxOptim *opt, const DrxHistory *hist, const DrxBatch *bt,
+                             const DrxHotHead *hot, int32_t loss_kind, const void *prepared, size_t prepared_bytes, void *scratch,
+                             size_t scratch_bytes, float *loss_out, void *const *events, void *stream);
+void drx_cdae_prep_forget(const void *prepared);
+
 /* off[0] = 0, off[b + 1] = sum_{b' <= b} (indptr[ids[b'] + 1] - indptr[ids[b']]) for device ids: the keep_off of a batch of users (DrxBatch)
  * or the touch offsets of a batch of CSR rows.  scratch: drx_point_sample_scratch_bytes(B). */
 int drx_batch_offsets(const int64_t *indptr, const int32_t *ids, int32_t B, int32_t *off, void *scratch, size_t scratch_bytes, void *stream);
