@@ -158,6 +158,7 @@ SIGNATURES = {
     'drx_cdae_step_sparse_hot': (C.c_int, [C.POINTER(CdaeParams), C.POINTER(Optim), C.POINTER(History), C.POINTER(Batch),
                                            C.POINTER(HotHead), C.c_int32, C.c_void_p, C.c_size_t, C.c_void_p, C.c_size_t,
                                            C.c_void_p, C.POINTER(C.c_void_p), C.c_void_p]),
+    'drx_cdae_hot_rows_for': (C.c_int32, [C.POINTER(CdaeParams), C.c_int32, C.c_int32, C.c_int32, C.c_int32]),
     'drx_cdae_prep_forget': (None, [C.c_void_p]),
     'drx_point_sample_scratch_bytes': (C.c_size_t, [C.c_int32]),
     'drx_list_sample_device': (C.c_int, [C.POINTER(ListGroups), C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_uint64, C.c_void_p, C.c_void_p,

@@ -6,6 +6,7 @@
                                           # streams, draw-ahead worker threads) alone, g++ -fsanitize, into
                                           # csrc/build/libdrx_host_<kind>.so; scripts/sanitize_host.sh runs tests/test_sampler.py on it
 """
+import glob
 import os
 import subprocess
 import sys
@@ -31,8 +32,7 @@ def _newer(target, deps):
 
 def build(force=False, verbose=True):
     os.makedirs(OBJ, exist_ok=True)
-    headers = [os.path.join(ROOT, 'include', 'drx.h')] + [os.path.join(CSRC, h) for h in
-               ('drx_common.hpp', 'drx_rows.hpp', 'drx_segreduce.hpp', 'drx_scan.hpp', 'drx_prep.hpp', 'drx_segstream.hpp')]
+    headers = [os.path.join(ROOT, 'include', 'drx.h')] + sorted(glob.glob(os.path.join(CSRC, '*.hpp')))
     objs = []
     procs = []
     for src in SOURCES:

@@ -1088,9 +1088,7 @@ struct BiasFinalExtra {
 //             update as the segment path's (DirectPolicyAdagrad::stream_update); rows no sample kept are not touched.
 // ------------------------------------------------------------------------------------------------
 constexpr int kHotSlice = 512;       // samples per partial (P: [B / kHotSlice, H, ld] floats)
-// rows of 64 / 128 floats only: with rows of 256 the reduction's partial workgroups need 72 registers (56 + 16 accumulators), above the
-// 64 that keep that launch at 8 waves per SIMD
-constexpr int kHotMaxG = 32;
+// (rows of 64 / 128 floats only: kHotMaxG, drx_prep.hpp)
 
 struct HotArgs {
   const float *dz1;             // [B, ld]
@@ -1499,6 +1497,73 @@ static PartBufs part_layout(Carver &cv, const DrxCdaeParams &P, int B, int n_tou
   return L;
 }
 
+// ---- the sampled step's three launches: forward/backward, the segmented reduction, the span finish ----------------------------------
+// (which variant of each: drx_prep.hpp forward_form / reduce_form / hot_head_fits; the reduction's launches: drx_segstream.hpp)
+template <int G, int J>
+static void launch_forward(ForwardForm form, const DrxCdaeParams &P, const DrxOptim &opt, const DrxHistory &hist, const DrxBatch &bt,
+                           float scale, uint32_t qthr, int32_t loss_kind, const SparseBufs &S, const float *ks_h, const float *ks_dot,
+                           hipStream_t st) {
+  constexpr int gpb = kBlock / G;
+  const dim3 groups((bt.B + gpb - 1) / gpb);
+  const bool adagrad = opt.kind == DRX_OPT_ADAGRAD;        // (compiled in: the throughput configuration's optimizer)
+  switch (form) {
+  case ForwardForm::ColumnShard:
+    hipLaunchKernelGGL((k_kshard_rest<G, J>), groups, dim3(kBlock), 0, st, P, opt, hist, bt, scale, qthr, loss_kind, S, ks_h, ks_dot);
+    break;
+  case ForwardForm::SharedUsers:
+    if constexpr (G >= 16 && J <= 2) {                      // (share_users(): rows of 64 .. 512 floats)
+      // work items: at most one per distinct user + one per full item, never more than triples
+      const long long wmax = (long long)(P.n_users < bt.B ? P.n_users : bt.B) + bt.B / share_item_triples(P.ld) + 1;
+      hipLaunchKernelGGL((adagrad ? k_items_fwd_bwd<G, J, DRX_OPT_ADAGRAD> : k_items_fwd_bwd<G, J>), dim3((unsigned)(wmax < bt.B ? wmax : bt.B)),
+                         dim3(kItemThreads), share_item_lds_bytes(P.ld), st, P, opt, hist, bt, scale, qthr, loss_kind, S);
+    }
+    break;
+  case ForwardForm::PerWorkgroup:
+    hipLaunchKernelGGL((k_sampled_fwd_bwd_wg<G, J>), dim3(bt.B), dim3(kBlock), (size_t)gpb * P.ld * 4, st, P, opt, hist, bt, scale, qthr,
+                       loss_kind, S);
+    break;
+  case ForwardForm::PerGroup:
+    hipLaunchKernelGGL((adagrad ? k_sampled_fwd_bwd<G, J, DRX_OPT_ADAGRAD> : k_sampled_fwd_bwd<G, J>), groups, dim3(kBlock), 0, st, P, opt, hist,
+                       bt, scale, qthr, loss_kind, S);
+    break;
+  }
+}
+
+// the segmented reduction (+ the bias column sums as extra workgroups) and the ONE launch that combines the chunk-crossing segments
+// (+ the bias update), phase event 3 between them; with a hot head (HA.H > 0: the streamed form, hot_head_fits) both launches carry
+// its workgroups too — the partials, one wave per (slice, 32 hot rows, 32 columns), and the finish, one workgroup per hot row
+template <int G, int J, class Policy>
+static int reduce_and_finish(ReduceForm form, const DrxCdaeParams &P, const DrxOptim &opt, const SparseBufs &S, const SegBufs &SB,
+                             const PlanBufs &PB, const SpanPlan &plan, const BiasArgs &BA, const HotArgs &HA, void *const *events,
+                             hipStream_t st) {
+  const Policy pol{P, opt, BA.B, HA.scale, S.dz1, (long long)(S.g2 - S.dz1), S.dz2};
+  const BiasFinalExtra<G, J> bias{P, opt, BA};
+  int rc = DRX_EINVAL;
+  if (HA.H == 0) rc = launch_reduce<G, J>(form, SB, PB, plan, pol, BA, st);
+  else if constexpr (kHotBuilt<G, J, Policy>) {
+    constexpr int NT = kStreamThreads<G>;
+    HotArgs part = HA;
+    part.first = BA.n_part;
+    const int n_hot = (HA.S * (HA.H / 32) * G / 8 + NT / 64 - 1) / (NT / 64);
+    using Front = ExtraPair<BiasPartialExtra<G, J, NT>, HotPartialExtra<4 * G, NT>>;
+    rc = launch_reduce_streamed<G, J>(SB, PB, plan, pol, BA.n_part + n_hot, Front{{P.ld, BA}, BA.n_part, {part}}, st);
+  }
+  if (rc) return rc;
+  DRX_HIP(phase_event(events, 3, st));
+  rc = DRX_EINVAL;
+  if (HA.H == 0) rc = launch_spans<G, J>(SB, PB, plan, pol, 1, bias, st);
+  else if constexpr (kHotBuilt<G, J, Policy>) {
+    HotArgs fin = HA;
+    fin.first = kSpanBlocks + 1;                            // (behind the hidden bias's workgroup)
+    using Finish = ExtraPair<BiasFinalExtra<G, J>, HotFinishExtra<4 * G, Policy>>;
+    rc = launch_spans<G, J>(SB, PB, plan, pol, 1 + HA.H, Finish{bias, fin.first, {fin, pol}}, st);
+  }
+  if (rc) return rc;
+  DRX_HIP(phase_event(events, 4, st));
+  DRX_HIP(phase_event(events, 5, st));
+  return DRX_OK;
+}
+
 }  // namespace drx
 
 using namespace drx;
@@ -1869,12 +1934,6 @@ static int step_sparse_impl(const DrxCdaeParams *p, const DrxOptim *opt, const D
   S.stamps = SB.stamps = h_stamps;
 #endif
   PlanBufs PB{S.pblock, S.pbs};
-  // rows collect long runs of touches (MovieLens shapes): k_seg_reduce_planned's LONG form (chunks of 64, 8 rows in flight), XCD placement of its workgroups
-  const bool long_segments = drx::long_segments(S.T, *p);
-#define EV(i) do { if (events) DRX_HIP(hipEventRecord((hipEvent_t)events[i], st)); } while (0)
-  // One workgroup per triple (its groups split the history) instead of one group per triple: when a group would walk many
-  // dependent load rounds.  Short histories (mean <= 64 items): only while the batch cannot fill the chip anyway.
-  constexpr int wg_long = 64;
   // DRX_BATCH_SHARE_USERS (lists prepared ahead through the history's transpose only): one forward workgroup per work item
   // (k_items_fwd_bwd); the reduction reads the items' summed gradient rows
   // (a list in the shared form has no gradient row per triple: the column-sharded step's forward kernels cannot read it)
@@ -1884,130 +1943,28 @@ static int step_sparse_impl(const DrxCdaeParams *p, const DrxOptim *opt, const D
   S.witem = share ? R.witem : nullptr;
   S.worder = share ? R.worder : nullptr;
   S.n_items = share ? R.n_du : nullptr;
-  if (H > 0) {
-    // the head exists on the streamed reduction's path alone (the single-GPU Adagrad step over short segments, ld = 64 / 128 / 256)
-    const Geom gm = pick_geom(p->ld);
-    const bool streamed_path = kStreamDepth > 0 && gm.J == 1 && gm.G >= 16 && gm.G <= kHotMaxG && p->ld == 4 * gm.G && !long_segments && !share &&
-                               opt->kind == DRX_OPT_ADAGRAD && bt->B < (1 << kStreamIndexBits) &&
-                               p->n_items < (1 << kStreamIndexBits) && p->n_users < (1 << kStreamIndexBits);
-    if (!streamed_path || ks_h) return DRX_EINVAL;
-  }
-  HotArgs HA{S.dz1, R.hmask, HB.part, HB.any, hot ? hot->item : nullptr, scale, bt->B, H, R.Bw, hot_slices(bt->B), 0};
-  const long long mean_hist = bt->n_touch_slots / (long long)bt->B;
-  const bool per_wg = mean_hist > wg_long || (bt->B <= 8192 && mean_hist > 16);
-  BiasArgs BA{S.dz1, S.bpart, S.lossb, loss_out, bt->B, n_bpart, rows_per_block};
-  // the segmented reduction (+ the bias column sums as extra workgroups) and the ONE launch that combines the chunk-crossing segments
-  // (+ the bias update), with the policy type POLT (optimizer at run time, or Adagrad compiled in)
-#define REDUCE_AND_SPANS(G, J, POLT)                                                                                   \
-  {                                                                                                                    \
-    POLT polk{*p, *opt, bt->B, scale, S.dz1, (long long)(S.g2 - S.dz1), S.dz2};                    \
-    BiasPartialExtra<G, J> bpx{p->ld, BA};                                                                             \
-    BiasFinalExtra<G, J> bfx{*p, *opt, BA};                                                                            \
-    const int cpb = kSegBlock / G;                                                                                     \
-    const dim3 rgrid(n_bpart + (S.n_chunks + cpb - 1) / cpb);                                                        \
-    const size_t lds_r = seg_reduce_lds_bytes(cpb, p->ld, long_segments);                                              \
-    bool streamed = false;                                                                                             \
-    if constexpr (kStreamDepth > 0 && J == 1 && G >= 16 && std::is_same<POLT, DirectPolicyAdagrad>::value) {           \
-      /* lists of short segments over rows of exactly 64 / 128 / 256 floats: the streamed form (drx_segstream.hpp) */  \
-      if (!long_segments && p->ld == 4 * G && bt->B < (1 << kStreamIndexBits) && p->n_items < (1 << kStreamIndexBits) &&           \
-          p->n_users < (1 << kStreamIndexBits)) { \
-        BiasPartialExtra<G, J, cpb * 64> bpxs{p->ld, BA};                                                              \
-        bool hot_launched = false;                                                                                     \
-        if constexpr (G <= kHotMaxG) {                                                                                 \
-        if (H > 0) {                                                                                                   \
-          /* + the hot head's partials: one wave per (slice, 32 hot rows, 32 columns) */                               \
-          HotArgs hpa = HA;                                                                                            \
-          hpa.first = n_bpart;                                                                                         \
-          const int n_hot = (HA.S * (H / 32) * G / 8 + cpb - 1) / cpb;                                                 \
-          using PX = ExtraPair<BiasPartialExtra<G, J, cpb * 64>, HotPartialExtra<4 * G, cpb * 64>>;                   \
-          const dim3 sgrid(n_bpart + n_hot + (S.n_chunks + cpb - 1) / cpb);                                            \
-          hipLaunchKernelGGL((k_seg_reduce_stream<4 * G, kStreamDepth, POLT, PX>), sgrid, dim3(cpb * 64),              \
-                             seg_stream_lds_bytes(p->ld, kStreamDepth), st, SB, PB, R.plan, polk, n_bpart + n_hot,      \
-                             PX{bpxs, n_bpart, HotPartialExtra<4 * G, cpb * 64>{hpa}});                                \
-          hot_launched = true;                                                                                         \
-        }                                                                                                              \
-        }                                                                                                              \
-        if (!hot_launched) {                                                                                           \
-          const dim3 sgrid(n_bpart + (S.n_chunks + cpb - 1) / cpb);                                                    \
-          hipLaunchKernelGGL((k_seg_reduce_stream<4 * G, kStreamDepth, POLT, BiasPartialExtra<G, J, cpb * 64>>), sgrid, dim3(cpb * 64), \
-                             seg_stream_lds_bytes(p->ld, kStreamDepth), st, SB, PB, R.plan, polk, n_bpart, bpxs);      \
-        }                                                                                                              \
-        streamed = true;                                                                                               \
-      }                                                                                                                \
-    }                                                                                                                  \
-    if (streamed) { }                                                                                                  \
-    else if (long_segments)                                                                                            \
-      hipLaunchKernelGGL((k_seg_reduce_planned<G, J, POLT, true, BiasPartialExtra<G, J>>), rgrid, dim3(kSegBlock), lds_r, st, SB, PB,    \
-                         R.plan, polk, n_bpart, bpx);                                                                  \
-    else                                                                                                               \
-      hipLaunchKernelGGL((k_seg_reduce_planned<G, J, POLT, false, BiasPartialExtra<G, J>>), rgrid, dim3(kSegBlock), lds_r, st, SB, PB,    \
-                         R.plan, polk, n_bpart, bpx);                                                                  \
-    EV(3);                                                                                                             \
-    bool finished_hot = false;                                                                                         \
-    if constexpr (kStreamDepth > 0 && J == 1 && G >= 16 && G <= kHotMaxG && std::is_same<POLT, DirectPolicyAdagrad>::value) { \
-      if (H > 0) {                                                                                                     \
-        /* + the hot head's finish: one workgroup per hot row behind the hidden bias's */                              \
-        HotArgs hfa = HA;                                                                                              \
-        hfa.first = kLongBlocks + kShortBlocks + 1;                                                                    \
-        using FX = ExtraPair<BiasFinalExtra<G, J>, HotFinishExtra<4 * G, POLT>>;                                      \
-        hipLaunchKernelGGL((k_span_planned<G, J, POLT, FX>), dim3(kLongBlocks + kShortBlocks + 1 + H), dim3(kFixBlock), lds_b, st, \
-                           SB, PB, R.plan, polk, kLongBlocks, kShortBlocks,                                            \
-                           FX{bfx, kLongBlocks + kShortBlocks + 1, HotFinishExtra<4 * G, POLT>{hfa, polk}});          \
-        finished_hot = true;                                                                                           \
-      }                                                                                                                \
-    }                                                                                                                  \
-    if (!finished_hot) {                                                                                               \
-      if (lds_b > 48 * 1024)                                                                                           \
-        DRX_HIP(hipFuncSetAttribute((const void *)k_span_planned<G, J, POLT, BiasFinalExtra<G, J>>,                   \
-                                    hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_b));                          \
-      hipLaunchKernelGGL((k_span_planned<G, J, POLT, BiasFinalExtra<G, J>>), dim3(kLongBlocks + kShortBlocks + 1),                \
-                         dim3(kFixBlock), lds_b, st, SB, PB, R.plan, polk, kLongBlocks, kShortBlocks, bfx);               \
-    }                                                                                                                  \
-    EV(4);                                                                                                             \
-    EV(5);                                                                                                             \
-  }
-#define CALL(G, J)                                                                                                     \
-  {                                                                                                                    \
-    const int gpb = kBlock / G;                                                                                        \
-    const size_t lds_b = ((size_t)(kFixBlock / G) * (p->ld + 1)) * 4;                                                  \
-    EV(0);                                                                                                             \
-    if (ks_h)                                                                                                          \
-      hipLaunchKernelGGL((k_kshard_rest<G, J>), dim3((bt->B + gpb - 1) / gpb), dim3(kBlock), 0, st, *p, *opt, *hist, *bt, scale, \
-                         qthr, loss_kind, S, ks_h, ks_dot);                                                            \
-    else if (share) {                                                                                                  \
-      /* work items: at most one per distinct user + one per full item, never more than triples */                   \
-      const long long wmax = (long long)(p->n_users < bt->B ? p->n_users : bt->B) + bt->B / share_item_triples(p->ld) + 1;                   \
-      const dim3 igrid((unsigned)(wmax < bt->B ? wmax : bt->B));                                                       \
-      if constexpr (G >= 16 && J <= 2) {                        /* (share_users(): rows of 64 .. 512 floats) */        \
-        if (opt->kind == DRX_OPT_ADAGRAD)                                                                              \
-          hipLaunchKernelGGL((k_items_fwd_bwd<G, J, DRX_OPT_ADAGRAD>), igrid, dim3(kItemThreads), share_item_lds_bytes(p->ld), st, *p, *opt, \
-                             *hist, *bt, scale, qthr, loss_kind, S);                                                   \
-        else                                                                                                           \
-          hipLaunchKernelGGL((k_items_fwd_bwd<G, J>), igrid, dim3(kItemThreads), share_item_lds_bytes(p->ld), st, *p, *opt, *hist, *bt, \
-                             scale, qthr, loss_kind, S);                                                               \
-      }                                                                                                                \
-    } else if (per_wg)                                                                                                 \
-      hipLaunchKernelGGL((k_sampled_fwd_bwd_wg<G, J>), dim3(bt->B), dim3(kBlock), (size_t)gpb * p->ld * 4, st, *p, *opt, *hist, \
-                         *bt, scale, qthr, loss_kind, S);                                                              \
-    else if (opt->kind == DRX_OPT_ADAGRAD)                                                                             \
-      hipLaunchKernelGGL((k_sampled_fwd_bwd<G, J, DRX_OPT_ADAGRAD>), dim3((bt->B + gpb - 1) / gpb), dim3(kBlock), 0, st, *p, *opt, \
-                         *hist, *bt, scale, qthr, loss_kind, S);                                                       \
-    else                                                                                                               \
-      hipLaunchKernelGGL((k_sampled_fwd_bwd<G, J>), dim3((bt->B + gpb - 1) / gpb), dim3(kBlock), 0, st, *p, *opt, *hist, *bt,  \
-                         scale, qthr, loss_kind, S);                                                                   \
-    EV(1);                                                                                                             \
-    if (!prepared) {                                                                                                   \
-      rc = prepare_impl(p, hist, bt, R, st, false, TouchPresence{nullptr, WireGeo{1, 0, 1}}, hot ? hot->slot : nullptr); \
-      if (rc) return rc;                                                                                               \
-    }                                                                                                                  \
-    EV(2);                                                                                                             \
-    if (opt->kind == DRX_OPT_ADAGRAD) { REDUCE_AND_SPANS(G, J, DirectPolicyAdagrad); }                                 \
-    else { REDUCE_AND_SPANS(G, J, DirectPolicy); }                                                                     \
-  }
+  // which variant of each launch (drx_prep.hpp)
+  const ReduceForm form = reduce_form(opt->kind, bt->B, S.T, *p);
+  const ForwardForm fwd = forward_form(ks_h != nullptr, share, bt->B, bt->n_touch_slots);
+  if (H > 0 && !hot_head_fits(form, p->ld, share, ks_h != nullptr)) return DRX_EINVAL;
+  const HotArgs HA{S.dz1, R.hmask, HB.part, HB.any, hot ? hot->item : nullptr, scale, bt->B, H, R.Bw, hot_slices(bt->B), 0};
+  const BiasArgs BA{S.dz1, S.bpart, S.lossb, loss_out, bt->B, n_bpart, rows_per_block};
+  DRX_HIP(phase_event(events, 0, st));
+#define CALL(G, J) launch_forward<G, J>(fwd, *p, *opt, *hist, *bt, scale, qthr, loss_kind, S, ks_h, ks_dot, st)
   DRX_DISPATCH_GEOM(p->ld, CALL);
 #undef CALL
-#undef REDUCE_AND_SPANS
-#undef EV
+  DRX_HIP(phase_event(events, 1, st));
+  if (!prepared) {
+    rc = prepare_impl(p, hist, bt, R, st, false, TouchPresence{nullptr, WireGeo{1, 0, 1}}, hot ? hot->slot : nullptr);
+    if (rc) return rc;
+  }
+  DRX_HIP(phase_event(events, 2, st));
+#define CALL(G, J) rc = opt->kind == DRX_OPT_ADAGRAD                                                                  \
+    ? reduce_and_finish<G, J, DirectPolicyAdagrad>(form, *p, *opt, S, SB, PB, R.plan, BA, HA, events, st)             \
+    : reduce_and_finish<G, J, DirectPolicy>(form, *p, *opt, S, SB, PB, R.plan, BA, HA, events, st)
+  DRX_DISPATCH_GEOM(p->ld, CALL);
+#undef CALL
+  if (rc) return rc;
   DRX_LAUNCH_CHECK();
   return DRX_OK;
 }
@@ -2147,8 +2104,7 @@ int drx_cdae_kshard_forward_prepared(const DrxCdaeParams *p, const DrxHistory *h
   hipStream_t st = (hipStream_t)stream;
   const float scale = 1.0f / (1.0f - bt->q);
   const uint32_t qthr = q_threshold(bt->q);
-  const long long mean_hist = bt->n_touch_slots / (long long)bt->B;
-  const bool per_wg = mean_hist > 64 || (bt->B <= 8192 && mean_hist > 16);      // as in step_sparse_impl
+  const bool per_wg = forward_per_workgroup(bt->B, bt->n_touch_slots);
 #define CALL(G, J)                                                                                                     \
   {                                                                                                                    \
     const int gpb = kBlock / G;                                                                                        \
@@ -2236,6 +2192,12 @@ int drx_cdae_step_sparse_hot(const DrxCdaeParams *p, const DrxOptim *opt, const 
   if (!hot_ok(p, hot)) return DRX_EINVAL;
   return step_sparse_impl(p, opt, hist, bt, loss_kind, prepared, prepared_bytes, scratch, scratch_bytes, loss_out, events, stream,
                           nullptr, nullptr, hot);
+}
+
+int32_t drx_cdae_hot_rows_for(const DrxCdaeParams *p, int32_t opt_kind, int32_t B, int32_t n_touch_slots, int32_t H) {
+  if (B < 1 || n_touch_slots < 0 || hot_rows(p, H) <= 0) return 0;
+  // (a list of shared users is one of long segments: never the streamed form)
+  return hot_head_fits(reduce_form(opt_kind, B, n_touch_slots + 2 * B, *p), p->ld, false, false) ? H : 0;
 }
 
 void drx_cdae_prep_forget(const void *prepared) {

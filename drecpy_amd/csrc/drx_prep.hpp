@@ -313,6 +313,71 @@ struct PrepBufs {
 // more than 8 touches per table row on average: rows collect long runs of touches (MovieLens shapes)
 static inline bool long_segments(int T, const DrxCdaeParams &P) { return (int64_t)T > 8 * ((int64_t)2 * P.n_items + P.n_users); }
 
+// ---- which variant of each of the sampled step's three launches runs: decided HERE, once (host only) -----------------------------------
+// The single-GPU step (drx_cdae.hip), the row-sharded step's local half (drx_shard.hip), the preparation's head check below and the
+// engine's question "would this step take a head?" (drx_cdae_hot_rows_for) all ask these functions; the launches themselves are
+// drx_segstream.hpp's launch_reduce / launch_spans.
+// ring depth of the streamed reduction in LDS-DMA instructions (KiB) per wave; 0: the planned kernel everywhere (a variant is a build:
+// scripts/build_variant.sh <name> "-DDRX_STREAM_DEPTH=..")
+#ifndef DRX_STREAM_DEPTH
+#define DRX_STREAM_DEPTH 4
+#endif
+constexpr int kStreamDepth = DRX_STREAM_DEPTH;
+constexpr int kStreamIndexBits = 28;                          // an item word of the streamed reduction: row index << 4 | kind
+// the hot head at rows of 64 / 128 floats only: with rows of 256 the reduction's partial workgroups need 72 registers (56 + 16
+// accumulators), above the 64 that keep that launch at 8 waves per SIMD
+constexpr int kHotMaxG = 32;
+
+// the segmented reduction: streamed (drx_segstream.hpp), or k_seg_reduce_planned in its LONG form (chunks of 64, 8 rows in flight, XCD
+// placement of its workgroups) or its short one
+enum class ReduceForm { Streamed, PlannedLong, PlannedShort };
+
+// the optimizer a policy type has compiled in (DirectPolicyT<KIND>, LocalPolicyT<KIND>; -1: chosen at run time)
+template <class Policy> struct PolicyKind;
+template <template <int> class PolicyT, int KIND> struct PolicyKind<PolicyT<KIND>> { static constexpr int value = KIND; };
+// compile-time half of "streamed": the (G, J, policy) the streamed kernel is instantiated for — pick_geom's G and J of rows of 64 / 128 /
+// 256 floats, Adagrad compiled in.  reduce_form() answers Streamed for no other combination.
+template <int G, int J, class Policy>
+constexpr bool kStreamBuilt = kStreamDepth > 0 && J == 1 && G >= 16 && PolicyKind<Policy>::value == DRX_OPT_ADAGRAD;
+// ... and of the head riding in it
+template <int G, int J, class Policy>
+constexpr bool kHotBuilt = kStreamBuilt<G, J, Policy> && G <= kHotMaxG;
+
+// K: the key space of the batch's touch list (the step's own parameters; the row-sharded step: global items, local users) with its row
+// width.  Streamed: lists of short segments over rows of exactly 64 / 128 / 256 floats, Adagrad, every index within an item word.
+static inline ReduceForm reduce_form(int opt_kind, int B, int T, const DrxCdaeParams &K) {
+  if (long_segments(T, K)) return ReduceForm::PlannedLong;
+  const Geom gm = pick_geom(K.ld);
+  const bool streamed = kStreamDepth > 0 && gm.J == 1 && gm.G >= 16 && K.ld == 4 * gm.G && opt_kind == DRX_OPT_ADAGRAD &&
+                        B < (1 << kStreamIndexBits) && K.n_items < (1 << kStreamIndexBits) && K.n_users < (1 << kStreamIndexBits);
+  return streamed ? ReduceForm::Streamed : ReduceForm::PlannedShort;
+}
+
+// The hot head (include/drx.h DrxHotHead) exists in lists of short segments made without a presence filter — all a preparation knows —
+static inline bool hot_list_fits(int T, const DrxCdaeParams &K, bool presence) { return !presence && !long_segments(T, K); }
+// ... and is trained by the streamed reduction of the single-GPU step alone: no shared-user lists, no column shards
+static inline bool hot_head_fits(ReduceForm form, int ld, bool share, bool kshard) {
+  return form == ReduceForm::Streamed && pick_geom(ld).G <= kHotMaxG && !share && !kshard;
+}
+
+// The forward/backward launch.  One workgroup per triple (its groups split the history) instead of one group per triple: when a group
+// would walk many dependent load rounds.  Short histories (mean <= 64 items): only while the batch cannot fill the chip anyway.
+static inline bool forward_per_workgroup(int B, int n_touch_slots) {
+  const long long mean_hist = n_touch_slots / (long long)B;
+  return mean_hist > 64 || (B <= 8192 && mean_hist > 16);
+}
+enum class ForwardForm { ColumnShard, SharedUsers, PerWorkgroup, PerGroup };      // k_kshard_rest, k_items_fwd_bwd, k_sampled_fwd_bwd_wg, k_sampled_fwd_bwd
+static inline ForwardForm forward_form(bool kshard, bool share, int B, int n_touch_slots) {
+  if (kshard) return ForwardForm::ColumnShard;
+  if (share) return ForwardForm::SharedUsers;
+  return forward_per_workgroup(B, n_touch_slots) ? ForwardForm::PerWorkgroup : ForwardForm::PerGroup;
+}
+
+// a step's phase events (nullptr: none wanted)
+static inline hipError_t phase_event(void *const *events, int i, hipStream_t st) {
+  return events ? hipEventRecord((hipEvent_t)events[i], st) : hipSuccess;
+}
+
 static PrepBufs prep_layout(Carver &cv, const DrxCdaeParams &P, int B, int n_touch_slots, int H = 0) {
   PrepBufs R{};
   R.T = n_touch_slots + 2 * B;
@@ -692,8 +757,8 @@ static int prepare_impl(const DrxCdaeParams *p, const DrxHistory *hist, const Dr
                         bool with_marks = false, TouchPresence pres = TouchPresence{nullptr, WireGeo{1, 0, 1}},
                         const int16_t *hot_slot = nullptr) {
   const int gpb = kBlock / 16;
-  // (the head exists on lists of short segments only: the transposed preparation below never builds one)
-  if (R.H > 0 && (!hot_slot || pres.present || long_segments(R.T, *p))) return DRX_EINVAL;
+  // (the transposed preparation below never builds a head)
+  if (R.H > 0 && (!hot_slot || !hot_list_fits(R.T, *p, pres.present != nullptr))) return DRX_EINVAL;
   if (hist->t_rank && hist->t_users && hist->t_pos && hist->t_items && !pres.present && long_segments(R.T, *p)) {
     const int32_t *row_end = nullptr;
     const int rc = prepare_transposed(p, hist, bt, R, st, with_marks, &row_end);

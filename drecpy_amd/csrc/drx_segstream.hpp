@@ -40,6 +40,7 @@
 //                                     before the stream starts, on the lane whose touch finishes the row)
 #pragma once
 #include "drx_segreduce.hpp"
+#include "drx_prep.hpp"
 
 namespace drx {
 
@@ -61,12 +62,7 @@ template <> struct LaneVec<1> { using T = float; };
 template <> struct LaneVec<2> { typedef float T __attribute__((ext_vector_type(2))); };
 template <> struct LaneVec<4> { typedef float T __attribute__((ext_vector_type(4))); };
 
-// ring depth of the streamed reduction in LDS-DMA instructions (KiB) per wave; 0: the planned kernel everywhere (a variant is a build:
-// scripts/build_variant.sh <name> "-DDRX_STREAM_DEPTH=..")
-#ifndef DRX_STREAM_DEPTH
-#define DRX_STREAM_DEPTH 4
-#endif
-constexpr int kStreamDepth = DRX_STREAM_DEPTH;
+// (the ring depth kStreamDepth and kStreamIndexBits: drx_prep.hpp, beside reduce_form())
 // The streamed kernels take their arguments (five structs of pointers) in ~106 scalar registers; a CU admits 256-thread workgroups up to
 // 800 / (sgprs rounded up to 16, + 16): 6 at 106, 8 at 80 (MI355X_MICROARCH: Residency).  Capped, the compiler parks the surplus in
 // lanes of a vector register (v_writelane / v_readlane): 8 workgroups = all 32 wave slots of a CU.
@@ -75,7 +71,6 @@ constexpr int kStreamDepth = DRX_STREAM_DEPTH;
 #endif
 #define DRX_STREAM_SGPR_CAP __attribute__((amdgpu_num_sgpr(DRX_STREAM_SGPRS)))
 constexpr int kStreamItems = 3 * (2 * kChunk - 1) + 3;        // a window's items at most (every touch a segment of its own), rounded up to a multiple of 4
-constexpr int kStreamIndexBits = 28;                          // an item word: row index << 4 | kind
 static inline size_t seg_stream_lds_bytes(int ld, int depth) {
   const int cpb = kSegBlock / (ld / 4);
   return (size_t)cpb * ((size_t)depth * 1024 + (size_t)kStreamItems * 4 + 128) + (size_t)cpb * (ld + 4) * 4;
@@ -349,6 +344,52 @@ __global__ __launch_bounds__((kSegBlock / (LD / 4)) * 64) DRX_STREAM_SGPR_CAP vo
       }
     }
   }
+}
+
+// ---- host side: the reduction and the span launch of a sampled step (drx_cdae.hip, drx_shard.hip) ------------------------------------
+// `front`: the n_front workgroups in front of the chunk workgroups.  The streamed form is one wave per chunk — its front is built for
+// kStreamThreads<G> threads, a planned form's for kSegBlock — so a caller says which form its front is for:
+template <int G> constexpr int kStreamThreads = (kSegBlock / G) * 64;
+
+template <int G, int J, class Policy, class Front>
+static int launch_reduce_streamed(const SegBufs &SB, const PlanBufs &PB, const SpanPlan &plan, const Policy &pol, int n_front,
+                                  const Front &front, hipStream_t st) {
+  if constexpr (kStreamBuilt<G, J, Policy>) {
+    constexpr int cpb = kSegBlock / G;
+    hipLaunchKernelGGL((k_seg_reduce_stream<4 * G, kStreamDepth, Policy, Front>), dim3(n_front + (SB.n_chunks + cpb - 1) / cpb),
+                       dim3(kStreamThreads<G>), seg_stream_lds_bytes(SB.ld, kStreamDepth), st, SB, PB, plan, pol, n_front, front);
+    return DRX_OK;
+  }
+  return DRX_EINVAL;             // (reduce_form() answers Streamed where kStreamBuilt holds only)
+}
+
+// the reduction in the form reduce_form() chose, the hidden bias's column-sum partials (BiasPartialExtra) in front
+template <int G, int J, class Policy>
+static int launch_reduce(ReduceForm form, const SegBufs &SB, const PlanBufs &PB, const SpanPlan &plan, const Policy &pol,
+                         const BiasArgs &BA, hipStream_t st) {
+  if (form == ReduceForm::Streamed)
+    return launch_reduce_streamed<G, J>(SB, PB, plan, pol, BA.n_part, BiasPartialExtra<G, J, kStreamThreads<G>>{SB.ld, BA}, st);
+  constexpr int cpb = kSegBlock / G;
+  using Front = BiasPartialExtra<G, J>;
+  const bool lng = form == ReduceForm::PlannedLong;
+  const auto kernel = lng ? k_seg_reduce_planned<G, J, Policy, true, Front> : k_seg_reduce_planned<G, J, Policy, false, Front>;
+  hipLaunchKernelGGL(kernel, dim3(BA.n_part + (SB.n_chunks + cpb - 1) / cpb), dim3(kSegBlock), seg_reduce_lds_bytes(cpb, SB.ld, lng), st,
+                     SB, PB, plan, pol, BA.n_part, Front{SB.ld, BA});
+  return DRX_OK;
+}
+
+// the ONE launch that combines the chunk-crossing segments, `extra`'s n_extra workgroups behind the span workgroups (they begin at
+// workgroup kSpanBlocks)
+constexpr int kSpanBlocks = kLongBlocks + kShortBlocks;
+template <int G, int J, class Policy, class Extra>
+static int launch_spans(const SegBufs &SB, const PlanBufs &PB, const SpanPlan &plan, const Policy &pol, int n_extra, const Extra &extra,
+                        hipStream_t st) {
+  const size_t lds = ((size_t)(kFixBlock / G) * (SB.ld + 1)) * 4;
+  if (lds > 48 * 1024)
+    DRX_HIP(hipFuncSetAttribute((const void *)k_span_planned<G, J, Policy, Extra>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
+  hipLaunchKernelGGL((k_span_planned<G, J, Policy, Extra>), dim3(kSpanBlocks + n_extra), dim3(kFixBlock), lds, st, SB, PB, plan, pol,
+                     kLongBlocks, kShortBlocks, extra);
+  return DRX_OK;
 }
 
 }  // namespace drx

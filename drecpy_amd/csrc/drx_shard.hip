@@ -734,6 +734,27 @@ static int check_local_params(const DrxCdaeParams *p, const DrxShard *sh) {
   return DRX_OK;
 }
 
+// the three launches of the step's local half: forward/backward, the segmented reduction (+ the hidden bias's column-sum partials) in the
+// form reduce_form() chose, the span launch (+ the bias's sentinel rows), a phase event around each
+template <int G, int J, int KIND>
+static int local_launches(ReduceForm form, const DrxCdaeParams &P, const DrxOptim &opt, const DrxHistory &hist, const DrxBatch &bt, float scale,
+                          uint32_t qthr, int32_t loss_kind, const ShardStep &S, const SegBufs &SB, const PlanBufs &PB, const SpanPlan &plan,
+                          const BiasArgs &BA, int units, void *const *events, hipStream_t st) {
+  constexpr int gpb = kBlock / G;
+  const LocalPolicyT<KIND> pol{P, opt, S.b_norm, S.n_items, S.ipr, scale, S.dz1, (long long)(S.g2 - S.dz1), S.dz2, S.gsend, S.X, S.G};
+  DRX_HIP(phase_event(events, 0, st));
+  hipLaunchKernelGGL((k_shard_fwd_bwd<G, J, KIND>), dim3((bt.B + gpb - 1) / gpb), dim3(kBlock), 0, st, P, opt, hist, bt, scale, qthr,
+                     loss_kind, S);
+  DRX_HIP(phase_event(events, 1, st));
+  int rc = launch_reduce<G, J>(form, SB, PB, plan, pol, BA, st);
+  if (rc) return rc;
+  DRX_HIP(phase_event(events, 2, st));
+  rc = launch_spans<G, J>(SB, PB, plan, pol, 1, ShardBiasExtra<G, J>{P.ld, units, BA, S.gsend, S.X}, st);
+  if (rc) return rc;
+  DRX_HIP(phase_event(events, 3, st));
+  return DRX_OK;
+}
+
 }  // namespace drx
 
 using namespace drx;
@@ -882,64 +903,14 @@ int drx_shard_step_local(const DrxCdaeParams *p, const DrxOptim *opt, const DrxS
   const int rows_per_block = (bt->B + B.n_bpart - 1) / B.n_bpart;
   const int n_bpart = (bt->B + rows_per_block - 1) / rows_per_block;
   BiasArgs BA{B.dz1, B.bpart, B.lossb, B.lossb /* non-null: the loss partials are always taken */, bt->B, n_bpart, rows_per_block};
-  const bool long_segments = drx::long_segments(B.T, key_params(*p, *sh));
-#define EV(i) do { if (events) DRX_HIP(hipEventRecord((hipEvent_t)events[i], st)); } while (0)
-#define REDUCE_AND_SPANS(G, J, KIND)                                                                                   \
-  {                                                                                                                    \
-    using POLT = LocalPolicyT<KIND>;                                                                                   \
-    POLT polk{*p, *opt, b_norm, sh->n_items, g.ipr, scale, B.dz1, (long long)(B.g2 - B.dz1), B.dz2, grad_send, X, g.wg()}; \
-    BiasPartialExtra<G, J> bpx{p->ld, BA};                                                                             \
-    ShardBiasExtra<G, J> bfx{p->ld, g.units, BA, grad_send, X};                                                        \
-    const int cpb = kSegBlock / G;                                                                                     \
-    const dim3 rgrid(n_bpart + (B.n_chunks + cpb - 1) / cpb);                                                          \
-    const size_t lds_r = seg_reduce_lds_bytes(cpb, p->ld, long_segments);                                              \
-    const size_t lds_b = ((size_t)(kFixBlock / G) * (p->ld + 1)) * 4;                                                  \
-    bool streamed = false;                                                                                             \
-    if constexpr (kStreamDepth > 0 && J == 1 && G >= 16 && KIND == DRX_OPT_ADAGRAD) {                                  \
-      /* lists of short segments over rows of exactly 64 / 128 / 256 floats: the streamed form (drx_segstream.hpp) */  \
-      if (!long_segments && p->ld == 4 * G && bt->B < (1 << kStreamIndexBits) && sh->n_items < (1 << kStreamIndexBits) && \
-          p->n_users < (1 << kStreamIndexBits)) {           /* (places in the exchange buffer are 32-bit float offsets: ShardXfer::foff) */ \
-        BiasPartialExtra<G, J, cpb * 64> bpxs{p->ld, BA};                                                              \
-        hipLaunchKernelGGL((k_seg_reduce_stream<4 * G, kStreamDepth, POLT, BiasPartialExtra<G, J, cpb * 64>>), rgrid, dim3(cpb * 64), \
-                           seg_stream_lds_bytes(p->ld, kStreamDepth), st, SB, PB, L.R.plan, polk, n_bpart, bpxs);      \
-        streamed = true;                                                                                               \
-      }                                                                                                                \
-    }                                                                                                                  \
-    if (streamed) { }                                                                                                  \
-    else if (long_segments)                                                                                            \
-      hipLaunchKernelGGL((k_seg_reduce_planned<G, J, POLT, true, BiasPartialExtra<G, J>>), rgrid, dim3(kSegBlock), lds_r, st, SB, PB, \
-                         L.R.plan, polk, n_bpart, bpx);                                                                \
-    else                                                                                                               \
-      hipLaunchKernelGGL((k_seg_reduce_planned<G, J, POLT, false, BiasPartialExtra<G, J>>), rgrid, dim3(kSegBlock), lds_r, st, SB, PB, \
-                         L.R.plan, polk, n_bpart, bpx);                                                                \
-    EV(2);                                                                                                             \
-    if (lds_b > 48 * 1024)                                                                                             \
-      DRX_HIP(hipFuncSetAttribute((const void *)k_span_planned<G, J, POLT, ShardBiasExtra<G, J>>,                      \
-                                  hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_b));                            \
-    hipLaunchKernelGGL((k_span_planned<G, J, POLT, ShardBiasExtra<G, J>>), dim3(kLongBlocks + kShortBlocks + 1), dim3(kFixBlock),   \
-                       lds_b, st, SB, PB, L.R.plan, polk, kLongBlocks, kShortBlocks, bfx);                             \
-    EV(3);                                                                                                             \
-  }
-#define CALL(G, J)                                                                                                     \
-  {                                                                                                                    \
-    const int gpb = kBlock / G;                                                                                        \
-    EV(0);                                                                                                             \
-    if (opt->kind == DRX_OPT_ADAGRAD) {                                                                                \
-      hipLaunchKernelGGL((k_shard_fwd_bwd<G, J, DRX_OPT_ADAGRAD>), dim3((bt->B + gpb - 1) / gpb), dim3(kBlock), 0, st, *p, *opt, *hist, \
-                         *bt, scale, qthr, loss_kind, S);                                                              \
-      EV(1);                                                                                                           \
-      REDUCE_AND_SPANS(G, J, DRX_OPT_ADAGRAD);                                                                         \
-    } else {                                                                                                           \
-      hipLaunchKernelGGL((k_shard_fwd_bwd<G, J, -1>), dim3((bt->B + gpb - 1) / gpb), dim3(kBlock), 0, st, *p, *opt, *hist, *bt, scale, \
-                         qthr, loss_kind, S);                                                                          \
-      EV(1);                                                                                                           \
-      REDUCE_AND_SPANS(G, J, -1);                                                                                      \
-    }                                                                                                                  \
-  }
+  // (streamed: the places in the exchange buffer are 32-bit float offsets too, ShardXfer::foff)
+  const ReduceForm form = reduce_form(opt->kind, bt->B, B.T, key_params(*p, *sh));
+#define CALL(G, J) rc = opt->kind == DRX_OPT_ADAGRAD                                                                  \
+    ? local_launches<G, J, DRX_OPT_ADAGRAD>(form, *p, *opt, *hist, *bt, scale, qthr, loss_kind, S, SB, PB, L.R.plan, BA, g.units, events, st) \
+    : local_launches<G, J, -1>(form, *p, *opt, *hist, *bt, scale, qthr, loss_kind, S, SB, PB, L.R.plan, BA, g.units, events, st)
   DRX_DISPATCH_GEOM(p->ld, CALL);
 #undef CALL
-#undef REDUCE_AND_SPANS
-#undef EV
+  if (rc) return rc;
   DRX_LAUNCH_CHECK();
   return DRX_OK;
 }

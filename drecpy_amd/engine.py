@@ -38,7 +38,6 @@ class CdaeEngine:
     # catalogues of at least HOT_MIN_ITEMS_PER_ROW * HOT_ROWS items and batches of at least HOT_MIN_BATCH triples, rows of 64 / 128
     # floats.  The environment variable DRX_HOT_ROWS (0 or a multiple of 32 up to 1024) overrides HOT_ROWS.
     HOT_ROWS, HOT_MIN_ITEMS_PER_ROW, HOT_MIN_BATCH = 64, 16, 8192
-    HOT_LDS = (64, 128)
 
     def __init__(self, n_users, n_items, k, device='cuda:0'):
         if not torch.cuda.is_available():
@@ -216,12 +215,10 @@ class CdaeEngine:
 
     def _hot_for(self, bt):
         """H of the hot head a batch is prepared / trained with by the single-GPU sampled step (0: none)."""
-        if self.hot_rows <= 0 or bt.B < self.hot_min_batch or self.ld not in self.HOT_LDS:
+        if self.hot_rows <= 0 or bt.B < self.hot_min_batch or getattr(self, 'opt_kind', None) is None:
             return 0
-        if getattr(self, 'opt_kind', None) != _lib.OPT_ADAGRAD:
-            return 0
-        T = bt.n_touch_slots + 2 * bt.B                 # lists of short segments only (drx_prep.hpp long_segments)
-        return self.hot_rows if T <= 8 * (2 * self.n_items + self.n_users) else 0
+        # (where the step takes one: the library's answer — streamed Adagrad reduction, rows of 64 / 128 floats)
+        return int(lib().drx_cdae_hot_rows_for(C.byref(self._params), self.opt_kind, bt.B, bt.n_touch_slots, self.hot_rows))
 
     def _hot_head(self, H):
         return _lib.HotHead(H, ptr(self._hot_slot) if H else None, ptr(self._hot_item) if H else None)

@@ -223,6 +223,9 @@ int drx_cdae_sparse_prepare_hot(const DrxCdaeParams *p, const DrxHistory *hist, 
 int drx_cdae_step_sparse_hot(const DrxCdaeParams *p, const DrxOptim *opt, const DrxHistory *hist, const DrxBatch *bt,
                              const DrxHotHead *hot, int32_t loss_kind, const void *prepared, size_t prepared_bytes, void *scratch,
                              size_t scratch_bytes, float *loss_out, void *const *events, void *stream);
+/* H where drx_cdae_step_sparse_hot given these arguments (opt_kind: DrxOptim.kind) accepts a head of H rows, 0 where it returns DRX_EINVAL:
+ * the library's own answer (the same functions the step asks), for a caller that decides whether to prepare a batch with a head */
+int32_t drx_cdae_hot_rows_for(const DrxCdaeParams *p, int32_t opt_kind, int32_t B, int32_t n_touch_slots, int32_t H);
 void drx_cdae_prep_forget(const void *prepared);
 
 /* off[0] = 0, off[b + 1] = sum_{b' <= b} (indptr[ids[b'] + 1] - indptr[ids[b']]) for device ids: the keep_off of a batch of users (DrxBatch)

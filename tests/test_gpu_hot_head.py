@@ -26,6 +26,12 @@ def _kept(indptr, indices, uids, N, seed, q):
     return batch_rows(indptr, indices, uids, N, keep)[2]
 
 
+def _hot_rows_for(eng, opt_kind, bt, H):
+    import ctypes as C
+    from drecpy_amd import _lib
+    return _lib.lib().drx_cdae_hot_rows_for(C.byref(eng._params), opt_kind, bt.B, bt.n_touch_slots, H)
+
+
 def _run(K, H, prepared, steps=3, U=30000, N=400, B=2048, seed=21, oracle=True, poison=None, uids_of=None):
     eng, p, rng = _engine(U, N, K, seed=seed)
     indptr, indices = synth_history(rng, U, N, 12, zipf=1.05)
@@ -144,6 +150,19 @@ def test_hot_head_on_an_unsupported_path_is_refused():
         eng.step_sparse(0, bt, 'bce', prepared=pb)
     torch.cuda.synchronize()
     assert torch.equal(eng.W, w)
+    # the library's own answer (drx_cdae_hot_rows_for, what _hot_for asks) is 0 exactly where the step refuses and H where it runs
+    assert _hot_rows_for(eng, _lib.OPT_ADAM, bt, 64) == 0 and eng._hot_for(bt) == 0
+    assert _hot_rows_for(eng, _lib.OPT_ROWWISE_ADAGRAD, bt, 64) == 0
+    eng.init_optimizer('rowwise_adagrad', 0.05, 1e-3)
+    with pytest.raises(_lib.DrxError):
+        eng.step_sparse(0, bt, 'bce', prepared=pb)
+    torch.cuda.synchronize()
+    assert torch.equal(eng.W, w)
+    eng.init_optimizer('adagrad', 0.05, 1e-3)
+    assert _hot_rows_for(eng, _lib.OPT_ADAGRAD, bt, 64) == 64 and eng._hot_for(bt) == 64
+    eng.step_sparse(0, bt, 'bce', prepared=pb)
+    torch.cuda.synchronize()
+    assert not torch.equal(eng.W, w)
 
 
 @pytest.mark.gpu
@@ -196,6 +215,17 @@ def test_no_head_at_rows_of_256_floats():
     bt, alive = eng.make_batch(rng.integers(0, U, size=B), rng.integers(0, N, size=B), (rng.random(B) < 0.3).astype(np.float32),
                                q=0.2, mask_seed=3)
     assert eng._hot_for(bt) == 0 and eng.prepare_sparse(bt, hot=True)._drx_hot == 0
+    assert _hot_rows_for(eng, _lib.OPT_ADAGRAD, bt, 64) == 0              # the library's answer, and its step's:
+    w = eng.W.clone()
+    eng._hot_for = lambda bt: 64                                            # (an engine that asked for a head all the same)
+    with pytest.raises(_lib.DrxError):
+        eng.step_sparse(0, bt, 'bce', hot=True)
+    torch.cuda.synchronize()
+    assert torch.equal(eng.W, w)
+    del eng._hot_for
+    eng.step_sparse(0, bt, 'bce', hot=True)                                # H = 0: the plain step runs
+    torch.cuda.synchronize()
+    assert not torch.equal(eng.W, w)
     buf = torch.empty(int(_lib.lib().drx_cdae_prep_bytes_hot(C.byref(eng._params), bt.B, bt.n_touch_slots, 64)), dtype=torch.uint8,
                       device=eng.device)
     rc = _lib.lib().drx_cdae_sparse_prepare_hot(C.byref(eng._params), C.byref(eng._hist), C.byref(bt), C.byref(eng._hot_head(64)),
