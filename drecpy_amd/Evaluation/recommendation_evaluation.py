@@ -1,6 +1,8 @@
 """Top-N recommendation evaluation with the protocol of DRecPy/Evaluation/Processes/recommendation_evaluation.py (used by
 examples/caser.py:17-18): per test user `model.recommend(user, n=max(k), novelty)` against the user's (sampled) test
-positives; user i draws from `random.Random(seed + i)`; result keys `metric@k`, rounded to 4 decimals."""
+positives; user i draws from `random.Random(seed + i)`; result keys `metric@k`, rounded to 4 decimals.
+batched=True (default off: the loop above) draws every user's positives first — same streams, same skipping — and asks the model for all
+lists in ONE `model.recommend_batch` call."""
 import logging
 import random
 
@@ -8,7 +10,7 @@ from ._protocol import MetricTable, as_k_list, resolve_metrics, sample_positives
 
 
 def recommendation_evaluation(model, ds_test=None, n_test_users=None, k=10, n_pos_interactions=None, novelty=False,
-                              ignore_low_predictions_threshold=None, seed=0, max_concurrent_threads=4, **kwds):
+                              ignore_low_predictions_threshold=None, seed=0, max_concurrent_threads=4, batched=False, **kwds):
     assert n_test_users is None or n_test_users > 0, f'The number of test users ({n_test_users}) should be > 0.'
     assert n_pos_interactions is None or n_pos_interactions > 0, \
         f'The number of positive interactions ({n_pos_interactions}) should be None or an integer > 0.'
@@ -19,6 +21,9 @@ def recommendation_evaluation(model, ds_test=None, n_test_users=None, k=10, n_po
     users = ds_test.unique('user').values_list('user', to_list=True)
     if n_test_users is not None:
         users = users[:n_test_users]
+    if batched:
+        return _evaluate_batched(model, ds_test, users, table, ks, threshold, n_pos_interactions, novelty,
+                                 ignore_low_predictions_threshold, seed)
     for offset, user in enumerate(users):
         user = user.item() if hasattr(user, 'item') else user
         try:
@@ -33,6 +38,36 @@ def recommendation_evaluation(model, ds_test=None, n_test_users=None, k=10, n_po
             relevancies = {item: (user_ds.select_one(f'item == {item}', ['interaction'], to_list=True) or 0)
                            for item in set(relevant) | set(recommendations)}
         except Exception as err:          # the reference logs and skips the user
+            logging.error(err)
+            continue
+        table.add(recommendations, relevant, best, relevancies)
+    return table.result()
+
+
+def _evaluate_batched(model, ds_test, users, table, ks, threshold, n_pos_interactions, novelty, low_threshold, seed):
+    drawn_users = []
+    for offset, user in enumerate(users):
+        user = user.item() if hasattr(user, 'item') else user
+        try:
+            user_ds = ds_test.select(f'user == {user}')
+            drawn = sample_positives(user_ds, threshold, n_pos_interactions, random.Random(seed + offset))
+            if drawn is None or not drawn[0]:
+                continue
+            if model.interaction_dataset.user_to_uid(user) is None:        # (logged and skipped, as recommend() raising in the loop is)
+                raise Exception(f'User {user} was not found.')
+        except Exception as err:
+            logging.error(err)
+            continue
+        drawn_users.append((user, user_ds, drawn[0], drawn[1]))
+    if not drawn_users:
+        return table.result()
+    lists = model.recommend_batch([u for u, _, _, _ in drawn_users], n=max(ks), novelty=novelty, interaction_threshold=low_threshold)
+    for (user, user_ds, relevant, best), ranked in zip(drawn_users, lists):
+        try:
+            recommendations = [item for _, item in ranked]
+            relevancies = {item: (user_ds.select_one(f'item == {item}', ['interaction'], to_list=True) or 0)
+                           for item in set(relevant) | set(recommendations)}
+        except Exception as err:
             logging.error(err)
             continue
         table.add(recommendations, relevant, best, relevancies)

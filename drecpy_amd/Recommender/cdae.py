@@ -532,6 +532,23 @@ class CDAE(RecommenderABC):
             idx, val = idx[0].cpu().numpy(), val[0].cpu().numpy()
         return [(float(v), int(i)) for v, i in zip(val, idx) if i >= 0]
 
+    def _recommend_batch(self, uids, n, novelty):
+        """Top-n of the whole catalogue for many users in one engine call (CdaeEngine.recommend: scores and selection fused on the
+        device, no score matrix).  Excluded under novelty: every (uid, iid) row of the frame whatever its value — the set
+        _all_user_items gives _rank —, uploaded once per engine (again after load(): _restore_engine builds a new one)."""
+        with self._device_lock:
+            eng = self._engine
+            if novelty and getattr(eng, '_excl', None) is None:
+                ip, cols, _ = self.interaction_dataset.interaction_csr()      # duplicates merged, columns ascending
+                eng.set_exclusions(ip, cols)
+            idx, val = eng.recommend(np.asarray(uids, dtype=np.int32), min(int(n), self.n_items), exclude=bool(novelty))
+            idx, val = idx.cpu().numpy().astype(np.int64), val.cpu().numpy()
+        if idx.shape[1] < n:
+            pad = n - idx.shape[1]
+            idx = np.concatenate([idx, np.full((len(idx), pad), -1, np.int64)], axis=1)
+            val = np.concatenate([val, np.full((len(val), pad), -np.inf, np.float32)], axis=1)
+        return idx, val
+
     def _all_user_items(self, uid):
         if not hasattr(self, '_user_items'):
             ds = self.interaction_dataset

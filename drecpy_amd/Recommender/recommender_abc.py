@@ -452,6 +452,47 @@ class RecommenderABC(ABC):
         ranked = self._rank(uid, range(self.n_items), n, novelty)
         return ranked if threshold is None else [pair for pair in ranked if pair[0] >= threshold]
 
+    def recommend_batch(self, user_ids, n=10, novelty=True, interaction_threshold=None, as_arrays=False):
+        """recommend() for many users in one call (no reference equivalent: recommender_abc.py:445-461 ranks one user per call).
+        Returns one entry per requested user, in request order, each `[(score, item_id), ...]` exactly as recommend(user, n, novelty,
+        interaction_threshold) returns it; an unknown user raises as recommend() does.  as_arrays=True returns
+        (scores float32 [R, n], item_ids object [R, n], counts int64 [R]) instead: row r holds counts[r] entries, then -inf / None."""
+        import numpy as np
+        uids = np.fromiter((self._require_user(user) for user in user_ids), dtype=np.int64)
+        n = self.n_items if n is None else int(n)
+        R = len(uids)
+        if R == 0 or n < 1:
+            idx, val = np.full((R, max(n, 0)), -1, np.int64), np.full((R, max(n, 0)), -np.inf)
+        else:
+            idx, val = self._recommend_batch(uids, n, novelty)
+        keep = idx >= 0
+        if interaction_threshold is not None:                   # (as _recommend: the low entries of a descending list are its tail)
+            keep &= val >= interaction_threshold
+        counts = keep.sum(axis=1).astype(np.int64)
+        to_item = self.interaction_dataset.iid_to_item
+        if not as_arrays:
+            return [[(float(val[r, j]), to_item(int(idx[r, j]))) for j in range(idx.shape[1]) if keep[r, j]] for r in range(R)]
+        scores = np.full(idx.shape, -np.inf, dtype=np.float32)
+        items = np.full(idx.shape, None, dtype=object)
+        for r in range(R):
+            c = 0
+            for j in np.flatnonzero(keep[r]):
+                scores[r, c], items[r, c] = val[r, j], to_item(int(idx[r, j]))
+                c += 1
+        return scores, items, counts
+
+    def _recommend_batch(self, uids, n, novelty):
+        """Hook: internal user ids [R] -> numpy (idx [R, n] internal item ids, -1 = missing; val [R, n], -inf = missing), each row in
+        recommend()'s order.  Default: one _recommend per user — the model's own arithmetic, whatever it is."""
+        import numpy as np
+        idx = np.full((len(uids), n), -1, dtype=np.int64)
+        val = np.full((len(uids), n), -np.inf, dtype=np.float64)
+        for r, uid in enumerate(uids):
+            ranked = self._recommend(int(uid), n, novelty, None)
+            for j, (score, iid) in enumerate(ranked[:n]):
+                idx[r, j], val[r, j] = iid, score
+        return idx, val
+
     def rank(self, user_id, item_ids, novelty=True, skip_invalid_items=True, **kwds):
         uid = self._require_user(user_id)
         ds = self.interaction_dataset

@@ -1,0 +1,387 @@
+// Batched top-n recommendation for CDAE: score[r, i] = sigmoid(h[r, :] . W2T[i, :] + b2[i]) for R users against the whole catalogue,
+// the n best eligible items per user — WITHOUT the [R, n_items] score matrix (drx_cdae_forward + drx_topk write and re-read it:
+// 4 MB per user at a 1 M-item catalogue).  Order = drx_topk's: descending score, ties by LARGER item index (heapq.nlargest over
+// (score, iid), cdae.py:103), carried by the same 64-bit key (monotone score bits << 32 | item).
+//
+// k_recommend   grid (user tiles of 128, item splits).  The products run on the matrix cores in fp32 (v_mfma_f32_32x32x2_f32: bit for
+//               bit a k-ordered fmaf chain; the item's bias is added to the finished sum) with the ITEM rows as the A operand and the
+//               users' hidden rows (LDS) as B, so that in the 32 x 32 accumulator tile a lane owns ONE user (column = lane & 31) and
+//               16 of its items per tile.  A wave owns 32 users and walks the split's items 128 at a time (4 tiles: 4 independent
+//               accumulators); the four waves of a workgroup read the same item rows (L1) for different users.  The W2T fragments
+//               of the next k chunk / item block and the block's biases are loaded while the current chunk multiplies.
+//               Selection is lane-local: every lane (user, half of the tile's rows) keeps its own candidate list in the scratch, its
+//               length, the key of its n-th best so far and a LOGIT bound derived from it in registers.  A finished block costs an add
+//               and a compare per score; only logits above the bound get the sigmoid, the exact key compare and a push.  A list that
+//               reaches its capacity (2 n) is cut back to its n best ELIGIBLE keys by the whole wave (exclusion lookup = a binary
+//               search in the user's CSR row, one key per lane; then the rank of every key among the list's keys, through LDS),
+//               which also raises the lane's bound.  No atomic read-modify-write: a list has one writer, and what it ends up
+//               holding is the n largest eligible keys its lane saw.
+// k_recommend_merge   one workgroup per user: the 2 x splits lists of the user ordered in LDS (bitonic network on <= 16384 keys),
+//               the n largest written out.
+// Every score is the same fmaf chain whatever the tile, the split or the neighbours of its user, and the keys are unique, so the
+// result is a function of the inputs alone (bit-identical between calls, request orders and chunkings).
+#include <hip/hip_runtime.h>
+#include "drx_common.hpp"
+
+namespace drx {
+namespace {
+
+typedef float f32x16 __attribute__((ext_vector_type(16)));
+typedef unsigned long long u64;
+
+constexpr int kRecUsers = 128;          // users of a workgroup: 32 per wave
+constexpr int kRecItems = 128;          // items of a block step: 4 accumulator tiles of 32
+constexpr int kRecKC = 16;              // k columns of a chunk
+constexpr int kRecKT = kRecKC / 8;      // k steps of 8 per chunk: 4 MFMAs per tile each
+constexpr int kRecMaxN = 128, kRecMaxLd = 256;
+constexpr int kRecMaxMerge = 16384;     // keys the merge orders in LDS (128 KiB)
+constexpr int kRecTargetGroups = 256;   // workgroups a launch aims for: one per CU (the kernel's registers and LDS allow no more)
+
+__device__ __forceinline__ uint32_t rec_ordered_bits(float f) {
+  if (f == 0.0f) f = 0.0f;              // -0.0 == 0.0 (as drx_topk)
+  const uint32_t u = __float_as_uint(f);
+  return (u & 0x80000000u) ? ~u : (u | 0x80000000u);
+}
+__device__ __forceinline__ float rec_score_of(u64 key) {
+  const uint32_t o = (uint32_t)(key >> 32);
+  return __uint_as_float((o & 0x80000000u) ? (o ^ 0x80000000u) : ~o);
+}
+
+// A logit bound for a score threshold s: every z below it has sigmoidf_(z) < s STRICTLY, whatever the rounding of expf (taken as
+// |computed - true| <= 1e-6 relative; the division and the addition of sigmoidf_ are monotone).  d ln(sigmoid) / dz = 1 - sigmoid:
+//   s <= 1/2                 a step of 4e-6 in z lowers the score by more than 2e-6 relative
+//   1 - s >= 2^-12           a step of 2e-6 * 4096 < 0.01 does
+//   1 - s <  2^-12           (z > 8.3, towards saturation, where many logits share one score) the constant 8: sigmoid(8) = 0.99966
+// 0.02 + 1e-5 |z| covers these and the error of the logf below.  s == 0 (or an empty list): no bound.
+__device__ __forceinline__ float rec_logit_bound(float s) {
+  if (!(s > 0.0f)) return -INFINITY;
+  const float om = 1.0f - s;
+  if (om < 0x1p-12f) return 8.0f;
+  const float z = logf(s / om);
+  return z - 0.02f - 1e-5f * fabsf(z);
+}
+
+struct RecArgs {
+  const float *W2T, *b2, *h;
+  const int32_t *uid;
+  const int64_t *xptr;          // exclusion CSR (or null)
+  const int32_t *xidx;
+  int R, N, ld;
+  int nch;                      // k chunks of kRecKC
+  int hs;                       // floats between users' rows in LDS
+  int n, cap;                   // list: wanted / capacity
+  int splits, ips;              // item splits, items per split (a multiple of kRecItems)
+  u64 *lists;                   // [tiles][splits][128][2][cap]
+  int *counts;                  // [tiles][splits][128][2]
+};
+
+// W2T fragments of one chunk of one item block: tile s, k step t: the lane's item row (lane & 31), 4 consecutive k of its half.
+// MFMA (t, c) multiplies k = 8 t + c (lanes 0..31) and k = 8 t + 4 + c (lanes 32..63) of the chunk.
+__device__ __forceinline__ void rec_load_a(const RecArgs &A, int item0, int kc, int col, int hh, float4 (&a)[4][kRecKT]) {
+#pragma unroll
+  for (int s = 0; s < 4; ++s) {
+    const unsigned row = min((unsigned)item0 + 32u * s + col, (unsigned)A.N - 1u);   // (rows behind the catalogue: any valid row, never looked at)
+    const float *p = A.W2T + (size_t)row * A.ld;
+#pragma unroll
+    for (int t = 0; t < kRecKT; ++t) {
+      // (no branch around a load: k steps behind the row read the row's last float4 — their columns of h are ZERO in LDS)
+      a[s][t] = *reinterpret_cast<const float4 *>(p + min(kc * kRecKC + 8 * t + 4 * hh, A.ld - 4));
+    }
+  }
+}
+
+// the biases of a block in accumulator layout: register g * 4 + q of tile s = item item0 + 32 s + 8 g + 4 half + q
+__device__ __forceinline__ void rec_load_bias(const RecArgs &A, int item0, int hh, f32x16 (&c)[4]) {
+  const bool whole = (unsigned)item0 + (unsigned)kRecItems <= (unsigned)A.N;       // wave-uniform: every block but the catalogue's last
+#pragma unroll
+  for (int s = 0; s < 4; ++s) {
+#pragma unroll
+    for (int g = 0; g < 4; ++g) {
+      const unsigned base = (unsigned)item0 + 32u * s + 8u * g + 4u * hh, N = (unsigned)A.N;   // (unsigned: n_items may be 2^31 - 1)
+      float4 v = f4_zero();
+      if (whole) v = *reinterpret_cast<const float4 *>(A.b2 + base);
+      else {
+        if (base < N) v.x = A.b2[base];
+        if (base + 1 < N) v.y = A.b2[base + 1];
+        if (base + 2 < N) v.z = A.b2[base + 2];
+        if (base + 3 < N) v.w = A.b2[base + 3];
+      }
+      c[s][4 * g] = v.x; c[s][4 * g + 1] = v.y; c[s][4 * g + 2] = v.z; c[s][4 * g + 3] = v.w;
+    }
+  }
+}
+
+__device__ __forceinline__ bool rec_excluded(const int32_t *xidx, int64_t lo, int64_t hi, int item) {
+  const int64_t end = hi;
+  while (lo < hi) {
+    const int64_t mid = lo + ((hi - lo) >> 1);
+    if (xidx[mid] < item) lo = mid + 1; else hi = mid;
+  }
+  return lo < end && xidx[lo] == item;
+}
+
+// The list of lane L (wave-uniform) cut back to its n best, in order, by the whole wave; L's registers follow.  The exclusion lookup
+// happens HERE, for all keys of the list at once (a push does not wait for a binary search of dependent loads): excluded keys drop
+// out before the ranks are taken, so the n-th best — the lane's new bound — is the n-th best ELIGIBLE key.
+__device__ __forceinline__ void rec_compact(const RecArgs &A, u64 *wave_lists, u64 *cb, int L, int lane, int64_t xlo, int64_t xhi, int &cnt,
+                                            u64 &tkey, float &zt) {
+  const int cL = __shfl(cnt, L, kWave);
+  const int64_t lo = __shfl(xlo, L, kWave), hi = __shfl(xhi, L, kWave);
+  u64 *list = wave_lists + (size_t)(2 * (L & 31) + (L >> 5)) * A.cap;
+  // L's pushes have reached the L2 (this fence waits for the wave's stores) and are read from there (the loads pass the L1):
+  // writer and readers are lanes of one wave, nothing beyond the CU's own L2 is involved
+  __builtin_amdgcn_fence(__ATOMIC_RELEASE, "workgroup");
+  u64 k[4];
+  int rank[4];
+  int alive = 0;
+#pragma unroll
+  for (int j = 0; j < 4; ++j) {
+    const int i = lane + 64 * j;
+    k[j] = i < cL ? __hip_atomic_load(list + i, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) : 0ull;
+    if (A.xptr && k[j] != 0ull && rec_excluded(A.xidx, lo, hi, (int)(uint32_t)k[j])) k[j] = 0ull;
+    cb[i] = k[j];
+    rank[j] = 0;
+    alive += __popcll(__ballot(k[j] != 0ull));
+  }
+  wave_lds_sync();
+  for (int i = 0; i < cL; ++i) {
+    const u64 o = cb[i];
+#pragma unroll
+    for (int j = 0; j < 4; ++j) rank[j] += o > k[j] ? 1 : 0;
+  }
+#pragma unroll
+  for (int j = 0; j < 4; ++j) {
+    if (k[j] != 0ull && rank[j] < A.n) list[rank[j]] = k[j];        // (keys are unique: the ranks of the live ones are 0 .. alive - 1)
+    if (k[j] != 0ull && rank[j] == A.n - 1) cb[256] = k[j];
+  }
+  wave_lds_sync();
+  const u64 nth = cb[256];
+  if (lane == L) {
+    if (alive >= A.n) { tkey = nth; zt = rec_logit_bound(rec_score_of(nth)); }    // (fewer: the bound stays where it was)
+    cnt = min(alive, A.n);
+  }
+  wave_lds_sync();
+}
+
+__global__ __launch_bounds__(256) void k_recommend(RecArgs A) {
+  extern __shared__ __align__(16) float lds[];
+  float *h_s = lds;                                                   // [128][hs]
+  float *dump_all = h_s + (size_t)kRecUsers * A.hs;                   // [4 waves][16 registers][64 lanes]
+  u64 *cb_all = reinterpret_cast<u64 *>(dump_all + 4 * 16 * 64);      // [4 waves][256 keys + the n-th + pad]
+  const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6, col = lane & 31, hh = lane >> 5;
+  const int tile = blockIdx.x, sp = blockIdx.y;
+  const int r0 = tile * kRecUsers;
+  const int ldp4 = A.nch * (kRecKC / 4);
+  for (int i = tid; i < kRecUsers * ldp4; i += 256) {
+    const int u = i / ldp4, c4 = i - u * ldp4;
+    float4 v = f4_zero();
+    if (r0 + u < A.R && 4 * c4 < A.ld) v = *reinterpret_cast<const float4 *>(A.h + (size_t)(r0 + u) * A.ld + 4 * c4);
+    *reinterpret_cast<float4 *>(h_s + (size_t)u * A.hs + 4 * c4) = v;
+  }
+  __syncthreads();
+  if (r0 + wave * 32 >= A.R) return;                                  // (no user in this wave; no barrier below)
+
+  float *dump = dump_all + wave * (16 * 64);
+  u64 *cb = cb_all + wave * 258;
+  const int ul = wave * 32 + col, r = r0 + ul;
+  const bool uvalid = r < A.R;
+  int64_t xlo = 0, xhi = 0;
+  if (uvalid && A.xptr) { const int u = A.uid[r]; xlo = A.xptr[u]; xhi = A.xptr[u + 1]; }
+  const size_t group = (size_t)tile * A.splits + sp;
+  u64 *wave_lists = A.lists + ((group * kRecUsers + wave * 32) * 2) * (size_t)A.cap;
+  u64 *mylist = wave_lists + (size_t)(2 * col + hh) * A.cap;
+  float zt = uvalid ? -INFINITY : INFINITY;                          // logits below it cannot enter the list
+  u64 tkey = 0ull;                                                    // the list's n-th best at its last compaction
+  int cnt = 0;
+
+  const int i_begin = sp * A.ips, i_end = (int)min((int64_t)A.N, (int64_t)i_begin + A.ips);
+  const int nblocks = (int)(((int64_t)i_end - i_begin + kRecItems - 1) / kRecItems);
+  const float *hrow = h_s + (size_t)ul * A.hs + 4 * hh;
+
+  f32x16 acc[4], bias[4];
+  float4 a0[4][kRecKT], a1[4][kRecKT];            // W2T fragments of the even / odd chunk in flight (nch is even)
+#pragma unroll
+  for (int s = 0; s < 4; ++s)
+#pragma unroll
+    for (int e = 0; e < 16; ++e) acc[s][e] = 0.f;
+  rec_load_a(A, i_begin, 0, col, hh, a0);
+
+  // one chunk: 4 MFMAs per tile and k step, the 4 tiles' accumulators back to back (independent)
+#define DRX_REC_CHUNK(a, kc)                                                                                         \
+  _Pragma("unroll") for (int t = 0; t < kRecKT; ++t) {                                                               \
+    if ((kc) * kRecKC + 8 * t < A.ld) {                       /* wave-uniform: k steps behind the row are skipped */  \
+      const float4 b = *reinterpret_cast<const float4 *>(hrow + (kc) * kRecKC + 8 * t);                              \
+      _Pragma("unroll") for (int s = 0; s < 4; ++s) acc[s] = __builtin_amdgcn_mfma_f32_32x32x2f32(a[s][t].x, b.x, acc[s], 0, 0, 0); \
+      _Pragma("unroll") for (int s = 0; s < 4; ++s) acc[s] = __builtin_amdgcn_mfma_f32_32x32x2f32(a[s][t].y, b.y, acc[s], 0, 0, 0); \
+      _Pragma("unroll") for (int s = 0; s < 4; ++s) acc[s] = __builtin_amdgcn_mfma_f32_32x32x2f32(a[s][t].z, b.z, acc[s], 0, 0, 0); \
+      _Pragma("unroll") for (int s = 0; s < 4; ++s) acc[s] = __builtin_amdgcn_mfma_f32_32x32x2f32(a[s][t].w, b.w, acc[s], 0, 0, 0); \
+    }                                                                                                                \
+  }
+
+  for (int blk = 0; blk < nblocks; ++blk) {
+    const int item0 = i_begin + blk * kRecItems;
+    for (int kc = 0; kc + 2 < A.nch; kc += 2) {                      // the fragments of the next chunk load while this one multiplies
+      rec_load_a(A, item0, kc + 1, col, hh, a1);
+      DRX_REC_CHUNK(a0, kc)
+      rec_load_a(A, item0, kc + 2, col, hh, a0);
+      DRX_REC_CHUNK(a1, kc + 1)
+    }
+    // the block's last two chunks; beside them its biases and the first fragments of the next block
+    rec_load_a(A, item0, A.nch - 1, col, hh, a1);
+    rec_load_bias(A, item0, hh, bias);
+    DRX_REC_CHUNK(a0, A.nch - 2)
+    rec_load_a(A, blk + 1 < nblocks ? item0 + kRecItems : item0, 0, col, hh, a0);
+    DRX_REC_CHUNK(a1, A.nch - 1)
+#undef DRX_REC_CHUNK
+    // the block's 128 x 32 logits of this wave: an add and a compare per score
+#pragma unroll
+    for (int s = 0; s < 4; ++s) {
+      uint32_t m = 0;
+#pragma unroll
+      for (int e = 0; e < 16; ++e) {
+        acc[s][e] += bias[s][e];
+        m |= (acc[s][e] >= zt) ? (1u << e) : 0u;
+      }
+      if (__ballot(m != 0)) {                                         // rare once the lists are warm
+#pragma unroll
+        for (int e = 0; e < 16; ++e) dump[e * 64 + lane] = acc[s][e]; // (a lane reads back its own words only)
+        const int ibase = item0 + 32 * s + 4 * hh;
+        while (__ballot(m != 0)) {
+          if (m != 0) {
+            const int e = __ffs(m) - 1;
+            m &= m - 1;
+            const unsigned item = (unsigned)ibase + 8u * (e >> 2) + (e & 3);
+            if (uvalid && item < (unsigned)i_end) {
+              const float sc = sigmoidf_(dump[e * 64 + lane]);
+              const u64 key = ((u64)rec_ordered_bits(sc) << 32) | item;
+              if (key > tkey) { mylist[cnt] = key; ++cnt; }
+            }
+          }
+          u64 full = __ballot(cnt >= A.cap);
+          while (full) {
+            const int L = __ffsll((long long)full) - 1;
+            full &= full - 1;
+            rec_compact(A, wave_lists, cb, L, lane, xlo, xhi, cnt, tkey, zt);
+          }
+        }
+      }
+#pragma unroll
+      for (int e = 0; e < 16; ++e) acc[s][e] = 0.f;
+    }
+  }
+  // every list down to its n best eligible keys at most, its length beside it
+  u64 over = __ballot(cnt > A.n || (A.xptr && cnt > 0));
+  while (over) {
+    const int L = __ffsll((long long)over) - 1;
+    over &= over - 1;
+    rec_compact(A, wave_lists, cb, L, lane, xlo, xhi, cnt, tkey, zt);
+  }
+  if (uvalid) A.counts[(group * kRecUsers + ul) * 2 + hh] = cnt;
+}
+
+__global__ __launch_bounds__(kBlock) void k_recommend_merge(const u64 *__restrict__ lists, const int *__restrict__ counts, int n, int cap,
+                                                            int splits, int npad, int32_t *__restrict__ out_idx,
+                                                            float *__restrict__ out_val) {
+  extern __shared__ __align__(16) unsigned long long keys[];
+  const size_t r = blockIdx.x;
+  const size_t tile = r / kRecUsers, ul = r % kRecUsers;
+  for (int i = threadIdx.x; i < npad; i += kBlock) {
+    u64 key = 0ull;
+    const int slot = i / n, j = i - slot * n;
+    if (slot < 2 * splits) {
+      const size_t lid = ((tile * splits + (slot >> 1)) * kRecUsers + ul) * 2 + (slot & 1);
+      if (j < min(counts[lid], n)) key = lists[lid * cap + j];
+    }
+    keys[i] = key;
+  }
+  for (int size = 2; size <= npad; size <<= 1) {
+    for (int stride = size >> 1; stride > 0; stride >>= 1) {
+      __syncthreads();
+      for (int t = threadIdx.x; t < (npad >> 1); t += kBlock) {
+        const int a = 2 * t - (t & (stride - 1));
+        const int b = a + stride;
+        const u64 ka = keys[a], kb = keys[b];
+        const bool desc = (a & size) == 0;
+        if (desc ? (ka < kb) : (ka > kb)) { keys[a] = kb; keys[b] = ka; }
+      }
+    }
+  }
+  __syncthreads();
+  for (int j = threadIdx.x; j < n; j += kBlock) {
+    const u64 key = j < npad ? keys[j] : 0ull;
+    if (key == 0ull) { out_idx[r * n + j] = -1; out_val[r * n + j] = -INFINITY; }
+    else { out_idx[r * n + j] = (int32_t)(key & 0xFFFFFFFFull); out_val[r * n + j] = rec_score_of(key); }
+  }
+}
+
+struct RecPlan {
+  int tiles, splits, ips, cap, nch, hs, npad;
+  size_t lds_main, lds_merge;
+};
+
+bool rec_plan(int R, int n_items, int ld, int n, RecPlan &P) {
+  if (R < 1 || n_items < 1 || ld < 4 || (ld & 3) || ld > kRecMaxLd || n < 1 || n > kRecMaxN) return false;
+  P.tiles = (R + kRecUsers - 1) / kRecUsers;
+  const int blocks = (int)(((int64_t)n_items + kRecItems - 1) / kRecItems);
+  int64_t want = (kRecTargetGroups + P.tiles - 1) / P.tiles;
+  if (want > kRecMaxMerge / (2 * n)) want = kRecMaxMerge / (2 * n);
+  if (want > blocks) want = blocks;
+  if (want > 65535) want = 65535;
+  if (want < 1) want = 1;
+  const int bps = (int)((blocks + want - 1) / want);                 // item blocks per split
+  P.ips = bps * kRecItems;
+  P.splits = (blocks + bps - 1) / bps;
+  P.cap = 2 * n < 32 ? 32 : 2 * n;
+  P.nch = 2 * ((ld + 2 * kRecKC - 1) / (2 * kRecKC));                // (even: the kernel alternates two fragment buffers)
+  P.hs = P.nch * kRecKC + 4;                                         // + 4: the 32 users of a wave spread over the LDS banks
+  P.npad = 2;
+  while (P.npad < 2 * P.splits * n) P.npad <<= 1;
+  P.lds_main = ((size_t)kRecUsers * P.hs + 4 * 16 * 64) * sizeof(float) + 4 * 258 * sizeof(u64);
+  P.lds_merge = (size_t)P.npad * sizeof(u64);
+  return true;
+}
+
+struct RecLayout { u64 *lists; int *counts; };
+RecLayout rec_layout(Carver &cv, const RecPlan &P) {
+  RecLayout L;
+  const size_t n_lists = (size_t)P.tiles * P.splits * kRecUsers * 2;
+  L.lists = cv.take<u64>(n_lists * P.cap);
+  L.counts = cv.take<int>(n_lists);
+  return L;
+}
+
+}  // namespace
+}  // namespace drx
+
+extern "C" size_t drx_cdae_recommend_scratch_bytes(int32_t R, int32_t n_items, int32_t ld, int32_t n) {
+  drx::RecPlan P;
+  if (!drx::rec_plan(R, n_items, ld, n, P)) return 0;
+  drx::Carver cv(nullptr, 0);
+  (void)drx::rec_layout(cv, P);
+  return drx::align_up(cv.off, 256) + 256;
+}
+
+extern "C" int drx_cdae_recommend(const DrxCdaeParams *p, const float *h, const int32_t *uid, int32_t R, int32_t n,
+                                  const int64_t *excl_indptr, const int32_t *excl_indices, int32_t *out_idx, float *out_val,
+                                  void *scratch, size_t scratch_bytes, void *stream) {
+  if (!p || !h || !out_idx || !out_val || !p->W2T || !p->b2 || R < 1 || n < 1 || p->n_items < 1 || p->ld < 4 || (p->ld & 3)) return DRX_EINVAL;
+  if ((excl_indptr != nullptr) != (excl_indices != nullptr) || (excl_indptr && !uid)) return DRX_EINVAL;
+  drx::RecPlan P;
+  if (!drx::rec_plan(R, p->n_items, p->ld, n, P)) return DRX_ENOTIMPL;      // n > 128 or rows wider than 256 floats: drx_cdae_forward + drx_topk
+  if (!scratch) return DRX_ESCRATCH;
+  drx::Carver cv(scratch, scratch_bytes);
+  const drx::RecLayout L = drx::rec_layout(cv, P);
+  if (!cv.ok()) return DRX_ESCRATCH;
+  hipStream_t st = (hipStream_t)stream;
+  drx::RecArgs A;
+  A.W2T = p->W2T; A.b2 = p->b2; A.h = h; A.uid = uid; A.xptr = excl_indptr; A.xidx = excl_indices;
+  A.R = R; A.N = p->n_items; A.ld = p->ld; A.nch = P.nch; A.hs = P.hs; A.n = n; A.cap = P.cap; A.splits = P.splits; A.ips = P.ips;
+  A.lists = L.lists; A.counts = L.counts;
+  DRX_HIP(hipFuncSetAttribute((const void *)drx::k_recommend, hipFuncAttributeMaxDynamicSharedMemorySize, (int)P.lds_main));
+  hipLaunchKernelGGL(drx::k_recommend, dim3(P.tiles, P.splits), dim3(256), P.lds_main, st, A);
+  DRX_HIP(hipFuncSetAttribute((const void *)drx::k_recommend_merge, hipFuncAttributeMaxDynamicSharedMemorySize, (int)P.lds_merge));
+  hipLaunchKernelGGL(drx::k_recommend_merge, dim3(R), dim3(drx::kBlock), P.lds_merge, st, L.lists, L.counts, n, P.cap, P.splits, P.npad,
+                     out_idx, out_val);
+  DRX_LAUNCH_CHECK();
+  return DRX_OK;
+}

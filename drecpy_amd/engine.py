@@ -659,6 +659,88 @@ class CdaeEngine:
                              stream_ptr(self.device)), 'drx_topk')
         return out_idx, out_val
 
+    # ---- batched top-n recommendation (include/drx.h drx_cdae_recommend) ------------------------------
+    RECOMMEND_CHUNK_USERS = 16384          # users per launch of the fused path: bounds its scratch (candidate keys only)
+    RECOMMEND_FALLBACK_BYTES = 1 << 30     # score-matrix bytes per chunk of the forward + drx_topk route (as ranking_evaluation's chunks)
+    RECOMMEND_MIN_FUSED_USERS = 1          # requests of fewer users take the forward + drx_topk route (scripts/recommend_bench.py measures both)
+
+    def set_exclusions(self, indptr, indices):
+        """CSR over users (columns ascending and unique) of the items recommend() never returns for a user; None = none."""
+        if indptr is None:
+            self._excl = None
+            return
+        ip = np.ascontiguousarray(indptr, dtype=np.int64)
+        ix = np.ascontiguousarray(indices, dtype=np.int32)
+        assert len(ip) == self.n_users + 1 and int(ip[-1]) == len(ix)
+        d_ip = torch.as_tensor(ip).to(self.device)
+        d_ix = torch.as_tensor(ix if len(ix) else np.zeros(1, np.int32)).to(self.device)
+        self._excl = (d_ip, d_ix, ip, ix)
+
+    def _hidden_rows(self, uid):
+        """[R, ld] hidden rows of the device users `uid`, as drx_cdae_forward writes them"""
+        bt, alive = self.make_batch(uid, n_touch_slots=0)
+        h = torch.empty(bt.B, self.ld, dtype=torch.float32, device=self.device)
+        check(lib().drx_cdae_forward(C.byref(self._params), C.byref(self._hist), C.byref(bt), ptr(h), None, stream_ptr(self.device)),
+              'drx_cdae_forward')
+        return h
+
+    def recommend(self, uids, n, exclude=None, chunk_users=None):
+        """(idx int32 [R, n], val float32 [R, n]) device tensors: the n best items of every user by (score, item) descending, -1 / -inf
+        behind the last eligible one.  exclude: None = the rows of set_exclusions() where one was given, False = nothing excluded.
+        The hidden rows come from forward(); scores and selection from drx_cdae_recommend, `chunk_users` users at a time — or, outside
+        its domain (n > 128, rows wider than 256 floats) and below RECOMMEND_MIN_FUSED_USERS users, from forward + drx_topk."""
+        uid = self._dev(uids, torch.int32).contiguous()
+        R, n = int(uid.numel()), int(n)
+        assert n >= 1
+        excl = getattr(self, '_excl', None) if exclude is None or exclude is True else None
+        assert not (exclude is True and excl is None), 'recommend(exclude=True) needs set_exclusions()'
+        out_idx = torch.empty(R, n, dtype=torch.int32, device=self.device)
+        out_val = torch.empty(R, n, dtype=torch.float32, device=self.device)
+        if R == 0:
+            return out_idx, out_val
+        L = lib()
+        fused = R >= self.RECOMMEND_MIN_FUSED_USERS and L.drx_cdae_recommend_scratch_bytes(1, self.n_items, self.ld, n) > 0
+        if not fused:
+            return self._recommend_by_matrix(uid, n, excl, out_idx, out_val)
+        chunk = int(chunk_users or self.RECOMMEND_CHUNK_USERS)
+        for lo in range(0, R, chunk):
+            u = uid[lo:lo + chunk]
+            r = int(u.numel())
+            h = self._hidden_rows(u)
+            need = int(L.drx_cdae_recommend_scratch_bytes(r, self.n_items, self.ld, n))
+            sc = getattr(self, '_rec_scratch', None)
+            if sc is None or sc.numel() < need:
+                self._rec_scratch = None
+                sc = self._rec_scratch = torch.empty(need, dtype=torch.uint8, device=self.device)
+            check(L.drx_cdae_recommend(C.byref(self._params), ptr(h), ptr(u), r, n, ptr(excl[0]) if excl else None,
+                                       ptr(excl[1]) if excl else None, ptr(out_idx[lo:lo + r]), ptr(out_val[lo:lo + r]), ptr(sc),
+                                       sc.numel(), stream_ptr(self.device)), 'drx_cdae_recommend')
+        return out_idx, out_val
+
+    def _recommend_by_matrix(self, uid, n, excl, out_idx, out_val):
+        """The score-matrix route: forward + host-built candidate mask + drx_topk, in chunks of users."""
+        R = int(uid.numel())
+        chunk = max(1, min(self.RECOMMEND_FALLBACK_BYTES // (4 * self.n_items), ((1 << 31) - 1) // self.n_items))   # (R * N < 2^31: drx_topk's long rows)
+        host_uid = uid.cpu().numpy()
+        for lo in range(0, R, chunk):
+            u = uid[lo:lo + chunk]
+            r = int(u.numel())
+            _, pred = self.forward(u)
+            mask = None
+            if excl is not None:
+                cand = np.ones((r, self.n_items), dtype=bool)
+                for j, x in enumerate(host_uid[lo:lo + r]):
+                    cand[j, excl[3][excl[2][x]:excl[2][x + 1]]] = False
+                mask = torch.as_tensor(pack_mask_bits(cand).view(np.int32)).to(self.device)
+            k = min(n, self.n_items)
+            idx, val = self.topk(pred, k, mask)
+            out_idx[lo:lo + r, :k] = idx
+            out_val[lo:lo + r, :k] = val
+            if k < n:
+                out_idx[lo:lo + r, k:] = -1
+                out_val[lo:lo + r, k:] = float('-inf')
+        return out_idx, out_val
+
 
 def pack_mask_bits(mask_bool):
     """bool [R,n] (numpy) -> uint32 words; bit (i & 31) of word (i >> 5) is flat element i."""

@@ -1,5 +1,5 @@
 """CDAE in the sampled sparse-Adagrad mode through the ordinary fit() call: triples are drawn on the GPU two batches ahead,
-the touch list of a batch is sorted one batch ahead, only touched rows are updated (engine.SampledPipeline).
+the touch list of a batch is sorted one batch ahead, only touched rows are updated (engine.SampledPipeline).  Ends with top-10 lists for a block of users through recommend_batch.
     python examples/cdae_sampled_scale.py [--users 1000000]"""
 import argparse
 import os
@@ -36,3 +36,9 @@ torch.cuda.synchronize()
 dt = time.time() - t0
 print(f'fit (id map, CSR, sampler, tables + {args.epochs} steps of {args.batch}): {dt:.2f} s')
 print('recommendations for user 0:', model.recommend(0, n=5))
+
+# top-10 lists for a block of users in ONE call: scores and selection fused on the device, no [users, items] score matrix
+block = list(range(min(4096, args.users)))
+t0 = time.time()
+scores, items, counts = model.recommend_batch(block, n=10, as_arrays=True)
+print(f'recommend_batch: top-10 for {len(block)} users in {time.time() - t0:.3f} s; user 0: {list(zip(scores[0, :counts[0]].tolist(), items[0, :counts[0]]))[:5]}')

@@ -763,6 +763,22 @@ size_t drx_topk_scratch_bytes(int32_t R, int32_t n);                 /* the same
 int drx_topk(const float *scores, const uint32_t *cand_mask, int32_t R, int32_t n, int32_t k,
              int32_t *out_idx, float *out_val, void *scratch, size_t scratch_bytes, void *stream);
 
+/* ---- batched top-n recommendation for CDAE (no reference equivalent: recommender_abc.py:445-461 ranks one user per call) ---------------
+ * For each of R users: the n best items of the whole catalogue by score[r, i] = sigmoid(h[r, :] . W2T[i, :] + b2[i]) among those not in
+ * the user's row of the exclusion CSR — order as drx_topk (descending score, ties by larger index), out_idx / out_val [R, n], missing
+ * = -1 / -inf.  The [R, n_items] score matrix is never written: the products run on the matrix cores in fp32 (a k-ordered fmaf chain,
+ * then the bias; drx_cdae_forward sums the same products in another order, so a score may differ from its prediction in the last ulp),
+ * the selection in registers, and the scratch holds candidate keys only: R (rounded up to 128) x item splits x 2 lists of max(2 n, 32)
+ * keys, whatever n_items.  The result is a function of the inputs alone: bit-identical between calls, request orders and chunkings.
+ *   h            [R, ld] hidden rows as drx_cdae_forward writes them (bt->uid = uid, pred = NULL)
+ *   uid          [R] the users (names the rows of the exclusion CSR; may be NULL without one)
+ *   excl_indptr  [n_users + 1], excl_indices: items never returned for a user, columns ascending and unique; both NULL = none
+ * Fused domain: ld <= 256, n <= 128; outside it DRX_ENOTIMPL (drx_cdae_recommend_scratch_bytes: 0) and the caller takes
+ * drx_cdae_forward + drx_topk. */
+size_t drx_cdae_recommend_scratch_bytes(int32_t R, int32_t n_items, int32_t ld, int32_t n);
+int drx_cdae_recommend(const DrxCdaeParams *p, const float *h, const int32_t *uid, int32_t R, int32_t n, const int64_t *excl_indptr,
+                       const int32_t *excl_indices, int32_t *out_idx, float *out_val, void *scratch, size_t scratch_bytes, void *stream);
+
 /* ---- stable device radix sort of (key, val) pairs (the inverted-index builder of the sparse steps; ties keep their input order).
  * Every key must be < 2^key_bits: the sort runs ceil(key_bits / digit) passes of 8-, 10- or 11-bit digits, i.e. it orders on
  * passes * digit >= key_bits bits — bits above key_bits are NOT ignored (DRX_EINVAL is not raised for them: the result is then ordered
