@@ -86,17 +86,23 @@ inline Geom pick_geom(int ld) {
   return {64, 4};
 }
 
-#define DRX_DISPATCH_GEOM(ld, CALL)                        \
-  do {                                                     \
-    drx::Geom g_ = drx::pick_geom(ld);                     \
-    if (g_.G == 4) { CALL(4, 1); }                         \
-    else if (g_.G == 8) { CALL(8, 1); }                    \
-    else if (g_.G == 16) { CALL(16, 1); }                  \
-    else if (g_.G == 32) { CALL(32, 1); }                  \
-    else if (g_.J == 1) { CALL(64, 1); }                   \
-    else if (g_.J == 2) { CALL(64, 2); }                   \
-    else { CALL(64, 4); }                                  \
-  } while (0)
+// A geometry as a type: inside the callable dispatch_geom is given, G and J are compile-time constants.
+template <int G_, int J_> struct GeomT { static constexpr int G = G_, J = J_; };
+
+// Calls f with the geometry of a row of ld floats and returns f's status.  f is a generic lambda,
+//   [&](auto g) -> int { constexpr int G = decltype(g)::G, J = decltype(g)::J; ...; return DRX_OK; }
+// DRX_HIP / DRX_LAUNCH_CHECK inside it return the lambda's status, which the caller checks.
+template <class F>
+inline int dispatch_geom(int ld, F &&f) {
+  const Geom g = pick_geom(ld);
+  if (g.G == 4) return f(GeomT<4, 1>{});
+  if (g.G == 8) return f(GeomT<8, 1>{});
+  if (g.G == 16) return f(GeomT<16, 1>{});
+  if (g.G == 32) return f(GeomT<32, 1>{});
+  if (g.J == 1) return f(GeomT<64, 1>{});
+  if (g.J == 2) return f(GeomT<64, 2>{});
+  return f(GeomT<64, 4>{});
+}
 
 // Orders the LDS traffic of ONE wave (its private scratch is written by some lanes and read by others): every LDS operation of the
 // wave issued so far has completed.  A workgroup barrier is not needed for that and would tie unrelated waves together.

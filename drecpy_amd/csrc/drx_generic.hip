@@ -424,22 +424,20 @@ static int rows_csr_adam(const int32_t *row_ptr, const int32_t *order, const flo
   if ((p_s != nullptr) != (src_s != nullptr) || (p_s && (!m_s || !v_s))) return DRX_EINVAL;
   if (((uintptr_t)src | (uintptr_t)p | (uintptr_t)m | (uintptr_t)v) & 15) return DRX_EINVAL;
   hipStream_t st = (hipStream_t)stream;
-#define CALL(G, J)                                                                                                          \
-  {                                                                                                                         \
-    const int gpb = kBlock / G;                                                                                             \
-    int blocks = (n_rows + gpb - 1) / gpb;                                                                                  \
-    if (blocks > 8192) blocks = 8192;                                                                                       \
-    if (group > 0)                                                                                                          \
-      hipLaunchKernelGGL((k_rows_csr_adam<G, J, true>), dim3(blocks), dim3(kBlock), 0, st, row_ptr, order, src, src_s, ld, n_rows, p, m, \
-                         v, p_s, m_s, v_s, alpha, alpha_s, l2_coef, beta1, beta2, eps, group);                              \
-    else                                                                                                                    \
-      hipLaunchKernelGGL((k_rows_csr_adam<G, J, false>), dim3(blocks), dim3(kBlock), 0, st, row_ptr, order, src, src_s, ld, n_rows, p, m, \
-                         v, p_s, m_s, v_s, alpha, alpha_s, l2_coef, beta1, beta2, eps, 1);                                  \
-  }
-  DRX_DISPATCH_GEOM(ld, CALL);
-#undef CALL
-  DRX_LAUNCH_CHECK();
-  return DRX_OK;
+  return dispatch_geom(ld, [&](auto g) -> int {
+    constexpr int G = decltype(g)::G, J = decltype(g)::J;
+    constexpr int gpb = kBlock / G;
+    int blocks = (n_rows + gpb - 1) / gpb;
+    if (blocks > 8192) blocks = 8192;
+    if (group > 0)
+      hipLaunchKernelGGL((k_rows_csr_adam<G, J, true>), dim3(blocks), dim3(kBlock), 0, st, row_ptr, order, src, src_s, ld, n_rows, p, m, v,
+                         p_s, m_s, v_s, alpha, alpha_s, l2_coef, beta1, beta2, eps, group);
+    else
+      hipLaunchKernelGGL((k_rows_csr_adam<G, J, false>), dim3(blocks), dim3(kBlock), 0, st, row_ptr, order, src, src_s, ld, n_rows, p, m, v,
+                         p_s, m_s, v_s, alpha, alpha_s, l2_coef, beta1, beta2, eps, 1);
+    DRX_LAUNCH_CHECK();
+    return DRX_OK;
+  });
 }
 
 int drx_rows_csr_adam(const int32_t *row_ptr, const int32_t *order, const float *src, const float *src_s, int32_t ld, int32_t n_rows,
@@ -592,17 +590,15 @@ int drx_scatter_rows(const uint32_t *keys, int32_t T, const float *src, const ui
     DRX_HIP(hipMemsetAsync(mask, 0, mbytes, st));
     hipLaunchKernelGGL(k_mask_mark, dim3((T + 255) / 256 < 2048 ? (T + 255) / 256 : 2048), dim3(256), 0, st, keys, T, W, n_rows, mask);
     ScatterPolicy mpol{src, src_index, coef, src_s, out, out_s, ld};
-#define CALLM(G, J)                                                                                                     \
-  {                                                                                                                     \
-    const int gpb = kBlock / G;                                                                                         \
-    int blocks = (n_rows + gpb - 1) / gpb;                                                                              \
-    if (blocks > 8192) blocks = 8192;                                                                                   \
-    hipLaunchKernelGGL((k_mask_sweep<G, J>), dim3(blocks), dim3(kBlock), 0, st, mask, W, n_rows, mpol);                 \
-  }
-    DRX_DISPATCH_GEOM(ld, CALLM);
-#undef CALLM
-    DRX_LAUNCH_CHECK();
-    return DRX_OK;
+    return dispatch_geom(ld, [&](auto g) -> int {
+      constexpr int G = decltype(g)::G, J = decltype(g)::J;
+      constexpr int gpb = kBlock / G;
+      int blocks = (n_rows + gpb - 1) / gpb;
+      if (blocks > 8192) blocks = 8192;
+      hipLaunchKernelGGL((k_mask_sweep<G, J>), dim3(blocks), dim3(kBlock), 0, st, mask, W, n_rows, mpol);
+      DRX_LAUNCH_CHECK();
+      return DRX_OK;
+    });
   }
   const int bits = bits_for((uint64_t)n_rows + 1);
   Carver cv(scratch, scratch_bytes);
@@ -614,38 +610,33 @@ int drx_scatter_rows(const uint32_t *keys, int32_t T, const float *src, const ui
   L.sb.keys_s = L.keys_s; L.sb.vals_s = L.vals_s;
   ScatterPolicy pol{src, src_index, coef, src_s, out, out_s, ld};
   DRX_HIP(hipMemsetAsync(L.sb.n_span, 0, 2 * sizeof(uint32_t), st));
-#define CALL(G, J)                                                                                                      \
-  {                                                                                                                     \
-    hipLaunchKernelGGL((k_seg_reduce<G, J, ScatterPolicy, 8>), dim3((L.sb.n_chunks + SEG_GPB(G) - 1) / SEG_GPB(G)),     \
-                       dim3(kBlock), 0, st, L.sb, pol);                                                                 \
-    hipLaunchKernelGGL((k_span_short<G, J, ScatterPolicy>), dim3(256), dim3(kBlock), 0, st, L.sb, pol);                 \
-    const size_t lds = ((size_t)(kFixBlock / G) * (ld + 1)) * 4;                                                        \
-    if (lds > 48 * 1024)                                                                                                \
-      DRX_HIP(hipFuncSetAttribute((const void *)k_span_long<G, J, ScatterPolicy>,                                       \
-                                  hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));                               \
-    hipLaunchKernelGGL((k_span_long<G, J, ScatterPolicy>), dim3(64), dim3(kFixBlock), lds, st, L.sb, pol);              \
-  }
-  DRX_DISPATCH_GEOM(ld, CALL);
-#undef CALL
-  DRX_LAUNCH_CHECK();
-  return DRX_OK;
+  return dispatch_geom(ld, [&](auto g) -> int {
+    constexpr int G = decltype(g)::G, J = decltype(g)::J;
+    hipLaunchKernelGGL((k_seg_reduce<G, J, ScatterPolicy, 8>), dim3((L.sb.n_chunks + SEG_GPB(G) - 1) / SEG_GPB(G)), dim3(kBlock), 0, st,
+                       L.sb, pol);
+    hipLaunchKernelGGL((k_span_short<G, J, ScatterPolicy>), dim3(256), dim3(kBlock), 0, st, L.sb, pol);
+    const size_t lds = ((size_t)(kFixBlock / G) * (ld + 1)) * 4;
+    if (lds > 48 * 1024)
+      DRX_HIP(hipFuncSetAttribute((const void *)k_span_long<G, J, ScatterPolicy>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
+    hipLaunchKernelGGL((k_span_long<G, J, ScatterPolicy>), dim3(64), dim3(kFixBlock), lds, st, L.sb, pol);
+    DRX_LAUNCH_CHECK();
+    return DRX_OK;
+  });
 }
 
 int drx_rows_dot(const float *x, int32_t B, const float *table, int32_t n_rows, int32_t ld, const float *bias, float *out,
                  void *stream) {
   if (!x || !table || !out || B < 1 || n_rows < 1 || ld < 4 || (ld & 3) || ld > DRX_MAX_K) return DRX_EINVAL;
   hipStream_t st = (hipStream_t)stream;
-#define CALL(G, J)                                                                                       \
-  {                                                                                                      \
-    const int gpb = kBlock / G;                                                                          \
-    int blocks = (n_rows + gpb - 1) / gpb;                                                               \
-    if (blocks > 2048) blocks = 2048;                                                                    \
-    hipLaunchKernelGGL((k_rows_dot<G, J>), dim3(blocks), dim3(kBlock), 0, st, x, B, table, n_rows, ld, bias, out); \
-  }
-  DRX_DISPATCH_GEOM(ld, CALL);
-#undef CALL
-  DRX_LAUNCH_CHECK();
-  return DRX_OK;
+  return dispatch_geom(ld, [&](auto g) -> int {
+    constexpr int G = decltype(g)::G, J = decltype(g)::J;
+    constexpr int gpb = kBlock / G;
+    int blocks = (n_rows + gpb - 1) / gpb;
+    if (blocks > 2048) blocks = 2048;
+    hipLaunchKernelGGL((k_rows_dot<G, J>), dim3(blocks), dim3(kBlock), 0, st, x, B, table, n_rows, ld, bias, out);
+    DRX_LAUNCH_CHECK();
+    return DRX_OK;
+  });
 }
 
 /* out[0] (+)= sum x[i]^2 in double; out: device double [1 + 1024] (out[1..] is scratch for the block partials) */

@@ -1,7 +1,11 @@
 // Row-group device helpers shared by the libdrx.so kernels (gfx950): coalesced float4 row access for a group of G
-// lanes, the hidden-layer activation, Keras optimizer updates, deterministic block reduction.
+// lanes, the hidden-layer activation, the embedding-bag gather, Keras optimizer updates, deterministic block reduction.
 #pragma once
 #include "drx_common.hpp"
+
+#ifndef DRX_GATHER_ROWS
+#define DRX_GATHER_ROWS 8
+#endif
 
 namespace drx {
 
@@ -47,6 +51,90 @@ __device__ __forceinline__ void hidden_act(const DrxCdaeParams &P, int u, float 
   load_row<G, J>(P.V, (size_t)u, P.ld, lane, v);
   load_row<G, J>(P.b, 0, P.ld, lane, bb);
   hidden_act_rows<G, J>(P, scale, lane, acc, v, bb, h);
+}
+
+// ------------------------------------------------------------------------------------------------
+// the input bag of one batch row (both modes: the sampled step's forward kernels in drx_cdae.hip, reference mode's in
+// drx_cdae_dense.hip) and the auxiliary per-step index the hidden-layer kernel builds in reference ("dense") mode
+// ------------------------------------------------------------------------------------------------
+struct DenseAux {
+  int32_t *cnt;    // [N]       #batch rows having item n as a positive  -> batch-mean target
+  uint32_t *km;    // [N, Bw]   bit b set: item n is a surviving (kept) input of batch row b
+  uint32_t *vm;    // [U, Bw]   bit b set: batch row b belongs to user u
+  uint32_t *tb;    // [B, Nw]   per-row target bits (DRX_TARGETS_PER_ROW) or nullptr
+  int32_t Bw, Nw;
+};
+
+// Gathers scale * sum_{kept} W[n] for one batch row.  MODE 0: plain; 1: also builds DenseAux;
+// 2: also emits the (key,val) touch list of the sampled mode.
+template <int G, int J, int MODE>
+__device__ __forceinline__ void gather_bag(const DrxCdaeParams &P, const DrxHistory &H, const DrxBatch &bt,
+                                           uint32_t qthr, int b, int lane, float4 (&acc)[J],
+                                           const DenseAux &aux, uint32_t *tkeys, uint32_t *tvals,
+                                           int touch_base, int part = 0, int nparts = 1, unsigned long long *stamps = nullptr) {
+  (void)stamps;
+#pragma unroll
+  for (int j = 0; j < J; ++j) acc[j] = f4_zero();
+  const int u = bt.uid[b];
+  const int64_t s = H.indptr[u], e = H.indptr[u + 1];
+#ifdef DRX_STAMPS
+  if (s >= 0) DRX_STAMP(stamps, b, 2, lane);          // (uses s: the stamp waits for the row pointers)
+  bool first_rows = true;
+#endif
+  const uint8_t *kp = bt.keep ? bt.keep + bt.keep_off[b] : nullptr;
+  // a group fetches CH history entries per round: its G lanes hold IPL each, so that narrow groups (rows of <= 32 floats:
+  // G = 4 or 8) do not walk the history in rounds of 4 or 8 dependent index loads
+  constexpr int IPL = G >= 16 ? 1 : 16 / G;
+  constexpr int CH = G * IPL;
+  for (int64_t c = s + (int64_t)part * CH; c < e; c += (int64_t)nparts * CH) {
+    int idx[IPL], kf[IPL];
+#pragma unroll
+    for (int r = 0; r < IPL; ++r) {
+      const int64_t j = c + r * G + lane;
+      idx[r] = -1; kf[r] = 0;
+      if (j < e) {
+        idx[r] = H.indices[j];
+        const uint32_t jj = (uint32_t)(j - s);
+        kf[r] = kp ? (kp[jj] != 0) : (hash_u32(bt.mask_seed, (uint32_t)b, jj) >= qthr);
+        if (MODE == 1) {
+          atomicAdd(&aux.cnt[idx[r]], 1);
+          if (aux.tb) atomicOr(&aux.tb[(size_t)b * aux.Nw + (idx[r] >> 5)], 1u << (idx[r] & 31));
+          if (kf[r]) atomicOr(&aux.km[(size_t)idx[r] * aux.Bw + (b >> 5)], 1u << (b & 31));
+        }
+        if (MODE == 2) {
+          tkeys[touch_base + jj] = kf[r] ? (uint32_t)idx[r] : DRX_KEY_NONE;
+          tvals[touch_base + jj] = (uint32_t)b;
+        }
+      }
+    }
+    const int n_here = (int)((e - c) < (int64_t)CH ? (e - c) : (int64_t)CH);
+    constexpr int NF = J == 1 ? DRX_GATHER_ROWS : 4;       // rows in flight per group
+#ifdef DRX_STAMPS
+    if (first_rows && idx[0] >= -1) DRX_STAMP(stamps, b, 3, lane);      // (uses idx: the stamp waits for the indices)
+#endif
+    for (int t = 0; t < n_here; t += NF) {
+      float4 r[NF][J];
+#pragma unroll
+      for (int q = 0; q < NF; ++q) {
+        const int tt = t + q;
+        int si = idx[0], sk = kf[0];
+#pragma unroll
+        for (int rr = 1; rr < IPL; ++rr) { si = (tt / G == rr) ? idx[rr] : si; sk = (tt / G == rr) ? kf[rr] : sk; }
+        const int iq = __shfl(si, tt % G, G);
+        const int kq = (tt < n_here) ? __shfl(sk, tt % G, G) : 0;
+#pragma unroll
+        for (int jx = 0; jx < J; ++jx) r[q][jx] = f4_zero();
+        if (kq) load_row<G, J>(P.W, (size_t)iq, P.ld, lane, r[q]);
+      }
+#pragma unroll
+      for (int q = 0; q < NF; ++q)
+#pragma unroll
+        for (int jx = 0; jx < J; ++jx) f4_add(acc[jx], r[q][jx]);
+#ifdef DRX_STAMPS
+      if (first_rows && acc[0].x == acc[0].x) { DRX_STAMP(stamps, b, 4, lane); first_rows = false; }      // (uses acc: after the first rows landed)
+#endif
+    }
+  }
 }
 
 // ------------------------------------------------------------------------------------------------

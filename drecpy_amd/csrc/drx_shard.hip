@@ -851,17 +851,15 @@ int drx_shard_gather_rows(const DrxCdaeParams *p, const DrxShard *sh, const uint
   if (rc) return rc;
   if (g.bypass && sh->world == 1) return DRX_OK;               // every request is the rank's own: nothing to gather
   hipStream_t st = (hipStream_t)stream;
-#define CALL(G, J)                                                                                                   \
-  {                                                                                                                  \
-    const int per = (kBlock / G) * (J == 1 ? 4 : 2);                                                                 \
-    int blocks = (n + per - 1) / per;                                                                                \
-    if (blocks > 16384) blocks = 16384;                                                                              \
-    hipLaunchKernelGGL((k_shard_gather_rows<G, J>), dim3(blocks), dim3(kBlock), 0, st, *p, g, so, recv_keys, n, out); \
-  }
-  DRX_DISPATCH_GEOM(p->ld, CALL);
-#undef CALL
-  DRX_LAUNCH_CHECK();
-  return DRX_OK;
+  return dispatch_geom(p->ld, [&](auto gm) -> int {
+    constexpr int G = decltype(gm)::G, J = decltype(gm)::J;
+    constexpr int per = (kBlock / G) * (J == 1 ? 4 : 2);
+    int blocks = (n + per - 1) / per;
+    if (blocks > 16384) blocks = 16384;
+    hipLaunchKernelGGL((k_shard_gather_rows<G, J>), dim3(blocks), dim3(kBlock), 0, st, *p, g, so, recv_keys, n, out);
+    DRX_LAUNCH_CHECK();
+    return DRX_OK;
+  });
 }
 
 size_t drx_shard_step_scratch_bytes(const DrxCdaeParams *p, int32_t B, int32_t n_touch_slots) {
@@ -905,11 +903,12 @@ int drx_shard_step_local(const DrxCdaeParams *p, const DrxOptim *opt, const DrxS
   BiasArgs BA{B.dz1, B.bpart, B.lossb, B.lossb /* non-null: the loss partials are always taken */, bt->B, n_bpart, rows_per_block};
   // (streamed: the places in the exchange buffer are 32-bit float offsets too, ShardXfer::foff)
   const ReduceForm form = reduce_form(opt->kind, bt->B, B.T, key_params(*p, *sh));
-#define CALL(G, J) rc = opt->kind == DRX_OPT_ADAGRAD                                                                  \
-    ? local_launches<G, J, DRX_OPT_ADAGRAD>(form, *p, *opt, *hist, *bt, scale, qthr, loss_kind, S, SB, PB, L.R.plan, BA, g.units, events, st) \
-    : local_launches<G, J, -1>(form, *p, *opt, *hist, *bt, scale, qthr, loss_kind, S, SB, PB, L.R.plan, BA, g.units, events, st)
-  DRX_DISPATCH_GEOM(p->ld, CALL);
-#undef CALL
+  rc = dispatch_geom(p->ld, [&](auto gm) -> int {
+    constexpr int G = decltype(gm)::G, J = decltype(gm)::J;
+    return opt->kind == DRX_OPT_ADAGRAD
+        ? local_launches<G, J, DRX_OPT_ADAGRAD>(form, *p, *opt, *hist, *bt, scale, qthr, loss_kind, S, SB, PB, L.R.plan, BA, g.units, events, st)
+        : local_launches<G, J, -1>(form, *p, *opt, *hist, *bt, scale, qthr, loss_kind, S, SB, PB, L.R.plan, BA, g.units, events, st);
+  });
   if (rc) return rc;
   DRX_LAUNCH_CHECK();
   return DRX_OK;
@@ -938,22 +937,20 @@ int drx_shard_apply(const DrxCdaeParams *p, const DrxOptim *opt, const DrxShard 
     }
   }
   hipStream_t st = (hipStream_t)stream;
-#define CALL(G, J)                                                                                                     \
-  {                                                                                                                    \
-    const int gpb = (kBlock / G) * (J == 1 ? 4 : 2);                                                                   \
-    int blocks = (n + gpb - 1) / gpb;                                                                                  \
-    if (blocks > 16384) blocks = 16384;                                                                                \
-    if (opt->kind == DRX_OPT_ADAGRAD)                                                                                  \
-      hipLaunchKernelGGL((k_shard_apply<G, J, DRX_OPT_ADAGRAD>), dim3(blocks + 1), dim3(kBlock), 0, st, *p, *opt, g, b_norm, so,    \
-                         recv_keys, n, (const uint32_t *)table, grad_recv, blocks, loss_out, do_bias);                 \
-    else                                                                                                               \
-      hipLaunchKernelGGL((k_shard_apply<G, J, -1>), dim3(blocks + 1), dim3(kBlock), 0, st, *p, *opt, g, b_norm, so, recv_keys, n, \
-                         (const uint32_t *)table, grad_recv, blocks, loss_out, do_bias);                               \
-  }
-  DRX_DISPATCH_GEOM(p->ld, CALL);
-#undef CALL
-  DRX_LAUNCH_CHECK();
-  return DRX_OK;
+  return dispatch_geom(p->ld, [&](auto gm) -> int {
+    constexpr int G = decltype(gm)::G, J = decltype(gm)::J;
+    constexpr int gpb = (kBlock / G) * (J == 1 ? 4 : 2);
+    int blocks = (n + gpb - 1) / gpb;
+    if (blocks > 16384) blocks = 16384;
+    if (opt->kind == DRX_OPT_ADAGRAD)
+      hipLaunchKernelGGL((k_shard_apply<G, J, DRX_OPT_ADAGRAD>), dim3(blocks + 1), dim3(kBlock), 0, st, *p, *opt, g, b_norm, so, recv_keys, n,
+                         (const uint32_t *)table, grad_recv, blocks, loss_out, do_bias);
+    else
+      hipLaunchKernelGGL((k_shard_apply<G, J, -1>), dim3(blocks + 1), dim3(kBlock), 0, st, *p, *opt, g, b_norm, so, recv_keys, n,
+                         (const uint32_t *)table, grad_recv, blocks, loss_out, do_bias);
+    DRX_LAUNCH_CHECK();
+    return DRX_OK;
+  });
 }
 
 }  // extern "C"

@@ -7,15 +7,16 @@ NAME=$1; FLAGS=${2:-}
 ROOT=$(cd "$(dirname "$0")/.." && pwd)
 OBJ=$ROOT/drecpy_amd/csrc/build/var_$NAME
 mkdir -p $OBJ
-SRCS="drx_cdae.hip drx_sort.hip drx_topk.hip drx_idmap.hip drx_sampler.hip drx_shard.hip drx_comm.hip drx_generic.hip drx_caser.hip drx_dmf.hip"
+# the source list is the library's own (drecpy_amd/build.py SOURCES): .hip with hipcc, .cpp with g++, as there
+SRCS=$(python3 -c "import runpy, sys; print(' '.join(runpy.run_path(sys.argv[1])['SOURCES']))" $ROOT/drecpy_amd/build.py)
 pids=""
 for s in $SRCS; do
-  /opt/rocm/bin/hipcc --offload-arch=gfx950 -O3 -fPIC -std=c++17 -I $ROOT/include -I $ROOT/drecpy_amd/csrc $FLAGS -c $ROOT/drecpy_amd/csrc/$s -o $OBJ/$s.o &
+  case $s in
+    *.hip) /opt/rocm/bin/hipcc --offload-arch=gfx950 -O3 -fPIC -std=c++17 -I $ROOT/include -I $ROOT/drecpy_amd/csrc $FLAGS -c $ROOT/drecpy_amd/csrc/$s -o $OBJ/$s.o & ;;
+    *)     g++ -pthread -O3 -fPIC -std=c++17 -I $ROOT/include -I $ROOT/drecpy_amd/csrc -c $ROOT/drecpy_amd/csrc/$s -o $OBJ/$s.o & ;;
+  esac
   pids="$pids $!"
 done
-for s in drx_host.cpp drx_shard_phase.cpp; do
-  g++ -pthread -O3 -fPIC -std=c++17 -I $ROOT/include -I $ROOT/drecpy_amd/csrc -c $ROOT/drecpy_amd/csrc/$s -o $OBJ/$s.o
-done
 for p in $pids; do wait $p; done
-/opt/rocm/bin/hipcc --offload-arch=gfx950 -shared -fPIC -pthread -o $ROOT/drecpy_amd/csrc/build/libdrx_$NAME.so $OBJ/*.o -ldl
+/opt/rocm/bin/hipcc --offload-arch=gfx950 -shared -fPIC -pthread -o $ROOT/drecpy_amd/csrc/build/libdrx_$NAME.so $(for s in $SRCS; do echo $OBJ/$s.o; done) -ldl
 echo $ROOT/drecpy_amd/csrc/build/libdrx_$NAME.so

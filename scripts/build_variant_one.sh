@@ -1,7 +1,8 @@
 #!/bin/bash
 # A variant of libdrx that differs from the shipped one in ONE translation unit (the others are linked from the regular build):
 #   bash scripts/build_variant_one.sh <name> <source.hip> "<flags>"   ->  drecpy_amd/csrc/build/libdrx_<name>.so
-# (scripts/build_variant.sh rebuilds everything: 9 compilations where a kernel experiment touches one file)
+# (scripts/build_variant.sh rebuilds everything: one compilation per entry of drecpy_amd/build.py SOURCES where a kernel experiment
+# touches one file)
 set -eu
 NAME=$1; SRC=$2; FLAGS=${3:-}
 ROOT=$(cd "$(dirname "$0")/.." && pwd)
