@@ -251,3 +251,42 @@ class Caser(RecommenderABC):
             idx, val = CdaeEngine.topk(self._topk_helper, sc, k, mask)
             idx, val = idx[0].cpu().numpy(), val[0].cpu().numpy()
         return [(float(v), int(i)) for v, i in zip(val, idx) if i >= 0]
+
+    RECOMMEND_MIN_FUSED_USERS = 1      # recommend_batch requests of fewer users rank per user (scripts/recommend_bench.py --model caser measures both)
+
+    def _recommend_batch(self, uids, n, novelty):
+        """Top-n of the whole catalogue for many users in one engine call (CaserEngine.recommend: the hidden rows of all requested
+        users from one drx_caser_hidden, scores and selection fused on the device — no logit rows, no host mask).  Values are logits,
+        as _rank returns them.  Excluded under novelty: the user's whole sequence (_rank's cand[seq] = False), uploaded once per engine
+        (again after load()); novelty=False excludes nothing (with the whole catalogue as candidates reference_rank makes no
+        difference).  Users whose sequence is shorter than L keep _rank's path, one at a time.  A logit here is a k-ordered fmaf chain
+        and may differ from recommend()'s in the last ulp: near-ties may come out in another order than per-user recommend() gives
+        (DESIGN.md section 3.5)."""
+        uids = np.asarray(uids, dtype=np.int64)
+        k = min(int(n), self.n_items)
+        with self._device_lock:
+            eng = self._engine
+            if type(self)._rank is not Caser._rank or len(uids) < self.RECOMMEND_MIN_FUSED_USERS or not eng.recommend_is_fused(eng.ld2, k):
+                return super()._recommend_batch(uids, n, novelty)
+            self._user_sequence(0)                                            # (builds _seq_ptr / _seq_items)
+            full = (self._seq_ptr[uids + 1] - self._seq_ptr[uids]) >= self.L
+            idx = np.full((len(uids), n), -1, dtype=np.int64)
+            val = np.full((len(uids), n), -np.inf, dtype=np.float64)
+            if not full.all():
+                idx[~full], val[~full] = super()._recommend_batch(uids[~full], n, novelty)
+            if full.any():
+                if novelty and getattr(eng, '_excl', None) is None:
+                    eng.set_exclusions(*self._sequence_csr())
+                u = uids[full]
+                before = np.stack([self._user_sequence(x)[-self.L:] for x in u])
+                d_idx, d_val = eng.recommend(u.astype(np.int32), before, k, exclude=bool(novelty))
+                idx[full, :k], val[full, :k] = d_idx.cpu().numpy().astype(np.int64), d_val.cpu().numpy().astype(np.float64)
+        return idx, val
+
+    def _sequence_csr(self):
+        """(indptr, indices): every user's sequence as a row of ascending unique items"""
+        self._user_sequence(0)
+        rows = [np.unique(self._seq_items[self._seq_ptr[u]:self._seq_ptr[u + 1]]) for u in range(self.n_users)]
+        ip = np.zeros(self.n_users + 1, dtype=np.int64)
+        ip[1:] = np.cumsum([len(r) for r in rows])
+        return ip, (np.concatenate(rows) if rows else np.zeros(0, np.int64)).astype(np.int32)

@@ -6,7 +6,8 @@ targets standardised to [0,1] when use_nce with min_interaction forced to 0 when
 (recommender_abc.py:141,463-465), cosine clipped at 1e-6, Keras BCE, l2(reg_rate) on the Dense kernels, dense Keras Adam
 with one apply per tower per step, `_predict` rescaled to the interaction range (dmf.py:101-106).
 Additions: `_rank` scores all candidates of a user in ONE launch instead of one `_predict` per item
-(recommender_abc.py:460), and `score_matrix(user_ids)` scores users against all items on the matrix cores (bf16).
+(recommender_abc.py:460), `score_matrix(user_ids)` scores users against all items on the matrix cores (bf16), and
+`recommend_batch` takes the fused fp32 scorer-selector (`_recommend_batch`).
 """
 from heapq import nlargest
 
@@ -214,6 +215,40 @@ class DMF(RecommenderABC):
             return []
         preds = self._as_array(self._predict_batch((np.full(len(iids), uid), np.asarray(iids), None))[0])
         return nlargest(n, [(self._rescale_value(float(p)), i) for p, i in zip(preds, iids)])
+
+    RECOMMEND_MIN_FUSED_USERS = 1      # recommend_batch requests of fewer users rank per user (scripts/recommend_bench.py --model dmf measures both)
+
+    def _recommend_batch_is_fused(self, n_users, n):
+        """The fused path computes DMF's OWN score (clipped cosine, rescaled): a subclass that overrides the prediction hooks
+        (ModifiedDMF) or binds a prediction scale keeps its arithmetic — one _recommend per user."""
+        cls, eng = type(self), self._engine
+        return (cls._predict_batch is DMF._predict_batch and cls._predict is DMF._predict and cls._rank is DMF._rank
+                and eng.scale_var is None and self.max_interaction > self.min_interaction
+                and n_users >= self.RECOMMEND_MIN_FUSED_USERS and eng.recommend_is_fused(eng.W, n))
+
+    def _recommend_batch(self, uids, n, novelty):
+        """Top-n of the whole catalogue for many users in one engine call (DmfEngine.recommend: the item tower once over the catalogue,
+        the user tower once per requested user, scores and selection fused on the device — no score matrix, no per-pair towers).
+        Excluded under novelty: every (uid, iid) row of the frame whatever its value — what _rank's select('uid == ...') removes —,
+        uploaded once per engine (again after load(): _restore_engine builds a new one).  Values: _rescale_value of the device's
+        fp32 score, in float64 on the host (monotone, so order and ties survive).  A score here is a k-ordered fmaf chain and may
+        differ from recommend()'s in the last ulp: near-ties may come out in another order than per-user recommend() gives
+        (DESIGN.md section 3.5)."""
+        k = min(int(n), self.n_items)
+        with self._device_lock:
+            if not self._recommend_batch_is_fused(len(uids), k):
+                return super()._recommend_batch(uids, n, novelty)
+            eng = self._engine
+            if novelty and getattr(eng, '_excl', None) is None:
+                ip, cols, _ = self.interaction_dataset.interaction_csr()      # duplicates merged, columns ascending
+                eng.set_exclusions(ip, cols)
+            idx, val = eng.recommend(np.asarray(uids, dtype=np.int32), k, exclude=bool(novelty))
+            idx, val = idx.cpu().numpy().astype(np.int64), val.cpu().numpy().astype(np.float64)
+        val = np.where(idx >= 0, self._rescale_value(val), -np.inf)
+        if k < n:
+            idx = np.concatenate([idx, np.full((len(idx), n - k), -1, np.int64)], axis=1)
+            val = np.concatenate([val, np.full((len(val), n - k), -np.inf)], axis=1)
+        return idx, val
 
     def score_matrix(self, user_ids):
         """[len(user_ids), n_items] clipped cosine scores via the bf16 MFMA scorer (raw user ids in)."""

@@ -455,7 +455,9 @@ class RecommenderABC(ABC):
     def recommend_batch(self, user_ids, n=10, novelty=True, interaction_threshold=None, as_arrays=False):
         """recommend() for many users in one call (no reference equivalent: recommender_abc.py:445-461 ranks one user per call).
         Returns one entry per requested user, in request order, each `[(score, item_id), ...]` exactly as recommend(user, n, novelty,
-        interaction_threshold) returns it; an unknown user raises as recommend() does.  as_arrays=True returns
+        interaction_threshold) returns it; an unknown user raises as recommend() does.  CDAE, DMF and Caser answer from the fused
+        scorer-selector: a score there is a k-ordered fmaf chain that may differ from recommend()'s in the last
+        ulp, so near-ties (inside the models' fp32 gates) may come out in another order than per-user recommend() gives.  as_arrays=True returns
         (scores float32 [R, n], item_ids object [R, n], counts int64 [R]) instead: row r holds counts[r] entries, then -inf / None."""
         import numpy as np
         uids = np.fromiter((self._require_user(user) for user in user_ids), dtype=np.int64)

@@ -22,6 +22,10 @@ class DrxError(RuntimeError):
     pass
 
 
+# epilogues of drx_rows_recommend (include/drx.h DRX_REC_*)
+DRX_REC_SIGMOID_BIAS, DRX_REC_BIAS, DRX_REC_CLIP = 0, 1, 2
+
+
 class CdaeParams(C.Structure):
     _fields_ = [('n_users', C.c_int32), ('n_items', C.c_int32), ('k', C.c_int32), ('ld', C.c_int32),
                 ('W', C.c_void_p), ('W2T', C.c_void_p), ('V', C.c_void_p), ('b', C.c_void_p), ('b2', C.c_void_p)]
@@ -267,6 +271,9 @@ SIGNATURES = {
     'drx_cdae_recommend_scratch_bytes': (C.c_size_t, [C.c_int32, C.c_int32, C.c_int32, C.c_int32]),
     'drx_cdae_recommend': (C.c_int, [C.POINTER(CdaeParams), C.c_void_p, C.c_void_p, C.c_int32, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p,
                                      C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p]),
+    'drx_rows_recommend_scratch_bytes': (C.c_size_t, [C.c_int32, C.c_int32, C.c_int32, C.c_int32]),
+    'drx_rows_recommend': (C.c_int, [C.c_void_p, C.c_void_p, C.c_int32, C.c_int32, C.c_int32, C.c_void_p, C.c_void_p, C.c_int32, C.c_int32,
+                                     C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p]),
     'drx_idmap_scratch_bytes': (C.c_size_t, [C.c_int64]),
     'drx_idmap_build': (C.c_int, [C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p,
                                   C.c_size_t, C.c_void_p]),

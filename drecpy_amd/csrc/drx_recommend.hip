@@ -1,11 +1,14 @@
-// Batched top-n recommendation for CDAE: score[r, i] = sigmoid(h[r, :] . W2T[i, :] + b2[i]) for R users against the whole catalogue,
-// the n best eligible items per user — WITHOUT the [R, n_items] score matrix (drx_cdae_forward + drx_topk write and re-read it:
-// 4 MB per user at a 1 M-item catalogue).  Order = drx_topk's: descending score, ties by LARGER item index (heapq.nlargest over
+// Batched top-n recommendation: score[r, i] = epilogue(q[r, :] . T[i, :] (+ bias[i])) for R query rows against a whole table of items,
+// the n best eligible items per row — WITHOUT the [R, n_items] score matrix (drx_cdae_forward + drx_topk write and re-read it:
+// 4 MB per user at a 1 M-item catalogue).  The epilogue is a template parameter (include/drx.h DRX_REC_*): sigmoid of the biased sum
+// (CDAE: q = hidden rows, T = W2T), the biased sum itself (Caser: q = [dense_0 output | user row], T = W1) or the sum clipped at 1e-6
+// from below, no bias (DMF: q / T = the l2-normalised tower outputs); everything else is shared.  Columns of q and T between the
+// model's width and ld must be ZERO, not merely unused: they are multiplied (0 x NaN would poison a row's scores).  Order = drx_topk's: descending score, ties by LARGER item index (heapq.nlargest over
 // (score, iid), cdae.py:103), carried by the same 64-bit key (monotone score bits << 32 | item).
 //
 // k_recommend   grid (user tiles of 128, item splits).  The products run on the matrix cores in fp32 (v_mfma_f32_32x32x2_f32: bit for
 //               bit a k-ordered fmaf chain; the item's bias is added to the finished sum) with the ITEM rows as the A operand and the
-//               users' hidden rows (LDS) as B, so that in the 32 x 32 accumulator tile a lane owns ONE user (column = lane & 31) and
+//               users' query rows (LDS) as B, so that in the 32 x 32 accumulator tile a lane owns ONE user (column = lane & 31) and
 //               16 of its items per tile.  A wave owns 32 users and walks the split's items 128 at a time (4 tiles: 4 independent
 //               accumulators); the four waves of a workgroup read the same item rows (L1) for different users.  The W2T fragments
 //               of the next k chunk / item block and the block's biases are loaded while the current chunk multiplies.
@@ -37,6 +40,8 @@ constexpr int kRecMaxN = 128, kRecMaxLd = 256;
 constexpr int kRecMaxMerge = 16384;     // keys the merge orders in LDS (128 KiB)
 constexpr int kRecTargetGroups = 256;   // workgroups a launch aims for: one per CU (the kernel's registers and LDS allow no more)
 
+// The key 0 means "empty slot" everywhere (rec_compact, the merge).  No finite float orders to 0 bits (that is -NaN with every payload
+// bit set), so a real key is never 0 whatever the sign of its score.
 __device__ __forceinline__ uint32_t rec_ordered_bits(float f) {
   if (f == 0.0f) f = 0.0f;              // -0.0 == 0.0 (as drx_topk)
   const uint32_t u = __float_as_uint(f);
@@ -52,7 +57,7 @@ __device__ __forceinline__ float rec_score_of(u64 key) {
 //   s <= 1/2                 a step of 4e-6 in z lowers the score by more than 2e-6 relative
 //   1 - s >= 2^-12           a step of 2e-6 * 4096 < 0.01 does
 //   1 - s <  2^-12           (z > 8.3, towards saturation, where many logits share one score) the constant 8: sigmoid(8) = 0.99966
-// 0.02 + 1e-5 |z| covers these and the error of the logf below.  s == 0 (or an empty list): no bound.
+// 0.02 + 1e-5 |z| covers these and the error of the logf below.  s == 0: no bound.
 __device__ __forceinline__ float rec_logit_bound(float s) {
   if (!(s > 0.0f)) return -INFINITY;
   const float om = 1.0f - s;
@@ -61,8 +66,27 @@ __device__ __forceinline__ float rec_logit_bound(float s) {
   return z - 0.02f - 1e-5f * fabsf(z);
 }
 
+// An epilogue: the score of a finished sum z (the item's bias already added where kBias), and for the score s of a list's n-th best a
+// bound on z: every z below it scores STRICTLY below s (such a z is dropped after one compare; the others take the exact key compare).
+// "No n-th best yet" is never read off a score's sign: rec_compact sets the bound only once a list holds n eligible keys.
+struct RecSigmoidBias {                   // DRX_REC_SIGMOID_BIAS
+  static constexpr bool kBias = true;
+  static __device__ __forceinline__ float score(float z) { return sigmoidf_(z); }
+  static __device__ __forceinline__ float bound(float s) { return rec_logit_bound(s); }
+};
+struct RecBias {                          // DRX_REC_BIAS: the sum is the compared value: exact, no margin (negative scores included)
+  static constexpr bool kBias = true;
+  static __device__ __forceinline__ float score(float z) { return z; }
+  static __device__ __forceinline__ float bound(float s) { return s; }
+};
+struct RecClip {                          // DRX_REC_CLIP: at the floor every item ties and the item index decides: no bound there
+  static constexpr bool kBias = false;
+  static __device__ __forceinline__ float score(float z) { return fmaxf(1e-6f, z); }
+  static __device__ __forceinline__ float bound(float s) { return s > 1e-6f ? s : -INFINITY; }
+};
+
 struct RecArgs {
-  const float *W2T, *b2, *h;
+  const float *table, *bias, *q;   // [N][ld] item rows, [N] (null: an epilogue without a bias), [R][ld] query rows
   const int32_t *uid;
   const int64_t *xptr;          // exclusion CSR (or null)
   const int32_t *xidx;
@@ -75,16 +99,16 @@ struct RecArgs {
   int *counts;                  // [tiles][splits][128][2]
 };
 
-// W2T fragments of one chunk of one item block: tile s, k step t: the lane's item row (lane & 31), 4 consecutive k of its half.
+// Table fragments of one chunk of one item block: tile s, k step t: the lane's item row (lane & 31), 4 consecutive k of its half.
 // MFMA (t, c) multiplies k = 8 t + c (lanes 0..31) and k = 8 t + 4 + c (lanes 32..63) of the chunk.
 __device__ __forceinline__ void rec_load_a(const RecArgs &A, int item0, int kc, int col, int hh, float4 (&a)[4][kRecKT]) {
 #pragma unroll
   for (int s = 0; s < 4; ++s) {
     const unsigned row = min((unsigned)item0 + 32u * s + col, (unsigned)A.N - 1u);   // (rows behind the catalogue: any valid row, never looked at)
-    const float *p = A.W2T + (size_t)row * A.ld;
+    const float *p = A.table + (size_t)row * A.ld;
 #pragma unroll
     for (int t = 0; t < kRecKT; ++t) {
-      // (no branch around a load: k steps behind the row read the row's last float4 — their columns of h are ZERO in LDS)
+      // (no branch around a load: k steps behind the row read the row's last float4 — their columns of q are ZERO in LDS)
       a[s][t] = *reinterpret_cast<const float4 *>(p + min(kc * kRecKC + 8 * t + 4 * hh, A.ld - 4));
     }
   }
@@ -99,12 +123,12 @@ __device__ __forceinline__ void rec_load_bias(const RecArgs &A, int item0, int h
     for (int g = 0; g < 4; ++g) {
       const unsigned base = (unsigned)item0 + 32u * s + 8u * g + 4u * hh, N = (unsigned)A.N;   // (unsigned: n_items may be 2^31 - 1)
       float4 v = f4_zero();
-      if (whole) v = *reinterpret_cast<const float4 *>(A.b2 + base);
+      if (whole) v = *reinterpret_cast<const float4 *>(A.bias + base);
       else {
-        if (base < N) v.x = A.b2[base];
-        if (base + 1 < N) v.y = A.b2[base + 1];
-        if (base + 2 < N) v.z = A.b2[base + 2];
-        if (base + 3 < N) v.w = A.b2[base + 3];
+        if (base < N) v.x = A.bias[base];
+        if (base + 1 < N) v.y = A.bias[base + 1];
+        if (base + 2 < N) v.z = A.bias[base + 2];
+        if (base + 3 < N) v.w = A.bias[base + 3];
       }
       c[s][4 * g] = v.x; c[s][4 * g + 1] = v.y; c[s][4 * g + 2] = v.z; c[s][4 * g + 3] = v.w;
     }
@@ -123,6 +147,7 @@ __device__ __forceinline__ bool rec_excluded(const int32_t *xidx, int64_t lo, in
 // The list of lane L (wave-uniform) cut back to its n best, in order, by the whole wave; L's registers follow.  The exclusion lookup
 // happens HERE, for all keys of the list at once (a push does not wait for a binary search of dependent loads): excluded keys drop
 // out before the ranks are taken, so the n-th best — the lane's new bound — is the n-th best ELIGIBLE key.
+template <class E>
 __device__ __forceinline__ void rec_compact(const RecArgs &A, u64 *wave_lists, u64 *cb, int L, int lane, int64_t xlo, int64_t xhi, int &cnt,
                                             u64 &tkey, float &zt) {
   const int cL = __shfl(cnt, L, kWave);
@@ -157,12 +182,13 @@ __device__ __forceinline__ void rec_compact(const RecArgs &A, u64 *wave_lists, u
   wave_lds_sync();
   const u64 nth = cb[256];
   if (lane == L) {
-    if (alive >= A.n) { tkey = nth; zt = rec_logit_bound(rec_score_of(nth)); }    // (fewer: the bound stays where it was)
+    if (alive >= A.n) { tkey = nth; zt = E::bound(rec_score_of(nth)); }    // (fewer: the bound stays where it was)
     cnt = min(alive, A.n);
   }
   wave_lds_sync();
 }
 
+template <class E>
 __global__ __launch_bounds__(256) void k_recommend(RecArgs A) {
   extern __shared__ __align__(16) float lds[];
   float *h_s = lds;                                                   // [128][hs]
@@ -175,7 +201,7 @@ __global__ __launch_bounds__(256) void k_recommend(RecArgs A) {
   for (int i = tid; i < kRecUsers * ldp4; i += 256) {
     const int u = i / ldp4, c4 = i - u * ldp4;
     float4 v = f4_zero();
-    if (r0 + u < A.R && 4 * c4 < A.ld) v = *reinterpret_cast<const float4 *>(A.h + (size_t)(r0 + u) * A.ld + 4 * c4);
+    if (r0 + u < A.R && 4 * c4 < A.ld) v = *reinterpret_cast<const float4 *>(A.q + (size_t)(r0 + u) * A.ld + 4 * c4);
     *reinterpret_cast<float4 *>(h_s + (size_t)u * A.hs + 4 * c4) = v;
   }
   __syncthreads();
@@ -199,7 +225,7 @@ __global__ __launch_bounds__(256) void k_recommend(RecArgs A) {
   const float *hrow = h_s + (size_t)ul * A.hs + 4 * hh;
 
   f32x16 acc[4], bias[4];
-  float4 a0[4][kRecKT], a1[4][kRecKT];            // W2T fragments of the even / odd chunk in flight (nch is even)
+  float4 a0[4][kRecKT], a1[4][kRecKT];            // table fragments of the even / odd chunk in flight (nch is even)
 #pragma unroll
   for (int s = 0; s < 4; ++s)
 #pragma unroll
@@ -228,18 +254,18 @@ __global__ __launch_bounds__(256) void k_recommend(RecArgs A) {
     }
     // the block's last two chunks; beside them its biases and the first fragments of the next block
     rec_load_a(A, item0, A.nch - 1, col, hh, a1);
-    rec_load_bias(A, item0, hh, bias);
+    if constexpr (E::kBias) rec_load_bias(A, item0, hh, bias);
     DRX_REC_CHUNK(a0, A.nch - 2)
     rec_load_a(A, blk + 1 < nblocks ? item0 + kRecItems : item0, 0, col, hh, a0);
     DRX_REC_CHUNK(a1, A.nch - 1)
 #undef DRX_REC_CHUNK
-    // the block's 128 x 32 logits of this wave: an add and a compare per score
+    // the block's 128 x 32 sums of this wave: an add (where there is a bias) and a compare per score
 #pragma unroll
     for (int s = 0; s < 4; ++s) {
       uint32_t m = 0;
 #pragma unroll
       for (int e = 0; e < 16; ++e) {
-        acc[s][e] += bias[s][e];
+        if constexpr (E::kBias) acc[s][e] += bias[s][e];
         m |= (acc[s][e] >= zt) ? (1u << e) : 0u;
       }
       if (__ballot(m != 0)) {                                         // rare once the lists are warm
@@ -252,7 +278,7 @@ __global__ __launch_bounds__(256) void k_recommend(RecArgs A) {
             m &= m - 1;
             const unsigned item = (unsigned)ibase + 8u * (e >> 2) + (e & 3);
             if (uvalid && item < (unsigned)i_end) {
-              const float sc = sigmoidf_(dump[e * 64 + lane]);
+              const float sc = E::score(dump[e * 64 + lane]);
               const u64 key = ((u64)rec_ordered_bits(sc) << 32) | item;
               if (key > tkey) { mylist[cnt] = key; ++cnt; }
             }
@@ -261,7 +287,7 @@ __global__ __launch_bounds__(256) void k_recommend(RecArgs A) {
           while (full) {
             const int L = __ffsll((long long)full) - 1;
             full &= full - 1;
-            rec_compact(A, wave_lists, cb, L, lane, xlo, xhi, cnt, tkey, zt);
+            rec_compact<E>(A, wave_lists, cb, L, lane, xlo, xhi, cnt, tkey, zt);
           }
         }
       }
@@ -274,7 +300,7 @@ __global__ __launch_bounds__(256) void k_recommend(RecArgs A) {
   while (over) {
     const int L = __ffsll((long long)over) - 1;
     over &= over - 1;
-    rec_compact(A, wave_lists, cb, L, lane, xlo, xhi, cnt, tkey, zt);
+    rec_compact<E>(A, wave_lists, cb, L, lane, xlo, xhi, cnt, tkey, zt);
   }
   if (uvalid) A.counts[(group * kRecUsers + ul) * 2 + hh] = cnt;
 }
@@ -350,38 +376,73 @@ RecLayout rec_layout(Carver &cv, const RecPlan &P) {
   return L;
 }
 
+size_t rec_scratch_bytes(int R, int n_items, int ld, int n) {
+  RecPlan P;
+  if (!rec_plan(R, n_items, ld, n, P)) return 0;
+  Carver cv(nullptr, 0);
+  (void)rec_layout(cv, P);
+  return align_up(cv.off, 256) + 256;
+}
+
+template <class E>
+int rec_launch(const RecArgs &A, const RecPlan &P, const RecLayout &L, int32_t *out_idx, float *out_val, hipStream_t st) {
+  DRX_HIP(hipFuncSetAttribute((const void *)k_recommend<E>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)P.lds_main));
+  hipLaunchKernelGGL(k_recommend<E>, dim3(P.tiles, P.splits), dim3(256), P.lds_main, st, A);
+  DRX_HIP(hipFuncSetAttribute((const void *)k_recommend_merge, hipFuncAttributeMaxDynamicSharedMemorySize, (int)P.lds_merge));
+  hipLaunchKernelGGL(k_recommend_merge, dim3(A.R), dim3(kBlock), P.lds_merge, st, L.lists, L.counts, A.n, P.cap, P.splits, P.npad, out_idx,
+                     out_val);
+  DRX_LAUNCH_CHECK();
+  return DRX_OK;
+}
+
+// the one host function behind drx_rows_recommend and drx_cdae_recommend
+int rec_run(const float *table, const float *bias, int n_items, int ld, int epilogue, const float *q, const int32_t *uid, int R, int n,
+            const int64_t *excl_indptr, const int32_t *excl_indices, int32_t *out_idx, float *out_val, void *scratch, size_t scratch_bytes,
+            void *stream) {
+  if (!table || !q || !out_idx || !out_val || R < 1 || n < 1 || n_items < 1 || ld < 4 || (ld & 3)) return DRX_EINVAL;
+  if (epilogue != DRX_REC_SIGMOID_BIAS && epilogue != DRX_REC_BIAS && epilogue != DRX_REC_CLIP) return DRX_EINVAL;
+  if ((epilogue == DRX_REC_CLIP) != (bias == nullptr)) return DRX_EINVAL;      // the clip has no bias, the other two need one
+  if ((excl_indptr != nullptr) != (excl_indices != nullptr) || (excl_indptr && !uid)) return DRX_EINVAL;
+  RecPlan P;
+  if (!rec_plan(R, n_items, ld, n, P)) return DRX_ENOTIMPL;      // n > 128 or rows wider than 256 floats: a score matrix + drx_topk
+  if (!scratch) return DRX_ESCRATCH;
+  Carver cv(scratch, scratch_bytes);
+  const RecLayout L = rec_layout(cv, P);
+  if (!cv.ok()) return DRX_ESCRATCH;
+  RecArgs A;
+  A.table = table; A.bias = bias; A.q = q; A.uid = uid; A.xptr = excl_indptr; A.xidx = excl_indices;
+  A.R = R; A.N = n_items; A.ld = ld; A.nch = P.nch; A.hs = P.hs; A.n = n; A.cap = P.cap; A.splits = P.splits; A.ips = P.ips;
+  A.lists = L.lists; A.counts = L.counts;
+  hipStream_t st = (hipStream_t)stream;
+  switch (epilogue) {
+    case DRX_REC_SIGMOID_BIAS: return rec_launch<RecSigmoidBias>(A, P, L, out_idx, out_val, st);
+    case DRX_REC_BIAS: return rec_launch<RecBias>(A, P, L, out_idx, out_val, st);
+    default: return rec_launch<RecClip>(A, P, L, out_idx, out_val, st);
+  }
+}
+
 }  // namespace
 }  // namespace drx
 
+extern "C" size_t drx_rows_recommend_scratch_bytes(int32_t R, int32_t n_items, int32_t ld, int32_t n) {
+  return drx::rec_scratch_bytes(R, n_items, ld, n);
+}
+
+extern "C" int drx_rows_recommend(const float *table, const float *bias, int32_t n_items, int32_t ld, int32_t epilogue, const float *q,
+                                  const int32_t *uid, int32_t R, int32_t n, const int64_t *excl_indptr, const int32_t *excl_indices,
+                                  int32_t *out_idx, float *out_val, void *scratch, size_t scratch_bytes, void *stream) {
+  return drx::rec_run(table, bias, n_items, ld, epilogue, q, uid, R, n, excl_indptr, excl_indices, out_idx, out_val, scratch, scratch_bytes,
+                      stream);
+}
+
 extern "C" size_t drx_cdae_recommend_scratch_bytes(int32_t R, int32_t n_items, int32_t ld, int32_t n) {
-  drx::RecPlan P;
-  if (!drx::rec_plan(R, n_items, ld, n, P)) return 0;
-  drx::Carver cv(nullptr, 0);
-  (void)drx::rec_layout(cv, P);
-  return drx::align_up(cv.off, 256) + 256;
+  return drx::rec_scratch_bytes(R, n_items, ld, n);
 }
 
 extern "C" int drx_cdae_recommend(const DrxCdaeParams *p, const float *h, const int32_t *uid, int32_t R, int32_t n,
                                   const int64_t *excl_indptr, const int32_t *excl_indices, int32_t *out_idx, float *out_val,
                                   void *scratch, size_t scratch_bytes, void *stream) {
-  if (!p || !h || !out_idx || !out_val || !p->W2T || !p->b2 || R < 1 || n < 1 || p->n_items < 1 || p->ld < 4 || (p->ld & 3)) return DRX_EINVAL;
-  if ((excl_indptr != nullptr) != (excl_indices != nullptr) || (excl_indptr && !uid)) return DRX_EINVAL;
-  drx::RecPlan P;
-  if (!drx::rec_plan(R, p->n_items, p->ld, n, P)) return DRX_ENOTIMPL;      // n > 128 or rows wider than 256 floats: drx_cdae_forward + drx_topk
-  if (!scratch) return DRX_ESCRATCH;
-  drx::Carver cv(scratch, scratch_bytes);
-  const drx::RecLayout L = drx::rec_layout(cv, P);
-  if (!cv.ok()) return DRX_ESCRATCH;
-  hipStream_t st = (hipStream_t)stream;
-  drx::RecArgs A;
-  A.W2T = p->W2T; A.b2 = p->b2; A.h = h; A.uid = uid; A.xptr = excl_indptr; A.xidx = excl_indices;
-  A.R = R; A.N = p->n_items; A.ld = p->ld; A.nch = P.nch; A.hs = P.hs; A.n = n; A.cap = P.cap; A.splits = P.splits; A.ips = P.ips;
-  A.lists = L.lists; A.counts = L.counts;
-  DRX_HIP(hipFuncSetAttribute((const void *)drx::k_recommend, hipFuncAttributeMaxDynamicSharedMemorySize, (int)P.lds_main));
-  hipLaunchKernelGGL(drx::k_recommend, dim3(P.tiles, P.splits), dim3(256), P.lds_main, st, A);
-  DRX_HIP(hipFuncSetAttribute((const void *)drx::k_recommend_merge, hipFuncAttributeMaxDynamicSharedMemorySize, (int)P.lds_merge));
-  hipLaunchKernelGGL(drx::k_recommend_merge, dim3(R), dim3(drx::kBlock), P.lds_merge, st, L.lists, L.counts, n, P.cap, P.splits, P.npad,
-                     out_idx, out_val);
-  DRX_LAUNCH_CHECK();
-  return DRX_OK;
+  if (!p || !p->W2T || !p->b2) return DRX_EINVAL;
+  return drx::rec_run(p->W2T, p->b2, p->n_items, p->ld, DRX_REC_SIGMOID_BIAS, h, uid, R, n, excl_indptr, excl_indices, out_idx, out_val,
+                      scratch, scratch_bytes, stream);
 }

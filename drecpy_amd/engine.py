@@ -33,7 +33,64 @@ def _forget_prepared(addr):
         pass
 
 
-class CdaeEngine:
+class RowsRecommender:
+    """The model-independent half of an engine's recommend(): the exclusion CSR on the device and the chunked launch of the fused
+    scorer-selector (include/drx.h drx_rows_recommend).  An engine brings n_users, n_items, device, the table
+    (+ bias), the epilogue and a function that computes the query rows of a chunk of users."""
+    RECOMMEND_CHUNK_USERS = 16384          # users per launch of the fused path: bounds its scratch (candidate keys only)
+
+    def set_exclusions(self, indptr, indices):
+        """CSR over users (columns ascending and unique) of the items recommend() never returns for a user; None = none."""
+        if indptr is None:
+            self._excl = None
+            return
+        ip = np.ascontiguousarray(indptr, dtype=np.int64)
+        ix = np.ascontiguousarray(indices, dtype=np.int32)
+        assert len(ip) == self.n_users + 1 and int(ip[-1]) == len(ix)
+        d_ip = torch.as_tensor(ip).to(self.device)
+        d_ix = torch.as_tensor(ix if len(ix) else np.zeros(1, np.int32)).to(self.device)
+        self._excl = (d_ip, d_ix, ip, ix)
+
+    def recommend_is_fused(self, ld, n):
+        """Whether rows of `ld` floats and lists of n lie in the fused domain (else drx_rows_recommend answers DRX_ENOTIMPL)."""
+        return int(lib().drx_rows_recommend_scratch_bytes(1, self.n_items, int(ld), int(n))) > 0
+
+    def _recommend_request(self, uids, n, exclude):
+        """(uid int32 on the device, n, the exclusion CSR or None, out_idx int32 [R, n], out_val float32 [R, n])"""
+        uid = uids.to(self.device, torch.int32) if torch.is_tensor(uids) else torch.as_tensor(np.ascontiguousarray(uids, dtype=np.int32)).to(self.device)
+        uid = uid.contiguous()
+        R, n = int(uid.numel()), int(n)
+        assert n >= 1
+        excl = getattr(self, '_excl', None) if exclude is None or exclude is True else None
+        assert not (exclude is True and excl is None), 'recommend(exclude=True) needs set_exclusions()'
+        out_idx = torch.empty(R, n, dtype=torch.int32, device=self.device)
+        out_val = torch.empty(R, n, dtype=torch.float32, device=self.device)
+        return uid, n, excl, out_idx, out_val
+
+    def _rows_recommend(self, table, bias, ld, epilogue, uid, n, excl, rows_of, out_idx, out_val, chunk_users=None):
+        """`chunk_users` users at a time: rows_of(lo, uid[lo:lo + r]) -> their [r, ld] query rows (padding columns ZERO), then one
+        drx_rows_recommend against `table` [n_items, ld] (+ `bias`) into out_idx / out_val [lo:lo + r].  The scratch is kept."""
+        L = lib()
+        R = int(uid.numel())
+        chunk = int(chunk_users or self.RECOMMEND_CHUNK_USERS)
+        assert table.is_contiguous() and tuple(table.shape) == (self.n_items, ld)
+        for lo in range(0, R, chunk):
+            u = uid[lo:lo + chunk]
+            r = int(u.numel())
+            q = rows_of(lo, u)
+            assert q.is_contiguous() and tuple(q.shape) == (r, ld) and q.dtype == torch.float32
+            need = int(L.drx_rows_recommend_scratch_bytes(r, self.n_items, ld, n))
+            sc = getattr(self, '_rec_scratch', None)
+            if sc is None or sc.numel() < need:
+                self._rec_scratch = None
+                sc = self._rec_scratch = torch.empty(need, dtype=torch.uint8, device=self.device)
+            check(L.drx_rows_recommend(ptr(table), ptr(bias), self.n_items, ld, epilogue, ptr(q), ptr(u), r, n,
+                                       ptr(excl[0]) if excl else None, ptr(excl[1]) if excl else None, ptr(out_idx[lo:lo + r]),
+                                       ptr(out_val[lo:lo + r]), ptr(sc), sc.numel(), stream_ptr(self.device)), 'drx_rows_recommend')
+        return out_idx, out_val
+
+
+class CdaeEngine(RowsRecommender):
     # the hot head of the sampled Adagrad step (include/drx.h DrxHotHead): the HOT_ROWS items of highest training-set degree, on
     # catalogues of at least HOT_MIN_ITEMS_PER_ROW * HOT_ROWS items and batches of at least HOT_MIN_BATCH triples, rows of 64 / 128
     # floats (DESIGN.md section 3.4).  The environment variable DRX_HOT_ROWS (0 or a multiple of 32 up to 1024) overrides HOT_ROWS.
@@ -660,21 +717,8 @@ class CdaeEngine:
         return out_idx, out_val
 
     # ---- batched top-n recommendation (include/drx.h drx_cdae_recommend; DESIGN.md section 3.5) ------------------------------
-    RECOMMEND_CHUNK_USERS = 16384          # users per launch of the fused path: bounds its scratch (candidate keys only)
     RECOMMEND_FALLBACK_BYTES = 1 << 30     # score-matrix bytes per chunk of the forward + drx_topk route (as ranking_evaluation's chunks)
     RECOMMEND_MIN_FUSED_USERS = 1          # requests of fewer users take the forward + drx_topk route (scripts/recommend_bench.py measures both)
-
-    def set_exclusions(self, indptr, indices):
-        """CSR over users (columns ascending and unique) of the items recommend() never returns for a user; None = none."""
-        if indptr is None:
-            self._excl = None
-            return
-        ip = np.ascontiguousarray(indptr, dtype=np.int64)
-        ix = np.ascontiguousarray(indices, dtype=np.int32)
-        assert len(ip) == self.n_users + 1 and int(ip[-1]) == len(ix)
-        d_ip = torch.as_tensor(ip).to(self.device)
-        d_ix = torch.as_tensor(ix if len(ix) else np.zeros(1, np.int32)).to(self.device)
-        self._excl = (d_ip, d_ix, ip, ix)
 
     def _hidden_rows(self, uid):
         """[R, ld] hidden rows of the device users `uid`, as drx_cdae_forward writes them"""
@@ -687,35 +731,17 @@ class CdaeEngine:
     def recommend(self, uids, n, exclude=None, chunk_users=None):
         """(idx int32 [R, n], val float32 [R, n]) device tensors: the n best items of every user by (score, item) descending, -1 / -inf
         behind the last eligible one.  exclude: None = the rows of set_exclusions() where one was given, False = nothing excluded.
-        The hidden rows come from forward(); scores and selection from drx_cdae_recommend, `chunk_users` users at a time — or, outside
-        its domain (n > 128, rows wider than 256 floats) and below RECOMMEND_MIN_FUSED_USERS users, from forward + drx_topk."""
-        uid = self._dev(uids, torch.int32).contiguous()
-        R, n = int(uid.numel()), int(n)
-        assert n >= 1
-        excl = getattr(self, '_excl', None) if exclude is None or exclude is True else None
-        assert not (exclude is True and excl is None), 'recommend(exclude=True) needs set_exclusions()'
-        out_idx = torch.empty(R, n, dtype=torch.int32, device=self.device)
-        out_val = torch.empty(R, n, dtype=torch.float32, device=self.device)
+        The hidden rows come from forward(); scores and selection from the fused scorer-selector (RowsRecommender), `chunk_users` users
+        at a time — or, outside its domain (n > 128, rows wider than 256 floats) and below RECOMMEND_MIN_FUSED_USERS users, from
+        forward + drx_topk."""
+        uid, n, excl, out_idx, out_val = self._recommend_request(uids, n, exclude)
+        R = int(uid.numel())
         if R == 0:
             return out_idx, out_val
-        L = lib()
-        fused = R >= self.RECOMMEND_MIN_FUSED_USERS and L.drx_cdae_recommend_scratch_bytes(1, self.n_items, self.ld, n) > 0
-        if not fused:
+        if not (R >= self.RECOMMEND_MIN_FUSED_USERS and self.recommend_is_fused(self.ld, n)):
             return self._recommend_by_matrix(uid, n, excl, out_idx, out_val)
-        chunk = int(chunk_users or self.RECOMMEND_CHUNK_USERS)
-        for lo in range(0, R, chunk):
-            u = uid[lo:lo + chunk]
-            r = int(u.numel())
-            h = self._hidden_rows(u)
-            need = int(L.drx_cdae_recommend_scratch_bytes(r, self.n_items, self.ld, n))
-            sc = getattr(self, '_rec_scratch', None)
-            if sc is None or sc.numel() < need:
-                self._rec_scratch = None
-                sc = self._rec_scratch = torch.empty(need, dtype=torch.uint8, device=self.device)
-            check(L.drx_cdae_recommend(C.byref(self._params), ptr(h), ptr(u), r, n, ptr(excl[0]) if excl else None,
-                                       ptr(excl[1]) if excl else None, ptr(out_idx[lo:lo + r]), ptr(out_val[lo:lo + r]), ptr(sc),
-                                       sc.numel(), stream_ptr(self.device)), 'drx_cdae_recommend')
-        return out_idx, out_val
+        return self._rows_recommend(self.W2T, self.b2, self.ld, _lib.DRX_REC_SIGMOID_BIAS, uid, n, excl, lambda lo, u: self._hidden_rows(u),
+                                    out_idx, out_val, chunk_users)
 
     def _recommend_by_matrix(self, uid, n, excl, out_idx, out_val):
         """The score-matrix route: forward + host-built candidate mask + drx_topk, in chunks of users."""

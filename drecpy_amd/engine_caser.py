@@ -16,10 +16,10 @@ import torch
 
 from . import _lib
 from ._lib import AdamSegments, CaserArgs, CaserDims, check, lib, ptr, stream_ptr
-from .engine import ADAM_B1, ADAM_B2, ADAM_EPS, CdaeEngine, _round_up
+from .engine import ADAM_B1, ADAM_B2, ADAM_EPS, CdaeEngine, RowsRecommender, _round_up
 
 
-class CaserEngine:
+class CaserEngine(RowsRecommender):
     ACTIVATIONS = {'relu': 0, 'tanh': 1, 'sigmoid': 2, 'linear': 3, None: 3}
 
     def __init__(self, n_users, n_items, L=5, T=3, neg_ratio=3, d=50, n_v=4, n_h=16, device='cuda:0', act_h='relu', act_mlp='relu'):
@@ -32,6 +32,7 @@ class CaserEngine:
             raise _lib.DrxError(f'Caser engine: activations {sorted(k for k in self.ACTIVATIONS if k)} are supported, got act_h={act_h!r}, act_mlp={act_mlp!r}')
         self.device = torch.device(device)
         self.U, self.N, self.L, self.T, self.d, self.n_v, self.n_h = n_users, n_items, L, T, d, n_v, n_h
+        self.n_users, self.n_items = int(n_users), int(n_items)      # (RowsRecommender's names)
         self.Tp = T + T * neg_ratio
         self.ld, self.ld2 = _round_up(d, 4), _round_up(2 * d, 4)
         self.nx = n_v + L * n_h
@@ -521,3 +522,25 @@ class CaserEngine:
         check(lib().drx_rows_dot(ptr(cat), B, ptr(self.W1), self.N, self.ld2, ptr(self.b1), ptr(out),
                                  stream_ptr(self.device)), 'drx_rows_dot')
         return out
+
+    # ---- batched top-n recommendation (include/drx.h drx_rows_recommend, DRX_REC_BIAS; DESIGN.md section 3.5) ----------------
+    def _hidden_rows(self, uid, bef):
+        """[B, ld2] rows [dense_0 output | user row] of drx_caser_hidden; zeros (not torch.empty) behind 2 d: the scorer multiplies them"""
+        cat = torch.zeros(int(uid.numel()), self.ld2, dtype=torch.float32, device=self.device)
+        A = self._args(uid, bef)
+        A.cat_out = cat.data_ptr()
+        check(lib().drx_caser_hidden(C.byref(self.D), C.byref(A), stream_ptr(self.device)), 'drx_caser_hidden')
+        return cat
+
+    def recommend(self, uids, before, n, exclude=None, chunk_users=None):
+        """(idx int32 [R, n], val float32 [R, n]) device tensors: the n best items of every (user, last L items) row by (logit, item)
+        descending — the values scores_all / _rank give —, -1 / -inf behind the last eligible one.  exclude as CdaeEngine.recommend.
+        The hidden rows of all requested users come from one drx_caser_hidden per chunk; scores and selection from the fused
+        scorer-selector.  Outside its domain (n > 128): DrxError — Caser._recommend_batch asks recommend_is_fused first."""
+        uid, n, excl, out_idx, out_val = self._recommend_request(uids, n, exclude)
+        R = int(uid.numel())
+        if R == 0:
+            return out_idx, out_val
+        bef = self._dev_i32(before).reshape(R, self.L)
+        return self._rows_recommend(self.W1, self.b1, self.ld2, _lib.DRX_REC_BIAS, uid, n, excl,
+                                    lambda lo, u: self._hidden_rows(u, bef[lo:lo + int(u.numel())].contiguous()), out_idx, out_val, chunk_users)

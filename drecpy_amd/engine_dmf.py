@@ -20,16 +20,17 @@ import torch
 
 from . import _lib
 from ._lib import AdamSegments, DmfArgs, DmfDims, DmfK0Update, check, lib, ptr, stream_ptr
-from .engine import ADAM_B1, ADAM_B2, ADAM_EPS, CdaeEngine, _round_up
+from .engine import ADAM_B1, ADAM_B2, ADAM_EPS, CdaeEngine, RowsRecommender, _round_up
 
 
-class DmfEngine:
+class DmfEngine(RowsRecommender):
     def __init__(self, n_users, n_items, user_factors=(64, 32), item_factors=(64, 32), l2_norm_vectors=True, device='cuda:0'):
         if not torch.cuda.is_available():
             raise _lib.DrxError('drecpy_amd needs a ROCm GPU (MI355X); there is no CPU fallback.')
         lib()
         self.device = torch.device(device)
         self.U, self.N = n_users, n_items
+        self.n_users, self.n_items = int(n_users), int(n_items)      # (RowsRecommender's names)
         self.factors = [list(user_factors), list(item_factors)]
         if not all(1 <= len(f) <= 4 and 1 <= min(f) and max(f) <= 128 for f in self.factors):
             raise _lib.DrxError(f'DMF engine: towers of 1..4 layers of width 1..128 are supported (a lane of one wavefront holds hidden units '
@@ -584,3 +585,31 @@ class DmfEngine:
         check(lib().drx_score_pairs_bf16(ptr(ru), n_u, ptr(ri), self.N, self.W, kdim, scale, ptr(out), pitch, stream_ptr(self.device)),
               'drx_score_pairs_bf16')
         return out[:, :self.N]
+
+    # ---- batched top-n recommendation (include/drx.h drx_rows_recommend, DRX_REC_CLIP; DESIGN.md section 3.5) ----------------
+    def _representations(self, tower, ids):
+        """[len(ids), self.W] l2-normalised outputs of one tower (0 = users, 1 = items) for the device ids `ids`: k_dmf_predict writes
+        whole rows, zero beyond the last factor (the scorer multiplies those columns)."""
+        B = int(ids.numel())
+        other = torch.zeros(B, dtype=torch.int32, device=self.device)       # (a pair needs a partner: id 0 of the other side, unused)
+        rep = torch.empty(B, self.W, dtype=torch.float32, device=self.device)
+        A = self._base_args(ids, other) if tower == 0 else self._base_args(other, ids)
+        if tower == 0:
+            A.rep_u_out = rep.data_ptr()
+        else:
+            A.rep_i_out = rep.data_ptr()
+        check(lib().drx_dmf_predict(C.byref(self.D), C.byref(A), stream_ptr(self.device)), 'drx_dmf_predict')
+        return rep
+
+    def recommend(self, uids, n, exclude=None, chunk_users=None):
+        """(idx int32 [R, n], val float32 [R, n]) device tensors: the n best items of every user by (max(1e-6, cosine), item) descending
+        — WITHOUT a bound prediction scale —, -1 / -inf behind the last eligible one.  exclude as CdaeEngine.recommend.  The item
+        tower runs ONCE per call over the catalogue (nothing is cached across calls: the parameters may have moved), the user tower
+        once per requested user; scores and selection come from the fused scorer-selector.  Outside its domain (n > 128): DrxError —
+        DMF._recommend_batch asks recommend_is_fused first and ranks per user instead."""
+        uid, n, excl, out_idx, out_val = self._recommend_request(uids, n, exclude)
+        if int(uid.numel()) == 0:
+            return out_idx, out_val
+        items = self._representations(1, torch.arange(self.N, dtype=torch.int32, device=self.device))
+        return self._rows_recommend(items, None, self.W, _lib.DRX_REC_CLIP, uid, n, excl, lambda lo, u: self._representations(0, u),
+                                    out_idx, out_val, chunk_users)

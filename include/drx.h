@@ -779,6 +779,26 @@ size_t drx_cdae_recommend_scratch_bytes(int32_t R, int32_t n_items, int32_t ld, 
 int drx_cdae_recommend(const DrxCdaeParams *p, const float *h, const int32_t *uid, int32_t R, int32_t n, const int64_t *excl_indptr,
                        const int32_t *excl_indices, int32_t *out_idx, float *out_val, void *scratch, size_t scratch_bytes, void *stream);
 
+/* ---- the same scorer-selector for any rows x table problem: score[r, i] = epilogue(q[r, :] . table[i, :] (+ bias[i])) ------------------
+ * drx_cdae_recommend is this call with table = W2T, bias = b2, DRX_REC_SIGMOID_BIAS; Caser.recommend_batch gives it the rows of
+ * drx_caser_hidden (cat_out) against dense_1 (W1, b1) with DRX_REC_BIAS — logits, as Caser's _rank returns them —, DMF.recommend_batch
+ * the l2-normalised tower outputs of drx_dmf_predict (rep_u_out of the requested users against rep_i_out of every item) with
+ * DRX_REC_CLIP.  Same contract as drx_cdae_recommend: order as drx_topk, -1 / -inf behind the last eligible item, scratch of candidate
+ * keys only, a result that is a function of the inputs alone; fused domain ld <= 256, ld % 4 == 0, n <= 128, outside it DRX_ENOTIMPL
+ * (scratch bytes 0).  DRX_EINVAL: an unknown epilogue, a bias with DRX_REC_CLIP, no bias with the other two.
+ *   table  [n_items, ld], q [R, ld]: columns between the model's width and ld must be ZERO (they are multiplied, not skipped)
+ *   bias   [n_items] or NULL (DRX_REC_CLIP)
+ * A score is a k-ordered fmaf chain (then the bias): it may differ in the last ulp from what the model's per-pair / per-row predict
+ * computes, so exact near-ties may come out in another order than a per-user rank gives. */
+#define DRX_REC_SIGMOID_BIAS 0   /* sigmoid(q . T[i] + bias[i])        (CDAE)  */
+#define DRX_REC_BIAS         1   /* q . T[i] + bias[i]                 (Caser) */
+#define DRX_REC_CLIP         2   /* max(1e-6, q . T[i]), bias == NULL  (DMF)   */
+size_t drx_rows_recommend_scratch_bytes(int32_t R, int32_t n_items, int32_t ld, int32_t n);
+int drx_rows_recommend(const float *table, const float *bias, int32_t n_items, int32_t ld, int32_t epilogue,
+                       const float *q, const int32_t *uid, int32_t R, int32_t n,
+                       const int64_t *excl_indptr, const int32_t *excl_indices,
+                       int32_t *out_idx, float *out_val, void *scratch, size_t scratch_bytes, void *stream);
+
 /* ---- stable device radix sort of (key, val) pairs (the inverted-index builder of the sparse steps; ties keep their input order).
  * Every key must be < 2^key_bits: the sort runs ceil(key_bits / digit) passes of 8-, 10- or 11-bit digits, i.e. it orders on
  * passes * digit >= key_bits bits — bits above key_bits are NOT ignored (DRX_EINVAL is not raised for them: the result is then ordered

@@ -12,6 +12,16 @@ repetitions after warm-up; score-matrix path: R in {1, 64, 1024}, >= 5 at R = 10
 minutes).  Per call: device time (events around the kernels alone, host work between them excluded) and end-to-end wall time
 (results on the host).  One process; every timed step runs under a watchdog of its own (faulthandler: the process exits if a step
 overruns).  Writes both series, their ratios, the achieved TFLOP/s of the fused path and its fraction of the fp32 matrix peak.
+
+    python scripts/recommend_bench.py --model dmf|caser [--out profiles/recommend_batch_<model>.json] [--n 10] [--quick]
+
+The other two models at the shapes the repository trains (bench_configs.py configuration 3: ml-1m-shaped DMF [64, 32]; configuration 5:
+ml-1m-shaped Caser), a fitted model, n = 10, novelty on, R in {1, 64, 1024, all users}: the fused path (DMF / Caser._recommend_batch:
+towers / hidden rows once per call + drx_rows_recommend) against the per-user default every caller took before it
+(RecommenderABC._recommend_batch: one _recommend per user) on the same model in the same run.  The per-user path is timed on at most 64
+users and extrapolated per user beyond that (the JSON says where).  What is timed is the hook — internal user ids in, numpy arrays out —,
+which is what recommend_batch runs before it maps items back to raw ids.  Device ms = events around the call on the current stream
+(for the per-user path that span includes the host's work between its launches).
 """
 import argparse
 import faulthandler
@@ -89,15 +99,140 @@ def matrix_call(eng, uid_host, n, ip, ix):
     return dev_ms, wall, torch.cat(out_i), torch.cat(out_v)
 
 
+def hook_call(fn, uids, n):
+    """-> (device ms, wall ms, idx, val) of one _recommend_batch-shaped call"""
+    e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+    torch.cuda.synchronize()
+    t0 = time.perf_counter()
+    e0.record()
+    idx, val = fn(uids, n, True)
+    e1.record()
+    torch.cuda.synchronize()
+    wall = (time.perf_counter() - t0) * 1e3
+    return e0.elapsed_time(e1), wall, idx, val
+
+
+def events_ms(fn, reps):
+    fn()
+    ms = []
+    for _ in range(reps):
+        e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+        torch.cuda.synchronize()
+        e0.record()
+        fn()
+        e1.record()
+        torch.cuda.synchronize()
+        ms.append(e0.elapsed_time(e1))
+    return median(ms)
+
+
+def dmf_parts(eng, uid, n, reps):
+    """where a fused DMF call spends its device time: the item tower over the catalogue, the user tower, the scorer-selector on rows of
+    eng.W floats — and the scorer on rows cut to the last factor (what a row stride separate from the row width would save)"""
+    from drecpy_amd import _lib
+    L = _lib.lib()
+    d_uid = torch.as_tensor(uid).to(eng.device)
+    all_items = torch.arange(eng.N, dtype=torch.int32, device=eng.device)
+    out = {'item_tower_ms': events_ms(lambda: eng._representations(1, all_items), reps),
+           'user_tower_ms': events_ms(lambda: eng._representations(0, d_uid), reps)}
+    ri, ru = eng._representations(1, all_items), eng._representations(0, d_uid)
+    R = int(d_uid.numel())
+    oi = torch.empty(R, n, dtype=torch.int32, device=eng.device)
+    ov = torch.empty(R, n, dtype=torch.float32, device=eng.device)
+    x = eng._excl
+    for name, ld in (('scorer_ms_rows_of_W', eng.W), ('scorer_ms_rows_of_last_factor', (eng.factors[0][-1] + 3) // 4 * 4)):
+        t, q = ri[:, :ld].contiguous(), ru[:, :ld].contiguous()
+        sb = int(L.drx_rows_recommend_scratch_bytes(R, eng.N, ld, n))
+        sc = torch.empty(sb, dtype=torch.uint8, device=eng.device)
+        out[name] = events_ms(lambda: _lib.check(L.drx_rows_recommend(_lib.ptr(t), None, eng.N, ld, _lib.DRX_REC_CLIP, _lib.ptr(q), _lib.ptr(d_uid), R, n,
+                                                                      _lib.ptr(x[0]), _lib.ptr(x[1]), _lib.ptr(oi), _lib.ptr(ov), _lib.ptr(sc), sb,
+                                                                      _lib.stream_ptr(eng.device)), 'drx_rows_recommend'), reps)
+    out['row_width'], out['last_factor'] = eng.W, eng.factors[0][-1]
+    return out
+
+
+def model_main(a):
+    """--model dmf | caser"""
+    from bench_configs import frame_of
+    from drecpy_amd.Dataset import InteractionDataset
+    from drecpy_amd.Recommender import DMF, Caser
+    from drecpy_amd.Recommender.recommender_abc import RecommenderABC
+    n = a.n
+    with step(600):
+        ds = InteractionDataset.read_df(frame_of('ml-1m'), verbose=False)
+        if a.model == 'dmf':
+            m = DMF(user_factors=[64, 32], item_factors=[64, 32], seed=10, verbose=False)
+            m.fit(ds, epochs=2, batch_size=256, learning_rate=1e-3, reg_rate=1e-4, neg_ratio=5)
+            config = 'bench_configs.py configuration 3: DMF [64, 32] / [64, 32], ml-1m shape'
+        else:
+            m = Caser(L=5, T=3, d=50, n_v=4, n_h=16, dropout_rate=0.5, seed=10, verbose=False)
+            m.fit(ds, epochs=2, batch_size=4096, learning_rate=5e-3, reg_rate=1e-6, neg_ratio=3)
+            config = 'bench_configs.py configuration 5: Caser L = 5, d = 50, ml-1m shape'
+        torch.cuda.synchronize()
+    crossover = type(m).RECOMMEND_MIN_FUSED_USERS
+    m.RECOMMEND_MIN_FUSED_USERS = 1                              # this run measures the fused path at every R
+    users = np.arange(m.n_users, dtype=np.int64)
+    if a.model == 'caser':
+        users = np.array([u for u in users if len(m._user_sequence(int(u))) >= m.L], dtype=np.int64)
+    rng = np.random.default_rng(0)
+    order = rng.permutation(users)
+    fused_fn = m._recommend_batch
+    per_user_fn = lambda uids, nn, nov: RecommenderABC._recommend_batch(m, uids, nn, nov)
+    res = {'model': a.model, 'config': config, 'n_users': int(m.n_users), 'n_items': int(m.n_items), 'n': n, 'novelty': True,
+           'timed': '_recommend_batch(internal user ids, n, novelty) -> numpy arrays; device_ms = events around the call',
+           'fused': {}, 'per_user': {}, 'ratio': {}}
+    PER_USER_MAX = 64
+    keep = {}
+    for R in [1, 64, 1024, len(order)]:
+        uids = order[:R]
+        reps = 5 if a.quick else 20
+        with step(240):
+            for _ in range(3):
+                hook_call(fused_fn, uids, n)
+            runs = [hook_call(fused_fn, uids, n) for _ in range(reps)]
+        d, w = median([r[0] for r in runs]), median([r[1] for r in runs])
+        res['fused'][str(R)] = {'device_ms': d, 'wall_ms': w, 'reps': reps, 'device_ms_min': min(r[0] for r in runs), 'users_per_s': R / (w * 1e-3)}
+        keep[R] = runs[-1][2]
+        print('fused', R, res['fused'][str(R)], flush=True)
+    for R in [1, 64, 1024, len(order)]:
+        timed = min(R, PER_USER_MAX)
+        uids = order[:timed]
+        reps = 2 if a.quick else (3 if timed > 1 else 10)
+        with step(500):
+            hook_call(per_user_fn, uids[:2], n)
+            runs = [hook_call(per_user_fn, uids, n) for _ in range(reps)]
+        d, w = median([r[0] for r in runs]) * R / timed, median([r[1] for r in runs]) * R / timed
+        res['per_user'][str(R)] = {'device_ms': d, 'wall_ms': w, 'reps': reps, 'users_timed': timed, 'extrapolated_per_user': R > timed,
+                                   'users_per_s': R / (w * 1e-3)}
+        f = res['fused'][str(R)]
+        same = float(np.mean([set(x.tolist()) == set(y.tolist()) for x, y in zip(runs[-1][2], keep[R][:timed])]))
+        res['ratio'][str(R)] = {'device': d / f['device_ms'], 'wall': w / f['wall_ms'], 'share_of_users_with_the_same_item_set': same}
+        print('per user', R, res['per_user'][str(R)], res['ratio'][str(R)], flush=True)
+    res['fused_slower_at'] = [int(R) for R, r in res['ratio'].items() if r['wall'] < 1.0]
+    res['min_fused_users'] = crossover
+    if a.model == 'dmf':
+        with step(240):
+            res['parts_at_all_users'] = dmf_parts(m._engine, order.astype(np.int32), n, 5 if a.quick else 20)
+    text = json.dumps(res, indent=1)
+    print(text)
+    if a.out:
+        os.makedirs(os.path.dirname(os.path.abspath(a.out)), exist_ok=True)
+        with open(a.out, 'w') as f:
+            f.write(text + '\n')
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument('--out', default=None)
+    ap.add_argument('--model', choices=('cdae', 'dmf', 'caser'), default='cdae')
     ap.add_argument('--items', type=int, default=1_000_000)
     ap.add_argument('--k', type=int, default=128)
     ap.add_argument('--n', type=int, default=10)
     ap.add_argument('--users', type=int, default=16384)
     ap.add_argument('--quick', action='store_true', help='fewer repetitions, no R = 16384')
     a = ap.parse_args()
+    if a.model != 'cdae':
+        return model_main(a)
     N, K, n, U = a.items, a.k, a.n, a.users
     dev = torch.device('cuda:0')
     with step(300):

@@ -1,0 +1,864 @@
+"""Batched top-n recommendation for DMF and Caser (drx_rows_recommend with the clip / bias epilogues, DmfEngine.recommend,
+CaserEngine.recommend, DMF / Caser.recommend_batch) against the fp64 oracles, mirroring tests/test_gpu_recommend.py.
+
+The judge is the fp64 oracle on fp64 copies of the fp32 parameters: oracle/dmf_oracle.py::forward (user u against every item) and
+oracle/caser_oracle.py::rank_scores.  Each model keeps the gate its predictions already have in this repository:
+  DMF     tau(s) = 1e-4 * max(|s|, 1e-6)                              (tests/test_gpu_dmf.py:63)
+  Caser   tau_r  = 2e-5 * max(1, max_i |s64[r, i]|), all scores of r  (tests/test_gpu_caser.py:66)
+(dmf_oracle.forward takes PAIRS: user u against N items means N copies of u's row through the user tower.  The score matrix here is
+built from the functions forward() is made of — l2_normalize, tower_fwd — with every tower run once, and forward() itself is called for
+the first requested users of every problem of up to 5000 items to confirm that the two agree to 1e-12.  caser rank_scores gathers a
+[1, N, 2 d] fp64 copy of dense_1 per user; beyond 65536 items the same expression, cat . W1^T + b1 with forward()'s own `cat`, runs in
+column blocks.)
+
+Glorot / Keras-default models put all scores of a user within a hair of each other, so the problems use SPREAD parameters (DMF: kernels
+~ N(0, 0.5), biases ~ N(-0.2, 0.1); Caser: embeddings ~ N(0, 0.5), W1 ~ N(0, 2 / sqrt(2 d)), b1 ~ N(0, 0.3)), and a DMF frame dense
+enough that item columns differ (an item's representation depends on its column of the interaction matrix alone).
+
+For every requested user with returned list L = [(v_j, i_j)]:
+  1. len(L) == min(n, eligible items); items distinct, in range, not excluded; -1 / -inf only behind the last real entry
+  2. |v_j - s64[r, i_j]| <= tau
+  3. L is sorted descending by (v_j, i_j), compared exactly
+  4. min_j s64[r, i_j] >= max over eligible non-returned i of s64[r, i] - 2 tau (tau of that best non-returned score)    (every user)
+  5. where the oracle's gap between ranks n and n + 1 exceeds 2 tau (tau of the n-th score) the item SET equals the oracle's; on the
+     main problems at least 0.80 of the users are separated, asserted from the oracle alone
+"""
+import ctypes as C
+import os
+import sys
+
+import numpy as np
+import pytest
+
+from oracle import caser_oracle as ca
+from oracle import data_oracle as do
+from oracle import dmf_oracle as dm
+
+pytestmark = pytest.mark.gpu
+
+FLOOR = 1e-6
+DRX_EINVAL, DRX_ENOTIMPL = -1, -3
+REC_SIGMOID_BIAS, REC_BIAS, REC_CLIP = 0, 1, 2
+
+
+def _tau_dmf(row):
+    return 1e-4 * np.maximum(np.abs(row), 1e-6)
+
+
+def _tau_caser(row):
+    return np.full(row.shape, 2e-5 * max(1.0, float(np.abs(row).max()) if row.size else 1.0))
+
+
+def _check(idx, val, s64, excl_rows, n, tau_of, min_separated=None):
+    """checks 1 - 5 of the module docstring; excl_rows[j] = excluded items of requested user j (or None); tau_of(row of s64) -> tau
+    per item.  Returns the separated share."""
+    R, N = s64.shape
+    assert idx.shape == (R, n) and val.shape == (R, n)
+    separated = 0
+    for j in range(R):
+        tau = tau_of(s64[j])
+        elig = np.ones(N, bool)
+        if excl_rows is not None:
+            elig[excl_rows[j]] = False
+        want = min(n, int(elig.sum()))
+        got = int((idx[j] >= 0).sum())
+        assert got == want, (j, got, want)
+        assert (idx[j, want:] == -1).all() and np.isneginf(val[j, want:]).all()                  # 1: padding behind the last entry only
+        items, vals = idx[j, :want].astype(np.int64), val[j, :want]
+        assert len(set(items.tolist())) == want and (items >= 0).all() and (items < N).all() and elig[items].all()
+        ref = s64[j, items]
+        assert (np.abs(vals.astype(np.float64) - ref) <= tau[items]).all(), (j, np.max(np.abs(vals - ref) / tau[items]))      # 2
+        for a in range(want - 1):                                                                # 3: exact (value, item) order
+            assert (vals[a], items[a]) > (vals[a + 1], items[a + 1]), (j, a)
+        rest = elig.copy()
+        rest[items] = False
+        if want and rest.any():
+            best = np.flatnonzero(rest)[np.argmax(s64[j, rest])]
+            assert ref.min() >= s64[j, best] - 2 * tau[best], j                                  # 4
+        se = np.where(elig, s64[j], -np.inf)
+        order = np.argsort(-se, kind='stable')
+        if int(elig.sum()) > n:
+            a, b = se[order[n - 1]], se[order[n]]
+            if a - b > 2 * tau[order[n - 1]]:
+                separated += 1
+                assert set(items.tolist()) == set(order[:n].tolist()), j                         # 5: the oracle's item set
+        else:
+            separated += 1
+            assert set(items.tolist()) == set(np.flatnonzero(elig).tolist()), j
+    share = separated / R
+    if min_separated is not None:
+        assert share >= min_separated, share
+    return share
+
+
+def _oracle_share(s64, excl_rows, n, tau_of):
+    """the separated share of check 5 from the oracle alone"""
+    sep = 0
+    for j in range(s64.shape[0]):
+        se = s64[j].copy()
+        if excl_rows is not None:
+            se[excl_rows[j]] = -np.inf
+        order = np.argsort(-se, kind='stable')
+        if np.isfinite(se).sum() <= n:
+            sep += 1
+        else:
+            sep += se[order[n - 1]] - se[order[n]] > 2 * tau_of(s64[j])[order[n - 1]]
+    return sep / s64.shape[0]
+
+
+def _tie_order_ok(idx, val):
+    for j in range(idx.shape[0]):
+        k = int((idx[j] >= 0).sum())
+        for a in range(k - 1):
+            if val[j, a] == val[j, a + 1]:
+                assert idx[j, a] > idx[j, a + 1], (j, a)
+            else:
+                assert val[j, a] > val[j, a + 1], (j, a)
+
+
+def _csr_of_rows(rows):
+    ip = np.concatenate([[0], np.cumsum([len(r) for r in rows])]).astype(np.int64)
+    ix = (np.concatenate(rows) if len(rows) and ip[-1] else np.zeros(0)).astype(np.int32)
+    return ip, ix
+
+
+class _Prob:
+    """One problem: parameters on an engine, the requested users, their oracle scores and excluded rows."""
+
+    def __init__(self, make_engine, uids, s64, rows, tau_of, before=None):
+        self.make_engine, self.uids, self.s64, self.rows, self.tau_of, self.before = make_engine, np.asarray(uids, np.int32), s64, rows, tau_of, before
+        self._eng = None
+
+    @property
+    def eng(self):
+        if self._eng is None:
+            self._eng = self.make_engine(True)
+        return self._eng
+
+    def rec(self, n, sel=None, eng=None, **kw):
+        sel = np.arange(len(self.uids)) if sel is None else np.asarray(sel)
+        eng = self.eng if eng is None else eng
+        if self.before is None:
+            return eng.recommend(self.uids[sel], n, **kw)
+        return eng.recommend(self.uids[sel], self.before[sel], n, **kw)
+
+    def check(self, idx, val, n, sel=None, excluded=True, min_separated=None):
+        sel = np.arange(len(self.uids)) if sel is None else np.asarray(sel)
+        rows = [self.rows[j] for j in sel] if excluded else None
+        return _check(idx.cpu().numpy(), val.cpu().numpy(), self.s64[sel], rows, n, self.tau_of, min_separated)
+
+
+# ---- DMF problems ------------------------------------------------------------------------------------------------------------------
+def _dmf_spread(rng, U, N, factors, sigma=0.5, bias=-0.2):
+    p = {}
+    for tower, n_in in (('u', N), ('i', U)):
+        prev = n_in
+        for l, f in enumerate(factors):
+            p[f'{tower}{l}_k'] = rng.normal(0, sigma, (prev, f)).astype(np.float32)
+            p[f'{tower}{l}_b'] = rng.normal(bias, 0.1, f).astype(np.float32)
+            prev = f
+    return p
+
+
+def _dmf_scores(p, dense, uids, nl):
+    p64 = {k: np.asarray(v, np.float64) for k, v in p.items()}
+    xu = dm.l2_normalize(dense[np.asarray(uids)])[0]
+    xi = dm.l2_normalize(dense.T.copy())[0]
+    nu = dm.l2_normalize(dm.tower_fwd(p64, 'u', xu, nl)[0][-1])[0]
+    ni = dm.l2_normalize(dm.tower_fwd(p64, 'i', xi, nl)[0][-1])[0]
+    s = np.maximum(FLOOR, nu @ ni.T)
+    N = dense.shape[1]
+    if N <= 5000:                                            # dmf_oracle.forward itself, pair by pair, for the first users
+        for j in range(min(2, len(uids))):
+            want, _ = dm.forward(p64, np.repeat(dense[uids[j]][None, :], N, axis=0), dense.T.copy(), nl, nl)
+            assert np.max(np.abs(want - s[j])) <= 1e-12
+    return s
+
+
+def _dmf_engine(p, dense, factors, excl):
+    from drecpy_amd.engine_dmf import DmfEngine
+    U, N = dense.shape
+    u, i = np.nonzero(dense)
+    v = dense[u, i]
+    csr, csc = do.interaction_csr(u, i, v, U, N), do.interaction_csr(i, u, v, N, U)
+    eng = DmfEngine(U, N, list(factors), list(factors))
+    eng.set_interactions(csr, csc)
+    eng.set_params(p)
+    if excl is True:
+        eng.set_exclusions(csr[0], csr[1])
+    elif excl is not None and excl is not False:
+        eng.set_exclusions(*excl)
+    return eng
+
+
+def _dmf_dense(rng, U, N, lo, hi, empty=()):
+    dense = np.zeros((U, N))
+    for u in range(U):
+        d = min(N, int(rng.integers(lo, hi + 1)))
+        cols, vals = rng.choice(N, d, replace=False), rng.integers(1, 6, d)
+        if u not in empty:
+            dense[u, cols] = vals
+    return dense
+
+
+_CACHE = {}
+
+
+def _dmf_problem(U=1000, N=4000, R=256, factors=(64, 32), lo=20, hi=80, seed=7):
+    """'DMF main' of the issue's input table and its variants: the generator whose separated shares were measured on the CPU"""
+    key = ('dmf', U, N, R, factors, lo, hi, seed)
+    if key not in _CACHE:
+        rng = np.random.default_rng(seed)
+        dense = _dmf_dense(rng, U, N, lo, hi)
+        p = _dmf_spread(rng, U, N, factors)
+        uids = rng.choice(U, R, replace=False)
+        s64 = _dmf_scores(p, dense, uids, len(factors))
+        rows = [np.flatnonzero(dense[u]) for u in uids]
+        _CACHE.clear()                                       # (one resident problem)
+        _CACHE[key] = _Prob(lambda excl: _dmf_engine(p, dense, factors, excl), uids, s64, rows, _tau_dmf)
+    return _CACHE[key]
+
+
+# ---- Caser problems ----------------------------------------------------------------------------------------------------------------
+def _caser_spread(rng, U, N, L, d, n_v=4, n_h=16):
+    p = ca.init_params(rng, U, N, L, d, n_v, n_h, np.float32)
+    p['item_emb'] = rng.normal(0, 0.5, p['item_emb'].shape).astype(np.float32)
+    p['user_emb'] = rng.normal(0, 0.5, p['user_emb'].shape).astype(np.float32)
+    p['W1'] = rng.normal(0, 2.0 / np.sqrt(2 * d), p['W1'].shape).astype(np.float32)
+    p['b1'] = rng.normal(0, 0.3, p['b1'].shape).astype(np.float32)
+    return p
+
+
+def _caser_scores(p, uids, before, block=1 << 16):
+    p64 = {k: np.asarray(v, np.float64) for k, v in p.items()}
+    N = p['W1'].shape[0]
+    if N <= block:
+        return np.stack([ca.rank_scores(p64, uids[r], before[r]) for r in range(len(uids))])
+    cat = ca.forward(p64, np.asarray(uids), np.asarray(before), np.zeros((len(uids), 1), np.int64))[1]['cat']
+    out = np.empty((len(uids), N))
+    for lo in range(0, N, block):
+        out[:, lo:lo + block] = cat @ p64['W1'][lo:lo + block].T + p64['b1'][lo:lo + block, 0]
+    return out
+
+
+def _caser_engine(p, U, N, L, d, excl, n_v=4, n_h=16):
+    from drecpy_amd.engine_caser import CaserEngine
+    eng = CaserEngine(U, N, L, 3, 3, d, n_v, n_h)
+    eng.set_params(p)
+    if excl is not None and excl is not False:
+        eng.set_exclusions(*excl)
+    return eng
+
+
+def _rows_by_user(U, uids, rows):
+    by_user = [np.zeros(0, np.int64)] * U
+    for u, r in zip(uids, rows):
+        by_user[int(u)] = r
+    return _csr_of_rows(by_user)
+
+
+def _caser_problem(U=300, N=50000, R=128, L=5, d=64, seed=7, mutate=None):
+    """'Caser main' of the issue's input table and its variants"""
+    key = ('caser', U, N, R, L, d, seed, mutate.__name__ if mutate else None)
+    if key not in _CACHE:
+        rng = np.random.default_rng(seed)
+        p = _caser_spread(rng, U, N, L, d)
+        uids = rng.choice(U, R, replace=False)
+        before = rng.integers(0, N, (R, L))
+        if mutate is not None:
+            mutate(p, rng)
+        s64 = _caser_scores(p, uids, before)
+        rows = [np.unique(rng.choice(N, int(rng.integers(5, 61)))) for _ in range(R)]
+        excl = _rows_by_user(U, uids, rows)
+        _CACHE.clear()
+        _CACHE[key] = _Prob(lambda e: _caser_engine(p, U, N, L, d, excl if e else None), uids, s64, rows, _tau_caser, before=before)
+        _CACHE[key].p = p
+    return _CACHE[key]
+
+
+# ---- 1. the lists match the oracle; with and without exclusions --------------------------------------------------------------------
+@pytest.mark.parametrize('name', ['dmf_main', 'dmf_12000', 'caser_main', 'caser_d50', 'caser_d8'])
+def test_fused_lists_match_the_oracle(name):
+    prob, ns = {'dmf_main': (lambda: _dmf_problem(), (1, 10, 64, 128)),
+                'dmf_12000': (lambda: _dmf_problem(N=12000, lo=60, hi=240), (1, 10, 64)),
+                'caser_main': (lambda: _caser_problem(), (1, 10, 64, 128)),
+                'caser_d50': (lambda: _caser_problem(N=20000, d=50), (1, 10, 64, 128)),
+                'caser_d8': (lambda: _caser_problem(d=8), (1, 10, 64, 128))}[name]
+    prob = prob()
+    for n in ns:
+        share = _oracle_share(prob.s64, prob.rows, n, prob.tau_of)
+        assert share >= 0.80, (n, share)                     # from the oracle alone, before the device is asked
+        idx, val = prob.rec(n)
+        prob.check(idx, val, n, min_separated=0.80)
+    if name == 'dmf_12000':                                  # (n = 128: 0.71 of the users separated on this frame; checks 1 - 5 without the cap)
+        idx, val = prob.rec(128)
+        prob.check(idx, val, 128)
+
+
+@pytest.mark.parametrize('model', ['dmf', 'caser'])
+def test_without_exclusions(model):
+    import torch
+    prob = _dmf_problem() if model == 'dmf' else _caser_problem()
+    idx, val = prob.rec(10, exclude=False)
+    prob.check(idx, val, 10, excluded=False, min_separated=0.80)
+    bare = prob.make_engine(False)                           # no exclusion CSR at all
+    idx2, val2 = prob.rec(10, eng=bare)
+    assert torch.equal(idx, idx2) and torch.equal(val, val2)
+
+
+# ---- 2. shapes that do not fill a tile ----------------------------------------------------------------------------------------------
+@pytest.mark.parametrize('N', [1, 31, 33, 150, 4097])
+@pytest.mark.parametrize('R', [1, 3, 65])
+@pytest.mark.parametrize('model', ['dmf', 'caser'])
+def test_shapes_that_do_not_fill_a_tile(model, N, R):
+    """n beyond the eligible items, a user whose whole catalogue is excluded (the first requested), one with nothing recorded / excluded
+    (the second)"""
+    rng = np.random.default_rng(1000 * N + R)
+    U = 80
+    uids = np.concatenate([[0, 1, 2][:R], rng.choice(np.arange(3, U), size=max(R - 3, 0), replace=False)]).astype(np.int32)
+    if model == 'dmf':
+        dense = _dmf_dense(rng, U, N, 5, 60, empty=(1,))
+        p = _dmf_spread(rng, U, N, (64, 32))
+        rows = [np.flatnonzero(dense[u]) for u in range(U)]
+        rows[0] = np.arange(N)
+        s64 = _dmf_scores(p, dense, uids, 2)
+        prob = _Prob(lambda e: _dmf_engine(p, dense, (64, 32), _csr_of_rows(rows)), uids, s64, [rows[u] for u in uids], _tau_dmf)
+    else:
+        L, d = 5, 50
+        p = _caser_spread(rng, U, N, L, d)
+        before = rng.integers(0, N, (len(uids), L))
+        rows = [np.unique(rng.choice(N, min(N, int(rng.integers(5, 61))))) for _ in range(U)]
+        rows[0], rows[1] = np.arange(N), np.zeros(0, np.int64)
+        s64 = _caser_scores(p, uids, before)
+        prob = _Prob(lambda e: _caser_engine(p, U, N, L, d, _csr_of_rows(rows)), uids, s64, [rows[u] for u in uids], _tau_caser, before=before)
+    for n in (10, 128):
+        idx, val = prob.rec(n)
+        prob.check(idx, val, n)
+        idx = idx.cpu().numpy()
+        assert (idx[0] == -1).all()
+        if R > 1:
+            assert (idx[1] >= 0).sum() == min(n, N)          # nothing recorded: nothing excluded
+
+
+def test_long_catalogue_and_scratch_is_not_a_score_matrix():
+    """a million items through the bias epilogue: many item splits, the merge near its key limit"""
+    from drecpy_amd import _lib
+    U, N, R, n, L, d = 300, 1_000_000, 128, 10, 5, 64
+    need = int(_lib.lib().drx_rows_recommend_scratch_bytes(R, N, 2 * d, n))
+    assert 0 < need < R * N // 4, need                      # a sixteenth of the fp32 score matrix
+    assert int(_lib.lib().drx_rows_recommend_scratch_bytes(R, 2_000_000_000, 2 * d, n)) < R * N // 4
+    prob = _caser_problem(U=U, N=N, R=R, L=L, d=d, seed=11)
+    idx, val = prob.rec(n)
+    assert prob.eng._rec_scratch.numel() < R * N // 4
+    prob.check(idx, val, n, min_separated=0.80)
+    _CACHE.clear()
+
+
+# ---- 3. widths that leave padding columns -------------------------------------------------------------------------------------------
+@pytest.mark.parametrize('last', [8, 30, 32, 64, 128])
+def test_dmf_widths(last):
+    """rows of 64 floats (128 for the last): the columns between the last factor and the row width are multiplied, and must be zero.
+    Buffers of the representations' sizes are filled with NaN and freed first, so that a row that was merely left unwritten would
+    poison its scores."""
+    import torch
+    factors = (64, last) if last <= 64 else (128,)
+    rng = np.random.default_rng(300 + last)
+    U, N, R = 300, 1500, 70
+    dense = _dmf_dense(rng, U, N, 20, 80)
+    p = _dmf_spread(rng, U, N, factors)
+    uids = rng.choice(U, R, replace=False)
+    s64 = _dmf_scores(p, dense, uids, len(factors))
+    prob = _Prob(lambda e: _dmf_engine(p, dense, factors, True), uids, s64, [np.flatnonzero(dense[u]) for u in uids], _tau_dmf)
+    assert prob.eng.W == (128 if last > 64 else 64)
+    for shape in ((N, prob.eng.W), (R, prob.eng.W)):         # (the sizes of the representation buffers: the allocator hands these blocks out again)
+        junk = torch.full(shape, float('nan'), device=prob.eng.device)
+        del junk
+    for n in (10, 128):
+        idx, val = prob.rec(n)
+        assert torch.isfinite(val[idx >= 0]).all()
+        prob.check(idx, val, n)
+
+
+@pytest.mark.parametrize('d', [7, 8, 50, 64])
+def test_caser_widths(d):
+    """row width roundup(2 d, 4): d = 7 and d = 50 leave two / zero padding columns of W1 and of the hidden rows"""
+    import torch
+    rng = np.random.default_rng(400 + d)
+    U, N, R, L = 120, 3000, 70, 5
+    p = _caser_spread(rng, U, N, L, d)
+    uids = rng.choice(U, R, replace=False)
+    before = rng.integers(0, N, (R, L))
+    s64 = _caser_scores(p, uids, before)
+    rows = [np.unique(rng.choice(N, int(rng.integers(5, 61)))) for _ in range(R)]
+    prob = _Prob(lambda e: _caser_engine(p, U, N, L, d, _rows_by_user(U, uids, rows)), uids, s64, rows, _tau_caser, before=before)
+    assert prob.eng.ld2 == (2 * d + 3) // 4 * 4
+    junk = torch.full((R, prob.eng.ld2), float('nan'), device=prob.eng.device)
+    del junk
+    for n in (10, 128):
+        idx, val = prob.rec(n)
+        assert torch.isfinite(val[idx >= 0]).all()
+        prob.check(idx, val, n)
+
+
+# ---- 4. exact ties --------------------------------------------------------------------------------------------------------------------
+def _dmf_tie_problem():
+    """A catalogue of 9000 items of which 300 are recorded by the 100 ordinary users and 36 (18 pairs) by ONE owner each: the two items
+    of a pair have byte-equal columns (one non-zero, normalised to 1), hence byte-equal representations.  Every other item is recorded
+    by nobody; with all biases of the item tower negative its representation is the zero vector, its cosine exactly 0 and its score
+    exactly 1e-6f.  The pairs straddle tile (32), block (128) and split boundaries."""
+    rng = np.random.default_rng(41)
+    U, N = 118, 9000
+    live = np.sort(rng.choice(N, 300, replace=False))
+    used = set(live.tolist())
+    pairs = []
+    for dlt in [1, 31, 32, 33, 127, 128, 129, 4095, 4096] * 2:
+        while True:
+            s = int(rng.integers(0, N - dlt))
+            if s not in used and s + dlt not in used:
+                break
+        used.update((s, s + dlt))
+        pairs.append((s, s + dlt))
+    dense = np.zeros((U, N))
+    for u in range(U):
+        d = int(rng.integers(20, 81))
+        dense[u, rng.choice(live, d, replace=False)] = rng.integers(1, 6, d)
+    for k, (a, b) in enumerate(pairs):                       # users 100 .. 117 own one pair each
+        dense[100 + k, a] = dense[100 + k, b] = rng.integers(1, 6)
+    p = _dmf_spread(rng, U, N, (64, 32))
+    p['i0_b'], p['i1_b'] = -np.abs(p['i0_b']) - 0.01, -np.abs(p['i1_b']) - 0.01
+    uids = np.arange(100)
+    s64 = _dmf_scores(p, dense, uids, 2)
+    rows = [np.flatnonzero(dense[u]) for u in uids]
+    return _Prob(lambda e: _dmf_engine(p, dense, (64, 32), True), uids, s64, rows, _tau_dmf), pairs, live
+
+
+def _count_pairs(idx, val, pairs, n):
+    pair_of = {a: b for a, b in pairs}
+    pair_of.update({b: a for a, b in pairs})
+    seen = cut = 0
+    for j in range(idx.shape[0]):
+        got = idx[j].tolist()
+        for pos, i in enumerate(got):
+            o = pair_of.get(i)
+            if o is None:
+                continue
+            if o in got:
+                seen += 1
+                assert val[j, pos] == val[j, got.index(o)]   # byte-equal rows: bit-equal scores
+                assert abs(got.index(o) - pos) == 1
+            elif pos == n - 1:
+                cut += 1
+                assert i > o, (j, i, o)                      # the tied pair at the cut: the larger index stays
+    return seen, cut
+
+
+def test_dmf_exact_ties_floor_and_duplicate_rows():
+    prob, pairs, live = _dmf_tie_problem()
+    s64 = prob.s64
+    dead = np.setdiff1d(np.arange(s64.shape[1]), np.concatenate([live, np.asarray(pairs).ravel()]))
+    assert (s64[:, dead] == FLOOR).all()                     # exactly the floor in the oracle too
+    seen_pairs = cut_pairs = floor_users = 0
+    for n in (1, 5, 10, 33, 128):
+        idx, val = prob.rec(n)
+        prob.check(idx, val, n)
+        idx, val = idx.cpu().numpy(), val.cpu().numpy()
+        _tie_order_ok(idx, val)
+        s, c = _count_pairs(idx, val, pairs, n)
+        seen_pairs, cut_pairs = seen_pairs + s, cut_pairs + c
+    # lists longer than the items above the floor: the floor items fill the tail in descending item index (no bound in this regime)
+    n = 128
+    only = np.sort(np.concatenate([live[:40], np.asarray(pairs).ravel()]))
+    rows = [np.setdiff1d(np.concatenate([live, prob.rows[j]]), only[~np.isin(only, prob.rows[j])]) for j in range(len(prob.uids))]
+    eng = prob.make_engine(True)
+    eng.set_exclusions(*_rows_by_user(118, prob.uids, rows))  # all but 40 of the recorded items excluded: fewer than n above the floor
+    idx, val = eng.recommend(prob.uids, n)
+    idx, val = idx.cpu().numpy(), val.cpu().numpy()
+    _check(idx, val, s64, rows, n, _tau_dmf)
+    _tie_order_ok(idx, val)
+    for j in range(len(prob.uids)):
+        elig = np.ones(s64.shape[1], bool)
+        elig[rows[j]] = False
+        above = elig & (s64[j] > 2 * FLOOR)
+        if (elig & (s64[j] > FLOOR) & ~above).any() or above.sum() >= n:
+            continue                                         # (a score within a factor 2 of the floor: the device may clip it)
+        floor_users += 1
+        k = int(above.sum())
+        assert set(idx[j, :k].tolist()) == set(np.flatnonzero(above).tolist())
+        assert (val[j, k:] == np.float32(FLOOR)).all()
+        assert idx[j, k:].tolist() == np.flatnonzero(elig & ~above)[::-1][:n - k].tolist(), j
+    assert seen_pairs > 0 and cut_pairs > 0 and floor_users > 0, (seen_pairs, cut_pairs, floor_users)
+
+
+def _caser_copies(p, rng):
+    N = p['W1'].shape[0]
+    src, dst, used = [], [], set()
+    for d in [1, 31, 32, 33, 127, 128, 129, 4095, 4096, 25000] * 4:
+        while True:
+            s = int(rng.integers(0, N))
+            if s not in used and (s + d) % N not in used:
+                break
+        used.update((s, (s + d) % N))
+        src.append(s)
+        dst.append((s + d) % N)
+    p['W1'][src] *= 3.0                                      # push the copied rows' logits up so that the pairs show up in the lists
+    p['W1'][dst] = p['W1'][src]
+    p['b1'][dst] = p['b1'][src]
+    p['_pairs'] = np.stack([src, dst], axis=1)
+
+
+def test_caser_exact_ties_duplicate_rows():
+    prob = _caser_problem(U=120, N=50000, R=96, d=64, seed=21, mutate=_caser_copies)
+    pairs = [(int(a), int(b)) for a, b in prob.p['_pairs']]
+    seen_pairs = cut_pairs = 0
+    for n in (1, 5, 10, 33):
+        idx, val = prob.rec(n, exclude=False)
+        prob.check(idx, val, n, excluded=False)
+        idx, val = idx.cpu().numpy(), val.cpu().numpy()
+        _tie_order_ok(idx, val)
+        s, c = _count_pairs(idx, val, pairs, n)
+        seen_pairs, cut_pairs = seen_pairs + s, cut_pairs + c
+    assert seen_pairs > 0 and cut_pairs > 0, (seen_pairs, cut_pairs)
+
+
+def _caser_all_negative(p, rng):
+    p['b1'] -= 12.0
+
+
+def test_caser_negative_nth_best_gets_a_full_list():
+    """every logit of every user is negative: a bound read off the sign of a score would never arrive"""
+    prob = _caser_problem(U=120, N=20000, R=96, d=50, seed=23, mutate=_caser_all_negative)
+    assert (prob.s64 < 0).all()
+    for n in (1, 10, 128):
+        idx, val = prob.rec(n)
+        assert (idx.cpu().numpy() >= 0).all() and (val.cpu().numpy() < 0).all()
+        prob.check(idx, val, n)
+
+
+# ---- 5. a function of the inputs alone ---------------------------------------------------------------------------------------------
+@pytest.mark.parametrize('model', ['dmf', 'caser'])
+def test_bit_identical_between_calls_orders_and_chunkings(model):
+    import torch
+    prob = _dmf_problem() if model == 'dmf' else _caser_problem()
+    R = len(prob.uids)
+    for n in (10, 100):
+        a_idx, a_val = prob.rec(n)
+        b_idx, b_val = prob.rec(n)
+        assert torch.equal(a_idx, b_idx) and torch.equal(a_val, b_val)
+        perm = np.random.default_rng(3).permutation(R)
+        c_idx, c_val = prob.rec(n, sel=perm, chunk_users=37)
+        inv = torch.as_tensor(np.argsort(perm)).to(a_idx.device)
+        assert torch.equal(a_idx, c_idx[inv]) and torch.equal(a_val, c_val[inv])
+        d_idx, d_val = prob.rec(n, sel=np.arange(5))         # other neighbours in the tile, another split count
+        assert torch.equal(a_idx[:5], d_idx) and torch.equal(a_val[:5], d_val)
+
+
+# ---- 7. the C ABI: one scorer behind both entry points; argument errors --------------------------------------------------------------
+def test_rows_recommend_sigmoid_equals_cdae_recommend_and_argument_errors():
+    import torch
+    from drecpy_amd import _lib
+    from drecpy_amd.engine import CdaeEngine
+    rng = np.random.default_rng(9)
+    U, N, K, R, n = 200, 20000, 50, 150, 10
+    eng = CdaeEngine(U, N, K)
+    eng.set_params(W=rng.normal(0, 0.05, (N, K)).astype(np.float32), W_=rng.normal(0, 2.0 / np.sqrt(K), (K, N)).astype(np.float32),
+                   V=rng.normal(0, 0.5, (U, K)).astype(np.float32), b=rng.normal(0, 0.1, K).astype(np.float32),
+                   b_=rng.normal(0, 0.3, N).astype(np.float32))
+    rows = [np.sort(rng.choice(N, int(rng.integers(5, 61)), replace=False)) for _ in range(U)]
+    ip, ix = _csr_of_rows(rows)
+    eng.set_history(ip, ix, with_transpose=False)
+    eng.set_exclusions(ip, ix)
+    uid = torch.as_tensor(rng.choice(U, R, replace=False).astype(np.int32)).to(eng.device)
+    h = eng._hidden_rows(uid)
+    L = _lib.lib()
+    sb = int(L.drx_rows_recommend_scratch_bytes(R, N, eng.ld, n))
+    assert sb == int(L.drx_cdae_recommend_scratch_bytes(R, N, eng.ld, n)) > 0
+    sc = torch.empty(sb, dtype=torch.uint8, device=eng.device)
+    out = [(torch.empty(R, n, dtype=torch.int32, device=eng.device), torch.empty(R, n, dtype=torch.float32, device=eng.device)) for _ in range(2)]
+    x = eng._excl
+    st = _lib.stream_ptr(eng.device)
+    assert L.drx_cdae_recommend(C.byref(eng._params), _lib.ptr(h), _lib.ptr(uid), R, n, _lib.ptr(x[0]), _lib.ptr(x[1]), _lib.ptr(out[0][0]),
+                                _lib.ptr(out[0][1]), _lib.ptr(sc), sb, st) == 0
+
+    def rows_rec(table=eng.W2T, bias=eng.b2, epilogue=REC_SIGMOID_BIAS, nn=n, ld=eng.ld, o=out[1]):
+        return L.drx_rows_recommend(_lib.ptr(table), _lib.ptr(bias), N, ld, epilogue, _lib.ptr(h), _lib.ptr(uid), R, nn, _lib.ptr(x[0]),
+                                    _lib.ptr(x[1]), _lib.ptr(o[0]), _lib.ptr(o[1]), _lib.ptr(sc), sb, st)
+    assert rows_rec() == 0
+    torch.cuda.synchronize()
+    assert torch.equal(out[0][0], out[1][0]) and torch.equal(out[0][1], out[1][1]) and (out[0][0] >= 0).all()
+    assert rows_rec(epilogue=3) == DRX_EINVAL and rows_rec(epilogue=-1) == DRX_EINVAL         # an unknown epilogue
+    assert rows_rec(epilogue=REC_CLIP) == DRX_EINVAL                                           # a bias with the clip
+    assert rows_rec(bias=None) == DRX_EINVAL and rows_rec(bias=None, epilogue=REC_BIAS) == DRX_EINVAL   # no bias with the other two
+    assert rows_rec(table=None) == DRX_EINVAL and rows_rec(ld=eng.ld + 2) == DRX_EINVAL
+    # outside the fused domain: DRX_ENOTIMPL, scratch bytes 0
+    big = (torch.empty(R, 300, dtype=torch.int32, device=eng.device), torch.empty(R, 300, dtype=torch.float32, device=eng.device))
+    for ep, bias in ((REC_SIGMOID_BIAS, eng.b2), (REC_BIAS, eng.b2), (REC_CLIP, None)):
+        assert rows_rec(epilogue=ep, bias=bias, nn=300, o=big) == DRX_ENOTIMPL
+    assert L.drx_rows_recommend_scratch_bytes(R, N, eng.ld, 300) == 0 and L.drx_rows_recommend_scratch_bytes(R, N, 260, n) == 0
+
+
+# ---- 8 - 10. the public layer on fitted models ---------------------------------------------------------------------------------------
+def _frame(seed, U=60, N=600, lo=40, hi=120):
+    """raw ids offset from the internal ones; values 1 - 5; every item recorded by at least three users; user 1000 + U has recorded the
+    whole catalogue, user 1001 + U only two items (shorter than Caser's L); timestamps = positions in a user's sequence"""
+    rng = np.random.default_rng(seed)
+    users, items, vals, ts = [], [], [], []
+
+    def add(u, its, vs):
+        users.extend([u] * len(its)); items.extend(int(70000 + i) for i in its); vals.extend(int(v) for v in vs); ts.extend(range(len(its)))
+    hist = [rng.choice(N, size=int(rng.integers(lo, hi + 1)), replace=False) for _ in range(U)]
+    deg = np.bincount(np.concatenate(hist), minlength=N)
+    for i in np.flatnonzero(deg < 3):
+        for u in rng.choice([u for u in range(U) if i not in hist[u]], size=3 - deg[i], replace=False):
+            hist[u] = np.append(hist[u], i)
+    for u in range(U):
+        add(1000 + u, hist[u], rng.integers(1, 6, size=len(hist[u])))
+    add(1000 + U, rng.permutation(N), [1] * N)
+    add(1001 + U, [5, 9], [4, 5])
+    return {'user': np.array(users), 'item': np.array(items), 'interaction': np.array(vals), 'timestamp': np.array(ts)}
+
+
+def _fitted(kind, frame_seed=31, seed=5, epochs=4, cls=None, threshold=3):
+    from drecpy_amd.Dataset import InteractionDataset
+    from drecpy_amd.Recommender import DMF, Caser
+    frame = _frame(frame_seed)
+    ds = InteractionDataset.read_df(frame, verbose=False)
+    U, N = len(set(frame['user'].tolist())), len(set(frame['item'].tolist()))
+    rng = np.random.default_rng(seed)
+    if kind == 'dmf':
+        model = (cls or DMF)(user_factors=[64, 32], item_factors=[64, 32], seed=seed, verbose=False, interaction_threshold=threshold)
+        model.fit(ds, epochs=epochs, batch_size=64, learning_rate=1e-3, reg_rate=1e-4, neg_ratio=3, initial_weights=_dmf_spread(rng, U, N, (64, 32)))
+    else:
+        model = (cls or Caser)(L=5, T=3, d=50, n_v=4, n_h=16, dropout_rate=0.5, sort_column='timestamp', seed=seed, verbose=False,
+                               interaction_threshold=threshold)
+        model.fit(ds, epochs=epochs, batch_size=32, learning_rate=1e-3, reg_rate=1e-5, neg_ratio=3, initial_weights=_caser_spread(rng, U, N, 5, 50))
+    model.RECOMMEND_MIN_FUSED_USERS = 1                      # (whatever crossover the class carries: these tests are about the fused path)
+    return model, frame
+
+
+def _model_scores(kind, model, raw_users, novelty=True):
+    """(oracle scores in the units recommend() returns, excluded internal items per user, tau_of) of the fitted model's CURRENT parameters"""
+    ds = model.interaction_dataset
+    p = {k: v for k, v in model._engine.get_params().items()}
+    uids = np.array([ds.user_to_uid(u) for u in raw_users])
+    ip, cols, vals = ds.interaction_csr()
+    recorded = [np.asarray(cols[ip[u]:ip[u + 1]], dtype=np.int64) for u in uids]
+    if kind == 'dmf':
+        dense = np.zeros((model.n_users, model.n_items))
+        for u in range(model.n_users):
+            dense[u, cols[ip[u]:ip[u + 1]]] = vals[ip[u]:ip[u + 1]]
+        lo, span = float(model.min_interaction), float(model.max_interaction - model.min_interaction)
+        s64 = lo + span * _dmf_scores(p, dense, uids, 2)
+        tau_of = lambda row: span * _tau_dmf((row - lo) / span)
+    else:
+        before = np.stack([model._user_sequence(u)[-model.L:] for u in uids])
+        s64 = _caser_scores(p, uids, before)
+        tau_of = _tau_caser
+    return s64, (recorded if novelty else None), tau_of
+
+
+def _as_arrays(ds, lists, n):
+    idx = np.array([[ds.item_to_iid(i) for _, i in a] + [-1] * (n - len(a)) for a in lists]).reshape(len(lists), n)
+    val = np.array([[s for s, _ in a] + [-np.inf] * (n - len(a)) for a in lists], dtype=np.float64).reshape(len(lists), n)
+    return idx, val
+
+
+def _check64(idx, val, s64, rows, n, tau_of):
+    """_check for the public layer: DMF's values are float64 (rescaled on the host); exact order as returned"""
+    return _check(idx, val, s64, rows, n, tau_of)
+
+
+def _long_users(frame, k=20, seed=2):
+    return [int(u) for u in np.random.default_rng(seed).permutation(np.arange(1000, 1060))[:k]]
+
+
+@pytest.mark.parametrize('kind', ['dmf', 'caser'])
+def test_recommend_batch_on_a_fitted_model(kind, tmp_path):
+    model, frame = _fitted(kind)
+    ds = model.interaction_dataset
+    everything_user = 1060
+    raw_users = _long_users(frame) + [everything_user]
+    n = 5
+    got = model.recommend_batch(raw_users, n=n)
+    one = [model.recommend(u, n=n) for u in raw_users]
+    assert len(got) == len(one) == len(raw_users)
+    raw_items = set(frame['item'].tolist())
+    for a, b in zip(got, one):                               # length, tuple shape and raw ids of recommend()
+        assert len(a) == len(b)                              # (scores: float, as recommend_batch gives them for every model; DMF.recommend's
+        #                                                      are numpy float64 — a float too — where the dataset's minimum is a numpy scalar)
+        assert all(type(x) is tuple and len(x) == 2 and type(x[0]) is float and isinstance(y[0], float) and type(x[1]) is type(y[1])
+                   and x[1] in raw_items for x, y in zip(a, b))
+    assert got[-1] == [] and one[-1] == []                   # that user has recorded every item
+    # each path against the oracle; where the oracle separates rank n from n + 1 the two paths return the same item SET, values within 2 tau
+    s64, recorded, tau_of = _model_scores(kind, model, raw_users)
+    _check64(*_as_arrays(ds, got, n), s64, recorded, n, tau_of)
+    _check64(*_as_arrays(ds, one, n), s64, recorded, n, tau_of)
+    sep = 0
+    for j, (a, b) in enumerate(zip(got, one)):
+        se = s64[j].copy()
+        se[recorded[j]] = -np.inf
+        order = np.argsort(-se, kind='stable')
+        tau = tau_of(s64[j])
+        if len(a) == n and se[order[n - 1]] - se[order[n]] > 2 * tau[order[n - 1]]:
+            sep += 1
+            assert {i for _, i in a} == {i for _, i in b}, j
+            vb = dict((i, s) for s, i in b)
+            assert all(abs(s - vb[i]) <= 2 * tau[ds.item_to_iid(i)] for s, i in a), j
+    assert sep > 0
+    # pairs recorded BELOW the interaction threshold are excluded too, and are not without novelty
+    low = {(int(u), int(i)) for u, i, v in zip(frame['user'], frame['item'], frame['interaction']) if v < 3}
+    assert low
+    for u, a in zip(raw_users, got):
+        mine = {i for uu, i in zip(frame['user'].tolist(), frame['item'].tolist()) if uu == u}
+        assert not mine & {i for _, i in a}
+    free = model.recommend_batch(raw_users, n=n, novelty=False)
+    assert len(free[-1]) == n
+    s64f, _, _ = _model_scores(kind, model, raw_users, novelty=False)
+    _check64(*_as_arrays(ds, free, n), s64f, None, n, tau_of)
+    # request order, repeated users
+    again = model.recommend_batch(raw_users[::-1] + raw_users[:3], n=n)
+    assert again == got[::-1] + got[:3]
+    # interaction_threshold cuts the tail; as_arrays carries the same content
+    cut = float(np.median([a[2][0] for a in got if len(a) == n]))
+    kept = model.recommend_batch(raw_users, n=n, interaction_threshold=cut)
+    assert kept == [[x for x in a if x[0] >= cut] for a in got] and any(len(a) < len(b) for a, b in zip(kept, got))
+    scores, items, counts = model.recommend_batch(raw_users, n=n, interaction_threshold=cut, as_arrays=True)
+    assert scores.dtype == np.float32 and scores.shape == items.shape == (len(raw_users), n)
+    for r, a in enumerate(kept):
+        assert counts[r] == len(a) and [i for i in items[r, :counts[r]]] == [i for _, i in a]
+        assert np.array_equal(scores[r, :counts[r]], np.array([s for s, _ in a], dtype=np.float32))
+        assert np.isneginf(scores[r, counts[r]:]).all()
+    # save / load: identical lists (the exclusion CSR is rebuilt for the restored engine)
+    path = str(tmp_path / f'{kind}.bin')
+    model.save(path)
+    from drecpy_amd.Recommender.recommender_abc import RecommenderABC
+    back = RecommenderABC.load(path)
+    assert getattr(back._engine, '_excl', None) is None
+    back.RECOMMEND_MIN_FUSED_USERS = 1
+    assert back.recommend_batch(raw_users, n=n) == got
+    with pytest.raises(AssertionError, match='was not found'):
+        model.recommend_batch([raw_users[0], 5], n=n)
+    # outside the fused domain (n = 300): the model still answers — one _recommend per user — within the same checks
+    few = raw_users[:3]
+    far = model.recommend_batch(few, n=300)
+    s3, r3 = s64[:3], recorded[:3]
+    _check64(*_as_arrays(ds, far, 300), s3, r3, 300, tau_of)
+
+
+@pytest.mark.parametrize('kind', ['dmf', 'caser'])
+def test_a_further_fit_is_reflected(kind):
+    """nothing of an earlier call survives a fit(): the lists follow the new parameters"""
+    model, frame = _fitted(kind)
+    raw_users = _long_users(frame)
+    n = 5
+    first = model.recommend_batch(raw_users, n=n)
+    from drecpy_amd.Dataset import InteractionDataset
+    rng = np.random.default_rng(77)
+    U, N = model.n_users, model.n_items
+    w = _dmf_spread(rng, U, N, (64, 32)) if kind == 'dmf' else _caser_spread(rng, U, N, 5, 50)
+    kw = dict(batch_size=64, reg_rate=1e-4) if kind == 'dmf' else dict(batch_size=32, reg_rate=1e-5)
+    model.fit(InteractionDataset.read_df(frame, verbose=False), epochs=3, learning_rate=1e-3, neg_ratio=3, initial_weights=w, **kw)
+    second = model.recommend_batch(raw_users, n=n)
+    assert second != first
+    s64, recorded, tau_of = _model_scores(kind, model, raw_users)
+    _check64(*_as_arrays(model.interaction_dataset, second, n), s64, recorded, n, tau_of)
+
+
+class _Counter:
+    """RecommenderABC._recommend wrapped by a counter (`skip`: internal users answered with [] instead of being ranked)"""
+
+    def __init__(self, monkeypatch, skip=()):
+        from drecpy_amd.Recommender.recommender_abc import RecommenderABC
+        self.calls, orig = [], RecommenderABC._recommend
+
+        def counted(model, uid, n, novelty, threshold):
+            self.calls.append(int(uid))
+            return [] if int(uid) in skip else orig(model, uid, n, novelty, threshold)
+        monkeypatch.setattr(RecommenderABC, '_recommend', counted)
+
+
+def test_dmf_takes_the_fused_path_and_subclasses_keep_theirs(monkeypatch):
+    model, frame = _fitted('dmf')
+    users = [1000 + (j % 60) for j in range(200)]
+    counter = _Counter(monkeypatch)
+    got = model.recommend_batch(users, n=5)
+    assert counter.calls == [] and len(got) == 200 and all(len(a) == 5 for a in got)
+    few = users[:4]
+    # a subclass with its own prediction hooks, and a bound prediction scale: one _recommend per user, the lists recommend() gives
+    sys.path.insert(0, os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), 'examples'))
+    try:
+        from extending_recommender_dmf import ModifiedDMF
+    finally:
+        sys.path.pop(0)
+    modified, _ = _fitted('dmf', cls=ModifiedDMF, epochs=2)
+    assert modified._engine.scale_var is not None
+    counter.calls.clear()
+    got = modified.recommend_batch(few, n=5)
+    assert len(counter.calls) == len(few)
+    assert got == [modified.recommend(u, n=5) for u in few]
+    from drecpy_amd.Recommender import Variable
+    scaled, _ = _fitted('dmf', epochs=2)
+    var = Variable([1.5], name='scale', device=scaled.device)
+    scaled._engine.bind_prediction_scale(var, broadcast_targets=False)
+    var.assign([1.5])
+    counter.calls.clear()
+    got = scaled.recommend_batch(few, n=5)
+    assert len(counter.calls) == len(few)
+    assert got == [scaled.recommend(u, n=5) for u in few]
+    # below RECOMMEND_MIN_FUSED_USERS: per user
+    model.RECOMMEND_MIN_FUSED_USERS = 5
+    counter.calls.clear()
+    model.recommend_batch(few, n=5)
+    assert len(counter.calls) == len(few)
+
+
+def test_caser_takes_the_fused_path_but_for_short_sequences(monkeypatch):
+    """a user whose sequence is shorter than L is the only one that goes per user.  (Its _rank hands the device a `before` row of fewer
+    than L items; that path is not run here: the counter answers for that user itself.)"""
+    model, frame = _fitted('caser')
+    ds = model.interaction_dataset
+    short = ds.user_to_uid(1061)
+    assert len(model._user_sequence(short)) == 2 < model.L
+    users = [1000 + (j % 60) for j in range(200)]
+    counter = _Counter(monkeypatch, skip=(short,))
+    got = model.recommend_batch(users, n=5)
+    assert counter.calls == [] and all(len(a) == 5 for a in got)
+    got = model.recommend_batch(users[:7] + [1061] + users[7:20] + [1061], n=5)
+    assert counter.calls == [short, short]
+    assert got[7] == [] and got[-1] == [] and all(len(a) == 5 for j, a in enumerate(got) if j not in (7, len(got) - 1))
+    assert got[:7] == model.recommend_batch(users[:7], n=5)
+
+
+@pytest.mark.parametrize('kind', ['dmf', 'caser'])
+def test_batched_recommendation_evaluation_equals_the_loop_on_the_gpu(kind):
+    from drecpy_amd.Dataset import InteractionDataset
+    from drecpy_amd.Evaluation import recommendation_evaluation
+    n = 5
+    for frame_seed in range(40, 60):                         # re-seeded until the oracle separates every evaluated user's ranks 1 .. n + 1
+        model, frame = _fitted(kind, frame_seed=frame_seed)
+        rng = np.random.default_rng(frame_seed)
+        raw_users = [int(u) for u in rng.permutation(np.arange(1000, 1060))[:12]]
+        s64, recorded, tau_of = _model_scores(kind, model, raw_users)
+        ok = True
+        for j in range(len(raw_users)):
+            se = s64[j].copy()
+            se[recorded[j]] = -np.inf
+            order = np.argsort(-se, kind='stable')[:n + 1]
+            top = se[order]
+            ok &= bool((top[:-1] - top[1:] > 2 * tau_of(s64[j])[order[:-1]]).all())
+        if ok:
+            break
+    assert ok, 'no seed separates the oracle ranks of every evaluated user'
+    tu, ti, tv = [], [], []
+    for j, u in enumerate(raw_users):                        # held-out positives: items the user has not recorded, some among its best
+        se = s64[j].copy()
+        se[recorded[j]] = -np.inf
+        best = np.argsort(-se)[:8]
+        for iid in list(best[rng.permutation(8)[:3]]) + rng.choice(np.setdiff1d(np.arange(model.n_items), recorded[j]), size=3, replace=False).tolist():
+            tu.append(u)
+            ti.append(model.interaction_dataset.iid_to_item(int(iid)))
+            tv.append(int(rng.integers(3, 6)))
+    ds_te = InteractionDataset.read_df({'user': np.array(tu), 'item': np.array(ti), 'interaction': np.array(tv)}, verbose=False)
+    for kw in (dict(k=[1, 3, 5], novelty=True), dict(k=5, novelty=True, n_pos_interactions=2, seed=4)):
+        a = recommendation_evaluation(model, ds_te, verbose=False, **kw)
+        b = recommendation_evaluation(model, ds_te, verbose=False, batched=True, **kw)
+        assert a == b and a and any(v > 0 for v in a.values()), (a, b)
