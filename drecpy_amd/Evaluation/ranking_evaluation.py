@@ -54,27 +54,11 @@ _RANK_CHUNK_BYTES = 1 << 30        # device bytes of one chunk's [R, N] predicti
 
 
 def _rank_chunk(model, tasks, novelty):
-    import torch
-    from ..engine import pack_mask_bits
     ds = model.interaction_dataset
-    eng = model._engine
-    R, N = len(tasks), model.n_items
     uids = np.array([ds.user_to_uid(t['user']) for t in tasks], dtype=np.int32)
-    cand = np.zeros((R, N), dtype=bool)
-    kmax = 1
-    for r, t in enumerate(tasks):
-        iids = [ds.item_to_iid(i) for i in t['items']]
-        iids = [i for i in iids if i is not None]                   # skip_invalid_items=True
-        cand[r, iids] = True
-        if novelty:
-            cand[r, model._all_user_items(int(uids[r]))] = False
-        kmax = max(kmax, int(cand[r].sum()))
-    with model._device_lock:
-        _, pred = eng.forward(uids)
-        mask = torch.as_tensor(pack_mask_bits(cand).view(np.int32)).to(eng.device)
-        idx, _ = eng.topk(pred, kmax, mask)
-        idx = idx.cpu().numpy()
-    return [[ds.iid_to_item(int(i)) for i in idx[r] if i >= 0] for r in range(R)]
+    iids = [[i for i in map(ds.item_to_iid, t['items']) if i is not None] for t in tasks]      # skip_invalid_items=True
+    ranked = model._rank_rows(uids, iids, model.n_items, novelty)
+    return [[ds.iid_to_item(i) for _, i in row] for row in ranked]
 
 
 def _batched_rank(model, tasks, novelty):
@@ -82,8 +66,7 @@ def _batched_rank(model, tasks, novelty):
     users as keep its prediction matrix under _RANK_CHUNK_BYTES (and R*N under 2^31, the index range of drx_topk's long-row
     path); a chunk that fails falls back to one model.rank() per user, and a user that still fails is logged and skipped like
     the reference does (ranking_evaluation.py:152-156) — its entry is None."""
-    N = max(int(model.n_items), 1)
-    per = max(1, min(_RANK_CHUNK_BYTES // (4 * N), ((1 << 31) - 1) // N))
+    per = model._engine.matrix_chunk_users(max(int(model.n_items), 1), _RANK_CHUNK_BYTES)
     out = []
     for lo in range(0, len(tasks), per):
         chunk = tasks[lo:lo + per]
@@ -132,7 +115,7 @@ def ranking_evaluation(model, ds_test=None, n_test_users=None, k=10, n_pos_inter
         if t is not None:
             tasks.append(t)
 
-    use_batched = hasattr(model, '_engine') and hasattr(model, '_all_user_items') and kwds.get('batched', True)
+    use_batched = hasattr(model, '_engine') and hasattr(model, '_rank_rows') and kwds.get('batched', True)
     if use_batched and tasks:
         ranked = _batched_rank(model, tasks, novelty)
     else:

@@ -230,27 +230,13 @@ class Caser(RecommenderABC):
         return self._seq_items[self._seq_ptr[uid]:self._seq_ptr[uid + 1]]
 
     def _rank(self, uid, iids, n, novelty):                               # caser.py:128-146
-        import torch
-        from ..engine import CdaeEngine, pack_mask_bits
         seq = self._user_sequence(uid)
-        cand = np.zeros(self.n_items, dtype=bool)
-        cand[np.fromiter((int(i) for i in iids), dtype=np.int64)] = True
+        cand = self._candidate_rows([iids])
         if novelty:
-            cand[seq] = False
+            cand[0, seq] = False
         elif getattr(self, 'reference_rank', True):
             cand[:] = True                                                # caser.py:146: nlargest over every item
-        k = min(int(n), int(cand.sum()))
-        if k <= 0:
-            return []
-        with self._device_lock:
-            sc = self._engine.scores_all(np.array([uid]), seq[-self.L:][None, :])
-            if not hasattr(self, '_topk_helper'):
-                self._topk_helper = CdaeEngine.__new__(CdaeEngine)
-                self._topk_helper.device = self._engine.device
-            mask = torch.as_tensor(pack_mask_bits(cand).view(np.int32)).to(sc.device)
-            idx, val = CdaeEngine.topk(self._topk_helper, sc, k, mask)
-            idx, val = idx[0].cpu().numpy(), val[0].cpu().numpy()
-        return [(float(v), int(i)) for v, i in zip(val, idx) if i >= 0]
+        return self._topk_of_candidates(cand, n, lambda: self._engine.scores_all(np.array([uid]), seq[-self.L:][None, :]))[0]
 
     RECOMMEND_MIN_FUSED_USERS = 1      # recommend_batch requests of fewer users rank per user (scripts/recommend_bench.py --model caser measures both)
 
@@ -263,25 +249,22 @@ class Caser(RecommenderABC):
         and may differ from recommend()'s in the last ulp: near-ties may come out in another order than per-user recommend() gives
         (DESIGN.md section 3.5)."""
         uids = np.asarray(uids, dtype=np.int64)
-        k = min(int(n), self.n_items)
-        with self._device_lock:
-            eng = self._engine
-            if type(self)._rank is not Caser._rank or len(uids) < self.RECOMMEND_MIN_FUSED_USERS or not eng.recommend_is_fused(eng.ld2, k):
-                return super()._recommend_batch(uids, n, novelty)
-            self._user_sequence(0)                                            # (builds _seq_ptr / _seq_items)
-            full = (self._seq_ptr[uids + 1] - self._seq_ptr[uids]) >= self.L
-            idx = np.full((len(uids), n), -1, dtype=np.int64)
-            val = np.full((len(uids), n), -np.inf, dtype=np.float64)
-            if not full.all():
-                idx[~full], val[~full] = super()._recommend_batch(uids[~full], n, novelty)
-            if full.any():
-                if novelty and getattr(eng, '_excl', None) is None:
-                    eng.set_exclusions(*self._sequence_csr())
-                u = uids[full]
-                before = np.stack([self._user_sequence(x)[-self.L:] for x in u])
-                d_idx, d_val = eng.recommend(u.astype(np.int32), before, k, exclude=bool(novelty))
-                idx[full, :k], val[full, :k] = d_idx.cpu().numpy().astype(np.int64), d_val.cpu().numpy().astype(np.float64)
+        eng = self._engine
+        if type(self)._rank is not Caser._rank or len(uids) < self.RECOMMEND_MIN_FUSED_USERS or not eng.recommend_is_fused(eng.ld2, min(int(n), self.n_items)):
+            return super()._recommend_batch(uids, n, novelty)
+        self._user_sequence(0)                                            # (builds _seq_ptr / _seq_items)
+        full = (self._seq_ptr[uids + 1] - self._seq_ptr[uids]) >= self.L
+        idx = np.full((len(uids), n), -1, dtype=np.int64)
+        val = np.full((len(uids), n), -np.inf, dtype=np.float64)
+        if not full.all():
+            idx[~full], val[~full] = super()._recommend_batch(uids[~full], n, novelty)
+        if full.any():
+            before = np.stack([self._user_sequence(x)[-self.L:] for x in uids[full]])
+            idx[full], val[full] = self._recommend_batch_fused(uids[full], n, novelty, before)
         return idx, val
+
+    def _exclusion_csr(self):
+        return self._sequence_csr()
 
     def _sequence_csr(self):
         """(indptr, indices): every user's sequence as a row of ascending unique items"""

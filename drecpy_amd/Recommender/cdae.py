@@ -514,40 +514,21 @@ class CDAE(RecommenderABC):
 
     def _rank(self, uid, iids, n, novelty):
         """Top-n of the candidates by (prediction, iid) — heapq.nlargest order (cdae.py:90-103) — on the device."""
-        import torch
-        from ..engine import pack_mask_bits
-        cand = np.zeros(self.n_items, dtype=bool)
-        cand[np.fromiter((int(i) for i in iids), dtype=np.int64)] = True
+        return self._rank_rows([uid], [iids], n, novelty)[0]
+
+    def _rank_rows(self, uids, iid_lists, n, novelty):
+        """_rank for many users in one engine call: row r holds the top-n of the candidates iid_lists[r] for the internal user uids[r]."""
+        cand = self._candidate_rows(iid_lists)
         if novelty:
-            cand[self._all_user_items(uid)] = False        # every (uid, iid) row of the frame, whatever its value
-        n_cand = int(cand.sum())
-        k = min(int(n), n_cand)
-        if k <= 0:
-            return []
-        with self._device_lock:
-            eng = self._engine
-            _, pred = eng.forward(np.array([uid], dtype=np.int32))
-            mask = torch.as_tensor(pack_mask_bits(cand).view(np.int32)).to(eng.device)
-            idx, val = eng.topk(pred, k, mask)
-            idx, val = idx[0].cpu().numpy(), val[0].cpu().numpy()
-        return [(float(v), int(i)) for v, i in zip(val, idx) if i >= 0]
+            for r, uid in enumerate(uids):
+                cand[r, self._all_user_items(uid)] = False        # every (uid, iid) row of the frame, whatever its value
+        return self._topk_of_candidates(cand, n, lambda: self._engine.forward(np.asarray(uids, dtype=np.int32))[1])
 
     def _recommend_batch(self, uids, n, novelty):
         """Top-n of the whole catalogue for many users in one engine call (CdaeEngine.recommend: scores and selection fused on the
         device, no score matrix).  Excluded under novelty: every (uid, iid) row of the frame whatever its value — the set
-        _all_user_items gives _rank —, uploaded once per engine (again after load(): _restore_engine builds a new one)."""
-        with self._device_lock:
-            eng = self._engine
-            if novelty and getattr(eng, '_excl', None) is None:
-                ip, cols, _ = self.interaction_dataset.interaction_csr()      # duplicates merged, columns ascending
-                eng.set_exclusions(ip, cols)
-            idx, val = eng.recommend(np.asarray(uids, dtype=np.int32), min(int(n), self.n_items), exclude=bool(novelty))
-            idx, val = idx.cpu().numpy().astype(np.int64), val.cpu().numpy()
-        if idx.shape[1] < n:
-            pad = n - idx.shape[1]
-            idx = np.concatenate([idx, np.full((len(idx), pad), -1, np.int64)], axis=1)
-            val = np.concatenate([val, np.full((len(val), pad), -np.inf, np.float32)], axis=1)
-        return idx, val
+        _all_user_items gives _rank."""
+        return self._recommend_batch_fused(uids, n, novelty)
 
     def _all_user_items(self, uid):
         if not hasattr(self, '_user_items'):

@@ -229,26 +229,14 @@ class DMF(RecommenderABC):
     def _recommend_batch(self, uids, n, novelty):
         """Top-n of the whole catalogue for many users in one engine call (DmfEngine.recommend: the item tower once over the catalogue,
         the user tower once per requested user, scores and selection fused on the device — no score matrix, no per-pair towers).
-        Excluded under novelty: every (uid, iid) row of the frame whatever its value — what _rank's select('uid == ...') removes —,
-        uploaded once per engine (again after load(): _restore_engine builds a new one).  Values: _rescale_value of the device's
-        fp32 score, in float64 on the host (monotone, so order and ties survive).  A score here is a k-ordered fmaf chain and may
-        differ from recommend()'s in the last ulp: near-ties may come out in another order than per-user recommend() gives
-        (DESIGN.md section 3.5)."""
-        k = min(int(n), self.n_items)
-        with self._device_lock:
-            if not self._recommend_batch_is_fused(len(uids), k):
-                return super()._recommend_batch(uids, n, novelty)
-            eng = self._engine
-            if novelty and getattr(eng, '_excl', None) is None:
-                ip, cols, _ = self.interaction_dataset.interaction_csr()      # duplicates merged, columns ascending
-                eng.set_exclusions(ip, cols)
-            idx, val = eng.recommend(np.asarray(uids, dtype=np.int32), k, exclude=bool(novelty))
-            idx, val = idx.cpu().numpy().astype(np.int64), val.cpu().numpy().astype(np.float64)
-        val = np.where(idx >= 0, self._rescale_value(val), -np.inf)
-        if k < n:
-            idx = np.concatenate([idx, np.full((len(idx), n - k), -1, np.int64)], axis=1)
-            val = np.concatenate([val, np.full((len(val), n - k), -np.inf)], axis=1)
-        return idx, val
+        Excluded under novelty: every (uid, iid) row of the frame whatever its value — what _rank's select('uid == ...') removes.
+        Values: _rescale_value of the device's fp32 score, in float64 on the host (monotone, so order and ties survive).  A score
+        here is a k-ordered fmaf chain and may differ from recommend()'s in the last ulp: near-ties may come out in another order
+        than per-user recommend() gives."""
+        if not self._recommend_batch_is_fused(len(uids), min(int(n), self.n_items)):
+            return super()._recommend_batch(uids, n, novelty)
+        idx, val = self._recommend_batch_fused(uids, n, novelty)
+        return idx, np.where(idx >= 0, self._rescale_value(val.astype(np.float64)), -np.inf)
 
     def score_matrix(self, user_ids):
         """[len(user_ids), n_items] clipped cosine scores via the bf16 MFMA scorer (raw user ids in)."""

@@ -33,6 +33,8 @@ from abc import ABC, abstractmethod
 from datetime import datetime
 from heapq import nlargest
 
+import numpy as np
+
 from .early_stopping import InvalidEpochValidationResultsException
 from .loss_tracker import LossTracker
 
@@ -152,10 +154,10 @@ class RecommenderABC(ABC):
         self.n_users, self.n_items, self.n_rows = ds.count_unique('uid'), ds.count_unique('iid'), len(ds)
 
     def _reset_fit_state(self):
-        """A second fit() of the same object starts clean: per-dataset caches of the models (user -> items tables, sequences,
-        top-k helpers), snapshots of the previous run and the registration lists (the reference appends to them again on every
+        """A second fit() of the same object starts clean: per-dataset caches of the models (user -> items tables,
+        sequences), snapshots of the previous run and the registration lists (the reference appends to them again on every
         fit(), recommender_abc.py:66-69 are only initialised in __init__ — duplicates there, a fresh list here)."""
-        for name in ('_user_items', '_ui_sorted', '_ui_ptr', '_seq_ptr', '_seq_items', '_topk_helper'):
+        for name in ('_user_items', '_ui_sorted', '_ui_ptr', '_seq_ptr', '_seq_items'):
             self.__dict__.pop(name, None)
         self.epoch_weights = {}
         self.trainable_vars = []
@@ -459,7 +461,6 @@ class RecommenderABC(ABC):
         scorer-selector: a score there is a k-ordered fmaf chain that may differ from recommend()'s in the last
         ulp, so near-ties (inside the models' fp32 gates) may come out in another order than per-user recommend() gives.  as_arrays=True returns
         (scores float32 [R, n], item_ids object [R, n], counts int64 [R]) instead: row r holds counts[r] entries, then -inf / None."""
-        import numpy as np
         uids = np.fromiter((self._require_user(user) for user in user_ids), dtype=np.int64)
         n = self.n_items if n is None else int(n)
         R = len(uids)
@@ -486,13 +487,33 @@ class RecommenderABC(ABC):
     def _recommend_batch(self, uids, n, novelty):
         """Hook: internal user ids [R] -> numpy (idx [R, n] internal item ids, -1 = missing; val [R, n], -inf = missing), each row in
         recommend()'s order.  Default: one _recommend per user — the model's own arithmetic, whatever it is."""
-        import numpy as np
         idx = np.full((len(uids), n), -1, dtype=np.int64)
         val = np.full((len(uids), n), -np.inf, dtype=np.float64)
         for r, uid in enumerate(uids):
             ranked = self._recommend(int(uid), n, novelty, None)
             for j, (score, iid) in enumerate(ranked[:n]):
                 idx[r, j], val[r, j] = iid, score
+        return idx, val
+
+    def _exclusion_csr(self):
+        """Hook: CSR over internal users (indptr, indices ascending and unique) of the items novelty=True keeps out of a user's
+        recommend_batch list.  Default: every (uid, iid) row of the frame, whatever its value."""
+        return self.interaction_dataset.interaction_csr()[:2]           # duplicates merged, columns ascending
+
+    def _recommend_batch_fused(self, uids, n, novelty, *query):
+        """What the models' _recommend_batch share: ONE engine.recommend(uids, *query, min(n, n_items)) for all users — under novelty
+        without the rows of _exclusion_csr, uploaded once per engine (again after load(): _restore_engine builds a new one) —,
+        downloaded as (idx int64 [R, n], val float32 [R, n]), -1 / -inf from column n_items on."""
+        with self._device_lock:
+            eng = self._engine
+            if novelty and getattr(eng, '_excl', None) is None:
+                eng.set_exclusions(*self._exclusion_csr())
+            idx, val = eng.recommend(np.asarray(uids, dtype=np.int32), *query, min(int(n), self.n_items), exclude=bool(novelty))
+            idx, val = idx.cpu().numpy().astype(np.int64), val.cpu().numpy()
+        pad = n - idx.shape[1]
+        if pad > 0:
+            idx = np.concatenate([idx, np.full((len(idx), pad), -1, np.int64)], axis=1)
+            val = np.concatenate([val, np.full((len(val), pad), -np.inf, np.float32)], axis=1)
         return idx, val
 
     def rank(self, user_id, item_ids, novelty=True, skip_invalid_items=True, **kwds):
@@ -517,6 +538,25 @@ class RecommenderABC(ABC):
             candidates -= set(self.interaction_dataset.select(f'uid == {uid}').values_list('iid', to_list=True))
         scored = ((self._predict(uid, iid), iid) for iid in candidates)
         return nlargest(n, (pair for pair in scored if pair[0] is not None))
+
+    def _candidate_rows(self, iid_lists):
+        """bool [len(iid_lists), n_items]: True at the internal item ids of each list"""
+        cand = np.zeros((len(iid_lists), self.n_items), dtype=bool)
+        for r, iids in enumerate(iid_lists):
+            cand[r, np.fromiter((int(i) for i in iids), dtype=np.int64)] = True
+        return cand
+
+    def _topk_of_candidates(self, cand, n, score_rows):
+        """For the models whose _rank selects on the device.  cand: host bool [R, n_items]; score_rows(): the device scores
+        [R, n_items] of the same rows (called under the device lock, and only if a candidate is left).  Per row the [(score, iid)] of
+        its at most n best candidates by (score, iid) descending — heapq.nlargest order."""
+        k = min(int(n), int(cand.sum(axis=1).max()))
+        if k <= 0:
+            return [[] for _ in cand]
+        with self._device_lock:
+            idx, val = self._engine.masked_topk(score_rows(), cand, k)
+            idx, val = idx.cpu().numpy(), val.cpu().numpy()
+        return [[(float(v), int(i)) for v, i in zip(vr, ir) if i >= 0] for vr, ir in zip(val, idx)]
 
     def _standardize_value(self, value):
         """[min_interaction, max_interaction] -> [0, 1] (recommender_abc.py:463-465)."""

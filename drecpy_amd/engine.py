@@ -33,11 +33,54 @@ def _forget_prepared(addr):
         pass
 
 
+def pack_mask_bits(mask_bool):
+    """bool [R,n] (numpy) -> uint32 words; bit (i & 31) of word (i >> 5) is flat element i."""
+    flat = np.asarray(mask_bool, dtype=bool).ravel()
+    pad = (-len(flat)) % 32
+    if pad:
+        flat = np.concatenate([flat, np.zeros(pad, bool)])
+    return np.packbits(flat, bitorder='little').view(np.uint32).copy()
+
+
 class RowsRecommender:
-    """The model-independent half of an engine's recommend(): the exclusion CSR on the device and the chunked launch of the fused
-    scorer-selector (include/drx.h drx_rows_recommend).  An engine brings n_users, n_items, device, the table
-    (+ bias), the epilogue and a function that computes the query rows of a chunk of users."""
+    """What the engines of all models share.  The model-independent half of recommend(): the exclusion CSR on the device and the
+    chunked launch of the fused scorer-selector (include/drx.h drx_rows_recommend) — an engine brings n_users,
+    n_items, device, the table (+ bias), the epilogue and a function that computes the query rows of a chunk of users.  And the
+    score-matrix route of rank(), ranking_evaluation and requests outside the fused domain: drx_topk under a host candidate mask."""
     RECOMMEND_CHUNK_USERS = 16384          # users per launch of the fused path: bounds its scratch (candidate keys only)
+
+    @staticmethod
+    def adam_alpha(lr, t, beta1=ADAM_B1, beta2=ADAM_B2):
+        """Keras-Adam lr_t for the 1-based step t, in fp32 like optimizer_v2/adam.py (SURVEY.md App. A.5)."""
+        f = np.float32
+        return float(f(lr) * np.sqrt(f(1.0) - np.power(f(beta2), f(t))) / (f(1.0) - np.power(f(beta1), f(t))))
+
+    def _dev_i32(self, a):
+        if torch.is_tensor(a):
+            return a.to(self.device, torch.int32).contiguous()
+        return torch.as_tensor(np.ascontiguousarray(a, dtype=np.int32)).to(self.device)
+
+    def topk(self, scores, k, cand_mask=None):
+        """Row-wise top-k with heapq.nlargest((score, iid)) ordering (cdae.py:103)."""
+        scores = scores.contiguous()
+        R, n = scores.shape
+        out_idx = torch.empty(R, k, dtype=torch.int32, device=self.device)
+        out_val = torch.empty(R, k, dtype=torch.float32, device=self.device)
+        sb = lib().drx_topk_scratch_bytes_k(R, n, k)
+        sc = torch.empty(sb, dtype=torch.uint8, device=self.device) if sb else None
+        check(lib().drx_topk(ptr(scores), ptr(cand_mask), R, n, k, ptr(out_idx), ptr(out_val), ptr(sc), sb,
+                             stream_ptr(self.device)), 'drx_topk')
+        return out_idx, out_val
+
+    def masked_topk(self, scores, cand, k):
+        """topk among the candidates `cand`, a host bool array [R, n_items]: -1 / -inf behind a row's last candidate."""
+        return self.topk(scores, k, torch.as_tensor(pack_mask_bits(cand).view(np.int32)).to(self.device))
+
+    @staticmethod
+    def matrix_chunk_users(n_items, budget_bytes):
+        """Users per chunk of the score-matrix route: their fp32 [R, n_items] matrix within `budget_bytes`, and R * n_items < 2^31
+        (the index range of drx_topk's long rows)."""
+        return max(1, min(budget_bytes // (4 * n_items), ((1 << 31) - 1) // n_items))
 
     def set_exclusions(self, indptr, indices):
         """CSR over users (columns ascending and unique) of the items recommend() never returns for a user; None = none."""
@@ -51,14 +94,21 @@ class RowsRecommender:
         d_ix = torch.as_tensor(ix if len(ix) else np.zeros(1, np.int32)).to(self.device)
         self._excl = (d_ip, d_ix, ip, ix)
 
+    def _exclusion_mask(self, host_uids):
+        """The rows of set_exclusions() as a host candidate mask, bool [len(host_uids), n_items]: False at a user's excluded items."""
+        _, _, ip, ix = self._excl
+        cand = np.ones((len(host_uids), self.n_items), dtype=bool)
+        for j, x in enumerate(host_uids):
+            cand[j, ix[ip[x]:ip[x + 1]]] = False
+        return cand
+
     def recommend_is_fused(self, ld, n):
         """Whether rows of `ld` floats and lists of n lie in the fused domain (else drx_rows_recommend answers DRX_ENOTIMPL)."""
         return int(lib().drx_rows_recommend_scratch_bytes(1, self.n_items, int(ld), int(n))) > 0
 
     def _recommend_request(self, uids, n, exclude):
         """(uid int32 on the device, n, the exclusion CSR or None, out_idx int32 [R, n], out_val float32 [R, n])"""
-        uid = uids.to(self.device, torch.int32) if torch.is_tensor(uids) else torch.as_tensor(np.ascontiguousarray(uids, dtype=np.int32)).to(self.device)
-        uid = uid.contiguous()
+        uid = self._dev_i32(uids)
         R, n = int(uid.numel()), int(n)
         assert n >= 1
         excl = getattr(self, '_excl', None) if exclude is None or exclude is True else None
@@ -314,12 +364,6 @@ class CdaeEngine(RowsRecommender):
             self._optim_struct, self._optim_for = o, self.s1
         o.alpha[0], o.alpha[1], o.alpha[2], o.alpha[3], o.alpha[4] = alphas
         return o
-
-    @staticmethod
-    def adam_alpha(lr, t, beta1=ADAM_B1, beta2=ADAM_B2):
-        """Keras-Adam lr_t for the 1-based step t, in fp32 like optimizer_v2/adam.py (SURVEY.md App. A.5)."""
-        f = np.float32
-        return float(f(lr) * np.sqrt(f(1.0) - np.power(f(beta2), f(t))) / (f(1.0) - np.power(f(beta1), f(t))))
 
     _ALPHA_CHUNK = 512
 
@@ -704,18 +748,6 @@ class CdaeEngine(RowsRecommender):
               'drx_point_sample_by_user' if by_user else 'drx_point_sample_recorded')
         return out
 
-    def topk(self, scores, k, cand_mask=None):
-        """Row-wise top-k with heapq.nlargest((score, iid)) ordering (cdae.py:103)."""
-        scores = scores.contiguous()
-        R, n = scores.shape
-        out_idx = torch.empty(R, k, dtype=torch.int32, device=self.device)
-        out_val = torch.empty(R, k, dtype=torch.float32, device=self.device)
-        sb = lib().drx_topk_scratch_bytes_k(R, n, k)
-        sc = torch.empty(sb, dtype=torch.uint8, device=self.device) if sb else None
-        check(lib().drx_topk(ptr(scores), ptr(cand_mask), R, n, k, ptr(out_idx), ptr(out_val), ptr(sc), sb,
-                             stream_ptr(self.device)), 'drx_topk')
-        return out_idx, out_val
-
     # ---- batched top-n recommendation (include/drx.h drx_cdae_recommend; DESIGN.md section 3.5) ------------------------------
     RECOMMEND_FALLBACK_BYTES = 1 << 30     # score-matrix bytes per chunk of the forward + drx_topk route (as ranking_evaluation's chunks)
     RECOMMEND_MIN_FUSED_USERS = 1          # requests of fewer users take the forward + drx_topk route (scripts/recommend_bench.py measures both)
@@ -746,35 +778,20 @@ class CdaeEngine(RowsRecommender):
     def _recommend_by_matrix(self, uid, n, excl, out_idx, out_val):
         """The score-matrix route: forward + host-built candidate mask + drx_topk, in chunks of users."""
         R = int(uid.numel())
-        chunk = max(1, min(self.RECOMMEND_FALLBACK_BYTES // (4 * self.n_items), ((1 << 31) - 1) // self.n_items))   # (R * N < 2^31: drx_topk's long rows)
+        chunk = self.matrix_chunk_users(self.n_items, self.RECOMMEND_FALLBACK_BYTES)
         host_uid = uid.cpu().numpy()
+        k = min(n, self.n_items)
         for lo in range(0, R, chunk):
             u = uid[lo:lo + chunk]
             r = int(u.numel())
             _, pred = self.forward(u)
-            mask = None
-            if excl is not None:
-                cand = np.ones((r, self.n_items), dtype=bool)
-                for j, x in enumerate(host_uid[lo:lo + r]):
-                    cand[j, excl[3][excl[2][x]:excl[2][x + 1]]] = False
-                mask = torch.as_tensor(pack_mask_bits(cand).view(np.int32)).to(self.device)
-            k = min(n, self.n_items)
-            idx, val = self.topk(pred, k, mask)
+            idx, val = self.topk(pred, k) if excl is None else self.masked_topk(pred, self._exclusion_mask(host_uid[lo:lo + r]), k)
             out_idx[lo:lo + r, :k] = idx
             out_val[lo:lo + r, :k] = val
             if k < n:
                 out_idx[lo:lo + r, k:] = -1
                 out_val[lo:lo + r, k:] = float('-inf')
         return out_idx, out_val
-
-
-def pack_mask_bits(mask_bool):
-    """bool [R,n] (numpy) -> uint32 words; bit (i & 31) of word (i >> 5) is flat element i."""
-    flat = np.asarray(mask_bool, dtype=bool).ravel()
-    pad = (-len(flat)) % 32
-    if pad:
-        flat = np.concatenate([flat, np.zeros(pad, bool)])
-    return np.packbits(flat, bitorder='little').view(np.uint32).copy()
 
 
 class DeviceBatchSource:

@@ -16,7 +16,7 @@ import torch
 
 from . import _lib
 from ._lib import AdamSegments, CaserArgs, CaserDims, check, lib, ptr, stream_ptr
-from .engine import ADAM_B1, ADAM_B2, ADAM_EPS, CdaeEngine, RowsRecommender, _round_up
+from .engine import ADAM_B1, ADAM_B2, ADAM_EPS, RowsRecommender, _round_up
 
 
 class CaserEngine(RowsRecommender):
@@ -137,11 +137,6 @@ class CaserEngine(RowsRecommender):
             t.copy_(snap['p'][n])
 
     # ---- helpers --------------------------------------------------------------------------------------------------
-    def _dev_i32(self, a):
-        if torch.is_tensor(a):
-            return a.to(self.device, torch.int32).contiguous()
-        return torch.as_tensor(np.ascontiguousarray(a, dtype=np.int32)).to(self.device)
-
     def _scatter(self, keys, T, src, ld, n_rows, out, src_s=None, out_s=None, stream=None):
         """keys / src / src_s / out / out_s: device addresses.  `out` (and `out_s`) must already be zero: step() clears the whole
         gradient arena once."""
@@ -514,10 +509,7 @@ class CaserEngine(RowsRecommender):
     def scores_all(self, uids, before):
         uid, bef = self._dev_i32(uids), self._dev_i32(before)
         B = uid.numel()
-        cat = torch.zeros(B, self.ld2, dtype=torch.float32, device=self.device)
-        A = self._args(uid, bef)
-        A.cat_out = cat.data_ptr()
-        check(lib().drx_caser_hidden(C.byref(self.D), C.byref(A), stream_ptr(self.device)), 'drx_caser_hidden')
+        cat = self._hidden_rows(uid, bef)
         out = torch.empty(B, self.N, dtype=torch.float32, device=self.device)
         check(lib().drx_rows_dot(ptr(cat), B, ptr(self.W1), self.N, self.ld2, ptr(self.b1), ptr(out),
                                  stream_ptr(self.device)), 'drx_rows_dot')

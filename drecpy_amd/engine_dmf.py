@@ -20,7 +20,7 @@ import torch
 
 from . import _lib
 from ._lib import AdamSegments, DmfArgs, DmfDims, DmfK0Update, check, lib, ptr, stream_ptr
-from .engine import ADAM_B1, ADAM_B2, ADAM_EPS, CdaeEngine, RowsRecommender, _round_up
+from .engine import ADAM_B1, ADAM_B2, ADAM_EPS, RowsRecommender, _round_up
 
 
 class DmfEngine(RowsRecommender):
@@ -159,11 +159,6 @@ class DmfEngine(RowsRecommender):
     def restore(self, snap, with_optimizer=False):
         for n, t in self.tensors().items():
             t.copy_(snap['p'][n])
-
-    def _i32(self, a):
-        if torch.is_tensor(a):
-            return a.to(self.device, torch.int32).contiguous()
-        return torch.as_tensor(np.ascontiguousarray(a, dtype=np.int32)).to(self.device)
 
     def _base_args(self, uid, iid):
         A = DmfArgs()
@@ -459,7 +454,7 @@ class DmfEngine(RowsRecommender):
         if applies is None:
             applies = (3, 1, 2, 0) if self.scale_var is not None else (2, 0, 1, None)
         n_app = applies[0]
-        alpha = [CdaeEngine.adam_alpha(self.lr, n_app * step_idx + j + 1, self.beta1, self.beta2) if j is not None else 0.0 for j in applies[1:]]
+        alpha = [self.adam_alpha(self.lr, n_app * step_idx + j + 1, self.beta1, self.beta2) if j is not None else 0.0 for j in applies[1:]]
         l2c = 2.0 * self.reg
         sg = AdamSegments()
         sg.n = len(self.seg)
@@ -530,7 +525,7 @@ class DmfEngine(RowsRecommender):
         self._stamp += 1
         A.stamp = self._stamp
         n_app = applies[0]
-        alpha = [CdaeEngine.adam_alpha(self.lr, n_app * step_idx + j + 1, self.beta1, self.beta2) if j is not None else 0.0 for j in applies[1:]]
+        alpha = [self.adam_alpha(self.lr, n_app * step_idx + j + 1, self.beta1, self.beta2) if j is not None else 0.0 for j in applies[1:]]
         for i, tw in c['sg_tw']:
             sg.alpha[i] = alpha[tw]
         # (the small weights' Adam in the launch that sums their partial gradients: drx_dmf_step_small — one launch less than
@@ -552,7 +547,7 @@ class DmfEngine(RowsRecommender):
     def predict(self, uids, iids, want_reps=False, scaled=True):
         """max(1e-6, cosine) for each (uid, iid) pair (dmf.py:88-96) — times the bound prediction scale unless scaled=False;
         optionally the normalised tower outputs [B, self.W]."""
-        uid, iid = self._i32(uids), self._i32(iids)
+        uid, iid = self._dev_i32(uids), self._dev_i32(iids)
         B = uid.numel()
         pred = torch.empty(B, dtype=torch.float32, device=self.device)
         A = self._base_args(uid, iid)
@@ -571,11 +566,10 @@ class DmfEngine(RowsRecommender):
 
     def score_matrix_bf16(self, uids):
         """[len(uids), N] cosine scores of the given users against ALL items on the matrix cores (bf16 operands)."""
-        uid = self._i32(uids)
+        uid = self._dev_i32(uids)
         n_u = uid.numel()
-        all_items = torch.arange(self.N, dtype=torch.int32, device=self.device)
-        _, _, ri = self.predict(torch.zeros(self.N, dtype=torch.int32, device=self.device), all_items, want_reps=True)
-        _, ru, _ = self.predict(uid, torch.zeros(n_u, dtype=torch.int32, device=self.device), want_reps=True)
+        ri = self._representations(1, torch.arange(self.N, dtype=torch.int32, device=self.device))
+        ru = self._representations(0, uid)
         pitch = _round_up(self.N, 32)                  # rows of 128-byte lines: a line then belongs to ONE tile of the scorer
         out = torch.empty(n_u, pitch, dtype=torch.float32, device=self.device)
         kdim = _round_up(self.factors[0][-1], 16)

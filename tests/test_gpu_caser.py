@@ -66,6 +66,26 @@ def _steps_match_oracle(d, L, n_v, n_h, T, neg, B, drop, update, steps=3):
         assert np.max(np.abs(sc[r] - want)) < 2e-5 * max(1.0, np.max(np.abs(want)))
 
 
+def test_scores_all_is_the_hidden_rows_times_the_output_table():
+    """scores_all = _hidden_rows (what the fused recommend() scores too) followed by drx_rows_dot, bit for bit"""
+    import torch
+    from drecpy_amd import _lib
+    from drecpy_amd.engine_caser import CaserEngine
+    rng = np.random.default_rng(9)
+    U, N, L, B = 12, 40, 5, 3
+    eng = CaserEngine(U, N, L, 3, 3, 50, 4, 16)
+    eng.set_params(ca.init_params(rng, U, N, L, 50, 4, 16, np.float64))
+    uids = rng.integers(0, U, size=B)
+    before = rng.integers(0, N, size=(B, L))
+    sc = eng.scores_all(uids, before)
+    assert tuple(sc.shape) == (B, N) and sc.dtype == torch.float32
+    cat = eng._hidden_rows(eng._dev_i32(uids), eng._dev_i32(before))
+    want = torch.empty(B, N, dtype=torch.float32, device='cuda')
+    _lib.check(_lib.lib().drx_rows_dot(_lib.ptr(cat), B, _lib.ptr(eng.W1), N, eng.ld2, _lib.ptr(eng.b1), _lib.ptr(want),
+                                       _lib.stream_ptr(eng.device)), 'drx_rows_dot')
+    assert torch.equal(sc, want)
+
+
 @pytest.mark.parametrize('d,L,n_v,n_h,T,neg,B,drop', [(100, 9, 4, 16, 3, 3, 64, True), (128, 16, 2, 8, 2, 2, 37, False), (72, 5, 4, 16, 3, 3, 50, True)])
 def test_torch_checker_matches_oracle_also_beyond_the_kernels_domain(d, L, n_v, n_h, T, neg, B, drop):
     """The second checker (tests/caser_torch_checker.py: the forward of caser.py:97-120 in torch operations, torch.autograd where the

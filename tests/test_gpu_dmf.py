@@ -134,6 +134,43 @@ def test_dmf_fit_matches_oracle_end_to_end():
     assert sm.shape == (1, N)
 
 
+@pytest.mark.parametrize('scaled', [False, True])
+def test_score_matrix_scores_the_rows_predict_gives(scaled):
+    """score_matrix_bf16 takes its rows from one tower at a time (_representations); they are the rows predict(want_reps=True)
+    hands out — a tower's row depends on its own id alone —, so the matrix equals, bit for bit, the scorer fed with those; with and
+    without a bound prediction scale."""
+    import torch
+    from drecpy_amd import _lib
+    from drecpy_amd.engine_dmf import DmfEngine
+    from drecpy_amd.Recommender import Variable
+    rng = np.random.default_rng(21)
+    U, N, R = 40, 70, 5
+    csr, csc, _ = _problem(rng, U, N, 900)
+    p = dm.init_params(rng, U, N, (64, 32), (64, 32), np.float64)
+    eng = DmfEngine(U, N)
+    eng.set_interactions(csr, csc)
+    if scaled:
+        eng.bind_prediction_scale(Variable([1.0]), broadcast_targets=True)
+        p = dict(p, extra_w=np.array([1.75]))
+    eng.set_params(p)
+    uids = rng.choice(U, size=R, replace=False)
+    sc = eng.score_matrix_bf16(uids)
+    assert tuple(sc.shape) == (R, N)
+    _, ru, _ = eng.predict(uids, np.zeros(R, np.int64), want_reps=True)
+    _, _, ri = eng.predict(np.zeros(N, np.int64), np.arange(N), want_reps=True)
+    pitch = 96                                              # (N rounded up to 32 floats: the scorer's row pitch)
+    want = torch.empty(R, pitch, dtype=torch.float32, device='cuda')
+    scale = _lib.ptr(eng.sw[eng._scale_slot:]) if scaled else None
+    _lib.check(_lib.lib().drx_score_pairs_bf16(_lib.ptr(ru), R, _lib.ptr(ri), N, eng.W, 32, scale, _lib.ptr(want), pitch,
+                                               _lib.stream_ptr(eng.device)), 'drx_score_pairs_bf16')
+    assert torch.equal(sc, want[:, :N])
+    if scaled:                                              # (the scale reaches the scores)
+        plain = torch.empty_like(want)
+        _lib.check(_lib.lib().drx_score_pairs_bf16(_lib.ptr(ru), R, _lib.ptr(ri), N, eng.W, 32, None, _lib.ptr(plain), pitch,
+                                                   _lib.stream_ptr(eng.device)), 'drx_score_pairs_bf16')
+        assert not torch.equal(sc, plain[:, :N])
+
+
 # ---- ModifiedDMF: the model BASELINE.json config 3 names (examples/extending_recommender_dmf.py) ------------------------------
 def _modified_engine(U, N, csr, csc, p, uf=(64, 32), itf=(64, 32)):
     from drecpy_amd.engine_dmf import DmfEngine

@@ -68,6 +68,36 @@ def test_topk_matches_heapq(n, k):
         assert (idx[r] >= 0).sum() == min(k, int(mask[r].sum()))
 
 
+@pytest.mark.parametrize('n,k', [(45, 7), (5, 1)])
+def test_masked_topk_packs_rows_that_share_words(n, k):
+    """masked_topk — the one place a host candidate mask becomes device words — where the packing can go wrong: rows of n bits
+    that are no multiple of 32, so a row's bits start inside a word of its neighbour's; a row with fewer candidates than k,
+    a row with none (ranking_evaluation: novelty removed every candidate of a user)."""
+    import torch
+    from drecpy_amd.engine import CdaeEngine, pack_mask_bits
+    eng = CdaeEngine(4, 8, 4)
+    rng = np.random.default_rng(n)
+    R = 3
+    scores = rng.random((R, n)).astype(np.float32)
+    scores[:, ::3] = scores[:, 1:2]                    # exact ties -> larger index must win
+    cand = np.zeros((R, n), dtype=bool)
+    cand[0] = True
+    cand[0, [0, n - 1]] = False                        # (the bits next to the neighbouring rows')
+    cand[2, [0, n - 1] if k > 1 else [n - 1]] = True   # fewer than k candidates where k allows it: the row's first and last bit
+    d_scores = torch.as_tensor(scores).cuda()
+    idx, val = eng.masked_topk(d_scores, cand, k)
+    ref_idx, ref_val = eng.topk(d_scores, k, torch.as_tensor(pack_mask_bits(cand).view(np.int32)).cuda())
+    assert idx.dtype == torch.int32 and val.dtype == torch.float32 and tuple(idx.shape) == tuple(val.shape) == (R, k)
+    assert torch.equal(idx, ref_idx) and torch.equal(val, ref_val)
+    idx, val = idx.cpu().numpy(), val.cpu().numpy()
+    for r in range(R):
+        want = co.rank_row(scores[r], np.flatnonzero(cand[r]), k)
+        got = [(float(v), int(i)) for v, i in zip(val[r], idx[r]) if i >= 0]
+        assert got == [(float(np.float32(v)), i) for v, i in want]
+        assert (idx[r] >= 0).sum() == min(k, int(cand[r].sum()))
+    assert (idx[1] == -1).all()                        # the row without a candidate: no entry
+
+
 @pytest.mark.parametrize('n,bits', [(1, 1), (63, 9), (64, 10), (4096, 18), (4097, 18), (100_003, 25), (1_440_000, 25), (300_000, 27), (70_000, 32),
                                     (200_000, 12), (500_000, 16), (33_000, 8)])      # narrow keys over many tiles: one- and two-pass plans
 def test_sort_pairs_is_a_stable_sort(n, bits):

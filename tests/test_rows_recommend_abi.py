@@ -3,6 +3,8 @@ DRX_REC_* epilogues, and drecpy_amd/_lib.py binds them with matching argument co
 import os
 import re
 
+import pytest
+
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 
 
@@ -37,3 +39,21 @@ def test_the_engines_share_one_launcher():
     for cls in (CdaeEngine, DmfEngine, CaserEngine):
         assert issubclass(cls, RowsRecommender) and cls._rows_recommend is RowsRecommender._rows_recommend
         assert cls.set_exclusions is RowsRecommender.set_exclusions and 'recommend' in vars(cls)
+        # ... and so do the score-matrix route's selection and the upload of host ids
+        for name in ('topk', 'masked_topk', '_dev_i32'):
+            assert getattr(cls, name) is getattr(RowsRecommender, name) and name in vars(RowsRecommender), (cls, name)
+    # no engine or model borrows them from the CDAE engine any more
+    from drecpy_amd import engine_dmf
+    from drecpy_amd.Recommender import caser
+    assert 'CdaeEngine' not in vars(engine_dmf) and 'CdaeEngine' not in vars(caser)
+
+
+@pytest.mark.parametrize('n_items', [1, 7, 3706, 1_000_000])
+def test_users_per_chunk_of_the_score_matrix_route(n_items):
+    """the chunk function of ranking_evaluation and CdaeEngine's score-matrix route against the literal expression; 4 * n_items * 7
+    bytes are the 7 users per chunk tests/test_evaluation.py forces"""
+    from drecpy_amd.engine import RowsRecommender
+    for budget in (1 << 30, 4 * n_items * 7):
+        want = max(1, min(budget // (4 * n_items), ((1 << 31) - 1) // n_items))
+        assert RowsRecommender.matrix_chunk_users(n_items, budget) == want
+    assert RowsRecommender.matrix_chunk_users(n_items, 4 * n_items * 7) == 7
