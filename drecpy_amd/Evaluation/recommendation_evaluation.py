@@ -2,7 +2,11 @@
 examples/caser.py:17-18): per test user `model.recommend(user, n=max(k), novelty)` against the user's (sampled) test
 positives; user i draws from `random.Random(seed + i)`; result keys `metric@k`, rounded to 4 decimals.
 batched=True (default off: the loop above) draws every user's positives first — same streams, same skipping — and asks the model for all
-lists in ONE `model.recommend_batch` call."""
+lists in ONE `model.recommend_batch` call.
+batched='ranks': the same protocol, but instead of lists ONE `model.catalogue_ranks` call for every (user, item) row of the drawn
+users' test data; each user's first min(max(k), eligible items) positions are rebuilt from the ranks (a position holds the test item
+whose rank it is, else a placeholder of relevance 0) and fed to the same metrics — no list is selected, so max(k) is not bounded by
+the fused selector's 128.  It takes no `ignore_low_predictions_threshold`."""
 import logging
 import random
 
@@ -21,9 +25,13 @@ def recommendation_evaluation(model, ds_test=None, n_test_users=None, k=10, n_po
     users = ds_test.unique('user').values_list('user', to_list=True)
     if n_test_users is not None:
         users = users[:n_test_users]
+    if isinstance(batched, str):
+        assert batched == 'ranks', f"batched: False, True or 'ranks' (got {batched!r})"
+        assert ignore_low_predictions_threshold is None, \
+            "batched='ranks' places items by their catalogue rank: it takes no ignore_low_predictions_threshold."
     if batched:
         return _evaluate_batched(model, ds_test, users, table, ks, threshold, n_pos_interactions, novelty,
-                                 ignore_low_predictions_threshold, seed)
+                                 ignore_low_predictions_threshold, seed, by_ranks=batched == 'ranks')
     for offset, user in enumerate(users):
         user = user.item() if hasattr(user, 'item') else user
         try:
@@ -44,7 +52,35 @@ def recommendation_evaluation(model, ds_test=None, n_test_users=None, k=10, n_po
     return table.result()
 
 
-def _evaluate_batched(model, ds_test, users, table, ks, threshold, n_pos_interactions, novelty, low_threshold, seed):
+class _Other:
+    """An item of a rebuilt list that is none of the user's test items: unique, relevance 0, equal to no id (nor its text)."""
+    __slots__ = ()
+
+
+def _lists_from_ranks(model, drawn_users, n, novelty):
+    """What recommend_batch(n) would list, as far as the metrics can tell, from ONE model.catalogue_ranks call over every (user, item)
+    row of the drawn users' test data: position p of a user's list holds the test item whose catalogue rank is p, every other of
+    the first min(n, eligible items) positions an _Other.  [[(None, item), ...], ...] like recommend_batch's lists."""
+    pair_users, pair_items, owner = [], [], []
+    for j, (user, user_ds, _, _) in enumerate(drawn_users):
+        items = user_ds.values_list('item', to_list=True)
+        pair_users += [user] * len(items)
+        pair_items += [item.item() if hasattr(item, 'item') else item for item in items]
+        owner += [j] * len(items)
+    ranks = model.catalogue_ranks(pair_users, pair_items, novelty=novelty)
+    ds = model.interaction_dataset
+    excl_ptr = model._exclusion_csr()[0] if novelty else None
+    lists = []
+    for user, _, _, _ in drawn_users:
+        taken = int(excl_ptr[ds.user_to_uid(user) + 1] - excl_ptr[ds.user_to_uid(user)]) if novelty else 0
+        lists.append([(None, _Other()) for _ in range(min(n, model.n_items - taken))])
+    for j, item, rank in zip(owner, pair_items, ranks):
+        if 0 <= rank < len(lists[j]):
+            lists[j][rank] = (None, ds.iid_to_item(ds.item_to_iid(item)))
+    return lists
+
+
+def _evaluate_batched(model, ds_test, users, table, ks, threshold, n_pos_interactions, novelty, low_threshold, seed, by_ranks=False):
     drawn_users = []
     for offset, user in enumerate(users):
         user = user.item() if hasattr(user, 'item') else user
@@ -61,11 +97,14 @@ def _evaluate_batched(model, ds_test, users, table, ks, threshold, n_pos_interac
         drawn_users.append((user, user_ds, drawn[0], drawn[1]))
     if not drawn_users:
         return table.result()
-    lists = model.recommend_batch([u for u, _, _, _ in drawn_users], n=max(ks), novelty=novelty, interaction_threshold=low_threshold)
+    if by_ranks:
+        lists = _lists_from_ranks(model, drawn_users, max(ks), novelty)
+    else:
+        lists = model.recommend_batch([u for u, _, _, _ in drawn_users], n=max(ks), novelty=novelty, interaction_threshold=low_threshold)
     for (user, user_ds, relevant, best), ranked in zip(drawn_users, lists):
         try:
             recommendations = [item for _, item in ranked]
-            relevancies = {item: (user_ds.select_one(f'item == {item}', ['interaction'], to_list=True) or 0)
+            relevancies = {item: 0 if isinstance(item, _Other) else (user_ds.select_one(f'item == {item}', ['interaction'], to_list=True) or 0)
                            for item in set(relevant) | set(recommendations)}
         except Exception as err:
             logging.error(err)

@@ -263,6 +263,24 @@ class Caser(RecommenderABC):
             idx[full], val[full] = self._recommend_batch_fused(uids[full], n, novelty, before)
         return idx, val
 
+    def _catalogue_ranks(self, uids, iids, novelty):
+        """Catalogue ranks of many (user, item) pairs in one engine call (CaserEngine.rank_items), under _recommend_batch's gates,
+        exclusions and values (logits): a subclass with its own _rank, and users whose sequence is shorter than L, take the default."""
+        uids, iids = np.asarray(uids, dtype=np.int64), np.asarray(iids, dtype=np.int64)
+        eng = self._engine
+        if type(self)._rank is not Caser._rank or not eng.rank_is_fused(eng.ld2):
+            return super()._catalogue_ranks(uids, iids, novelty)
+        self._user_sequence(0)                                            # (builds _seq_ptr / _seq_items)
+        full = (self._seq_ptr[uids + 1] - self._seq_ptr[uids]) >= self.L
+        ranks = np.full(len(uids), -1, dtype=np.int64)
+        scores = np.full(len(uids), -np.inf, dtype=np.float64)
+        if not full.all():
+            ranks[~full], scores[~full] = super()._catalogue_ranks(uids[~full], iids[~full], novelty)
+        if full.any():
+            before = np.stack([self._user_sequence(x)[-self.L:] for x in uids[full]])
+            ranks[full], scores[full] = self._catalogue_ranks_fused(uids[full], iids[full], novelty, before)
+        return ranks, scores
+
     def _exclusion_csr(self):
         return self._sequence_csr()
 

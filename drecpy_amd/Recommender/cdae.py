@@ -530,6 +530,13 @@ class CDAE(RecommenderABC):
         _all_user_items gives _rank."""
         return self._recommend_batch_fused(uids, n, novelty)
 
+    def _catalogue_ranks(self, uids, iids, novelty):
+        """Catalogue ranks of many (user, item) pairs in one engine call (CdaeEngine.rank_items: scores and counting fused on the
+        device), on _recommend_batch's arithmetic and exclusions.  Rows wider than the fused domain: one _recommend per user."""
+        if not self._engine.rank_is_fused(self._engine.ld):
+            return super()._catalogue_ranks(uids, iids, novelty)
+        return self._catalogue_ranks_fused(uids, iids, novelty)
+
     def _all_user_items(self, uid):
         if not hasattr(self, '_user_items'):
             ds = self.interaction_dataset

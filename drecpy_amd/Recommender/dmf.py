@@ -221,10 +221,13 @@ class DMF(RecommenderABC):
     def _recommend_batch_is_fused(self, n_users, n):
         """The fused path computes DMF's OWN score (clipped cosine, rescaled): a subclass that overrides the prediction hooks
         (ModifiedDMF) or binds a prediction scale keeps its arithmetic — one _recommend per user."""
+        return self._fused_score_is_own(n_users) and self._engine.recommend_is_fused(self._engine.W, n)
+
+    def _fused_score_is_own(self, n_users):
         cls, eng = type(self), self._engine
         return (cls._predict_batch is DMF._predict_batch and cls._predict is DMF._predict and cls._rank is DMF._rank
                 and eng.scale_var is None and self.max_interaction > self.min_interaction
-                and n_users >= self.RECOMMEND_MIN_FUSED_USERS and eng.recommend_is_fused(eng.W, n))
+                and n_users >= self.RECOMMEND_MIN_FUSED_USERS)
 
     def _recommend_batch(self, uids, n, novelty):
         """Top-n of the whole catalogue for many users in one engine call (DmfEngine.recommend: the item tower once over the catalogue,
@@ -237,6 +240,14 @@ class DMF(RecommenderABC):
             return super()._recommend_batch(uids, n, novelty)
         idx, val = self._recommend_batch_fused(uids, n, novelty)
         return idx, np.where(idx >= 0, self._rescale_value(val.astype(np.float64)), -np.inf)
+
+    def _catalogue_ranks(self, uids, iids, novelty):
+        """Catalogue ranks of many (user, item) pairs in one engine call (DmfEngine.rank_items), under _recommend_batch's gate (without
+        its bound on n), exclusions and values: a subclass with its own prediction hooks keeps its arithmetic."""
+        if not (self._fused_score_is_own(len(np.unique(uids))) and self._engine.rank_is_fused(self._engine.W)):
+            return super()._catalogue_ranks(uids, iids, novelty)
+        rank, score = self._catalogue_ranks_fused(uids, iids, novelty)
+        return rank, np.where(rank >= 0, self._rescale_value(score), -np.inf)
 
     def score_matrix(self, user_ids):
         """[len(user_ids), n_items] clipped cosine scores via the bf16 MFMA scorer (raw user ids in)."""

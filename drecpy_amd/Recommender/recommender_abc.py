@@ -516,6 +516,58 @@ class RecommenderABC(ABC):
             val = np.concatenate([val, np.full((len(val), pad), -np.inf, np.float32)], axis=1)
         return idx, val
 
+    def catalogue_ranks(self, user_ids, item_ids, novelty=True, return_scores=False):
+        """Where in the WHOLE catalogue given items stand for given users (no reference equivalent): for the parallel sequences of raw
+        ids, np.int64 [P] — the 0-based position of item_ids[p] in what recommend(user_ids[p], n=None, novelty) would list, on
+        recommend_batch's arithmetic —, -1 where the item is unknown to the model or excluded for that user under novelty; an unknown
+        user raises as recommend() does.  return_scores=True: (ranks, np.float64 [P] the values recommend_batch reports, -inf beside
+        a -1).  What full-catalogue HR@k / NDCG@k / MRR need, for any k, without lists (recommendation_evaluation(batched='ranks')).
+        One query row per pair: a user with T held-out items costs T rows.  CDAE, DMF and Caser answer from the fused scorer-counter
+        (DESIGN.md section 3.5)."""
+        assert self.fitted is True, 'The model requires to be fitted before being able to make predictions.'
+        uids = np.fromiter((self._require_user(user) for user in user_ids), dtype=np.int64)
+        to_iid = self.interaction_dataset.item_to_iid
+        iids = np.fromiter((-1 if iid is None else iid for iid in (to_iid(item) for item in item_ids)), dtype=np.int64)
+        assert len(uids) == len(iids), f'catalogue_ranks takes parallel sequences ({len(uids)} users, {len(iids)} items)'
+        if len(uids) == 0:
+            ranks, scores = np.zeros(0, np.int64), np.zeros(0, np.float64)
+        else:
+            ranks, scores = self._catalogue_ranks(uids, iids, novelty)
+        return (ranks, scores) if return_scores else ranks
+
+    def _catalogue_ranks(self, uids, iids, novelty):
+        """Hook: parallel internal ids [P] (iid -1 = unknown item) -> numpy (ranks int64 [P], -1 = not listed; scores float64 [P], -inf
+        beside a -1).  Default: positions in one _recommend(uid, n_items, novelty, None) per distinct user — the model's own
+        arithmetic, whatever it is."""
+        ranks = np.full(len(uids), -1, dtype=np.int64)
+        scores = np.full(len(uids), -np.inf, dtype=np.float64)
+        for uid in np.unique(uids):
+            place = {iid: (j, score) for j, (score, iid) in enumerate(self._recommend(int(uid), self.n_items, novelty, None))}
+            for p in np.flatnonzero(uids == uid):
+                if int(iids[p]) in place:
+                    ranks[p], scores[p] = place[int(iids[p])]
+        return ranks, scores
+
+    def _catalogue_ranks_fused(self, uids, iids, novelty, *query):
+        """What the models' _catalogue_ranks share, beside _recommend_batch_fused: ONE engine.rank_items(uids, *query, iids) for all
+        pairs — under novelty without the rows of _exclusion_csr, uploaded once per engine —, downloaded as (ranks int64 [P], scores
+        float64 [P]).  The device ignores a target's own exclusion: an excluded pair is set to -1 / -inf here."""
+        uids, iids = np.asarray(uids, dtype=np.int64), np.asarray(iids, dtype=np.int64)
+        with self._device_lock:
+            eng = self._engine
+            if novelty and getattr(eng, '_excl', None) is None:
+                eng.set_exclusions(*self._exclusion_csr())
+            rank, score = eng.rank_items(uids.astype(np.int32), *query, iids.astype(np.int32), exclude=bool(novelty))
+            rank, score = rank.cpu().numpy().astype(np.int64), score.cpu().numpy().astype(np.float64)
+            if novelty:
+                _, _, ip, ix = eng._excl
+                cells = np.repeat(np.arange(len(ip) - 1, dtype=np.int64), np.diff(ip)) * self.n_items + ix      # ascending: rows, then columns
+                wanted = uids * self.n_items + iids
+                at = np.minimum(np.searchsorted(cells, wanted), max(len(cells) - 1, 0))
+                excluded = (cells[at] == wanted) if len(cells) else np.zeros(len(wanted), bool)
+                rank[excluded & (iids >= 0)], score[excluded & (iids >= 0)] = -1, -np.inf
+        return rank, score
+
     def rank(self, user_id, item_ids, novelty=True, skip_invalid_items=True, **kwds):
         uid = self._require_user(user_id)
         ds = self.interaction_dataset

@@ -23,6 +23,9 @@
 //               the n largest written out.
 // Every score is the same fmaf chain whatever the tile, the split or the neighbours of its user, and the keys are unique, so the
 // result is a function of the inputs alone (bit-identical between calls, request orders and chunkings).
+//
+// drx_rows_rank_items (k_rank_keys / k_rank_count / k_rank_finish, at the end of this file) answers the other question on the same walk:
+// where in the whole catalogue a GIVEN item stands for a row — a count of larger keys instead of a selection.
 #include <hip/hip_runtime.h>
 #include "drx_common.hpp"
 
@@ -69,20 +72,41 @@ __device__ __forceinline__ float rec_logit_bound(float s) {
 // An epilogue: the score of a finished sum z (the item's bias already added where kBias), and for the score s of a list's n-th best a
 // bound on z: every z below it scores STRICTLY below s (such a z is dropped after one compare; the others take the exact key compare).
 // "No n-th best yet" is never read off a score's sign: rec_compact sets the bound only once a list holds n eligible keys.
+// The counting kernels (k_rank_count, below) want the bound from both sides for ONE item's sum z and score s: band(z, s, zlo, zhi) gives
+// zlo <= zhi such that every sum above zhi scores STRICTLY above s and every sum below zlo STRICTLY below it; the sums in between
+// (the band) take the exact score and key compare, so only speed rests on the band's width.  A side without a proof is open (+-inf).
 struct RecSigmoidBias {                   // DRX_REC_SIGMOID_BIAS
   static constexpr bool kBias = true;
   static __device__ __forceinline__ float score(float z) { return sigmoidf_(z); }
   static __device__ __forceinline__ float bound(float s) { return rec_logit_bound(s); }
+  // the mirror image of rec_logit_bound, by the same derivation (a step of 0.02 + 1e-5 |z| upwards raises the score by more than
+  // 2e-6 relative while 1 - s >= 2^-12).  Towards saturation many sums share the score: open above.  Below 1e-30 (0 included) the
+  // quotient of sigmoidf_ leaves the normal floats and the relative-error argument with them: open below, and sigmoid(-60) = 8.7e-27
+  // lies above every such s.
+  static __device__ __forceinline__ void band(float z, float s, float &zlo, float &zhi) {
+    (void)z;
+    if (!(s >= 1e-30f)) { zlo = -INFINITY; zhi = -60.0f; return; }
+    zlo = rec_logit_bound(s);
+    const float om = 1.0f - s;
+    if (om < 0x1p-12f) { zhi = INFINITY; return; }
+    const float zs = logf(s / om);
+    zhi = zs + 0.02f + 1e-5f * fabsf(zs);
+  }
 };
 struct RecBias {                          // DRX_REC_BIAS: the sum is the compared value: exact, no margin (negative scores included)
   static constexpr bool kBias = true;
   static __device__ __forceinline__ float score(float z) { return z; }
   static __device__ __forceinline__ float bound(float s) { return s; }
+  static __device__ __forceinline__ void band(float z, float s, float &zlo, float &zhi) { (void)s; zlo = zhi = z; }   // the band: z == zt
 };
 struct RecClip {                          // DRX_REC_CLIP: at the floor every item ties and the item index decides: no bound there
   static constexpr bool kBias = false;
   static __device__ __forceinline__ float score(float z) { return fmaxf(1e-6f, z); }
   static __device__ __forceinline__ float bound(float s) { return s > 1e-6f ? s : -INFINITY; }
+  static __device__ __forceinline__ void band(float z, float s, float &zlo, float &zhi) {
+    if (s > 1e-6f) { zlo = zhi = z; return; }       // above the floor the score is the sum
+    zlo = -INFINITY; zhi = 1e-6f;                   // at the floor: everything at or below it ties, everything above it is ahead
+  }
 };
 
 struct RecArgs {
@@ -421,6 +445,328 @@ int rec_run(const float *table, const float *bias, int n_items, int ld, int epil
   }
 }
 
+// ---- catalogue ranks of given (row, item) pairs (drx_rows_rank_items) ------------------------------------------------------------------
+// rank[r] = the number of eligible items i != t[r] whose key is larger than the key of the row's target t[r]: the position of t[r] in
+// the list k_recommend + k_recommend_merge would give for an unbounded n.  Counting needs no lists: the same product walk, two compares
+// per score.
+// k_rank_keys    grid (user tiles).  The targets' own sums and keys: a wave walks its 32 rows and computes the 128-item block that holds
+//                a row's target (none when it is the block just done), with k_recommend's fragment loads and MFMA order — the same
+//                chain, bit for bit.  The lane that owns the element writes tz[r] / tkey[r].
+// k_rank_count   grid (user tiles, item splits).  The walk of k_recommend over the split; per lane the target's key and the band
+//                zlo <= zhi of its epilogue.  A finished tile gives two bit masks (ahead for certain / in the band); the bits of items
+//                behind the split's end, of the target and of excluded items are cleared, the first mask is counted, the band's bits
+//                take the exact key compare.  Exclusions: a cursor into the user's ascending CSR row, advanced block by block.
+// k_rank_finish  a row's 2 x splits partial counts summed in a fixed order (no atomics anywhere).
+struct RankArgs {
+  const int32_t *target;         // [R]
+  float *tz;                     // [R] the target's biased sum
+  u64 *tkey;                     // [R] its key; 0: a target outside the catalogue
+  int *partial;                  // [tiles][splits][128][2]
+};
+
+// (as the head of k_recommend) the tile's query rows into LDS, zero behind R and behind ld
+__device__ __forceinline__ void rank_load_q(const RecArgs &A, float *h_s, int tid, int r0) {
+  const int ldp4 = A.nch * (kRecKC / 4);
+  for (int i = tid; i < kRecUsers * ldp4; i += 256) {
+    const int u = i / ldp4, c4 = i - u * ldp4;
+    float4 v = f4_zero();
+    if (r0 + u < A.R && 4 * c4 < A.ld) v = *reinterpret_cast<const float4 *>(A.q + (size_t)(r0 + u) * A.ld + 4 * c4);
+    *reinterpret_cast<float4 *>(h_s + (size_t)u * A.hs + 4 * c4) = v;
+  }
+}
+
+// one chunk of k_recommend's walk: 4 MFMAs per tile and k step, in its order
+__device__ __forceinline__ void rank_chunk(const RecArgs &A, const float4 (&a)[4][kRecKT], int kc, const float *hrow, f32x16 (&acc)[4]) {
+#pragma unroll
+  for (int t = 0; t < kRecKT; ++t) {
+    if (kc * kRecKC + 8 * t < A.ld) {
+      const float4 b = *reinterpret_cast<const float4 *>(hrow + kc * kRecKC + 8 * t);
+#pragma unroll
+      for (int s = 0; s < 4; ++s) acc[s] = __builtin_amdgcn_mfma_f32_32x32x2f32(a[s][t].x, b.x, acc[s], 0, 0, 0);
+#pragma unroll
+      for (int s = 0; s < 4; ++s) acc[s] = __builtin_amdgcn_mfma_f32_32x32x2f32(a[s][t].y, b.y, acc[s], 0, 0, 0);
+#pragma unroll
+      for (int s = 0; s < 4; ++s) acc[s] = __builtin_amdgcn_mfma_f32_32x32x2f32(a[s][t].z, b.z, acc[s], 0, 0, 0);
+#pragma unroll
+      for (int s = 0; s < 4; ++s) acc[s] = __builtin_amdgcn_mfma_f32_32x32x2f32(a[s][t].w, b.w, acc[s], 0, 0, 0);
+    }
+  }
+}
+
+// The biased sums of the block at item0 in acc (the walk both kernels share).  a0 holds chunk 0 of the block on entry and chunk 0 of
+// the block at item_next on return.
+template <class E>
+__device__ __forceinline__ void rank_block(const RecArgs &A, int item0, int item_next, int col, int hh, const float *hrow,
+                                           float4 (&a0)[4][kRecKT], float4 (&a1)[4][kRecKT], f32x16 (&acc)[4]) {
+  f32x16 bias[4];
+#pragma unroll
+  for (int s = 0; s < 4; ++s)
+#pragma unroll
+    for (int e = 0; e < 16; ++e) acc[s][e] = 0.f;
+  for (int kc = 0; kc + 2 < A.nch; kc += 2) {
+    rec_load_a(A, item0, kc + 1, col, hh, a1);
+    rank_chunk(A, a0, kc, hrow, acc);
+    rec_load_a(A, item0, kc + 2, col, hh, a0);
+    rank_chunk(A, a1, kc + 1, hrow, acc);
+  }
+  rec_load_a(A, item0, A.nch - 1, col, hh, a1);
+  if constexpr (E::kBias) rec_load_bias(A, item0, hh, bias);
+  rank_chunk(A, a0, A.nch - 2, hrow, acc);
+  rec_load_a(A, item_next, 0, col, hh, a0);
+  rank_chunk(A, a1, A.nch - 1, hrow, acc);
+  if constexpr (E::kBias) {
+#pragma unroll
+    for (int s = 0; s < 4; ++s)
+#pragma unroll
+      for (int e = 0; e < 16; ++e) acc[s][e] += bias[s][e];
+  }
+}
+
+template <class E>
+__global__ __launch_bounds__(256) void k_rank_keys(RecArgs A, RankArgs K) {
+  extern __shared__ __align__(16) float lds[];
+  float *h_s = lds;                                                   // [128][hs]
+  float *dump_all = h_s + (size_t)kRecUsers * A.hs;                   // [4 waves][16 registers][64 lanes]
+  const int tid = threadIdx.x, lane = tid & 63, col = lane & 31, hh = lane >> 5;
+  const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
+  const int r0 = blockIdx.x * kRecUsers;
+  rank_load_q(A, h_s, tid, r0);
+  __syncthreads();
+  if (r0 + wave * 32 >= A.R) return;                                  // (no row in this wave; no barrier below)
+
+  float *dump = dump_all + wave * (16 * 64);
+  const float *hrow = h_s + (size_t)(wave * 32 + col) * A.hs + 4 * hh;
+  f32x16 acc[4];
+  float4 a0[4][kRecKT], a1[4][kRecKT];
+  int done = -1;                                                      // the block acc holds
+  for (int j = 0; j < 32; ++j) {
+    const int r = r0 + wave * 32 + j;
+    if (r >= A.R) break;
+    const int t = __builtin_amdgcn_readfirstlane(K.target[r]);
+    if ((unsigned)t >= (unsigned)A.N) {
+      if (lane == j) { K.tz[r] = 0.f; K.tkey[r] = 0ull; }
+      continue;
+    }
+    const int item0 = t & ~(kRecItems - 1);
+    if (item0 != done) {
+      rec_load_a(A, item0, 0, col, hh, a0);
+      rank_block<E>(A, item0, item0, col, hh, hrow, a0, a1, acc);
+      done = item0;
+    }
+    // element (item t, row j) of the block: tile ts, register te of the lane with column j in half th
+    const int off = t - item0, ts = off >> 5, m = off & 31, te = 4 * (m >> 3) + (m & 3), th = (m >> 2) & 1;
+#pragma unroll
+    for (int s = 0; s < 4; ++s) {
+      if (s == ts) {
+#pragma unroll
+        for (int e = 0; e < 16; ++e) dump[e * 64 + lane] = acc[s][e];   // (a lane reads back its own words only)
+      }
+    }
+    if (lane == 32 * th + j) {
+      const float z = dump[te * 64 + lane];
+      K.tz[r] = z;
+      K.tkey[r] = ((u64)rec_ordered_bits(E::score(z)) << 32) | (unsigned)t;
+    }
+  }
+}
+
+template <class E>
+__global__ __launch_bounds__(256) void k_rank_count(RecArgs A, RankArgs K) {
+  extern __shared__ __align__(16) float lds[];
+  float *h_s = lds;                                                   // [128][hs]
+  float *dump_all = h_s + (size_t)kRecUsers * A.hs;                   // [4 waves][16 registers][64 lanes]
+  const int tid = threadIdx.x, lane = tid & 63, col = lane & 31, hh = lane >> 5;
+  const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
+  const int tile = blockIdx.x, sp = blockIdx.y;
+  const int r0 = tile * kRecUsers;
+  rank_load_q(A, h_s, tid, r0);
+  __syncthreads();
+  if (r0 + wave * 32 >= A.R) return;                                  // (no row in this wave; no barrier below)
+
+  float *dump = dump_all + wave * (16 * 64);
+  const int ul = wave * 32 + col, r = r0 + ul;
+  const bool uvalid = r < A.R;
+  const int i_begin = sp * A.ips, i_end = (int)min((int64_t)A.N, (int64_t)i_begin + A.ips);
+  const int nblocks = (int)(((int64_t)i_end - i_begin + kRecItems - 1) / kRecItems);
+  const float *hrow = h_s + (size_t)ul * A.hs + 4 * hh;
+
+  u64 tkey = 0ull;
+  float zlo = INFINITY, zhi = INFINITY;                               // (no row, no target: nothing is counted)
+  unsigned t = 0xFFFFFFFFu;
+  int64_t xc = 0, xhi = 0;                                            // the cursor into the user's exclusion row, its end
+  if (uvalid) {
+    tkey = K.tkey[r];
+    if (tkey != 0ull) {
+      t = (unsigned)tkey;
+      E::band(K.tz[r], rec_score_of(tkey), zlo, zhi);
+      if (A.xptr) {
+        const int u = A.uid[r];
+        int64_t lo = A.xptr[u];
+        const int64_t end = A.xptr[u + 1];
+        xhi = end;
+        int64_t hi = end;
+        while (lo < hi) {                                             // the first entry at or behind the split's first item
+          const int64_t mid = lo + ((hi - lo) >> 1);
+          if (A.xidx[mid] < i_begin) lo = mid + 1; else hi = mid;
+        }
+        xc = lo;
+      }
+    }
+  }
+  // the target's place, if it lies in this lane's half of a tile: the tile's first item and the register (else no tile matches)
+  const unsigned tm = t & 31u;
+  const unsigned t_tile = (t != 0xFFFFFFFFu && ((tm >> 2) & 1u) == (unsigned)hh) ? (t & ~31u) : 0xFFFFFFFFu;
+  const uint32_t t_bit = 1u << (4u * (tm >> 3) + (tm & 3u));
+
+  f32x16 acc[4];
+  float4 a0[4][kRecKT], a1[4][kRecKT];
+  int cnt = 0;
+  rec_load_a(A, i_begin, 0, col, hh, a0);
+  for (int blk = 0; blk < nblocks; ++blk) {
+    const int item0 = i_begin + blk * kRecItems;
+    // the excluded items of the block in this lane's half: bit 16 s + e of xm (the loads overlap the products below)
+    u64 xm = 0ull;
+    while (xc < xhi) {
+      const unsigned off = (unsigned)A.xidx[xc] - (unsigned)item0;
+      if (off >= (unsigned)kRecItems) break;                          // (behind the block; entries ascend, none lies before it)
+      ++xc;
+      if (((off >> 2) & 1u) == (unsigned)hh) xm |= 1ull << (16u * (off >> 5) + 4u * ((off & 31u) >> 3) + (off & 3u));
+    }
+    rank_block<E>(A, item0, blk + 1 < nblocks ? item0 + kRecItems : item0, col, hh, hrow, a0, a1, acc);
+    const bool whole = (unsigned)item0 + (unsigned)kRecItems <= (unsigned)i_end;   // wave-uniform: every block but the split's last
+#pragma unroll
+    for (int s = 0; s < 4; ++s) {
+      const unsigned ibase = (unsigned)item0 + 32u * s + 4u * hh;
+      uint32_t ma = 0, mb = 0, keep = 0xFFFFu;
+#pragma unroll
+      for (int e = 0; e < 16; ++e) {
+        const float z = acc[s][e];
+        ma |= (z > zhi) ? (1u << e) : 0u;
+        mb |= (z >= zlo && z <= zhi) ? (1u << e) : 0u;
+      }
+      if (!whole) {
+        keep = 0;
+#pragma unroll
+        for (int e = 0; e < 16; ++e) keep |= (ibase + 8u * (e >> 2) + (e & 3) < (unsigned)i_end) ? (1u << e) : 0u;
+      }
+      keep &= ~(uint32_t)((xm >> (16 * s)) & 0xFFFFull);
+      if ((unsigned)item0 + 32u * s == t_tile) keep &= ~t_bit;        // i != t, whatever the band
+      ma &= keep;
+      mb &= keep;
+      cnt += __popc(ma);
+      if (__ballot(mb != 0)) {                                        // the band: rare unless many items tie with the target
+#pragma unroll
+        for (int e = 0; e < 16; ++e) dump[e * 64 + lane] = acc[s][e]; // (a lane reads back its own words only)
+        while (mb != 0) {
+          const int e = __ffs(mb) - 1;
+          mb &= mb - 1;
+          const unsigned item = ibase + 8u * (e >> 2) + (e & 3);
+          const u64 key = ((u64)rec_ordered_bits(E::score(dump[e * 64 + lane])) << 32) | item;
+          cnt += key > tkey ? 1 : 0;
+        }
+      }
+    }
+  }
+  if (uvalid) K.partial[(((size_t)tile * A.splits + sp) * kRecUsers + ul) * 2 + hh] = cnt;
+}
+
+__global__ __launch_bounds__(kBlock) void k_rank_finish(const int *__restrict__ partial, const u64 *__restrict__ tkey, int R, int splits,
+                                                        int32_t *__restrict__ out_rank, float *__restrict__ out_score) {
+  const int r = blockIdx.x * kBlock + threadIdx.x;
+  if (r >= R) return;
+  const u64 key = tkey[r];
+  if (key == 0ull) { out_rank[r] = -1; out_score[r] = -INFINITY; return; }
+  const size_t tile = r / kRecUsers, ul = r % kRecUsers;
+  int sum = 0;
+  for (int sp = 0; sp < splits; ++sp) {
+    const int *p = partial + ((tile * splits + sp) * kRecUsers + ul) * 2;
+    sum += p[0];
+    sum += p[1];
+  }
+  out_rank[r] = sum;
+  out_score[r] = rec_score_of(key);
+}
+
+struct RankPlan {
+  int tiles, splits, ips, nch, hs;
+  int room;                      // splits the scratch has room for: what the launch aims at, so that n_items does not size it
+  size_t lds;
+};
+
+// as rec_plan without the merge's cap on the splits
+bool rank_plan(int R, int n_items, int ld, RankPlan &P) {
+  if (R < 1 || n_items < 1 || ld < 4 || (ld & 3) || ld > kRecMaxLd) return false;
+  P.tiles = (R + kRecUsers - 1) / kRecUsers;
+  const int blocks = (int)(((int64_t)n_items + kRecItems - 1) / kRecItems);
+  int64_t want = (kRecTargetGroups + P.tiles - 1) / P.tiles;
+  if (want > blocks) want = blocks;
+  if (want > 65535) want = 65535;
+  if (want < 1) want = 1;
+  const int bps = (int)((blocks + want - 1) / want);                 // item blocks per split
+  P.ips = bps * kRecItems;
+  P.splits = (blocks + bps - 1) / bps;
+  P.room = (int)want;                                                // (>= splits)
+  P.nch = 2 * ((ld + 2 * kRecKC - 1) / (2 * kRecKC));
+  P.hs = P.nch * kRecKC + 4;
+  P.lds = ((size_t)kRecUsers * P.hs + 4 * 16 * 64) * sizeof(float);
+  return true;
+}
+
+RankArgs rank_layout(Carver &cv, const RankPlan &P, int R) {
+  RankArgs K;
+  K.target = nullptr;
+  K.tz = cv.take<float>((size_t)R);
+  K.tkey = cv.take<u64>((size_t)R);
+  K.partial = cv.take<int>((size_t)P.tiles * P.room * kRecUsers * 2);
+  return K;
+}
+
+size_t rank_scratch_bytes(int R, int n_items, int ld) {
+  RankPlan P;
+  if (!rank_plan(R, n_items, ld, P)) return 0;
+  Carver cv(nullptr, 0);
+  (void)rank_layout(cv, P, R);
+  return align_up(cv.off, 256) + 256;
+}
+
+template <class E>
+int rank_launch(const RecArgs &A, const RankArgs &K, const RankPlan &P, int32_t *out_rank, float *out_score, hipStream_t st) {
+  DRX_HIP(hipFuncSetAttribute((const void *)k_rank_keys<E>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)P.lds));
+  hipLaunchKernelGGL(k_rank_keys<E>, dim3(P.tiles), dim3(256), P.lds, st, A, K);
+  DRX_HIP(hipFuncSetAttribute((const void *)k_rank_count<E>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)P.lds));
+  hipLaunchKernelGGL(k_rank_count<E>, dim3(P.tiles, P.splits), dim3(256), P.lds, st, A, K);
+  hipLaunchKernelGGL(k_rank_finish, dim3((A.R + kBlock - 1) / kBlock), dim3(kBlock), 0, st, K.partial, K.tkey, A.R, P.splits, out_rank,
+                     out_score);
+  DRX_LAUNCH_CHECK();
+  return DRX_OK;
+}
+
+int rank_run(const float *table, const float *bias, int n_items, int ld, int epilogue, const float *q, const int32_t *uid,
+             const int32_t *target, int R, const int64_t *excl_indptr, const int32_t *excl_indices, int32_t *out_rank, float *out_score,
+             void *scratch, size_t scratch_bytes, void *stream) {
+  if (!table || !q || !target || !out_rank || !out_score || R < 1 || n_items < 1 || ld < 4 || (ld & 3)) return DRX_EINVAL;
+  if (epilogue != DRX_REC_SIGMOID_BIAS && epilogue != DRX_REC_BIAS && epilogue != DRX_REC_CLIP) return DRX_EINVAL;
+  if ((epilogue == DRX_REC_CLIP) != (bias == nullptr)) return DRX_EINVAL;
+  if ((excl_indptr != nullptr) != (excl_indices != nullptr) || (excl_indptr && !uid)) return DRX_EINVAL;
+  RankPlan P;
+  if (!rank_plan(R, n_items, ld, P)) return DRX_ENOTIMPL;         // rows wider than 256 floats
+  if (!scratch) return DRX_ESCRATCH;
+  Carver cv(scratch, scratch_bytes);
+  RankArgs K = rank_layout(cv, P, R);
+  if (!cv.ok()) return DRX_ESCRATCH;
+  K.target = target;
+  RecArgs A;
+  A.table = table; A.bias = bias; A.q = q; A.uid = uid; A.xptr = excl_indptr; A.xidx = excl_indices;
+  A.R = R; A.N = n_items; A.ld = ld; A.nch = P.nch; A.hs = P.hs; A.n = 0; A.cap = 0; A.splits = P.splits; A.ips = P.ips;
+  A.lists = nullptr; A.counts = nullptr;
+  hipStream_t st = (hipStream_t)stream;
+  switch (epilogue) {
+    case DRX_REC_SIGMOID_BIAS: return rank_launch<RecSigmoidBias>(A, K, P, out_rank, out_score, st);
+    case DRX_REC_BIAS: return rank_launch<RecBias>(A, K, P, out_rank, out_score, st);
+    default: return rank_launch<RecClip>(A, K, P, out_rank, out_score, st);
+  }
+}
+
 }  // namespace
 }  // namespace drx
 
@@ -433,6 +779,16 @@ extern "C" int drx_rows_recommend(const float *table, const float *bias, int32_t
                                   int32_t *out_idx, float *out_val, void *scratch, size_t scratch_bytes, void *stream) {
   return drx::rec_run(table, bias, n_items, ld, epilogue, q, uid, R, n, excl_indptr, excl_indices, out_idx, out_val, scratch, scratch_bytes,
                       stream);
+}
+
+extern "C" size_t drx_rows_rank_items_scratch_bytes(int32_t R, int32_t n_items, int32_t ld) { return drx::rank_scratch_bytes(R, n_items, ld); }
+
+extern "C" int drx_rows_rank_items(const float *table, const float *bias, int32_t n_items, int32_t ld, int32_t epilogue, const float *q,
+                                   const int32_t *uid, const int32_t *target, int32_t R, const int64_t *excl_indptr,
+                                   const int32_t *excl_indices, int32_t *out_rank, float *out_score, void *scratch, size_t scratch_bytes,
+                                   void *stream) {
+  return drx::rank_run(table, bias, n_items, ld, epilogue, q, uid, target, R, excl_indptr, excl_indices, out_rank, out_score, scratch,
+                       scratch_bytes, stream);
 }
 
 extern "C" size_t drx_cdae_recommend_scratch_bytes(int32_t R, int32_t n_items, int32_t ld, int32_t n) {

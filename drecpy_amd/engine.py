@@ -139,6 +139,51 @@ class RowsRecommender:
                                        ptr(out_val[lo:lo + r]), ptr(sc), sc.numel(), stream_ptr(self.device)), 'drx_rows_recommend')
         return out_idx, out_val
 
+    # ---- catalogue ranks of given (user, item) pairs (include/drx.h drx_rows_rank_items) ----------------------
+    def rank_is_fused(self, ld):
+        """Whether rows of `ld` floats lie in the fused domain of drx_rows_rank_items (else it answers DRX_ENOTIMPL)."""
+        return int(lib().drx_rows_rank_items_scratch_bytes(1, self.n_items, int(ld))) > 0
+
+    def _rank_request(self, uids, items, exclude):
+        """(uid int32 [P], target int32 [P] on the device, the exclusion CSR or None)"""
+        uid, target = self._dev_i32(uids).reshape(-1), self._dev_i32(items).reshape(-1)
+        assert uid.numel() == target.numel(), 'rank_items takes parallel users and items'
+        excl = getattr(self, '_excl', None) if exclude is None or exclude is True else None
+        assert not (exclude is True and excl is None), 'rank_items(exclude=True) needs set_exclusions()'
+        return uid, target, excl
+
+    def _rows_rank_items(self, table, bias, ld, epilogue, uid, target, excl, rows_of, chunk_rows=None):
+        """The chunked launch beside _rows_recommend: `chunk_rows` (user, item) rows at a time, rows_of(lo, uid[lo:lo + r]) -> their
+        [r, ld] query rows (padding columns ZERO), then one drx_rows_rank_items against `table` [n_items, ld] (+ `bias`).  Returns
+        device tensors (rank int32 [P]: the number of eligible items ahead of the target, -1 for a target outside the catalogue;
+        score float32 [P]).  The scratch is kept."""
+        L = lib()
+        P = int(uid.numel())
+        chunk = int(chunk_rows or self.RECOMMEND_CHUNK_USERS)
+        assert table.is_contiguous() and tuple(table.shape) == (self.n_items, ld)
+        out_rank = torch.empty(P, dtype=torch.int32, device=self.device)
+        out_score = torch.empty(P, dtype=torch.float32, device=self.device)
+        for lo in range(0, P, chunk):
+            u, t = uid[lo:lo + chunk], target[lo:lo + chunk]
+            r = int(u.numel())
+            q = rows_of(lo, u)
+            assert q.is_contiguous() and tuple(q.shape) == (r, ld) and q.dtype == torch.float32
+            need = int(L.drx_rows_rank_items_scratch_bytes(r, self.n_items, ld))
+            sc = getattr(self, '_rank_scratch', None)
+            if sc is None or sc.numel() < need:
+                self._rank_scratch = None
+                sc = self._rank_scratch = torch.empty(need, dtype=torch.uint8, device=self.device)
+            check(L.drx_rows_rank_items(ptr(table), ptr(bias), self.n_items, ld, epilogue, ptr(q), ptr(u), ptr(t), r,
+                                        ptr(excl[0]) if excl else None, ptr(excl[1]) if excl else None, ptr(out_rank[lo:lo + r]),
+                                        ptr(out_score[lo:lo + r]), ptr(sc), sc.numel(), stream_ptr(self.device)), 'drx_rows_rank_items')
+        return out_rank, out_score
+
+    @staticmethod
+    def _rows_per_distinct(uid, rows_of_users):
+        """Query rows of the pairs `uid`, computed once per distinct user by rows_of_users(distinct uid) and gathered."""
+        distinct, inverse = torch.unique(uid, return_inverse=True)
+        return rows_of_users(distinct.to(torch.int32).contiguous())[inverse].contiguous()
+
 
 class CdaeEngine(RowsRecommender):
     # the hot head of the sampled Adagrad step (include/drx.h DrxHotHead): the HOT_ROWS items of highest training-set degree, on
@@ -774,6 +819,17 @@ class CdaeEngine(RowsRecommender):
             return self._recommend_by_matrix(uid, n, excl, out_idx, out_val)
         return self._rows_recommend(self.W2T, self.b2, self.ld, _lib.DRX_REC_SIGMOID_BIAS, uid, n, excl, lambda lo, u: self._hidden_rows(u),
                                     out_idx, out_val, chunk_users)
+
+    def rank_items(self, uids, items, exclude=None, chunk_rows=None):
+        """(rank int32 [P], score float32 [P]) device tensors for the parallel users / items: the position of items[p] in the list
+        recommend(uids[p], n = unbounded, exclude) would give — whatever the item's own exclusion —, and its score; -1 / -inf for an
+        item outside the catalogue.  One row per pair: a user with T items costs T rows.  Hidden rows once per distinct user; the same
+        table, bias and epilogue as recommend().  Rows wider than 256 floats: DrxError (rank_is_fused tells)."""
+        uid, target, excl = self._rank_request(uids, items, exclude)
+        if int(uid.numel()) == 0:
+            return torch.empty(0, dtype=torch.int32, device=self.device), torch.empty(0, dtype=torch.float32, device=self.device)
+        return self._rows_rank_items(self.W2T, self.b2, self.ld, _lib.DRX_REC_SIGMOID_BIAS, uid, target, excl,
+                                     lambda lo, u: self._rows_per_distinct(u, self._hidden_rows), chunk_rows)
 
     def _recommend_by_matrix(self, uid, n, excl, out_idx, out_val):
         """The score-matrix route: forward + host-built candidate mask + drx_topk, in chunks of users."""

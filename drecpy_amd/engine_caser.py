@@ -536,3 +536,16 @@ class CaserEngine(RowsRecommender):
         bef = self._dev_i32(before).reshape(R, self.L)
         return self._rows_recommend(self.W1, self.b1, self.ld2, _lib.DRX_REC_BIAS, uid, n, excl,
                                     lambda lo, u: self._hidden_rows(u, bef[lo:lo + int(u.numel())].contiguous()), out_idx, out_val, chunk_users)
+
+    def rank_items(self, uids, before, items, exclude=None, chunk_rows=None):
+        """(rank int32 [P], score float32 [P]) device tensors for the parallel (user, last L items) rows / items: the position of
+        items[p] in the list recommend(uids[p], before[p], n = unbounded, exclude) would give — whatever the item's own exclusion —,
+        and its logit; -1 / -inf for an item outside the catalogue.  One row per pair (a user with T items costs T rows, its hidden
+        row computed T times: the rows are cheap beside the catalogue walk)."""
+        uid, target, excl = self._rank_request(uids, items, exclude)
+        P = int(uid.numel())
+        if P == 0:
+            return torch.empty(0, dtype=torch.int32, device=self.device), torch.empty(0, dtype=torch.float32, device=self.device)
+        bef = self._dev_i32(before).reshape(P, self.L)
+        return self._rows_rank_items(self.W1, self.b1, self.ld2, _lib.DRX_REC_BIAS, uid, target, excl,
+                                     lambda lo, u: self._hidden_rows(u, bef[lo:lo + int(u.numel())].contiguous()), chunk_rows)

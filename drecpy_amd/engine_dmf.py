@@ -607,3 +607,15 @@ class DmfEngine(RowsRecommender):
         items = self._representations(1, torch.arange(self.N, dtype=torch.int32, device=self.device))
         return self._rows_recommend(items, None, self.W, _lib.DRX_REC_CLIP, uid, n, excl, lambda lo, u: self._representations(0, u),
                                     out_idx, out_val, chunk_users)
+
+    def rank_items(self, uids, items, exclude=None, chunk_rows=None):
+        """(rank int32 [P], score float32 [P]) device tensors for the parallel users / items: the position of items[p] in the list
+        recommend(uids[p], n = unbounded, exclude) would give — whatever the item's own exclusion —, and its score max(1e-6, cosine);
+        -1 / -inf for an item outside the catalogue.  One row per pair: a user with T items costs T rows.  The item tower runs ONCE per
+        call, the user tower once per distinct user of a chunk."""
+        uid, target, excl = self._rank_request(uids, items, exclude)
+        if int(uid.numel()) == 0:
+            return torch.empty(0, dtype=torch.int32, device=self.device), torch.empty(0, dtype=torch.float32, device=self.device)
+        table = self._representations(1, torch.arange(self.N, dtype=torch.int32, device=self.device))
+        return self._rows_rank_items(table, None, self.W, _lib.DRX_REC_CLIP, uid, target, excl,
+                                     lambda lo, u: self._rows_per_distinct(u, lambda d: self._representations(0, d)), chunk_rows)

@@ -799,6 +799,24 @@ int drx_rows_recommend(const float *table, const float *bias, int32_t n_items, i
                        const int64_t *excl_indptr, const int32_t *excl_indices,
                        int32_t *out_idx, float *out_val, void *scratch, size_t scratch_bytes, void *stream);
 
+/* ---- catalogue ranks of given (row, item) pairs: where in the WHOLE catalogue an item stands for a query row -------------------------
+ * For each of R rows (query row q[r, :], user uid[r], target item target[r]):
+ *   out_rank[r]  = #{ i != target[r], i not in the exclusion row of uid[r], key(r, i) > key(r, target[r]) }
+ *   out_score[r] = the target's score
+ * with key = drx_rows_recommend's (monotone score bits << 32 | item; the score is the same k-ordered fmaf chain, then the bias, then the
+ * epilogue): out_rank[r] is the position of target[r] in the list drx_rows_recommend would return for the row if n were unbounded, bit
+ * for bit, ties to the larger item index.  The target's own exclusion is ignored here (the caller decides what an excluded target
+ * means).  A target outside [0, n_items) gives out_rank = -1, out_score = -inf.  One target per row: a user with T held-out items costs
+ * T rows.  No score matrix and no lists: the scratch holds two words per row and the rows' partial counts (R rounded up to 128 x item
+ * splits x 2), whatever n_items.  Counts are summed in a fixed order without atomics: the result is a function of the inputs alone.
+ * Arguments, padding columns (ZERO), epilogues and argument errors as drx_rows_recommend; fused domain ld <= 256, ld % 4 == 0, outside
+ * it DRX_ENOTIMPL (scratch bytes 0). */
+size_t drx_rows_rank_items_scratch_bytes(int32_t R, int32_t n_items, int32_t ld);
+int drx_rows_rank_items(const float *table, const float *bias, int32_t n_items, int32_t ld, int32_t epilogue,
+                        const float *q, const int32_t *uid, const int32_t *target, int32_t R,
+                        const int64_t *excl_indptr, const int32_t *excl_indices,
+                        int32_t *out_rank, float *out_score, void *scratch, size_t scratch_bytes, void *stream);
+
 /* ---- stable device radix sort of (key, val) pairs (the inverted-index builder of the sparse steps; ties keep their input order).
  * Every key must be < 2^key_bits: the sort runs ceil(key_bits / digit) passes of 8-, 10- or 11-bit digits, i.e. it orders on
  * passes * digit >= key_bits bits — bits above key_bits are NOT ignored (DRX_EINVAL is not raised for them: the result is then ordered

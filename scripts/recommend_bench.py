@@ -22,6 +22,13 @@ towers / hidden rows once per call + drx_rows_recommend) against the per-user de
 users and extrapolated per user beyond that (the JSON says where).  What is timed is the hook — internal user ids in, numpy arrays out —,
 which is what recommend_batch runs before it maps items back to raw ids.  Device ms = events around the call on the current stream
 (for the per-user path that span includes the host's work between its launches).
+
+    python scripts/recommend_bench.py --ranks [--model dmf|caser] [--out profiles/rank_items.json] [--quick]
+
+Catalogue ranks of given (user, item) pairs (rank_items: drx_rows_rank_items, counting instead of selecting) beside recommend (n = 10)
+at the same R from the same run: R = 1 / 64 / 1024 / 16 384 pairs of distinct users at N = 1 M, K = 128, novelty on (CDAE; the engine
+calls with the hidden rows, and the two library calls alone on the same rows: k_rank_keys + k_rank_count + k_rank_finish against
+k_recommend + k_recommend_merge); with --model the hooks _catalogue_ranks / _recommend_batch of the fitted ml-1m-shaped model.
 """
 import argparse
 import faulthandler
@@ -213,12 +220,138 @@ def model_main(a):
     if a.model == 'dmf':
         with step(240):
             res['parts_at_all_users'] = dmf_parts(m._engine, order.astype(np.int32), n, 5 if a.quick else 20)
+    write_result(res, a.out)
+
+
+def write_result(res, out):
     text = json.dumps(res, indent=1)
     print(text)
-    if a.out:
-        os.makedirs(os.path.dirname(os.path.abspath(a.out)), exist_ok=True)
-        with open(a.out, 'w') as f:
+    if out:
+        os.makedirs(os.path.dirname(os.path.abspath(out)), exist_ok=True)
+        with open(out, 'w') as f:
             f.write(text + '\n')
+
+
+def pair_call(fn):
+    """-> (device ms, wall ms) of one engine call whose two result tensors are copied to the host"""
+    e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+    torch.cuda.synchronize()
+    t0 = time.perf_counter()
+    e0.record()
+    a, b = fn()
+    e1.record()
+    a, b = a.cpu(), b.cpu()
+    wall = (time.perf_counter() - t0) * 1e3
+    return e0.elapsed_time(e1), wall
+
+
+def timed_pair(fn, reps):
+    for _ in range(3):
+        pair_call(fn)
+    runs = [pair_call(fn) for _ in range(reps)]
+    return {'device_ms': median([r[0] for r in runs]), 'wall_ms': median([r[1] for r in runs]), 'device_ms_min': min(r[0] for r in runs),
+            'reps': reps}
+
+
+def cdae_engine(U, N, K):
+    """the headline catalogue: parameters with the spread of a trained model, the synthetic set's histories as exclusions"""
+    dev = torch.device('cuda:0')
+    eng = CdaeEngine(U, N, K)
+    g = torch.Generator(device=dev)
+    g.manual_seed(1)
+    for t, std in ((eng.W, 0.05), (eng.W2T, 2.0 / np.sqrt(K)), (eng.V, 0.5)):
+        t[:, :K].copy_(torch.randn(t.shape[0], K, generator=g, device=dev) * std)
+    eng.b[:K].copy_(torch.randn(K, generator=g, device=dev) * 0.1)
+    eng.b2.copy_(torch.randn(N, generator=g, device=dev) * 0.3)
+    ip, ix = synth.synth_history(10_000_000, N, 23.4, 5, 1.05, seed=0, device='cpu', user_hi=U)
+    ip, ix = ip.numpy(), ix.numpy()
+    eng.set_history(ip, ix, with_transpose=False)
+    eng.set_exclusions(ip, ix)
+    eng.RECOMMEND_MIN_FUSED_USERS = 1                            # this run measures the fused path at every R
+    torch.cuda.synchronize()
+    return eng, ip, ix
+
+
+def ranks_main(a):
+    """--ranks: rank_items beside recommend(n) at the same R, CDAE at the headline catalogue"""
+    from drecpy_amd import _lib
+    L = _lib.lib()
+    N, K, n, U = a.items, a.k, a.n, a.users
+    with step(300):
+        eng, ip, ix = cdae_engine(U, N, K)
+    dev = eng.device
+    rng = np.random.default_rng(0)
+    res = {'n_items': N, 'k': K, 'n': n, 'novelty': True, 'mean_history': float(len(ix) / U),
+           'timed': 'engine: CdaeEngine.rank_items / recommend (hidden rows included), results copied to the host; kernels: the library call alone '
+                    'on the same hidden rows (drx_rows_rank_items: k_rank_keys + k_rank_count + k_rank_finish; drx_rows_recommend: k_recommend + '
+                    'k_recommend_merge), events around it',
+           'rank_items': {}, 'recommend': {}, 'rank_over_recommend': {}}
+    for R in [1, 64, 1024] + ([] if a.quick else [16384]):
+        reps = 5 if a.quick else (20 if R >= 16384 else 30)
+        uid = torch.as_tensor(rng.choice(U, size=R, replace=False).astype(np.int32)).to(dev)
+        items = torch.as_tensor(rng.integers(0, N, R).astype(np.int32)).to(dev)
+        with step(400):
+            rk = timed_pair(lambda: eng.rank_items(uid, items), reps)
+            rc = timed_pair(lambda: eng.recommend(uid, n), reps)
+            h = eng._hidden_rows(uid)
+            x = eng._excl
+            orank, oscore = torch.empty(R, dtype=torch.int32, device=dev), torch.empty(R, dtype=torch.float32, device=dev)
+            oidx, oval = torch.empty(R, n, dtype=torch.int32, device=dev), torch.empty(R, n, dtype=torch.float32, device=dev)
+            sb = max(int(L.drx_rows_rank_items_scratch_bytes(R, N, eng.ld)), int(L.drx_rows_recommend_scratch_bytes(R, N, eng.ld, n)))
+            sc = torch.empty(sb, dtype=torch.uint8, device=dev)
+            rk['kernels_ms'] = events_ms(lambda: _lib.check(L.drx_rows_rank_items(
+                _lib.ptr(eng.W2T), _lib.ptr(eng.b2), N, eng.ld, _lib.DRX_REC_SIGMOID_BIAS, _lib.ptr(h), _lib.ptr(uid), _lib.ptr(items), R, _lib.ptr(x[0]),
+                _lib.ptr(x[1]), _lib.ptr(orank), _lib.ptr(oscore), _lib.ptr(sc), sb, _lib.stream_ptr(dev)), 'drx_rows_rank_items'), reps)
+            rc['kernels_ms'] = events_ms(lambda: _lib.check(L.drx_rows_recommend(
+                _lib.ptr(eng.W2T), _lib.ptr(eng.b2), N, eng.ld, _lib.DRX_REC_SIGMOID_BIAS, _lib.ptr(h), _lib.ptr(uid), R, n, _lib.ptr(x[0]),
+                _lib.ptr(x[1]), _lib.ptr(oidx), _lib.ptr(oval), _lib.ptr(sc), sb, _lib.stream_ptr(dev)), 'drx_rows_recommend'), reps)
+            # the two answers agree: the rank of a list's entry is its position
+            got, _ = eng.rank_items(uid.repeat_interleave(n)[:4096], oidx.reshape(-1)[:4096])
+            same = bool((got.cpu().numpy() == np.tile(np.arange(n), R)[:4096]).all())
+        res['rank_items'][str(R)], res['recommend'][str(R)] = rk, rc
+        res['rank_over_recommend'][str(R)] = {'kernels': rk['kernels_ms'] / rc['kernels_ms'], 'device': rk['device_ms'] / rc['device_ms'],
+                                              'wall': rk['wall_ms'] / rc['wall_ms'], 'rank_of_a_listed_item_is_its_position': same}
+        print(R, 'rank_items', rk, 'recommend', rc, res['rank_over_recommend'][str(R)], flush=True)
+    res['slower_than_1.25x_recommend_at'] = [int(R) for R, r in res['rank_over_recommend'].items() if r['kernels'] > 1.25]
+    write_result(res, a.out)
+
+
+def ranks_model_main(a):
+    """--ranks --model dmf | caser: the hooks _catalogue_ranks / _recommend_batch of a fitted ml-1m-shaped model"""
+    from bench_configs import frame_of
+    from drecpy_amd.Dataset import InteractionDataset
+    from drecpy_amd.Recommender import DMF, Caser
+    n = a.n
+    with step(600):
+        ds = InteractionDataset.read_df(frame_of('ml-1m'), verbose=False)
+        if a.model == 'dmf':
+            m = DMF(user_factors=[64, 32], item_factors=[64, 32], seed=10, verbose=False)
+            m.fit(ds, epochs=2, batch_size=256, learning_rate=1e-3, reg_rate=1e-4, neg_ratio=5)
+        else:
+            m = Caser(L=5, T=3, d=50, n_v=4, n_h=16, dropout_rate=0.5, seed=10, verbose=False)
+            m.fit(ds, epochs=2, batch_size=4096, learning_rate=5e-3, reg_rate=1e-6, neg_ratio=3)
+        torch.cuda.synchronize()
+    m.RECOMMEND_MIN_FUSED_USERS = 1
+    users = np.arange(m.n_users, dtype=np.int64)
+    if a.model == 'caser':
+        users = np.array([u for u in users if len(m._user_sequence(int(u))) >= m.L], dtype=np.int64)
+    rng = np.random.default_rng(0)
+    order = rng.permutation(users)
+    res = {'model': a.model, 'n_users': int(m.n_users), 'n_items': int(m.n_items), 'n': n, 'novelty': True,
+           'timed': '_catalogue_ranks(internal user ids, internal item ids, novelty) and _recommend_batch(internal user ids, n, novelty) -> numpy '
+                    'arrays; device_ms = events around the call', 'rank_items': {}, 'recommend': {}, 'rank_over_recommend': {}}
+    for R in [1, 64, 1024, len(order)]:
+        uids, iids = order[:R], rng.integers(0, m.n_items, R)
+        reps = 5 if a.quick else 20
+        with step(400):
+            for name, fn in (('rank_items', lambda: m._catalogue_ranks(uids, iids, True)), ('recommend', lambda: m._recommend_batch(uids, n, True))):
+                for _ in range(3):
+                    fn()
+                runs = [hook_call(lambda *_: fn(), None, None)[:2] for _ in range(reps)]
+                res[name][str(R)] = {'device_ms': median([r[0] for r in runs]), 'wall_ms': median([r[1] for r in runs]), 'reps': reps}
+        res['rank_over_recommend'][str(R)] = {k: res['rank_items'][str(R)][k + '_ms'] / res['recommend'][str(R)][k + '_ms'] for k in ('device', 'wall')}
+        print(R, res['rank_items'][str(R)], res['recommend'][str(R)], res['rank_over_recommend'][str(R)], flush=True)
+    write_result(res, a.out)
 
 
 def main():
@@ -230,25 +363,17 @@ def main():
     ap.add_argument('--n', type=int, default=10)
     ap.add_argument('--users', type=int, default=16384)
     ap.add_argument('--quick', action='store_true', help='fewer repetitions, no R = 16384')
+    ap.add_argument('--ranks', action='store_true', help='rank_items beside recommend at the same R (default --out profiles/rank_items.json)')
     a = ap.parse_args()
+    if a.ranks:
+        a.out = a.out or os.path.join('profiles', 'rank_items.json' if a.model == 'cdae' else f'rank_items_{a.model}.json')
+        return ranks_main(a) if a.model == 'cdae' else ranks_model_main(a)
     if a.model != 'cdae':
         return model_main(a)
     N, K, n, U = a.items, a.k, a.n, a.users
     dev = torch.device('cuda:0')
     with step(300):
-        eng = CdaeEngine(U, N, K)
-        g = torch.Generator(device=dev)
-        g.manual_seed(1)
-        for t, std in ((eng.W, 0.05), (eng.W2T, 2.0 / np.sqrt(K)), (eng.V, 0.5)):
-            t[:, :K].copy_(torch.randn(t.shape[0], K, generator=g, device=dev) * std)
-        eng.b[:K].copy_(torch.randn(K, generator=g, device=dev) * 0.1)
-        eng.b2.copy_(torch.randn(N, generator=g, device=dev) * 0.3)
-        ip, ix = synth.synth_history(10_000_000, N, 23.4, 5, 1.05, seed=0, device='cpu', user_hi=U)
-        ip, ix = ip.numpy(), ix.numpy()
-        eng.set_history(ip, ix, with_transpose=False)
-        eng.set_exclusions(ip, ix)
-        eng.RECOMMEND_MIN_FUSED_USERS = 1                        # this run measures the fused path at every R
-        torch.cuda.synchronize()
+        eng, ip, ix = cdae_engine(U, N, K)
     rng = np.random.default_rng(0)
     res = {'n_items': N, 'k': K, 'n': n, 'novelty': True, 'mean_history': float(len(ix) / U), 'fused': {}, 'score_matrix': {}, 'ratio': {}}
     fused_rs = [1, 64, 1024] + ([] if a.quick else [16384])
@@ -283,12 +408,7 @@ def main():
     slower = [int(R) for R, r in res['ratio'].items() if r['device'] < 1.0 or r['wall'] < 1.0]
     res['fused_slower_at'] = slower
     res['min_fused_users'] = CdaeEngine.RECOMMEND_MIN_FUSED_USERS
-    text = json.dumps(res, indent=1)
-    print(text)
-    if a.out:
-        os.makedirs(os.path.dirname(os.path.abspath(a.out)), exist_ok=True)
-        with open(a.out, 'w') as f:
-            f.write(text + '\n')
+    write_result(res, a.out)
 
 
 if __name__ == '__main__':
