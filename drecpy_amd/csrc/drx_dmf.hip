@@ -293,9 +293,12 @@ __global__ __launch_bounds__(64 * WV) void k_dmf_gather(DrxDmfDims D, DrxDmfArgs
   // (longest rows first, long ones in segments: include/drx.h DrxDmfArgs::work_order; a device-prepared batch brings a list built there)
   const bool listed = A.work_order && (!A.nd_dev || A.n_work_dev);
   const int total = listed ? (A.n_work_dev ? A.n_work_dev[0] : A.n_work) : n_du + (A.nd_dev ? A.nd_dev[1] : A.n_di);
+  // (a device-built list without partial rows cuts nothing — all rows fit a segment, or the list came out UNCUT although A.seg_len, set
+  // by the host before the list existed, is not 0: k_dmf_work_order — and a work item then takes its whole row)
+  const int seg_len = !listed || (A.n_work_dev && A.n_work_dev[1] == 0) ? 0 : A.seg_len;
   for (int it0 = blockIdx.x; it0 < total; it0 += gridDim.x) {
     const int enc = listed ? A.work_order[it0] : it0;
-    const int it = enc & 0xFFFFFF, seg = listed ? (int)((unsigned)enc >> 24) : 0, seg_len = listed ? A.seg_len : 0;
+    const int it = enc & 0xFFFFFF, seg = listed ? (int)((unsigned)enc >> 24) : 0;
     const int tw = it < n_du ? 0 : 1, d = tw ? it - n_du : it;
     if (tw) tower_gather_q<WV, NU>(D, 1, Ti, d, k, w, part + w * W, seg, seg_len);
     else tower_gather_q<WV, NU>(D, 0, Tu, d, k, w, part + w * W, seg, seg_len);
@@ -1104,9 +1107,9 @@ static __global__ __launch_bounds__(1024) void k_dmf_work_order(const int64_t *_
                                                                 const int32_t *__restrict__ du, const int32_t *__restrict__ di,
                                                                 const int32_t *__restrict__ nd, int seg_len, int32_t *__restrict__ order,
                                                                 int order_cap, int32_t *__restrict__ zseg, int32_t *__restrict__ out2) {
-  __shared__ int count[33], start[33], parts, entries;
+  __shared__ int count[33], start[33], parts, entries, over;
   if (threadIdx.x < 33) count[threadIdx.x] = 0;
-  if (threadIdx.x == 0) { parts = 0; entries = 0; }
+  if (threadIdx.x == 0) { parts = 0; entries = 0; over = 0; }
   __syncthreads();
   const int n_u = nd[0], n = n_u + nd[1];
   auto degree = [&](int i) {
@@ -1115,9 +1118,12 @@ static __global__ __launch_bounds__(1024) void k_dmf_work_order(const int64_t *_
     return (int)(ip[id + 1] - ip[id]);
   };
   auto cls = [](int d) { return d <= 0 ? 0 : 32 - __clz(d); };
-  auto segs = [seg_len](int d) { const int ns = seg_len > 0 && d > seg_len ? (d + seg_len - 1) / seg_len : 1; return ns > 255 ? 255 : ns; };
+  // (NOT clamped: an id of more than 255 segments — zseg holds their number in 8 bits — makes the whole list uncut, as the host helper's
+  // DRX_EINVAL makes its caller do; a clamped count would drop the row's tail, every segment ending at its start + seg_len)
+  auto segs = [seg_len](int d) { return seg_len > 0 && d > seg_len ? (int)(((int64_t)d + seg_len - 1) / seg_len) : 1; };
   for (int i = threadIdx.x; i < n; i += blockDim.x) {
     const int d = degree(i), ns = segs(d);
+    if (ns > 255) { over = 1; continue; }
     atomicAdd(&count[cls(d)], ns);
     atomicAdd(&entries, ns);
   }
@@ -1127,7 +1133,8 @@ static __global__ __launch_bounds__(1024) void k_dmf_work_order(const int64_t *_
     for (int c = 32; c >= 0; --c) { start[c] = run; run += count[c]; }
   }
   __syncthreads();
-  const bool fits = entries <= order_cap;               // (the caller's capacity rule guarantees it; if not: uncut, one entry per id)
+  // (the caller's capacity rule and a seg_len >= longest row / 255 guarantee it; if not: uncut, one entry per id, no partial row)
+  const bool fits = !over && entries <= order_cap;
   if (!fits) {
     __syncthreads();
     if (threadIdx.x < 33) count[threadIdx.x] = 0;

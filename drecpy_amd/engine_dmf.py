@@ -195,6 +195,32 @@ class DmfEngine(RowsRecommender):
             total += (4 * n + 15) & ~15
         return offs, lens, total
 
+    @staticmethod
+    def host_work_list(off_u, off_i, B, seg_len, order=None, zseg=None):
+        """The gather's work list of a host-prepared batch of B samples (host code only: no device, no instance): off_u / off_i =
+        int32 prefix sums of the degrees of the batch's distinct users / items (drx_batch_distinct), seg_len = the engine's segment
+        length.  The list is CUT (drx_dmf_work_order with seg_len) when all three hold: no id needs more than 255 segments, the
+        entries fit the list (2 B + _ORDER_EXTRA), and the partial rows fit _zpart (at most _ORDER_EXTRA: a batch of few distinct
+        ids leaves room in the list for more partial rows than that — the entries alone do not bound them).  Otherwise UNCUT (seg_len
+        0, one entry per distinct id, no partial row): rare, slower on the long rows, correct all the same.
+        Returns (n_work, seg_len in use, n_part, order, zseg); order [2 B + _ORDER_EXTRA] / zseg [2 B] int32 are filled in place when
+        given."""
+        off_u, off_i = np.ascontiguousarray(off_u, np.int32), np.ascontiguousarray(off_i, np.int32)
+        cap = 2 * B + DmfEngine._ORDER_EXTRA
+        order = np.empty(cap, np.int32) if order is None else order
+        zseg = np.empty(2 * B, np.int32) if zseg is None else zseg
+        n_part = C.c_int32(0)
+        build = lambda seg: int(lib().drx_dmf_work_order(off_u.ctypes.data, len(off_u) - 1, off_i.ctypes.data, len(off_i) - 1, seg,
+                                                         order.ctypes.data, cap, zseg.ctypes.data, C.byref(n_part)))
+        seg = int(seg_len)
+        n_work = build(seg)
+        if seg > 0 and (n_work < 0 or n_part.value > DmfEngine._ORDER_EXTRA):
+            seg = 0
+            n_work = build(0)
+        if n_work < 0:
+            check(n_work, 'drx_dmf_work_order')
+        return n_work, seg, int(n_part.value), order, zseg
+
     def prepare_batch(self, uids, iids, y):
         """Host half of a step, free of device work (DMF.fit() runs it on the sampler's worker thread): the distinct users / items of
         the batch (ascending), every sample's index among them, the samples per distinct id as a CSR (samples ascending: the order of
@@ -222,19 +248,11 @@ class DmfEngine(RowsRecommender):
         # the gather's work items, LONGEST row / column first (include/drx.h DrxDmfArgs::work_order): a popular item's column has
         # thousands of non-zeros and is the launch's critical path when its workgroup happens to start late
         # the gather's work items: longest rows / columns first, long ones cut into segments of _seg_len non-zeros (include/drx.h
-        # DrxDmfArgs::work_order; uncut when the segments would not fit the list: rare, correct all the same)
-        n_part = C.c_int32(0)
-        seg = self._seg_len
-        n_work = int(L_.drx_dmf_work_order(base + at['off_u'], nd[0], base + at['off_i'], nd[1], seg, base + at['order'],
-                                           2 * B + self._ORDER_EXTRA, base + at['zseg'], C.byref(n_part)))
-        if n_work < 0:
-            seg = 0
-            n_work = int(L_.drx_dmf_work_order(base + at['off_u'], nd[0], base + at['off_i'], nd[1], 0, base + at['order'],
-                                               2 * B + self._ORDER_EXTRA, base + at['zseg'], C.byref(n_part)))
-            if n_work < 0:
-                check(n_work, 'drx_dmf_work_order')
+        # DrxDmfArgs::work_order; uncut when the segments would not fit the list or their partial rows _zpart: host_work_list)
+        i32 = lambda name: buf[at[name]:at[name] + 4 * lens[self._BATCH_ARRAYS.index(name)]].view(np.int32)
+        n_work, seg, n_part, _, _ = self.host_work_list(off_u, off_i, B, self._seg_len, i32('order'), i32('zseg'))
         return {'buf': buf, 'offs': offs, 'B': B, 'n_du': nd[0], 'n_di': nd[1], 'Tu': int(off_u[-1]), 'Ti': int(off_i[-1]),
-                'n_work': n_work, 'seg_len': seg, 'n_part': int(n_part.value),
+                'n_work': n_work, 'seg_len': seg, 'n_part': n_part,
                 'y_mean': float(y32.astype(np.float64).mean())}
 
     # ---- batches drawn and prepared ON THE DEVICE (DMF.fit(device_sampler=True): throughput mode) --------------------------------

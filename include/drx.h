@@ -682,8 +682,10 @@ typedef struct DrxDmfArgs {
   int32_t n_work, seg_len;
   const int32_t *zseg;
   float *zpart;
-  /* the list built on the DEVICE (drx_dmf_work_order_device, for batches prepared there: nd_dev set): n_work_dev[0] = its entries —
-   * n_work above is then the list's CAPACITY and sizes the launch; NULL: a host-built list (ignored with nd_dev), or none */
+  /* the list built on the DEVICE (drx_dmf_work_order_device, for batches prepared there: nd_dev set): n_work_dev [2] = {its entries, its
+   * partial rows} — n_work above is then the list's CAPACITY and sizes the launch; a list of NO partial rows is read as uncut whatever
+   * seg_len says (the device decides that after the host filled this struct); zpart holds the partial rows that list can have (at most
+   * 2 nnz / seg_len).  NULL: a host-built list (ignored with nd_dev), or none */
   const int32_t *n_work_dev;
 } DrxDmfArgs;
 /* Host helper for DrxDmfArgs::work_order / zseg: the gather's work items (distinct users 0 .. n_u - 1 with off_u[i + 1] - off_u[i]
@@ -695,8 +697,11 @@ int32_t drx_dmf_work_order(const int32_t *off_u, int32_t n_u, const int32_t *off
                            int32_t order_cap, int32_t *zseg, int32_t *n_part);
 /* The same list for a batch whose distinct ids live on the device (drx_dmf_batch_distinct_device: du / di, nd_dev = {n_du, n_di}): degrees
  * from the interaction matrix's two index pointers, one workgroup, classes by bit length of the degree (descending; inside a class in no
- * particular order: a work item writes its own row, the result does not depend on the order).  out2 = {entries, partial rows}.  The
- * caller guarantees that the entries fit: order_cap >= 2 B + 2 nnz / seg_len (every distinct id brings its own row or column once). */
+ * particular order: a work item writes its own row, the result does not depend on the order).  out2 = {entries, partial rows}.  A
+ * caller that wants segments guarantees that the entries fit — order_cap >= 2 B + 2 nnz / seg_len (every distinct id brings its own row or
+ * column once) — and that no id needs more than 255 of them (seg_len >= longest row or column / 255).  Where either does not hold the
+ * WHOLE list comes out uncut instead (the host helper's DRX_ESCRATCH / DRX_EINVAL, answered on the device): one entry per distinct id,
+ * every zseg 0, out2 = {n_du + n_di, 0}, which the gather reads as seg_len = 0.  order_cap >= n_du + n_di always. */
 int drx_dmf_work_order_device(const int64_t *u_indptr, const int64_t *i_indptr, const int32_t *du, const int32_t *di, const int32_t *nd_dev,
                               int32_t seg_len, int32_t *order, int32_t order_cap, int32_t *zseg, int32_t *out2, void *stream);
 /* Host helper for the arrays above: the distinct ids of a batch, ascending.  distinct [<= B], inv [B], gptr [<= B+1], grows [B],

@@ -3,6 +3,7 @@ bf16-MFMA all-pairs scorer against the fp32 cosine."""
 import numpy as np
 import pytest
 
+import dmf_shapes as ds
 from oracle import data_oracle as do
 from oracle import dmf_oracle as dm
 
@@ -674,3 +675,233 @@ def test_the_cached_argument_structs_of_host_batches_change_nothing(modified):
     ga, gb = engs[0].get_params(), engs[1].get_params()
     for k in ga:
         assert np.array_equal(ga[k], gb[k]), k
+
+
+# ---- the segmented gather at its limits, against the oracle (shapes: dmf_shapes.py; the lists themselves: test_dmf_work_list.py) ----------
+_LIMIT_CASES = {
+    # name: (matrix, batches, user tower, item tower, overridden seg_len)
+    'blocks-4096': (lambda: ds.blocks(), lambda: [ds.blocks_batch(4096, 10 + s) for s in range(2)], (32, 16), (24, 16), 8),
+    'blocks-256': (lambda: ds.blocks(), lambda: [ds.blocks_batch(256, 20 + s) for s in range(3)], (32, 16), (24, 16), 8),
+    'wide': (lambda: ds.wide(), lambda: [ds.wide_batch(30 + s) for s in range(2)], (32, 16), (24, 16), 8),
+    'one-long-row': (lambda: ds.one_long_row(), lambda: [ds.one_long_row_batch(64, 40 + s) for s in range(3)], (16, 8), (24, 8), 8),
+    'units2-first': (lambda: ds.plain(), lambda: [ds.plain_batch(200, 50 + s) for s in range(3)], (96, 32), (128, 32), 8),
+    'units2-deep': (lambda: ds.plain(), lambda: [ds.plain_batch(200, 60 + s) for s in range(3)], (48, 96), (64, 96), 8),
+    'tall': (lambda: ds.tall(), lambda: [ds.tall_batch(64, 70 + s) for s in range(3)], (32, 16), (24, 16), None),
+}
+_limit_refs = {}
+
+
+def _limit_reference(name):
+    """The case's matrix, batches and start parameters, and the fp64 oracle's losses and parameters after the steps — computed once per
+    case and shared by the tests of it (read-only)."""
+    if name not in _limit_refs:
+        mk_m, mk_b, uf, itf, seg = _LIMIT_CASES[name]
+        m, batches = mk_m(), mk_b()
+        rng = np.random.default_rng(sum(map(ord, name)))
+        p0 = dm.init_params(rng, m['U'], m['N'], uf, itf, np.float64)
+        for k in p0:
+            if k.endswith('_b'):
+                p0[k] = rng.normal(0, 0.05, size=p0[k].shape)
+        dense = ds.dense(m)
+        p = {k: v.copy() for k, v in p0.items()}
+        st = dm.adam_state(p)
+        losses = []
+        for s, (u, i, y) in enumerate(batches):
+            xu, xi = dense[u], dense[:, i].T.copy()
+            # (a cosine next to the clip at 1e-6 gets its gradient or not by the last bits of a sum: not what these cases are about)
+            cos = dm.forward(p, xu, xi, len(uf), len(itf), True)[1]['s']
+            assert not np.any((cos > 1e-7) & (cos < 1e-5)), name
+            losses.append(dm.step(p, st, s, xu, xi, y.astype(np.float64), 2e-3, 1e-3, len(uf), len(itf), True))
+        _limit_refs[name] = {'m': m, 'batches': batches, 'uf': uf, 'itf': itf, 'seg': seg, 'p0': p0, 'losses': losses, 'p': p}
+    return _limit_refs[name]
+
+
+def _limit_engine(ref, update):
+    from drecpy_amd.engine_dmf import DmfEngine
+    m = ref['m']
+    eng = DmfEngine(m['U'], m['N'], ref['uf'], ref['itf'], True)
+    eng.set_interactions(m['csr'], m['csc'])
+    assert update == 'scatter' or eng.first_layer_update == 'scan'
+    eng.first_layer_update = update
+    eng.set_params(ref['p0'])
+    eng.lr, eng.reg = 2e-3, 1e-3
+    if ref['seg'] is not None:
+        eng._seg_len = ref['seg']
+    return eng
+
+
+def _limit_steps(eng, ref, device, prepared):
+    """The case's steps on `eng` with the gates of test_dmf_steps_with_empty_rows_columns_and_repeated_ids against the shared oracle run:
+    relative loss error < 1e-4 every step, parameters atol 3e-5 after the last.  device: the batch goes through prepare_batch_device.
+    prepared(eng, prep): the case's own assertions about the work list the batch got.  Returns the losses and the parameters."""
+    import torch
+    losses = []
+    for s, (u, i, y) in enumerate(ref['batches']):
+        if device:
+            prep = eng.prepare_batch_device(len(u), 0, 0, triples=[torch.as_tensor(a).cuda() for a in (u, i, y)])
+        else:
+            prep = eng.prepare_batch(u, i, y)
+        lg = eng.step(s, prep, want_loss=True)
+        prepared(eng, prep)
+        lo = ref['losses'][s]
+        print(f'step {s}: loss {lg:.9g} oracle {lo:.9g} rel {abs(lg - lo) / abs(lo):.3g}')
+        assert abs(lg - lo) / abs(lo) < 1e-4, (s, lg, lo)
+        losses.append(lg)
+    g = eng.get_params()
+    print({k: float(np.max(np.abs(g[k] - ref['p'][k]))) for k in g})
+    for k in ref['p']:
+        np.testing.assert_allclose(g[k], ref['p'][k], rtol=0, atol=3e-5, err_msg=k)
+    return losses, g
+
+
+def _nw(prep):
+    return prep['device']['nw'].cpu().numpy().tolist()
+
+
+@pytest.mark.parametrize('update', ['scan', 'scatter'])
+def test_dmf_steps_of_a_batch_whose_partial_rows_would_not_fit_run_uncut(update):
+    """48 x 1200, 40 rows of 138 segments of 8 and about 1070 columns of 5 in a batch of 4096: about 10 700 list entries — they fit the
+    list of 2 B + 4096 — of which about 9 600 are partial rows, more than the 4096 + 8 rows of _zpart.  Judged by its entries alone this
+    batch ran segmented and the gather wrote its partial rows past the buffer; host_work_list counts them and hands out the uncut list."""
+    ref = _limit_reference('blocks-4096')
+    (u, i, _), B = ref['batches'][0], 4096
+    _, (entries, seg, parts, ns) = ds.rules(*ds.batch_offsets(ref['m'], u, i), B, 8)
+    assert seg == 8 and ns.max() >= 128                               # by its entries alone: segmented, segment numbers with the sign bit
+    assert entries > ds.GATHER_GRID and entries <= 2 * B + ds.ORDER_EXTRA and parts > ds.ORDER_EXTRA + 8
+
+    def prepared(eng, prep):
+        assert (prep['seg_len'], prep['n_part'], prep['n_work']) == (0, 0, prep['n_du'] + prep['n_di'])
+    _limit_steps(_limit_engine(ref, update), ref, False, prepared)
+
+
+@pytest.mark.parametrize('update', ['scan', 'scatter'])
+def test_dmf_steps_with_segments_next_to_every_limit_of_the_list(update):
+    """3000 x 3000, every user and item twice in a batch of 6000: segments in use (seg_len 8) with an id of 138 of them — segment
+    numbers >= 128 set the sign bit of the list's int32 entries —, more than 8192 work items — the gather's grid-stride loop — and the
+    partial rows within _zpart's 4096."""
+    ref = _limit_reference('wide')
+
+    def prepared(eng, prep):
+        deg = np.diff(ref['m']['csr'][0])
+        assert prep['seg_len'] == 8 and 0 < prep['n_part'] <= eng._ORDER_EXTRA
+        assert prep['n_work'] > ds.GATHER_GRID and -(-int(deg.max()) // 8) >= 128 and prep['n_du'] == 3000
+    _limit_steps(_limit_engine(ref, update), ref, False, prepared)
+
+
+@pytest.mark.parametrize('update', ['scan', 'scatter'])
+def test_dmf_steps_of_a_batch_whose_segments_would_not_fit_the_list_run_uncut(update):
+    """The 40 rows of 138 segments in a batch of 256: 5520 entries and more against a list of 2 B + 4096 = 4608 — drx_dmf_work_order
+    answers DRX_ESCRATCH and the batch gets the uncut list."""
+    ref = _limit_reference('blocks-256')
+    (u, i, _), B = ref['batches'][0], 256
+    off_u, off_i = ds.batch_offsets(ref['m'], u, i)
+    assert np.sum(-(-np.concatenate([np.diff(off_u), np.diff(off_i)]) // 8)) > 2 * B + ds.ORDER_EXTRA
+
+    def prepared(eng, prep):
+        assert (prep['seg_len'], prep['n_part'], prep['n_work']) == (0, 0, prep['n_du'] + prep['n_di'])
+    _limit_steps(_limit_engine(ref, update), ref, False, prepared)
+
+
+def test_dmf_steps_with_a_row_of_more_than_255_segments():
+    """4 x 2100, user 0 holds all 2100 items: 263 segments of 8, more than the 8 bits of zseg count.  The host helper answers DRX_EINVAL
+    and the batch gets the uncut list; drx_dmf_work_order_device must answer the same way — one entry per id, no partial row, which the
+    gather reads as seg_len 0 — and the step on it equal the host-prepared one bit for bit.  (A segment count clamped to 255 covers
+    2040 non-zeros: the last 60 of the row are lost.  What that does to the oracle is computed first: the test can see it.)"""
+    from oracle import cdae_oracle as co
+    ref = _limit_reference('one-long-row')
+    m, p0 = ref['m'], ref['p0']
+    # the tail a clamped list loses, in the oracle: first-layer outputs and loss of the first batch with and without it
+    u, i, y = ref['batches'][0]
+    dense = ds.dense(m)
+    xu, xi = dm.l2_normalize(dense[u])[0], dm.l2_normalize(dense[:, i].T.copy())[0]
+    lost = xu.copy()
+    lost[u == 0, 255 * 8:] = 0
+    (pa, ca), (pb, cb) = dm.forward(p0, xu, xi, 2, 2, False), dm.forward(p0, lost, xi, 2, 2, False)
+    la, lb = (float(co.bce_elem(y.astype(np.float64), p_, xu.dtype).mean()) for p_ in (pa, pb))
+    shift = float(np.max(np.abs(ca['pu'][0] - cb['pu'][0])))
+    moved = abs(la - lb) / ref['losses'][0]
+    print(f'losing the tail: first-layer output moves by {shift:.3g}, the loss of step 0 by {moved:.3g} of itself')
+    assert shift > 100 * 3e-5 and moved > 100 * 1e-4                      # a hundred times the gates below
+
+    def host_prepared(eng, prep):
+        assert eng._device_seg_len() == 8
+        assert (prep['seg_len'], prep['n_part'], prep['n_work']) == (0, 0, prep['n_du'] + prep['n_di'])
+
+    def device_prepared(eng, prep):
+        nd = prep['device']['nd'].cpu().numpy().tolist()
+        assert eng._device_seg_len() == 8 and _nw(prep) == [nd[0] + nd[1], 0]
+        assert not prep['device']['zseg'].cpu().numpy()[:nd[0] + nd[1]].any()
+    _limit_steps(_limit_engine(ref, 'scatter'), ref, False, host_prepared)
+    lh, gh = _limit_steps(_limit_engine(ref, 'scan'), ref, False, host_prepared)
+    ld, gd = _limit_steps(_limit_engine(ref, 'scan'), ref, True, device_prepared)
+    assert lh == ld
+    for k in gh:
+        assert np.array_equal(gh[k], gd[k]), k
+
+
+@pytest.mark.parametrize('case,update,device', [('units2-first', 'scatter', False), ('units2-deep', 'scan', False), ('units2-deep', 'scatter', False),
+                                                ('units2-deep', 'scan', True)])
+def test_dmf_steps_with_segments_and_two_unit_slots_per_lane(case, update, device):
+    """Towers wider than a wavefront — a lane holds units k and k + 64, rows of 128 floats in z0 and _zpart — with rows and columns cut
+    into 2..5 segments of 8 (120 x 80, 2500 cells, items of the first quarter).  'units2-first': first layers of 96 / 128 units (the
+    gather's second slot holds sums; first-layer update by scatter, which host batches alone can take); 'units2-deep': first layers of
+    48 / 64, second of 96 (the scan update, and with it device-prepared batches)."""
+    ref = _limit_reference(case)
+
+    def prepared(eng, prep):
+        assert eng.W == 128
+        if device:
+            n, parts = _nw(prep)
+            assert eng._device_seg_len() == 8 and parts > 0 and n > parts
+        else:
+            assert prep['seg_len'] == 8 and prep['n_part'] > 0 and prep['n_work'] == prep['n_du'] + prep['n_di'] + prep['n_part']
+    _limit_steps(_limit_engine(ref, update), ref, device, prepared)
+
+
+def test_dmf_steps_with_a_column_cut_at_the_default_segment_length():
+    """Nothing overridden: 1100 x 30 with item 0 rated by everyone — a column of 1100 non-zeros, 2 segments of the default 1024, in most
+    samples of the batch; its row of K0u takes the first-layer update's workgroup path."""
+    ref = _limit_reference('tall')
+
+    def prepared(eng, prep):
+        assert eng._seg_len == 1024 and eng._k0_long >= 1
+        assert prep['seg_len'] == 1024 and prep['n_part'] >= 1 and prep['n_work'] == prep['n_du'] + prep['n_di'] + prep['n_part']
+    _limit_steps(_limit_engine(ref, 'scan'), ref, False, prepared)
+
+
+def test_the_device_work_list_is_uncut_when_its_segments_do_not_fit():
+    """drx_dmf_work_order_device with an order_cap below the segmented entry count (the host helper: DRX_ESCRATCH): one entry per id and
+    no segment, out2 = {n, 0}, every zseg 0, degree classes non-increasing along the list."""
+    import ctypes as C
+    import torch
+    from drecpy_amd import _lib
+    L_ = _lib.lib()
+    rng = np.random.default_rng(39)
+    U, N, B, seg_len = 300, 200, 256, 8
+    csr, csc, _ = _problem(rng, U, N, 9000)
+    du = np.sort(rng.choice(U, size=140, replace=False)).astype(np.int32)
+    di = np.sort(rng.choice(N, size=90, replace=False)).astype(np.int32)
+    n = len(du) + len(di)
+    ipu, ipi = np.asarray(csr[0], np.int64), np.asarray(csc[0], np.int64)
+    off_u = np.concatenate([[0], np.cumsum(ipu[du + 1] - ipu[du])]).astype(np.int32)
+    off_i = np.concatenate([[0], np.cumsum(ipi[di + 1] - ipi[di])]).astype(np.int32)
+    deg = np.concatenate([np.diff(off_u), np.diff(off_i)])
+    cap = int(np.sum(-(-deg // seg_len))) - 1                       # one entry short of the segmented list
+    assert cap > n
+    want, zs_h, n_part = np.zeros(cap, np.int32), np.zeros(n, np.int32), C.c_int32(0)
+    assert L_.drx_dmf_work_order(off_u.ctypes.data, len(du), off_i.ctypes.data, len(di), seg_len, want.ctypes.data, cap, zs_h.ctypes.data,
+                                 C.byref(n_part)) == -2                  # DRX_ESCRATCH
+    dev = torch.device('cuda:0')
+    t = lambda a: torch.as_tensor(a).to(dev)
+    d_ipu, d_ipi, d_du, d_di = t(ipu), t(ipi), t(du), t(di)
+    nd = t(np.array([len(du), len(di)], np.int32))
+    order, zseg, out2 = torch.full((cap,), -1, dtype=torch.int32, device=dev), torch.full((2 * B,), -1, dtype=torch.int32, device=dev), torch.zeros(2, dtype=torch.int32, device=dev)
+    _lib.check(L_.drx_dmf_work_order_device(d_ipu.data_ptr(), d_ipi.data_ptr(), d_du.data_ptr(), d_di.data_ptr(), nd.data_ptr(), seg_len,
+                                            order.data_ptr(), cap, zseg.data_ptr(), out2.data_ptr(), _lib.stream_ptr(dev)), 'drx_dmf_work_order_device')
+    torch.cuda.synchronize()
+    assert out2.cpu().numpy().tolist() == [n, 0]
+    got = order.cpu().numpy().view(np.uint32)
+    assert sorted(got[:n].tolist()) == list(range(n)) and np.all(got[n:] == 0xFFFFFFFF)          # no segment bits; nothing written beyond
+    assert not zseg.cpu().numpy()[:n].any()
+    cls = np.array([int(d).bit_length() for d in deg])
+    assert np.all(np.diff(cls[got[:n]]) <= 0)
