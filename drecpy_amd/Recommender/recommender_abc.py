@@ -522,8 +522,9 @@ class RecommenderABC(ABC):
         recommend_batch's arithmetic —, -1 where the item is unknown to the model or excluded for that user under novelty; an unknown
         user raises as recommend() does.  return_scores=True: (ranks, np.float64 [P] the values recommend_batch reports, -inf beside
         a -1).  What full-catalogue HR@k / NDCG@k / MRR need, for any k, without lists (recommendation_evaluation(batched='ranks')).
-        One query row per pair: a user with T held-out items costs T rows.  CDAE, DMF and Caser answer from the fused scorer-counter
-        (DESIGN.md section 3.5)."""
+        CDAE, DMF and Caser answer from the fused scorer-counter: users with several pairs through its list
+        form (drx_rows_rank_lists: one catalogue walk per user and group of its items), scattered pairs through its pair form
+        (drx_rows_rank_items: one query row and one walk per pair); both give the same bits."""
         assert self.fitted is True, 'The model requires to be fitted before being able to make predictions.'
         uids = np.fromiter((self._require_user(user) for user in user_ids), dtype=np.int64)
         to_iid = self.interaction_dataset.item_to_iid
@@ -549,16 +550,27 @@ class RecommenderABC(ABC):
         return ranks, scores
 
     def _catalogue_ranks_fused(self, uids, iids, novelty, *query):
-        """What the models' _catalogue_ranks share, beside _recommend_batch_fused: ONE engine.rank_items(uids, *query, iids) for all
-        pairs — under novelty without the rows of _exclusion_csr, uploaded once per engine —, downloaded as (ranks int64 [P], scores
-        float64 [P]).  The device ignores a target's own exclusion: an excluded pair is set to -1 / -inf here."""
+        """What the models' _catalogue_ranks share, beside _recommend_batch_fused: ONE engine call for all pairs — under novelty
+        without the rows of _exclusion_csr, uploaded once per engine —, downloaded as (ranks int64 [P], scores float64 [P]).  With at
+        least engine.RANK_LISTS_MIN_MEAN pairs per distinct user the pairs are grouped (_grouped_pairs) and answered by
+        engine.rank_lists — one catalogue walk per row of a user's items —, else by engine.rank_items(uids, *query, iids), one walk
+        per pair; the two give the same bits.  `query`: per-pair arrays (Caser's `before`); a user's rows take those of its first
+        pair.  The device ignores a target's own exclusion: an excluded pair is set to -1 / -inf here."""
         uids, iids = np.asarray(uids, dtype=np.int64), np.asarray(iids, dtype=np.int64)
         with self._device_lock:
             eng = self._engine
             if novelty and getattr(eng, '_excl', None) is None:
                 eng.set_exclusions(*self._exclusion_csr())
-            rank, score = eng.rank_items(uids.astype(np.int32), *query, iids.astype(np.int32), exclude=bool(novelty))
-            rank, score = rank.cpu().numpy().astype(np.int64), score.cpu().numpy().astype(np.float64)
+            group = eng.rank_lists_group(eng.rank_ld())
+            if group > 0 and len(uids) >= eng.RANK_LISTS_MIN_MEAN * len(np.unique(uids)):
+                order, starts, indptr = self._grouped_pairs(uids, iids, group)
+                rows = [np.asarray(x)[order[starts]] for x in query]
+                r, s = eng.rank_lists(uids[order[starts]].astype(np.int32), *rows, indptr, iids[order].astype(np.int32), exclude=bool(novelty))
+                rank, score = np.empty(len(uids), np.int64), np.empty(len(uids), np.float64)
+                rank[order], score[order] = r.cpu().numpy(), s.cpu().numpy()
+            else:
+                rank, score = eng.rank_items(uids.astype(np.int32), *query, iids.astype(np.int32), exclude=bool(novelty))
+                rank, score = rank.cpu().numpy().astype(np.int64), score.cpu().numpy().astype(np.float64)
             if novelty:
                 _, _, ip, ix = eng._excl
                 cells = np.repeat(np.arange(len(ip) - 1, dtype=np.int64), np.diff(ip)) * self.n_items + ix      # ascending: rows, then columns
@@ -567,6 +579,20 @@ class RecommenderABC(ABC):
                 excluded = (cells[at] == wanted) if len(cells) else np.zeros(len(wanted), bool)
                 rank[excluded & (iids >= 0)], score[excluded & (iids >= 0)] = -1, -np.inf
         return rank, score
+
+    @staticmethod
+    def _grouped_pairs(uids, iids, group):
+        """The pairs as rows of one user's ascending items, for engine.rank_lists: (order, starts, indptr) — `order` the stable
+        permutation by (uid, iid), `starts` the positions in it at which a row begins (a new user, or `group` items of the same
+        user: a long user is split so that it does not make its whole tile walk the catalogue again), `indptr` int64 [rows + 1]."""
+        P = len(uids)
+        order = np.lexsort((iids, uids))
+        su = uids[order]
+        first = np.concatenate([[True], su[1:] != su[:-1]])
+        user_start = np.flatnonzero(first)
+        within = np.arange(P) - np.repeat(user_start, np.diff(np.concatenate([user_start, [P]])))
+        starts = np.flatnonzero(first | (within % int(group) == 0))
+        return order, starts, np.concatenate([starts, [P]]).astype(np.int64)
 
     def rank(self, user_id, item_ids, novelty=True, skip_invalid_items=True, **kwds):
         uid = self._require_user(user_id)

@@ -767,6 +767,314 @@ int rank_run(const float *table, const float *bias, int n_items, int ld, int epi
   }
 }
 
+// ---- catalogue ranks of a row's LIST of targets (drx_rows_rank_lists) ------------------------------------------------------------------
+// The pair form above scores a user with T targets against the catalogue T times.  Here row r owns targets[tptr[r] .. tptr[r + 1]),
+// ascending, and costs one counting walk per G of them; every rank and score is what the pair form gives for (q[r], uid[r], target),
+// bit for bit: the same key from the same rank_block<E>, the same band, the same exclusion rule, integer counts.
+// k_rankl_keys    grid (user tiles).  A wave merges the ascending lists of its 32 rows: the next 128-item block is the wave-minimum of
+//                 the lanes' cursors, computed ONCE; every lane whose row has targets in it takes them out of the per-wave dump, tile by
+//                 tile, and writes tz / tkey.  At most min(sum of the rows' lengths, blocks of the catalogue) blocks per wave.
+// k_rankl_count   grid (user tiles, item splits).  k_rank_count's walk; the thresholds (zlo, zhi, tkey) of up to G targets per row and
+//                 their running counts live in LDS, [target][row] (a lane's own column: conflict-free), not in registers.  A finished
+//                 tile first takes one compare against the row's LOWEST zlo; only a tile in which some score of some lane reaches it
+//                 builds the masks per target.  A wave whose longest row holds more than G targets walks again for the next G.
+// k_rankl_finish  a target's 2 x splits partial counts summed in a fixed order (no atomics anywhere).
+struct RankListArgs {
+  const int64_t *tptr;           // [R + 1] offsets into targets / out_rank / out_score (absolute)
+  const int32_t *targets;
+  int64_t base, P;               // tptr[0] and tptr[R] - tptr[0]: the scratch is indexed by p - base
+  float *tz;                     // [P] a target's biased sum
+  u64 *tkey;                     // [P] its key; 0: a target outside the catalogue
+  int *partial;                  // [P][2 x splits]
+  int G;                         // targets of a row whose state LDS holds at a time
+};
+
+constexpr int kRankListMaxG = 32;
+constexpr size_t kRecLdsBytes = 160 * 1024;                             // LDS of a workgroup on gfx950
+constexpr size_t kRankListSlot = (size_t)kRecUsers * (2 * sizeof(float) + sizeof(u64) + 2 * sizeof(int));   // one target of every row
+
+// the targets of row r, clamped into [base, base + P): whatever the offsets hold, no access leaves the scratch
+__device__ __forceinline__ void rankl_row(const RankListArgs &K, int r, int R, int64_t &beg, int64_t &end) {
+  beg = end = K.base;
+  if (r < R) {
+    const int64_t hi = K.base + K.P;
+    beg = min(max(K.tptr[r], K.base), hi);
+    end = min(max(K.tptr[r + 1], beg), hi);
+  }
+}
+
+template <class E>
+__global__ __launch_bounds__(256) void k_rankl_keys(RecArgs A, RankListArgs K) {
+  extern __shared__ __align__(16) float lds[];
+  float *h_s = lds;                                                   // [128][hs]
+  float *dump_all = h_s + (size_t)kRecUsers * A.hs;                   // [4 waves][16 registers][64 lanes]
+  const int tid = threadIdx.x, lane = tid & 63, col = lane & 31, hh = lane >> 5;
+  const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
+  const int r0 = blockIdx.x * kRecUsers;
+  rank_load_q(A, h_s, tid, r0);
+  __syncthreads();
+  if (r0 + wave * 32 >= A.R) return;                                  // (no row in this wave; no barrier below)
+
+  float *dump = dump_all + wave * (16 * 64);
+  const float *hrow = h_s + (size_t)(wave * 32 + col) * A.hs + 4 * hh;
+  int64_t cur, end;                                                   // the row's cursor (both halves of a column carry it)
+  rankl_row(K, r0 + wave * 32 + col, A.R, cur, end);
+  f32x16 acc[4];
+  float4 a0[4][kRecKT], a1[4][kRecKT];
+  for (;;) {
+    int t = 0;
+    while (cur < end) {                                               // targets outside the catalogue: no key
+      t = K.targets[cur];
+      if ((unsigned)t < (unsigned)A.N) break;
+      if (hh == 0) { K.tz[cur - K.base] = 0.f; K.tkey[cur - K.base] = 0ull; }
+      ++cur;
+    }
+    int b = cur < end ? (t >> 7) : 0x7FFFFFFF;
+#pragma unroll
+    for (int m = 32; m >= 1; m >>= 1) b = min(b, __shfl_xor(b, m, kWave));
+    b = __builtin_amdgcn_readfirstlane(b);
+    if (b == 0x7FFFFFFF) break;                                       // every list is done
+    const int item0 = b * kRecItems;
+    rec_load_a(A, item0, 0, col, hh, a0);
+    rank_block<E>(A, item0, item0, col, hh, hrow, a0, a1, acc);
+    // (an unsorted row may leave a target of this block behind: its lane still points at the block, which is then computed again;
+    //  the lane that set the minimum always advances, so the loop ends)
+#pragma unroll
+    for (int s = 0; s < 4; ++s) {
+      const unsigned tile0 = (unsigned)item0 + 32u * s;
+      if (__ballot(cur < end && ((unsigned)t & ~31u) == tile0)) {
+#pragma unroll
+        for (int e = 0; e < 16; ++e) dump[e * 64 + lane] = acc[s][e];   // (a lane reads back its own words only)
+        while (cur < end && (unsigned)t < (unsigned)A.N && ((unsigned)t & ~31u) == tile0) {
+          const int m = t & 31;
+          if (((m >> 2) & 1) == hh) {                                 // element (item t, this column): register te of this half
+            const float z = dump[(4 * (m >> 3) + (m & 3)) * 64 + lane];
+            K.tz[cur - K.base] = z;
+            K.tkey[cur - K.base] = ((u64)rec_ordered_bits(E::score(z)) << 32) | (unsigned)t;
+          }
+          ++cur;
+          if (cur < end) t = K.targets[cur];
+        }
+      }
+    }
+  }
+}
+
+template <class E>
+__global__ __launch_bounds__(256) void k_rankl_count(RecArgs A, RankListArgs K) {
+  extern __shared__ __align__(16) float lds[];
+  float *h_s = lds;                                                   // [128][hs]
+  float *dump_all = h_s + (size_t)kRecUsers * A.hs;                   // [4 waves][16 registers][64 lanes]
+  const int G = K.G;
+  float *zlo_s = dump_all + 4 * 16 * 64;                              // [G][128] per target and row: the band,
+  float *zhi_s = zlo_s + (size_t)G * kRecUsers;
+  u64 *key_s = reinterpret_cast<u64 *>(zhi_s + (size_t)G * kRecUsers);  //                        the target's key
+  int *cnt_s = reinterpret_cast<int *>(key_s + (size_t)G * kRecUsers);  // [G][2 halves][128]     and the lane's running count
+  const int tid = threadIdx.x, lane = tid & 63, col = lane & 31, hh = lane >> 5;
+  const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
+  const int tile = blockIdx.x, sp = blockIdx.y;
+  const int r0 = tile * kRecUsers;
+  rank_load_q(A, h_s, tid, r0);
+  __syncthreads();
+  if (r0 + wave * 32 >= A.R) return;                                  // (no row in this wave; no barrier below)
+
+  float *dump = dump_all + wave * (16 * 64);
+  const int ul = wave * 32 + col, r = r0 + ul;
+  const int i_begin = sp * A.ips, i_end = (int)min((int64_t)A.N, (int64_t)i_begin + A.ips);
+  const int nblocks = (int)(((int64_t)i_end - i_begin + kRecItems - 1) / kRecItems);
+  const float *hrow = h_s + (size_t)ul * A.hs + 4 * hh;
+  int64_t beg, end;
+  rankl_row(K, r, A.R, beg, end);
+  int longest = (int)min(end - beg, (int64_t)0x7FFFFFFF);
+#pragma unroll
+  for (int m = 32; m >= 1; m >>= 1) longest = max(longest, __shfl_xor(longest, m, kWave));
+  longest = __builtin_amdgcn_readfirstlane(longest);
+
+  f32x16 acc[4];
+  float4 a0[4][kRecKT], a1[4][kRecKT];
+  for (int g0 = 0; g0 < longest; g0 += G) {                           // wave-uniform: one walk per G targets of the longest row
+    const int gw = min(G, longest - g0);
+    float zmin = INFINITY;                                            // the row's lowest zlo: below it nothing is counted for any target
+    for (int g = 0; g < gw; ++g) {
+      const int64_t p = beg + g0 + g;
+      u64 tkey = 0ull;
+      float zlo = INFINITY, zhi = INFINITY;                           // (no target: nothing is counted)
+      if (p < end) {
+        tkey = K.tkey[p - K.base];
+        if (tkey != 0ull) E::band(K.tz[p - K.base], rec_score_of(tkey), zlo, zhi);
+      }
+      if (hh == 0) { zlo_s[g * kRecUsers + ul] = zlo; zhi_s[g * kRecUsers + ul] = zhi; key_s[g * kRecUsers + ul] = tkey; }
+      cnt_s[(2 * g + hh) * kRecUsers + ul] = 0;
+      zmin = fminf(zmin, zlo);
+    }
+    int64_t xc = 0, xhi = 0;                                          // the cursor into the user's exclusion row, its end
+    if (A.xptr && beg + g0 < end) {
+      const int u = A.uid[r];
+      int64_t lo = A.xptr[u];
+      const int64_t xend = A.xptr[u + 1];
+      xhi = xend;
+      int64_t hi = xend;
+      while (lo < hi) {                                               // the first entry at or behind the split's first item
+        const int64_t mid = lo + ((hi - lo) >> 1);
+        if (A.xidx[mid] < i_begin) lo = mid + 1; else hi = mid;
+      }
+      xc = lo;
+    }
+    wave_lds_sync();
+
+    rec_load_a(A, i_begin, 0, col, hh, a0);
+    for (int blk = 0; blk < nblocks; ++blk) {
+      const int item0 = i_begin + blk * kRecItems;
+      u64 xm = 0ull;                                                  // the excluded items of the block in this lane's half (as k_rank_count)
+      while (xc < xhi) {
+        const unsigned off = (unsigned)A.xidx[xc] - (unsigned)item0;
+        if (off >= (unsigned)kRecItems) break;
+        ++xc;
+        if (((off >> 2) & 1u) == (unsigned)hh) xm |= 1ull << (16u * (off >> 5) + 4u * ((off & 31u) >> 3) + (off & 3u));
+      }
+      rank_block<E>(A, item0, blk + 1 < nblocks ? item0 + kRecItems : item0, col, hh, hrow, a0, a1, acc);
+      const bool whole = (unsigned)item0 + (unsigned)kRecItems <= (unsigned)i_end;   // wave-uniform: every block but the split's last
+#pragma unroll
+      for (int s = 0; s < 4; ++s) {
+        uint32_t m0 = 0;
+#pragma unroll
+        for (int e = 0; e < 16; ++e) m0 |= (acc[s][e] >= zmin) ? (1u << e) : 0u;
+        if (!__ballot(m0 != 0)) continue;                             // zlo <= zhi: a score below every zlo is ahead of no target
+        const unsigned tile0 = (unsigned)item0 + 32u * s, ibase = tile0 + 4u * hh;
+        uint32_t keep = 0xFFFFu;
+        if (!whole) {
+          keep = 0;
+#pragma unroll
+          for (int e = 0; e < 16; ++e) keep |= (ibase + 8u * (e >> 2) + (e & 3) < (unsigned)i_end) ? (1u << e) : 0u;
+        }
+        keep &= ~(uint32_t)((xm >> (16 * s)) & 0xFFFFull);
+        bool dumped = false;                                          // wave-uniform
+        for (int g = 0; g < gw; ++g) {
+          const float zlo = zlo_s[g * kRecUsers + ul], zhi = zhi_s[g * kRecUsers + ul];
+          const u64 tkey = key_s[g * kRecUsers + ul];
+          uint32_t ma = 0, mb = 0;
+#pragma unroll
+          for (int e = 0; e < 16; ++e) {
+            const float z = acc[s][e];
+            ma |= (z > zhi) ? (1u << e) : 0u;
+            mb |= (z >= zlo && z <= zhi) ? (1u << e) : 0u;
+          }
+          const unsigned t = (unsigned)tkey, tm = t & 31u;
+          uint32_t kg = keep;
+          if (tkey != 0ull && (t & ~31u) == tile0 && ((tm >> 2) & 1u) == (unsigned)hh) kg &= ~(1u << (4u * (tm >> 3) + (tm & 3u)));   // i != t
+          ma &= kg;
+          mb &= kg;
+          int c = __popc(ma);
+          if (__ballot(mb != 0)) {                                    // the band: rare unless many items tie with the target
+            if (!dumped) {
+#pragma unroll
+              for (int e = 0; e < 16; ++e) dump[e * 64 + lane] = acc[s][e];   // (a lane reads back its own words only)
+              dumped = true;
+            }
+            while (mb != 0) {
+              const int e = __ffs(mb) - 1;
+              mb &= mb - 1;
+              const unsigned item = ibase + 8u * (e >> 2) + (e & 3);
+              const u64 key = ((u64)rec_ordered_bits(E::score(dump[e * 64 + lane])) << 32) | item;
+              c += key > tkey ? 1 : 0;
+            }
+          }
+          cnt_s[(2 * g + hh) * kRecUsers + ul] += c;
+        }
+      }
+    }
+    for (int g = 0; g < gw; ++g) {
+      const int64_t p = beg + g0 + g;
+      if (p < end) K.partial[(size_t)(p - K.base) * (2 * A.splits) + 2 * sp + hh] = cnt_s[(2 * g + hh) * kRecUsers + ul];
+    }
+    wave_lds_sync();                                                  // (the next group's thresholds overwrite what the other half read)
+  }
+}
+
+__global__ __launch_bounds__(kBlock) void k_rankl_finish(const int *__restrict__ partial, const u64 *__restrict__ tkey, int64_t base, int64_t P,
+                                                         int splits, int32_t *__restrict__ out_rank, float *__restrict__ out_score) {
+  const int64_t pi = (int64_t)blockIdx.x * kBlock + threadIdx.x;
+  if (pi >= P) return;
+  const u64 key = tkey[pi];
+  if (key == 0ull) { out_rank[base + pi] = -1; out_score[base + pi] = -INFINITY; return; }
+  const int *p = partial + (size_t)pi * (2 * splits);
+  int sum = 0;
+  for (int j = 0; j < 2 * splits; ++j) sum += p[j];
+  out_rank[base + pi] = sum;
+  out_score[base + pi] = rec_score_of(key);
+}
+
+// G: what LDS holds beside the tile's query rows and the dump at this ld
+int rankl_group(int ld) {
+  RankPlan P;
+  if (!rank_plan(1, 1, ld, P) || P.lds + kRankListSlot > kRecLdsBytes) return 0;
+  const size_t g = (kRecLdsBytes - P.lds) / kRankListSlot;
+  return g > (size_t)kRankListMaxG ? kRankListMaxG : (int)g;
+}
+
+RankListArgs rankl_layout(Carver &cv, const RankPlan &P, int64_t n_targets) {
+  RankListArgs K{};
+  K.tz = cv.take<float>((size_t)n_targets);
+  K.tkey = cv.take<u64>((size_t)n_targets);
+  K.partial = cv.take<int>((size_t)n_targets * 2 * P.room);           // (room, not splits: n_items does not size it)
+  return K;
+}
+
+size_t rankl_scratch_bytes(int R, int64_t n_targets, int n_items, int ld) {
+  RankPlan P;
+  if (n_targets < 0 || !rank_plan(R, n_items, ld, P) || rankl_group(ld) < 1) return 0;
+  Carver cv(nullptr, 0);
+  (void)rankl_layout(cv, P, n_targets);
+  return align_up(cv.off, 256) + 256;
+}
+
+template <class E>
+int rankl_launch(const RecArgs &A, const RankListArgs &K, const RankPlan &P, int32_t *out_rank, float *out_score, hipStream_t st) {
+  const size_t lds_count = P.lds + (size_t)K.G * kRankListSlot;
+  DRX_HIP(hipFuncSetAttribute((const void *)k_rankl_keys<E>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)P.lds));
+  hipLaunchKernelGGL(k_rankl_keys<E>, dim3(P.tiles), dim3(256), P.lds, st, A, K);
+  DRX_HIP(hipFuncSetAttribute((const void *)k_rankl_count<E>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_count));
+  hipLaunchKernelGGL(k_rankl_count<E>, dim3(P.tiles, P.splits), dim3(256), lds_count, st, A, K);
+  hipLaunchKernelGGL(k_rankl_finish, dim3((unsigned)((K.P + kBlock - 1) / kBlock)), dim3(kBlock), 0, st, K.partial, K.tkey, K.base, K.P,
+                     P.splits, out_rank, out_score);
+  DRX_LAUNCH_CHECK();
+  return DRX_OK;
+}
+
+int rankl_run(const float *table, const float *bias, int n_items, int ld, int epilogue, const float *q, const int32_t *uid, int R,
+              const int64_t *target_indptr, const int32_t *targets, const int64_t *excl_indptr, const int32_t *excl_indices,
+              int32_t *out_rank, float *out_score, void *scratch, size_t scratch_bytes, void *stream) {
+  if (!table || !q || !target_indptr || !targets || !out_rank || !out_score || R < 1 || n_items < 1 || ld < 4 || (ld & 3)) return DRX_EINVAL;
+  if (epilogue != DRX_REC_SIGMOID_BIAS && epilogue != DRX_REC_BIAS && epilogue != DRX_REC_CLIP) return DRX_EINVAL;
+  if ((epilogue == DRX_REC_CLIP) != (bias == nullptr)) return DRX_EINVAL;
+  if ((excl_indptr != nullptr) != (excl_indices != nullptr) || (excl_indptr && !uid)) return DRX_EINVAL;
+  RankPlan P;
+  const int G = rankl_group(ld);
+  if (!rank_plan(R, n_items, ld, P) || G < 1) return DRX_ENOTIMPL;   // rows wider than 256 floats
+  hipStream_t st = (hipStream_t)stream;
+  int64_t ends[2] = {0, 0};                                           // the offsets are device data: the two that size the call come back
+  DRX_HIP(hipMemcpyAsync(&ends[0], target_indptr, sizeof(int64_t), hipMemcpyDeviceToHost, st));
+  DRX_HIP(hipMemcpyAsync(&ends[1], target_indptr + R, sizeof(int64_t), hipMemcpyDeviceToHost, st));
+  DRX_HIP(hipStreamSynchronize(st));
+  const int64_t n_targets = ends[1] - ends[0];
+  if (ends[0] < 0 || n_targets < 0 || n_targets > ((int64_t)1 << 40)) return DRX_EINVAL;
+  if (n_targets == 0) return DRX_OK;
+  if (!scratch || scratch_bytes < rankl_scratch_bytes(R, n_targets, n_items, ld)) return DRX_ESCRATCH;   // (what the size function says, to the byte)
+  Carver cv(scratch, scratch_bytes);
+  RankListArgs K = rankl_layout(cv, P, n_targets);
+  if (!cv.ok()) return DRX_ESCRATCH;
+  K.tptr = target_indptr; K.targets = targets; K.base = ends[0]; K.P = n_targets; K.G = G;
+  RecArgs A;
+  A.table = table; A.bias = bias; A.q = q; A.uid = uid; A.xptr = excl_indptr; A.xidx = excl_indices;
+  A.R = R; A.N = n_items; A.ld = ld; A.nch = P.nch; A.hs = P.hs; A.n = 0; A.cap = 0; A.splits = P.splits; A.ips = P.ips;
+  A.lists = nullptr; A.counts = nullptr;
+  switch (epilogue) {
+    case DRX_REC_SIGMOID_BIAS: return rankl_launch<RecSigmoidBias>(A, K, P, out_rank, out_score, st);
+    case DRX_REC_BIAS: return rankl_launch<RecBias>(A, K, P, out_rank, out_score, st);
+    default: return rankl_launch<RecClip>(A, K, P, out_rank, out_score, st);
+  }
+}
+
 }  // namespace
 }  // namespace drx
 
@@ -789,6 +1097,20 @@ extern "C" int drx_rows_rank_items(const float *table, const float *bias, int32_
                                    void *stream) {
   return drx::rank_run(table, bias, n_items, ld, epilogue, q, uid, target, R, excl_indptr, excl_indices, out_rank, out_score, scratch,
                        scratch_bytes, stream);
+}
+
+extern "C" int32_t drx_rows_rank_lists_group(int32_t ld) { return drx::rankl_group(ld); }
+
+extern "C" size_t drx_rows_rank_lists_scratch_bytes(int32_t R, int64_t P, int32_t n_items, int32_t ld) {
+  return drx::rankl_scratch_bytes(R, P, n_items, ld);
+}
+
+extern "C" int drx_rows_rank_lists(const float *table, const float *bias, int32_t n_items, int32_t ld, int32_t epilogue, const float *q,
+                                   const int32_t *uid, int32_t R, const int64_t *target_indptr, const int32_t *targets,
+                                   const int64_t *excl_indptr, const int32_t *excl_indices, int32_t *out_rank, float *out_score,
+                                   void *scratch, size_t scratch_bytes, void *stream) {
+  return drx::rankl_run(table, bias, n_items, ld, epilogue, q, uid, R, target_indptr, targets, excl_indptr, excl_indices, out_rank,
+                        out_score, scratch, scratch_bytes, stream);
 }
 
 extern "C" size_t drx_cdae_recommend_scratch_bytes(int32_t R, int32_t n_items, int32_t ld, int32_t n) {

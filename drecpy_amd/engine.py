@@ -178,6 +178,65 @@ class RowsRecommender:
                                         ptr(out_score[lo:lo + r]), ptr(sc), sc.numel(), stream_ptr(self.device)), 'drx_rows_rank_items')
         return out_rank, out_score
 
+    # ---- the same for rows that own a LIST of targets (include/drx.h drx_rows_rank_lists): one counting walk per row, not per pair ----
+    # pairs are grouped per user when there are at least this many per distinct user (RecommenderABC._catalogue_ranks_fused;
+    # DESIGN.md section 3.5 has the measurement behind the value)
+    RANK_LISTS_MIN_MEAN = 2.0
+
+    def rank_ld(self):
+        """The width of this engine's query rows in the fused scorer (what rank_is_fused / rank_lists_group are asked about)."""
+        raise NotImplementedError
+
+    def rank_lists_group(self, ld):
+        """G: the targets of one row that drx_rows_rank_lists counts in ONE walk at rows of `ld` floats (a longer row walks again for
+        every further G); 0 outside the fused domain."""
+        return int(lib().drx_rows_rank_lists_group(int(ld)))
+
+    def _rank_lists_request(self, uids, indptr, items, exclude):
+        """(uid int32 [R] on the device, the offsets int64 [R + 1] on the host and on the device, targets int32 [P] on the device,
+        the exclusion CSR or None)"""
+        uid, targets = self._dev_i32(uids).reshape(-1), self._dev_i32(items).reshape(-1)
+        ip = indptr.cpu().numpy() if torch.is_tensor(indptr) else np.asarray(indptr)
+        ip = np.ascontiguousarray(ip, dtype=np.int64).reshape(-1)
+        assert len(ip) == uid.numel() + 1 and ip[0] == 0 and ip[-1] == targets.numel() and (np.diff(ip) >= 0).all(), \
+            'rank_lists takes CSR offsets [R + 1] over the items: 0 first, ascending, len(items) last'
+        excl = getattr(self, '_excl', None) if exclude is None or exclude is True else None
+        assert not (exclude is True and excl is None), 'rank_lists(exclude=True) needs set_exclusions()'
+        return uid, ip, torch.as_tensor(ip).to(self.device), targets, excl
+
+    def _rows_rank_lists(self, table, bias, ld, epilogue, uid, indptr, targets, excl, rows_of, chunk_rows=None):
+        """The chunked launch beside _rows_rank_items for rows that own lists: `indptr` = (host, device) int64 [R + 1] offsets of row
+        r's ascending targets in `targets` [P].  `chunk_rows` rows at a time: rows_of(lo, uid[lo:lo + r]) -> their [r, ld] query rows
+        (padding columns ZERO), then one drx_rows_rank_lists at the offsets from `lo` on (they are absolute: outputs land in place).
+        Returns device tensors (rank int32 [P], score float32 [P]) parallel to `targets`, -1 / -inf for a target outside the
+        catalogue.  The scratch is kept."""
+        L = lib()
+        ip, d_ip = indptr
+        R, P = int(uid.numel()), int(targets.numel())
+        chunk = int(chunk_rows or self.RECOMMEND_CHUNK_USERS)
+        assert table.is_contiguous() and tuple(table.shape) == (self.n_items, ld)
+        out_rank = torch.empty(P, dtype=torch.int32, device=self.device)
+        out_score = torch.empty(P, dtype=torch.float32, device=self.device)
+        for lo in range(0, R, chunk):
+            u = uid[lo:lo + chunk]
+            r = int(u.numel())
+            p = int(ip[lo + r] - ip[lo])
+            if p == 0:
+                continue
+            q = rows_of(lo, u)
+            assert q.is_contiguous() and tuple(q.shape) == (r, ld) and q.dtype == torch.float32
+            need = int(L.drx_rows_rank_lists_scratch_bytes(r, p, self.n_items, ld))
+            if need == 0:
+                raise _lib.DrxError(f'drx_rows_rank_lists: rows of {ld} floats lie outside the fused domain (rank_is_fused tells)')
+            sc = getattr(self, '_rank_scratch', None)
+            if sc is None or sc.numel() < need:
+                self._rank_scratch = None
+                sc = self._rank_scratch = torch.empty(need, dtype=torch.uint8, device=self.device)
+            check(L.drx_rows_rank_lists(ptr(table), ptr(bias), self.n_items, ld, epilogue, ptr(q), ptr(u), r, ptr(d_ip[lo:]), ptr(targets),
+                                        ptr(excl[0]) if excl else None, ptr(excl[1]) if excl else None, ptr(out_rank), ptr(out_score),
+                                        ptr(sc), sc.numel(), stream_ptr(self.device)), 'drx_rows_rank_lists')
+        return out_rank, out_score
+
     @staticmethod
     def _rows_per_distinct(uid, rows_of_users):
         """Query rows of the pairs `uid`, computed once per distinct user by rows_of_users(distinct uid) and gathered."""
@@ -829,6 +888,20 @@ class CdaeEngine(RowsRecommender):
         if int(uid.numel()) == 0:
             return torch.empty(0, dtype=torch.int32, device=self.device), torch.empty(0, dtype=torch.float32, device=self.device)
         return self._rows_rank_items(self.W2T, self.b2, self.ld, _lib.DRX_REC_SIGMOID_BIAS, uid, target, excl,
+                                     lambda lo, u: self._rows_per_distinct(u, self._hidden_rows), chunk_rows)
+
+    def rank_ld(self):
+        return self.ld
+
+    def rank_lists(self, uids, indptr, items, exclude=None, chunk_rows=None):
+        """rank_items for rows that own several items: row r = user uids[r] with the ASCENDING items[indptr[r]:indptr[r + 1]] (CSR
+        offsets [R + 1]; a row may be empty, a user may own several rows).  (rank int32 [P], score float32 [P]) device tensors
+        parallel to `items`, bit for bit what rank_items gives for the pairs — at one catalogue walk per rank_lists_group(ld) items
+        of a row instead of one per item."""
+        uid, ip, d_ip, targets, excl = self._rank_lists_request(uids, indptr, items, exclude)
+        if int(targets.numel()) == 0:
+            return torch.empty(0, dtype=torch.int32, device=self.device), torch.empty(0, dtype=torch.float32, device=self.device)
+        return self._rows_rank_lists(self.W2T, self.b2, self.ld, _lib.DRX_REC_SIGMOID_BIAS, uid, (ip, d_ip), targets, excl,
                                      lambda lo, u: self._rows_per_distinct(u, self._hidden_rows), chunk_rows)
 
     def _recommend_by_matrix(self, uid, n, excl, out_idx, out_val):

@@ -549,3 +549,18 @@ class CaserEngine(RowsRecommender):
         bef = self._dev_i32(before).reshape(P, self.L)
         return self._rows_rank_items(self.W1, self.b1, self.ld2, _lib.DRX_REC_BIAS, uid, target, excl,
                                      lambda lo, u: self._hidden_rows(u, bef[lo:lo + int(u.numel())].contiguous()), chunk_rows)
+
+    def rank_ld(self):
+        return self.ld2
+
+    def rank_lists(self, uids, before, indptr, items, exclude=None, chunk_rows=None):
+        """rank_items for rows that own several items: row r = (user uids[r], last L items before[r]) with the ASCENDING
+        items[indptr[r]:indptr[r + 1]] (CSR offsets [R + 1]).  (rank int32 [P], logit float32 [P]) device tensors parallel to `items`,
+        bit for bit what rank_items gives for the pairs, at one catalogue walk and ONE hidden row per rank_lists_group(ld2) items of
+        a row."""
+        uid, ip, d_ip, targets, excl = self._rank_lists_request(uids, indptr, items, exclude)
+        if int(targets.numel()) == 0:
+            return torch.empty(0, dtype=torch.int32, device=self.device), torch.empty(0, dtype=torch.float32, device=self.device)
+        bef = self._dev_i32(before).reshape(int(uid.numel()), self.L)
+        return self._rows_rank_lists(self.W1, self.b1, self.ld2, _lib.DRX_REC_BIAS, uid, (ip, d_ip), targets, excl,
+                                     lambda lo, u: self._hidden_rows(u, bef[lo:lo + int(u.numel())].contiguous()), chunk_rows)

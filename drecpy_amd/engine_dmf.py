@@ -637,3 +637,17 @@ class DmfEngine(RowsRecommender):
         table = self._representations(1, torch.arange(self.N, dtype=torch.int32, device=self.device))
         return self._rows_rank_items(table, None, self.W, _lib.DRX_REC_CLIP, uid, target, excl,
                                      lambda lo, u: self._rows_per_distinct(u, lambda d: self._representations(0, d)), chunk_rows)
+
+    def rank_ld(self):
+        return self.W
+
+    def rank_lists(self, uids, indptr, items, exclude=None, chunk_rows=None):
+        """rank_items for rows that own several items: row r = user uids[r] with the ASCENDING items[indptr[r]:indptr[r + 1]] (CSR
+        offsets [R + 1]).  (rank int32 [P], score float32 [P]) device tensors parallel to `items`, bit for bit what rank_items gives
+        for the pairs, at one catalogue walk per rank_lists_group(W) items of a row.  Towers as in rank_items."""
+        uid, ip, d_ip, targets, excl = self._rank_lists_request(uids, indptr, items, exclude)
+        if int(targets.numel()) == 0:
+            return torch.empty(0, dtype=torch.int32, device=self.device), torch.empty(0, dtype=torch.float32, device=self.device)
+        table = self._representations(1, torch.arange(self.N, dtype=torch.int32, device=self.device))
+        return self._rows_rank_lists(table, None, self.W, _lib.DRX_REC_CLIP, uid, (ip, d_ip), targets, excl,
+                                     lambda lo, u: self._rows_per_distinct(u, lambda d: self._representations(0, d)), chunk_rows)

@@ -811,14 +811,37 @@ int drx_rows_recommend(const float *table, const float *bias, int32_t n_items, i
  * with key = drx_rows_recommend's (monotone score bits << 32 | item; the score is the same k-ordered fmaf chain, then the bias, then the
  * epilogue): out_rank[r] is the position of target[r] in the list drx_rows_recommend would return for the row if n were unbounded, bit
  * for bit, ties to the larger item index.  The target's own exclusion is ignored here (the caller decides what an excluded target
- * means).  A target outside [0, n_items) gives out_rank = -1, out_score = -inf.  One target per row: a user with T held-out items costs
- * T rows.  No score matrix and no lists: the scratch holds two words per row and the rows' partial counts (R rounded up to 128 x item
+ * means).  A target outside [0, n_items) gives out_rank = -1, out_score = -inf.  One target per row: through THIS entry point a user with T
+ * held-out items costs T rows and T catalogue walks (drx_rows_rank_lists below takes a row's items as one list).  No score matrix and no lists: the scratch holds two words per row and the rows' partial counts (R rounded up to 128 x item
  * splits x 2), whatever n_items.  Counts are summed in a fixed order without atomics: the result is a function of the inputs alone.
  * Arguments, padding columns (ZERO), epilogues and argument errors as drx_rows_recommend; fused domain ld <= 256, ld % 4 == 0, outside
  * it DRX_ENOTIMPL (scratch bytes 0). */
 size_t drx_rows_rank_items_scratch_bytes(int32_t R, int32_t n_items, int32_t ld);
 int drx_rows_rank_items(const float *table, const float *bias, int32_t n_items, int32_t ld, int32_t epilogue,
                         const float *q, const int32_t *uid, const int32_t *target, int32_t R,
+                        const int64_t *excl_indptr, const int32_t *excl_indices,
+                        int32_t *out_rank, float *out_score, void *scratch, size_t scratch_bytes, void *stream);
+
+/* ---- the same for rows that own a LIST of targets: all of a user's held-out items in one scoring pass ---------------------------------
+ * R query rows (q [R, ld], uid [R]); row r owns targets[target_indptr[r] .. target_indptr[r + 1]).  target_indptr is a DEVICE pointer to
+ * R + 1 offsets, absolute into targets, out_rank and out_score: a chunk of rows is launched with target_indptr + lo and the same three
+ * pointers.  P = target_indptr[R] - target_indptr[0] sizes the scratch (the call reads the two offsets back: one synchronisation of
+ * the stream); P = 0 returns DRX_OK and writes nothing, slots outside [target_indptr[0], target_indptr[R]) are never written.
+ * A row's targets ascend as signed ints, duplicates allowed; a row may be empty; an unsorted row is memory-safe, its results unspecified.
+ * For every target p of row r, out_rank[p] / out_score[p] are bit for bit what drx_rows_rank_items returns for the single pair
+ * (q[r], uid[r], targets[p]): -1 / -inf outside [0, n_items), the target's own exclusion ignored, the row's other targets counted like
+ * any item.  Cost: the blocks that hold a target once per 32 rows, then ONE counting walk of the catalogue per
+ * drx_rows_rank_lists_group(ld) targets of the longest row of a wave's 32 rows (G: what the workgroup's local memory holds beside
+ * the tile's query rows: 32 up to ld = 64, 26 at 128, 4 at 256) — split longer rows into rows of at most G that share q and uid.
+ * No atomics, sums in a fixed order: a function of the inputs alone.  The scratch holds two words and 2 x splits partial counts per
+ * target, no score matrix, and does not depend on n_items once the catalogue has more 128-item blocks than the launch has splits.
+ * Epilogues, padding columns (ZERO) and argument errors as drx_rows_rank_items; fused domain ld <= 256, ld % 4 == 0, outside it
+ * DRX_ENOTIMPL (group and scratch bytes 0). */
+int32_t drx_rows_rank_lists_group(int32_t ld);
+size_t drx_rows_rank_lists_scratch_bytes(int32_t R, int64_t P, int32_t n_items, int32_t ld);
+int drx_rows_rank_lists(const float *table, const float *bias, int32_t n_items, int32_t ld, int32_t epilogue,
+                        const float *q, const int32_t *uid, int32_t R,
+                        const int64_t *target_indptr, const int32_t *targets,
                         const int64_t *excl_indptr, const int32_t *excl_indices,
                         int32_t *out_rank, float *out_score, void *scratch, size_t scratch_bytes, void *stream);
 

@@ -29,6 +29,15 @@ Catalogue ranks of given (user, item) pairs (rank_items: drx_rows_rank_items, co
 at the same R from the same run: R = 1 / 64 / 1024 / 16 384 pairs of distinct users at N = 1 M, K = 128, novelty on (CDAE; the engine
 calls with the hidden rows, and the two library calls alone on the same rows: k_rank_keys + k_rank_count + k_rank_finish against
 k_recommend + k_recommend_merge); with --model the hooks _catalogue_ranks / _recommend_batch of the fitted ml-1m-shaped model.
+
+    python scripts/recommend_bench.py --ranks --targets 1,2,4,10,16 [--model dmf|caser] [--out profiles/rank_lists.json] [--quick]
+
+The SAME P = R x T pairs (R users with T ascending items each) through the pair form (rank_items: one query row and one catalogue walk
+per pair) and through the list form (rank_lists: one row per user): the library calls alone on the same hidden rows (the pair form in
+the engine's chunks of 16 384 rows) and the engine calls, median and min of >= 20 calls each, and whether the two answers are equal.
+CDAE, K = 128, at N = 1 M items / R = 16 384 users and at the ml-1m shape (N = 3706, R = 6040); with --model the hook
+_catalogue_ranks of the fitted ml-1m-shaped model with the routing forced either way.  Writes the smallest T from which on the list
+form is faster at both shapes by more than the spread of the two series (RowsRecommender.RANK_LISTS_MIN_MEAN).
 """
 import argparse
 import faulthandler
@@ -316,15 +325,146 @@ def ranks_main(a):
     write_result(res, a.out)
 
 
-def ranks_model_main(a):
-    """--ranks --model dmf | caser: the hooks _catalogue_ranks / _recommend_batch of a fitted ml-1m-shaped model"""
+def spread_ms(fn, reps):
+    """events around fn() alone -> {median, min, reps}"""
+    fn()
+    ms = []
+    for _ in range(reps):
+        e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+        torch.cuda.synchronize()
+        e0.record()
+        fn()
+        e1.record()
+        torch.cuda.synchronize()
+        ms.append(e0.elapsed_time(e1))
+    return {'median_ms': median(ms), 'min_ms': min(ms), 'reps': reps}
+
+
+def faster_beyond_spread(pair, lists, key='median_ms', low='min_ms'):
+    """median against median, the min - median distance of both series as the spread"""
+    return pair[key] - lists[key] > (pair[key] - pair[low]) + (lists[key] - lists[low])
+
+
+def smallest_winning_t(shapes, targets, series):
+    """the smallest T from which on the list form is faster at every shape, by more than the spread (None: at no measured T)"""
+    best = None
+    for T in sorted(targets, reverse=True):
+        if all(faster_beyond_spread(s[str(T)]['pair'][series], s[str(T)]['lists'][series]) for s in shapes):
+            best = T
+        else:
+            break
+    return best
+
+
+def rank_lists_main(a):
+    """--ranks --targets: the same pairs through rank_items and through rank_lists, CDAE at two catalogues"""
+    from drecpy_amd import _lib
+    L = _lib.lib()
+    K = a.k
+    targets = [int(t) for t in a.targets.split(',')]
+    reps = 5 if a.quick else 20
+    res = {'k': K, 'novelty': True, 'targets': targets, 'group': int(L.drx_rows_rank_lists_group(K)),
+           'timed': 'kernels: the library calls alone on the same hidden rows, events around them (pair form: drx_rows_rank_items in chunks of '
+                    '16 384 rows: k_rank_keys + k_rank_count + k_rank_finish; list form: ONE drx_rows_rank_lists: k_rankl_keys + k_rankl_count + '
+                    'k_rankl_finish); engine: CdaeEngine.rank_items / rank_lists (hidden rows included), device = events around the call, wall = '
+                    'results on the host.  median / min of `reps` calls after warm-up', 'shapes': {}}
+    for name, N, U in (('headline', a.items, a.users), ('ml-1m', 3706, 6040)):
+        with step(300):
+            eng, ip, ix = cdae_engine(U, N, K)
+        dev = eng.device
+        rng = np.random.default_rng(0)
+        x = eng._excl
+        users = torch.as_tensor(np.arange(U, dtype=np.int32)).to(dev)
+        h = eng._hidden_rows(users)
+        out = {}
+        for T in targets:
+            lists = np.sort(np.stack([rng.choice(N, size=T, replace=False) for _ in range(U)]), axis=1).astype(np.int32)
+            indptr = np.arange(U + 1, dtype=np.int64) * T
+            P = U * T
+            d_items, d_ip = torch.as_tensor(lists.reshape(-1)).to(dev), torch.as_tensor(indptr).to(dev)
+            d_pu = users.repeat_interleave(T).contiguous()
+            hp = h.repeat_interleave(T, dim=0).contiguous()
+            r1, s1 = torch.empty(P, dtype=torch.int32, device=dev), torch.empty(P, dtype=torch.float32, device=dev)
+            r2, s2 = torch.empty(P, dtype=torch.int32, device=dev), torch.empty(P, dtype=torch.float32, device=dev)
+            chunk = eng.RECOMMEND_CHUNK_USERS
+            sb = max(int(L.drx_rows_rank_items_scratch_bytes(min(P, chunk), N, eng.ld)), int(L.drx_rows_rank_lists_scratch_bytes(U, P, N, eng.ld)))
+            sc = torch.empty(sb, dtype=torch.uint8, device=dev)
+
+            def pair_kernels():
+                for lo in range(0, P, chunk):
+                    r = min(chunk, P - lo)
+                    _lib.check(L.drx_rows_rank_items(_lib.ptr(eng.W2T), _lib.ptr(eng.b2), N, eng.ld, _lib.DRX_REC_SIGMOID_BIAS, _lib.ptr(hp[lo:]),
+                                                     _lib.ptr(d_pu[lo:]), _lib.ptr(d_items[lo:]), r, _lib.ptr(x[0]), _lib.ptr(x[1]), _lib.ptr(r1[lo:]),
+                                                     _lib.ptr(s1[lo:]), _lib.ptr(sc), sb, _lib.stream_ptr(dev)), 'drx_rows_rank_items')
+
+            def list_kernels():
+                _lib.check(L.drx_rows_rank_lists(_lib.ptr(eng.W2T), _lib.ptr(eng.b2), N, eng.ld, _lib.DRX_REC_SIGMOID_BIAS, _lib.ptr(h), _lib.ptr(users), U,
+                                                 _lib.ptr(d_ip), _lib.ptr(d_items), _lib.ptr(x[0]), _lib.ptr(x[1]), _lib.ptr(r2), _lib.ptr(s2), _lib.ptr(sc),
+                                                 sb, _lib.stream_ptr(dev)), 'drx_rows_rank_lists')
+            with step(600):
+                row = {'pairs': P, 'pair': {'kernels': spread_ms(pair_kernels, reps)}, 'lists': {'kernels': spread_ms(list_kernels, reps)}}
+                row['equal'] = bool(torch.equal(r1, r2) and torch.equal(s1, s2))
+                for form, fn in (('pair', lambda: eng.rank_items(d_pu, d_items)), ('lists', lambda: eng.rank_lists(users, indptr, d_items))):
+                    for _ in range(2):
+                        pair_call(fn)
+                    runs = [pair_call(fn) for _ in range(reps)]
+                    row[form]['device'] = {'median_ms': median([r[0] for r in runs]), 'min_ms': min(r[0] for r in runs), 'reps': reps}
+                    row[form]['wall'] = {'median_ms': median([r[1] for r in runs]), 'min_ms': min(r[1] for r in runs), 'reps': reps}
+            row['pair_over_lists'] = {k: row['pair'][k]['median_ms'] / row['lists'][k]['median_ms'] for k in ('kernels', 'device', 'wall')}
+            row['lists_faster_beyond_spread'] = {k: bool(faster_beyond_spread(row['pair'][k], row['lists'][k])) for k in ('kernels', 'device', 'wall')}
+            out[str(T)] = row
+            print(name, 'T', T, json.dumps(row), flush=True)
+        res['shapes'][name] = {'n_items': N, 'users': U, 'mean_history': float(len(ix) / U), 'by_targets': out}
+        del eng, h
+        torch.cuda.empty_cache()
+    by = [s['by_targets'] for s in res['shapes'].values()]
+    res['smallest_T_faster_at_both_shapes'] = {k: smallest_winning_t(by, targets, k) for k in ('kernels', 'device', 'wall')}
+    res['all_equal'] = all(r['equal'] for s in by for r in s.values())
+    res['rank_lists_min_mean_in_the_engine'] = CdaeEngine.RANK_LISTS_MIN_MEAN
+    write_result(res, a.out)
+
+
+def rank_lists_model_main(a):
+    """--ranks --targets --model dmf | caser: the hook _catalogue_ranks of a fitted ml-1m-shaped model, the routing forced either way"""
+    from drecpy_amd.engine import RowsRecommender
+    m, users = fitted_ml1m(a.model)
+    rng = np.random.default_rng(0)
+    targets = [int(t) for t in a.targets.split(',')]
+    reps = 5 if a.quick else 20
+    R = min(1024, len(users))
+    uids = rng.permutation(users)[:R]
+    res = {'model': a.model, 'n_users': int(m.n_users), 'n_items': int(m.n_items), 'users': R, 'novelty': True, 'targets': targets,
+           'timed': '_catalogue_ranks(internal user ids, internal item ids, novelty) -> numpy arrays with RANK_LISTS_MIN_MEAN = inf (pair) and 0 '
+                    '(lists); device = events around the call', 'by_targets': {}}
+    keep = RowsRecommender.RANK_LISTS_MIN_MEAN
+    for T in targets:
+        pu = np.repeat(uids, T)
+        pi = np.concatenate([rng.choice(m.n_items, size=T, replace=False) for _ in uids])
+        row, got = {}, {}
+        with step(600):
+            for form, mean in (('pair', float('inf')), ('lists', 0.0)):
+                RowsRecommender.RANK_LISTS_MIN_MEAN = mean
+                for _ in range(2):
+                    got[form] = m._catalogue_ranks(pu, pi, True)
+                runs = [hook_call(lambda *_: m._catalogue_ranks(pu, pi, True), None, None)[:2] for _ in range(reps)]
+                row[form] = {'device': {'median_ms': median([r[0] for r in runs]), 'min_ms': min(r[0] for r in runs), 'reps': reps},
+                             'wall': {'median_ms': median([r[1] for r in runs]), 'min_ms': min(r[1] for r in runs), 'reps': reps}}
+            RowsRecommender.RANK_LISTS_MIN_MEAN = keep
+        row['equal'] = bool(np.array_equal(got['pair'][0], got['lists'][0]) and np.array_equal(got['pair'][1], got['lists'][1]))
+        row['pair_over_lists'] = {k: row['pair'][k]['median_ms'] / row['lists'][k]['median_ms'] for k in ('device', 'wall')}
+        res['by_targets'][str(T)] = row
+        print('T', T, json.dumps(row), flush=True)
+    write_result(res, a.out)
+
+
+def fitted_ml1m(model):
+    """a fitted ml-1m-shaped DMF / Caser (bench_configs.py configurations 3 / 5) and the internal users the fused hooks answer"""
     from bench_configs import frame_of
     from drecpy_amd.Dataset import InteractionDataset
     from drecpy_amd.Recommender import DMF, Caser
-    n = a.n
     with step(600):
         ds = InteractionDataset.read_df(frame_of('ml-1m'), verbose=False)
-        if a.model == 'dmf':
+        if model == 'dmf':
             m = DMF(user_factors=[64, 32], item_factors=[64, 32], seed=10, verbose=False)
             m.fit(ds, epochs=2, batch_size=256, learning_rate=1e-3, reg_rate=1e-4, neg_ratio=5)
         else:
@@ -333,8 +473,15 @@ def ranks_model_main(a):
         torch.cuda.synchronize()
     m.RECOMMEND_MIN_FUSED_USERS = 1
     users = np.arange(m.n_users, dtype=np.int64)
-    if a.model == 'caser':
+    if model == 'caser':
         users = np.array([u for u in users if len(m._user_sequence(int(u))) >= m.L], dtype=np.int64)
+    return m, users
+
+
+def ranks_model_main(a):
+    """--ranks --model dmf | caser: the hooks _catalogue_ranks / _recommend_batch of a fitted ml-1m-shaped model"""
+    n = a.n
+    m, users = fitted_ml1m(a.model)
     rng = np.random.default_rng(0)
     order = rng.permutation(users)
     res = {'model': a.model, 'n_users': int(m.n_users), 'n_items': int(m.n_items), 'n': n, 'novelty': True,
@@ -364,7 +511,12 @@ def main():
     ap.add_argument('--users', type=int, default=16384)
     ap.add_argument('--quick', action='store_true', help='fewer repetitions, no R = 16384')
     ap.add_argument('--ranks', action='store_true', help='rank_items beside recommend at the same R (default --out profiles/rank_items.json)')
+    ap.add_argument('--targets', default=None, help='with --ranks: T1,T2,...: the same R x T pairs through rank_items and rank_lists '
+                                                    '(default --out profiles/rank_lists.json)')
     a = ap.parse_args()
+    if a.ranks and a.targets:
+        a.out = a.out or os.path.join('profiles', 'rank_lists.json' if a.model == 'cdae' else f'rank_lists_{a.model}.json')
+        return rank_lists_main(a) if a.model == 'cdae' else rank_lists_model_main(a)
     if a.ranks:
         a.out = a.out or os.path.join('profiles', 'rank_items.json' if a.model == 'cdae' else f'rank_items_{a.model}.json')
         return ranks_main(a) if a.model == 'cdae' else ranks_model_main(a)
