@@ -524,14 +524,18 @@ struct BiasFinalExtra {
 // The HOT HEAD (include/drx.h DrxHotHead): the W rows of the H hottest items take no part in the touch list; their gradients are the
 // dense product (1/(1-q)) * M^T * dz1 of the batch's transposed 0/1 kept-mask M [H, B] (k_sparse_touches) with dz1 [B, ld], read once
 // as a stream instead of one random row gather per touch.  Two stages riding in the launches the step already has:
-//   partials: extra workgroups of k_seg_reduce_stream — one WAVE per (slice of kHotSlice samples, 32 hot rows, 32 columns): a 32 x 32
-//             tile of P[s] = M_slice^T * dz1_slice on v_mfma_f32_32x32x16_bf16.  dz1 is split exactly into hi + mid + lo bf16 (8
-//             significant bits each: 24 = the fp32 significand), so three MFMAs per k-step sum the fp32 values; a 0/1 A operand is
-//             exact in bf16; accumulation is fp32.  16 accumulators per lane: the launch keeps its 64-VGPR budget;
+//   partials: extra workgroups of k_seg_reduce_stream — one WAVE per (slice of kHotSlice samples, strip of 16 columns, group of up to 64
+//             hot rows): up to four 16 x 16 tiles of P[s] = M_slice^T * dz1_slice on v_mfma_f32_16x16x32_bf16, so dz1 is read ONCE per
+//             row group (H <= 64: once).  dz1 is split exactly into hi + mid + lo bf16 (8 significant bits each: 24 = the fp32
+//             significand), so three MFMAs per k-step and tile sum the fp32 values; a 0/1 A operand is exact in bf16; accumulation is
+//             fp32.  16 accumulators per lane: the launch keeps its 64-VGPR budget.  The waves of row group 0 hold every dz1 element of
+//             their (slice, strip) in registers: they also leave the slice's column sums — the hidden bias's partials, BiasArgs::part
+//             with a head — and the wave of strip 0 the slice's loss partial; the launch carries no BiasPartialExtra workgroups then;
 //   finish:   extra workgroups of k_span_planned — one per hot row: the slices' partials summed in a fixed order, the row's Adagrad
 //             update as the segment path's (DirectPolicyAdagrad::stream_update); rows no sample kept are not touched.
 // ------------------------------------------------------------------------------------------------
 constexpr int kHotSlice = 512;       // samples per partial (P: [B / kHotSlice, H, ld] floats)
+constexpr int kHotGroup = 64;        // hot rows a partial wave takes: four 16-row tiles
 // (rows of 64 / 128 floats only: kHotMaxG, drx_prep.hpp)
 
 struct HotArgs {
@@ -542,12 +546,15 @@ struct HotArgs {
   const int32_t *item;          // [H]
   float scale;                  // 1 / (1 - q)
   int B, H, Bw, S, first;       // first: the launch's first workgroup of this stage
+  float *bpart;                 // [S, ld] the slices' column sums of dz1, then [S] their loss partials (BiasArgs::part of a step with a head)
+  const float *lossb;           // [B], or nullptr: no loss wanted
 };
 
 static inline int hot_slices(int B) { return (B + kHotSlice - 1) / kHotSlice; }
+static inline int hot_groups(int H) { return (H + kHotGroup - 1) / kHotGroup; }
 
 typedef __bf16 hot_bf16x8 __attribute__((ext_vector_type(8)));
-typedef float hot_f32x16 __attribute__((ext_vector_type(16)));
+typedef float hot_f32x4 __attribute__((ext_vector_type(4)));
 typedef uint32_t hot_u32x4 __attribute__((ext_vector_type(4)));
 
 // NT: threads of the launch it rides in (k_seg_reduce_stream<LD>: (kSegBlock / (LD / 4)) waves)
@@ -555,60 +562,104 @@ template <int LD, int NT>
 struct HotPartialExtra {
   HotArgs A;
   __device__ __forceinline__ void operator()(float *) const {
-    constexpr int CT = LD / 32, NW = NT / 64;
-    const int lane = threadIdx.x & 63, wv = (int)(threadIdx.x >> 6);
-    const int hbs = A.H / 32;
-    const int task = ((int)blockIdx.x - A.first) * NW + wv;        // column tile fastest: the waves of a workgroup share a slice's rows
-    if (task >= A.S * hbs * CT) return;
-    const int ct = task % CT, hb = (task / CT) % hbs, s = task / (CT * hbs);
-    const int r = lane & 31, hh = lane >> 5;                       // A[row r][k = 8 hh + j], B[k = 8 hh + j][col r]
-    const uint32_t *const mrow = A.mask + (size_t)(hb * 32 + r) * A.Bw;
-    const float *const col = A.dz1 + ct * 32 + r;
-    hot_f32x16 acc;
-#pragma unroll
-    for (int i = 0; i < 16; ++i) acc[i] = 0.f;
-    uint32_t seen = 0u;
+    constexpr int CS = LD / 16, NW = NT / 64;
+    const int lane = threadIdx.x & 63, wv = __builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6));
+    const int ngr = (A.H + kHotGroup - 1) / kHotGroup;
+    const int task = ((int)blockIdx.x - A.first) * NW + wv;        // column strip fastest: the waves of a workgroup read neighbouring
+    if (task >= A.S * ngr * CS) return;                            // 64-byte pieces of the same dz1 rows
+    const int cs = task % CS, rg = (task / CS) % ngr, s = task / (CS * ngr);
+    const int c = lane & 15, kq = lane >> 4;                       // A[row c][k = 8 kq + j], B[k = 8 kq + j][col c]
+    const int nt = min(kHotGroup, A.H - rg * kHotGroup) / 16;      // row tiles of this group: 4, or 2 (H a multiple of 32)
+    // (wave-uniform bases in scalar registers + one 32-bit offset per lane: a slice of dz1 is 512 rows, a tile's mask rows 16 * Bw words)
     const int b_begin = s * kHotSlice, b_end = min(A.B, b_begin + kHotSlice);
-    for (int b0 = b_begin; b0 < b_end; b0 += 32) {                // one mask word: two k-steps of 16 samples
-      const uint32_t word = mrow[b0 >> 5];                         // (bits of samples >= B are never set)
-      seen |= word;
+    const uint32_t *const mgrp = A.mask + (size_t)rg * kHotGroup * A.Bw;
+    const float *const slice = A.dz1 + (size_t)b_begin * LD + cs * 16;
+    const uint32_t mlane = (uint32_t)c * (uint32_t)A.Bw, xlane = (uint32_t)(8 * kq * LD + c);
+    hot_f32x4 acc[4];
 #pragma unroll
-      for (int t = 0; t < 2; ++t) {
-        const uint32_t bits = (word >> (16 * t + 8 * hh)) & 0xFFu;
-        if (__ballot(bits != 0u) == 0ull) continue;                // no sample of these 16 kept a row of these 32
-        const int kb = b0 + 16 * t + 8 * hh;
-        float x[8];
+    for (int t = 0; t < 4; ++t) acc[t] = hot_f32x4{0.f, 0.f, 0.f, 0.f};
+    uint32_t seen = 0u;                                            // bit t: this lane's row of tile t has a kept sample in the slice
+    float bsum = 0.f;                                              // this lane's share of the column sum (row group 0)
+    for (int b0 = b_begin; b0 < b_end; b0 += 32) {                // one mask word: one k-step of 32 samples
+      float x[8];
+      uint32_t w[4];
+      {
+        const float *const rows = slice + (size_t)(b0 - b_begin) * LD;
+        const uint32_t *const words = mgrp + (b0 >> 5);
+        const int left = A.B - b0 - 8 * kq;                        // rows past the batch (the batch's last k-step only) read as 0
+        if (left >= 8) {
 #pragma unroll
-        for (int j = 0; j < 8; ++j) x[j] = kb + j < A.B ? col[(size_t)(kb + j) * LD] : 0.f;
-        hot_u32x4 a, bh, bm, bl;
+          for (int j = 0; j < 8; ++j) x[j] = rows[xlane + (uint32_t)(j * LD)];
+        } else {
 #pragma unroll
-        for (int i = 0; i < 4; ++i) {
-          a[i] = ((bits >> (2 * i)) & 1u) * 0x3F80u | ((bits >> (2 * i + 1)) & 1u) * 0x3F800000u;      // bf16 1.0 or 0
-          uint32_t hv[2], mv[2], lv[2];
-#pragma unroll
-          for (int e = 0; e < 2; ++e) {                            // v = hi + mid + lo exactly (truncations; the rests are exact)
-            const float v = x[2 * i + e];
-            hv[e] = __float_as_uint(v) & 0xFFFF0000u;
-            const float r1 = v - __uint_as_float(hv[e]);
-            mv[e] = __float_as_uint(r1) & 0xFFFF0000u;
-            lv[e] = __float_as_uint(r1 - __uint_as_float(mv[e])) & 0xFFFF0000u;
-          }
-          bh[i] = (hv[0] >> 16) | hv[1];
-          bm[i] = (mv[0] >> 16) | mv[1];
-          bl[i] = (lv[0] >> 16) | lv[1];
+          for (int j = 0; j < 8; ++j) x[j] = j < left ? rows[xlane + (uint32_t)(j * LD)] : 0.f;
         }
+        // (a group of two tiles reads its second tile's words twice and drops them: no branch around an MFMA, whose accumulators the
+        // compiler would otherwise move through VGPRs at every k-step)
+#pragma unroll
+        for (int t = 0; t < 4; ++t) w[t] = (words + (size_t)(16 * min(t, nt - 1)) * A.Bw)[mlane] & (t < nt ? ~0u : 0u);
+      }
+      // (a k-step without a mask bit is not skipped: its dz1 values are the bias's)
+      hot_u32x4 bh, bm, bl;
+#pragma unroll
+      for (int i = 0; i < 4; ++i) {
+        uint32_t hv[2], mv[2], lv[2];
+#pragma unroll
+        for (int e = 0; e < 2; ++e) {                              // v = hi + mid + lo exactly (truncations; the rests are exact)
+          const float v = x[2 * i + e];
+          bsum += v;                                               // (k-steps ascending, j = 0 .. 7 inside a step)
+          hv[e] = __float_as_uint(v) & 0xFFFF0000u;
+          const float r1 = v - __uint_as_float(hv[e]);
+          mv[e] = __float_as_uint(r1) & 0xFFFF0000u;
+          lv[e] = __float_as_uint(r1 - __uint_as_float(mv[e])) & 0xFFFF0000u;
+        }
+        bh[i] = (hv[0] >> 16) | hv[1];
+        bm[i] = (mv[0] >> 16) | mv[1];
+        bl[i] = (lv[0] >> 16) | lv[1];
+      }
+#pragma unroll
+      for (int t = 0; t < 4; ++t) {                                // (a tile past the group's last: A = 0)
+        seen |= (w[t] != 0u ? 1u : 0u) << t;
+        const uint32_t bits = (w[t] >> (8 * kq)) & 0xFFu;
+        hot_u32x4 a;
+#pragma unroll
+        for (int i = 0; i < 4; ++i) a[i] = ((bits >> (2 * i)) & 1u) * 0x3F80u | ((bits >> (2 * i + 1)) & 1u) * 0x3F800000u;      // bf16 1.0 or 0
         const hot_bf16x8 av = __builtin_bit_cast(hot_bf16x8, a);
-        acc = __builtin_amdgcn_mfma_f32_32x32x16_bf16(av, __builtin_bit_cast(hot_bf16x8, bh), acc, 0, 0, 0);
-        acc = __builtin_amdgcn_mfma_f32_32x32x16_bf16(av, __builtin_bit_cast(hot_bf16x8, bm), acc, 0, 0, 0);
-        acc = __builtin_amdgcn_mfma_f32_32x32x16_bf16(av, __builtin_bit_cast(hot_bf16x8, bl), acc, 0, 0, 0);
+        acc[t] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(av, __builtin_bit_cast(hot_bf16x8, bh), acc[t], 0, 0, 0);
+        acc[t] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(av, __builtin_bit_cast(hot_bf16x8, bm), acc[t], 0, 0, 0);
+        acc[t] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(av, __builtin_bit_cast(hot_bf16x8, bl), acc[t], 0, 0, 0);
       }
     }
-    // D: column r, row (i & 3) + 8 (i >> 2) + 4 hh of register i
-    float *const out = A.part + ((size_t)s * A.H + hb * 32) * LD + ct * 32 + r;
+    // D of tile t: column c, row 4 kq + register
+    float *const out = A.part + ((size_t)s * A.H + rg * kHotGroup) * LD + cs * 16 + c;
 #pragma unroll
-    for (int i = 0; i < 16; ++i) out[(size_t)((i & 3) + 8 * (i >> 2) + 4 * hh) * LD] = acc[i];
-    const uint32_t rows_seen = (uint32_t)__ballot(seen != 0u);    // (lanes r and r + 32 read the same row)
-    if (ct == 0 && lane == 0) A.any[(size_t)s * hbs + hb] = rows_seen;
+    for (int t = 0; t < 4; ++t)
+      if (t < nt) {
+#pragma unroll
+        for (int i = 0; i < 4; ++i) out[(size_t)(16 * t + 4 * kq + i) * LD] = acc[t][i];
+      }
+    if (cs == 0) {                                                 // the rows of this group a sample of the slice kept (lanes c, c + 16, .. read the same row)
+      uint32_t rows[4];
+#pragma unroll
+      for (int t = 0; t < 4; ++t) rows[t] = (uint32_t)__ballot((seen >> t) & 1u) & 0xFFFFu;
+      if (lane == 0) {
+        uint32_t *const any = A.any + (size_t)s * (A.H / 32) + rg * (kHotGroup / 32);
+        any[0] = rows[0] | (rows[1] << 16);
+        if (nt > 2) any[1] = rows[2] | (rows[3] << 16);
+      }
+    }
+    if (rg == 0) {
+      // the slice's column sums of these 16 columns: the four lane groups in a fixed order
+      const float g1 = __shfl(bsum, c + 16, 64), g2 = __shfl(bsum, c + 32, 64), g3 = __shfl(bsum, c + 48, 64);
+      if (kq == 0) A.bpart[(size_t)s * LD + cs * 16 + c] = ((bsum + g1) + g2) + g3;
+      if (cs == 0 && A.lossb) {                                    // ... and the slice's loss partial, a fixed order too
+        float l = 0.f;
+        for (int b = b_begin + lane; b < b_end; b += 64) l += A.lossb[b];
+#pragma unroll
+        for (int o = 32; o > 0; o >>= 1) l += __shfl_xor(l, o, 64);
+        if (lane == 0) A.bpart[(size_t)A.S * LD + s] = l;
+      }
+    }
   }
 };
 
@@ -702,12 +753,15 @@ static int hot_recorded(const void *prepared) {
 }
 
 // the hot head's partials and row flags (behind the step's other buffers: a step without a head keeps its layout)
-struct HotBufs { float *part; uint32_t *any; };
+// (+ the hidden bias's and the loss's partials of a step with a head, one row per slice: SparseBufs::bpart has 1024 rows, a batch of more
+// than 1024 slices would not fit them)
+struct HotBufs { float *part; uint32_t *any; float *bpart; };
 static HotBufs hot_layout(Carver &cv, const DrxCdaeParams &P, int B, int H) {
-  HotBufs HB{nullptr, nullptr};
+  HotBufs HB{nullptr, nullptr, nullptr};
   if (H <= 0) return HB;
   HB.part = cv.take<float>((size_t)hot_slices(B) * H * P.ld);
   HB.any = cv.take<uint32_t>((size_t)hot_slices(B) * (H / 32));
+  HB.bpart = cv.take<float>((size_t)hot_slices(B) * (P.ld + 1));
   return HB;
 }
 
@@ -745,7 +799,8 @@ static void launch_forward(ForwardForm form, const DrxCdaeParams &P, const DrxOp
 
 // the segmented reduction (+ the bias column sums as extra workgroups) and the ONE launch that combines the chunk-crossing segments
 // (+ the bias update), phase event 3 between them; with a hot head (HA.H > 0: the streamed form, hot_head_fits) both launches carry
-// its workgroups too — the partials, one wave per (slice, 32 hot rows, 32 columns), and the finish, one workgroup per hot row
+// its workgroups too — the partials, one wave per (slice, 16 columns, up to 64 hot rows), which leave the bias column sums as well (BA.part
+// is their carve then: no BiasPartialExtra workgroups in front) — and the finish, one workgroup per hot row
 template <int G, int J, class Policy>
 static int reduce_and_finish(ReduceForm form, const DrxCdaeParams &P, const DrxOptim &opt, const SparseBufs &S, const SegBufs &SB,
                              const PlanBufs &PB, const SpanPlan &plan, const BiasArgs &BA, const HotArgs &HA, void *const *events,
@@ -757,10 +812,9 @@ static int reduce_and_finish(ReduceForm form, const DrxCdaeParams &P, const DrxO
   else if constexpr (kHotBuilt<G, J, Policy>) {
     constexpr int NT = kStreamThreads<G>;
     HotArgs part = HA;
-    part.first = BA.n_part;
-    const int n_hot = (HA.S * (HA.H / 32) * G / 8 + NT / 64 - 1) / (NT / 64);
-    using Front = ExtraPair<BiasPartialExtra<G, J, NT>, HotPartialExtra<4 * G, NT>>;
-    rc = launch_reduce_streamed<G, J>(SB, PB, plan, pol, BA.n_part + n_hot, Front{{P.ld, BA}, BA.n_part, {part}}, st);
+    part.first = 0;
+    const int n_hot = (HA.S * hot_groups(HA.H) * (G / 4) + NT / 64 - 1) / (NT / 64);      // waves: (slice, row group, strip of 16 columns)
+    rc = launch_reduce_streamed<G, J>(SB, PB, plan, pol, n_hot, HotPartialExtra<4 * G, NT>{part}, st);
   }
   if (rc) return rc;
   DRX_HIP(phase_event(events, 3, st));
@@ -848,8 +902,11 @@ static int step_sparse_impl(const DrxCdaeParams *p, const DrxOptim *opt, const D
   const ReduceForm form = reduce_form(opt->kind, bt->B, S.T, *p);
   const ForwardForm fwd = forward_form(ks_h != nullptr, share, bt->B, bt->n_touch_slots);
   if (H > 0 && !hot_head_fits(form, p->ld, share, ks_h != nullptr)) return DRX_EINVAL;
-  const HotArgs HA{S.dz1, R.hmask, HB.part, HB.any, hot ? hot->item : nullptr, scale, bt->B, H, R.Bw, hot_slices(bt->B), 0};
-  const BiasArgs BA{S.dz1, S.bpart, S.lossb, loss_out, bt->B, n_bpart, rows_per_block};
+  const HotArgs HA{S.dz1, R.hmask, HB.part, HB.any, hot ? hot->item : nullptr, scale, bt->B, H, R.Bw, hot_slices(bt->B), 0, HB.bpart,
+                   loss_out ? S.lossb : nullptr};
+  // (with a head the hidden bias's partials are the slices' column sums its partial waves leave)
+  const BiasArgs BA = H > 0 ? BiasArgs{S.dz1, HB.bpart, S.lossb, loss_out, bt->B, hot_slices(bt->B), kHotSlice}
+                            : BiasArgs{S.dz1, S.bpart, S.lossb, loss_out, bt->B, n_bpart, rows_per_block};
   DRX_HIP(phase_event(events, 0, st));
   (void)dispatch_geom(p->ld, [&](auto g) -> int {
     launch_forward<decltype(g)::G, decltype(g)::J>(fwd, *p, *opt, *hist, *bt, scale, qthr, loss_kind, S, ks_h, ks_dot, st);
@@ -857,7 +914,8 @@ static int step_sparse_impl(const DrxCdaeParams *p, const DrxOptim *opt, const D
   });
   DRX_HIP(phase_event(events, 1, st));
   if (!prepared) {
-    rc = prepare_impl(p, hist, bt, R, st, false, TouchPresence{nullptr, WireGeo{1, 0, 1}}, hot ? hot->slot : nullptr);
+    rc = prepare_impl(p, hist, bt, R, st, false, TouchPresence{nullptr, WireGeo{1, 0, 1}}, hot ? hot->slot : nullptr,
+                      hot ? hot->item : nullptr);
     if (rc) return rc;
   }
   DRX_HIP(phase_event(events, 2, st));
@@ -1002,7 +1060,7 @@ int drx_cdae_sparse_prepare_hot(const DrxCdaeParams *p, const DrxHistory *hist, 
   PrepBufs R = prep_layout(cp, *p, bt->B, bt->n_touch_slots, hot->H);
   if (!cp.ok()) return DRX_ESCRATCH;
   hot_record(prepared, 0);
-  rc = prepare_impl(p, hist, bt, R, (hipStream_t)stream, true, TouchPresence{nullptr, WireGeo{1, 0, 1}}, hot->slot);
+  rc = prepare_impl(p, hist, bt, R, (hipStream_t)stream, true, TouchPresence{nullptr, WireGeo{1, 0, 1}}, hot->slot, hot->item);
   if (rc) return rc;
   hot_record(prepared, hot->H);
   if (p->ld <= 16) order_by_degree(bt, R, (hipStream_t)stream, true);

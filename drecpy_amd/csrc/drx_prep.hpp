@@ -47,11 +47,27 @@ struct TouchPresence {
 // M[slot][b / 32].  A workgroup's 16 samples are exactly one 16-bit half of a mask word: it gathers its halves of all H rows in LDS
 // (the ORs commute) and STORES them, zeros included — no atomics to global memory (one per hot touch made this kernel 47 -> 81 us and
 // slowed the forward kernel beside it by 18 us), no clearing beforehand; the last workgroup also zeroes the half behind the batch.
+// Which slot an item has is asked of a table in LDS, not of slot[item] (one random global read per kept entry into a table of n_items
+// entries): every workgroup hashes item[0 .. H) into an open-addressed table of 2^tbits >= 4 H entries (linear probing; the items are
+// distinct, so what a lookup finds does not depend on the order of the inserts).  DRX_HOT_LDS_LOOKUP=0 (a variant build) reads slot[].
+#ifndef DRX_HOT_LDS_LOOKUP
+#define DRX_HOT_LDS_LOOKUP 1
+#endif
 struct HotMark {
   const int16_t *slot;          // [n_items] or nullptr: no head
   uint32_t *mask;               // [H, Bw]
   int H, Bw;
+  const int32_t *item;          // [H] the hot items, slot order
+  int tbits;                    // log2 of the lookup table's entries
 };
+static inline int hot_table_bits(int H) {
+  int b = 0;
+  while ((1 << b) < 4 * H) ++b;
+  return b;
+}
+// dynamic LDS of k_sparse_touches: the table's keys (int32) and slots (uint16)
+static inline size_t hot_table_lds_bytes(int H) { return H > 0 && DRX_HOT_LDS_LOOKUP ? ((size_t)6 << hot_table_bits(H)) : 0; }
+__device__ __forceinline__ uint32_t hot_table_home(int item, int tbits) { return ((uint32_t)item * 2654435761u) >> (32 - tbits); }
 
 static __global__ __launch_bounds__(kBlock) void k_sparse_touches(int n_items, DrxHistory H, DrxBatch bt, uint32_t qthr, uint32_t *keys,
                                                            uint32_t *vals, int T, uint8_t *solo, uint32_t *zero_a,
@@ -65,8 +81,21 @@ static __global__ __launch_bounds__(kBlock) void k_sparse_touches(int n_items, D
   for (int w = blockIdx.x * kBlock + threadIdx.x; w < n_zero_b; w += gridDim.x * kBlock) zero_b[w] = 0u;
   for (int w = blockIdx.x * kBlock + threadIdx.x; w < n_zero_c; w += gridDim.x * kBlock) zero_c[w] = 0u;      // (the sort's counters and tile words)
   __shared__ uint32_t hm[DRX_MAX_HOT];
+  extern __shared__ __align__(16) int hot_table[];                // [2^tbits] items (-1: free), then [2^tbits] uint16 slots
+  const uint32_t tmask = (1u << hot.tbits) - 1u;
+  uint16_t *const hot_slot_of = reinterpret_cast<uint16_t *>(hot_table + tmask + 1);
   if (hot.slot) {                                                  // (workgroup-uniform)
     for (int i = threadIdx.x; i < hot.H; i += kBlock) hm[i] = 0u;
+    if (DRX_HOT_LDS_LOOKUP) {
+      for (int i = threadIdx.x; i <= (int)tmask; i += kBlock) hot_table[i] = -1;
+      __syncthreads();
+      for (int i = threadIdx.x; i < hot.H; i += kBlock) {
+        const int it = hot.item[i];
+        uint32_t at = hot_table_home(it, hot.tbits);
+        while (atomicCAS(&hot_table[at], -1, it) != -1) at = (at + 1u) & tmask;      // (at most H of >= 4 H entries are ever taken)
+        hot_slot_of[at] = (uint16_t)i;
+      }
+    }
     __syncthreads();
   }
   if (b < bt.B) {
@@ -81,7 +110,16 @@ static __global__ __launch_bounds__(kBlock) void k_sparse_touches(int n_items, D
     const uint32_t jj = (uint32_t)(j - s);
     const bool kf = kp ? (kp[jj] != 0) : (hash_u32(bt.mask_seed, (uint32_t)b, jj) >= qthr);
     const int item = H.indices[j];
-    const int hs = hot.slot && kf ? (int)hot.slot[item] : -1;
+    int hs = -1;
+    if (hot.slot && kf) {
+      if (DRX_HOT_LDS_LOOKUP) {
+        for (uint32_t at = hot_table_home(item, hot.tbits);; at = (at + 1u) & tmask) {
+          const int k = hot_table[at];
+          if (k == item) hs = (int)hot_slot_of[at];
+          if (k == item || k == -1) break;
+        }
+      } else hs = (int)hot.slot[item];
+    }
     keys[base + jj] = kf && hs < 0 ? (uint32_t)item : DRX_KEY_NONE;
     vals[base + jj] = (uint32_t)b;
     if (hs >= 0) atomicOr(&hm[hs], 1u << (b & 15));
@@ -755,10 +793,10 @@ static int prepare_transposed(const DrxCdaeParams *p, const DrxHistory *hist, co
 
 static int prepare_impl(const DrxCdaeParams *p, const DrxHistory *hist, const DrxBatch *bt, const PrepBufs &R, hipStream_t st,
                         bool with_marks = false, TouchPresence pres = TouchPresence{nullptr, WireGeo{1, 0, 1}},
-                        const int16_t *hot_slot = nullptr) {
+                        const int16_t *hot_slot = nullptr, const int32_t *hot_item = nullptr) {
   const int gpb = kBlock / 16;
   // (the transposed preparation below never builds a head)
-  if (R.H > 0 && (!hot_slot || !hot_list_fits(R.T, *p, pres.present != nullptr))) return DRX_EINVAL;
+  if (R.H > 0 && (!hot_slot || !hot_item || !hot_list_fits(R.T, *p, pres.present != nullptr))) return DRX_EINVAL;
   if (hist->t_rank && hist->t_users && hist->t_pos && hist->t_items && !pres.present && long_segments(R.T, *p)) {
     const int32_t *row_end = nullptr;
     const int rc = prepare_transposed(p, hist, bt, R, st, with_marks, &row_end);
@@ -783,9 +821,9 @@ static int prepare_impl(const DrxCdaeParams *p, const DrxHistory *hist, const Dr
   uint32_t *sort_zero = nullptr;
   size_t sort_zero_words = 0;
   sort_pairs_zero_region(R.sort_temp, (size_t)R.T, R.bits, &sort_zero, &sort_zero_words);
-  hipLaunchKernelGGL(k_sparse_touches, dim3((bt->B + gpb - 1) / gpb), dim3(kBlock), 0, st, p->n_items, *hist, *bt,
+  hipLaunchKernelGGL(k_sparse_touches, dim3((bt->B + gpb - 1) / gpb), dim3(kBlock), hot_table_lds_bytes(R.H), st, p->n_items, *hist, *bt,
                      q_threshold(bt->q), R.keys, R.vals, R.T, R.solo_v, R.plan.cnt, plan_zero_words(R), R.order_work, 512,
-                     sort_zero, (int)sort_zero_words, pres, HotMark{R.H > 0 ? hot_slot : nullptr, R.hmask, R.H, R.Bw});
+                     sort_zero, (int)sort_zero_words, pres, HotMark{R.H > 0 ? hot_slot : nullptr, R.hmask, R.H, R.Bw, hot_item, hot_table_bits(R.H)});
   // the launch order (see k_degree_counts): its counts ride in the sort's first launch, its scatter in the plan + marks launch below
   const bool fused_order = with_marks && p->ld > 16;
   const SortRider rider{fused_order ? bt->keep_off : nullptr, bt->B, R.order_work};

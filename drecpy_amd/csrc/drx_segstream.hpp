@@ -65,11 +65,13 @@ template <> struct LaneVec<4> { typedef float T __attribute__((ext_vector_type(4
 // (the ring depth kStreamDepth and kStreamIndexBits: drx_prep.hpp, beside reduce_form())
 // The streamed kernels take their arguments (five structs of pointers) in ~106 scalar registers; a CU admits 256-thread workgroups up to
 // 800 / (sgprs rounded up to 16, + 16): 6 at 106, 8 at 80 (MI355X_MICROARCH: Residency).  Capped, the compiler parks the surplus in
-// lanes of a vector register (v_writelane / v_readlane): 8 workgroups = all 32 wave slots of a CU.
+// lanes of a vector register (v_writelane / v_readlane): 8 workgroups = all 32 wave slots of a CU.  amdgpu_waves_per_eu(8) holds the
+// vector registers (VGPRs + AGPRs) of every front riding in the launch to the 64 of 8 waves per SIMD: left alone, the register allocator
+// gave the hot head's partial waves (drx_cdae.hip HotPartialExtra) 62 + 16 for no gain; held, they take 60 without scratch.
 #ifndef DRX_STREAM_SGPRS
 #define DRX_STREAM_SGPRS 80
 #endif
-#define DRX_STREAM_SGPR_CAP __attribute__((amdgpu_num_sgpr(DRX_STREAM_SGPRS)))
+#define DRX_STREAM_SGPR_CAP __attribute__((amdgpu_num_sgpr(DRX_STREAM_SGPRS), amdgpu_waves_per_eu(8)))
 constexpr int kStreamItems = 3 * (2 * kChunk - 1) + 3;        // a window's items at most (every touch a segment of its own), rounded up to a multiple of 4
 static inline size_t seg_stream_lds_bytes(int ld, int depth) {
   const int cpb = kSegBlock / (ld / 4);
