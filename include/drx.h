@@ -237,7 +237,26 @@ int drx_batch_offsets(const int64_t *indptr, const int32_t *ids, int32_t B, int3
  * neg_ratio/(neg_ratio+1) = uniform (u,i) outside u's positives, positives = uniform user then uniform positive.
  * Also writes keep_off[B+1] (exclusive prefix sum of deg(uid[b])).
  * host_mailbox (optional): 8 bytes of PINNED host memory; the last kernel stores ((uint64)tag << 32) | keep_off[B] there with one
- * system-scope store, so a host that runs ahead learns the batch's touch count by polling for its tag — no copy, no event. */
+ * system-scope store, so a host that runs ahead learns the batch's touch count by polling for its tag — no copy, no event.
+ *
+ * THE STREAM.  Draw b reads h(k) = drx_hash_u32(seed, b, k), k = 0, 1, 2, ...; every index below is (h * n) >> 32 in 64-bit integers:
+ *   k = 0      the kind: a negative iff h(0) * (neg_ratio + 1) > 2^32 (the kernel's double expression, exact in integers: h(0) / 2^32
+ *              and its product with neg_ratio + 1 are both representable while neg_ratio < 2^21), else a positive; neg_ratio = 0 never
+ *              gives a negative
+ *   k = 1 ..   the attempts, each taking the next unused counters, at most 4096 attempts per draw:
+ *     negative attempt, TWO counters: user u = (h * n_users) >> 32, then item i = (h * n_items) >> 32; accepted iff i is not in u's row
+ *              of `recorded` (of `hist` where recorded is NULL) — a user who records nothing accepts every item
+ *     positive attempt, ONE counter: user u = (h * n_users) >> 32; a user without a positive (deg = 0 in hist) is rejected and no second
+ *              counter is taken; otherwise a SECOND counter picks position (h * deg) >> 32 of u's row of hist, and the attempt is accepted
+ *   uid[b], iid[b] = the accepted pair.
+ *   y[b]:  positive: 1 (drx_point_sample*), or the pair's value v = pos_values[position in hist] (drx_point_sample_valued) — raw when
+ *          vrange <= 0, (v - vmin) / vrange in float32 (one subtraction, one division) when vrange > 0;
+ *          negative: 0, or (0 - vmin) / vrange in float32 where values are given and vrange > 0.
+ *   WHEN THE 4096 ATTEMPTS RUN OUT (a frame in which almost no user is eligible) the draw is still written, silently and with a WRONG
+ *   label: a negative gets the last rejected pair — a recorded pair — with the negative's target; a positive gets the last user drawn —
+ *   who has no positive —, item 0 and y = 1 (values or not).  Callers must not rely on this: it is what the code does today, not a
+ *   contract, and no frame should reach it.
+ * Restated on the CPU by oracle/data_oracle.py::point_sample_counter (tests/test_gpu_point_sampler.py compares bit for bit, y included). */
 size_t drx_point_sample_scratch_bytes(int32_t B);
 int drx_point_sample(const DrxHistory *hist, int32_t n_users, int32_t n_items, int32_t B, int32_t neg_ratio,
                      uint64_t seed, int32_t *uid, int32_t *iid, float *y, int32_t *keep_off,

@@ -260,3 +260,65 @@ def list_sample_counter(twin, n, n_inputs, n_targets, neg_ratio, seed):
             picked.append(v)
             after[d, T + i] = v
     return grp, before, after
+
+
+def point_sample_counter(pos_indptr, pos_indices, rec_indptr, rec_indices, n_users, n_items, B, neg_ratio, seed, values=None, vmin=0.0,
+                         vrange=0.0, max_tries=4096):
+    """CPU restatement of the device point sampler (include/drx.h, "THE STREAM"): B triples from the counter-based generator
+    h(k) = drx_hash_u32(seed, b, k).  pos: the CSR of positives (the kernel's `hist`); rec: the CSR of every recorded pair, columns
+    ascending (rec_indptr None: pos stands in for it); values: the positives' values, aligned with pos_indices (drx_point_sample_valued).
+    Returns (uid int32, iid int32, y float32, attempts int32, exhausted bool).  All draws still open make their next attempt together,
+    so the cost is a few numpy passes per attempt round; every index is integer arithmetic, the standardisation is float32."""
+    from oracle.cdae_oracle import drx_hash_u32
+    pos_indptr = np.asarray(pos_indptr, np.int64)
+    pos_indices = np.asarray(pos_indices, np.int64)
+    if rec_indptr is None:
+        rec_indptr, rec_indices = pos_indptr, pos_indices
+    rec_indptr = np.asarray(rec_indptr, np.int64)
+    # membership of (u, i) in `recorded`: one sorted array of keys u * n_items + i (a set statement, not the kernel's row search)
+    rec_keys = np.sort(np.repeat(np.arange(n_users, dtype=np.int64), np.diff(rec_indptr)) * n_items + np.asarray(rec_indices, np.int64))
+
+    def scaled(d, k, n):                                # (h(k) * n) >> 32 per draw
+        return ((drx_hash_u32(seed, d.astype(np.uint32), k.astype(np.uint32)).astype(np.uint64) * np.asarray(n, np.uint64))
+                >> np.uint64(32)).astype(np.int64)
+    d_all = np.arange(B, dtype=np.int64)
+    h0 = drx_hash_u32(seed, d_all.astype(np.uint32), np.zeros(B, np.uint32)).astype(np.uint64)
+    negative = h0 * np.uint64(neg_ratio + 1) > np.uint64(1 << 32)
+    uid, iid = np.zeros(B, np.int64), np.zeros(B, np.int64)
+    at = np.full(B, -1, np.int64)                       # an accepted positive's position in pos
+    c = np.ones(B, np.int64)                            # the next unused counter of every draw
+    attempts = np.zeros(B, np.int32)
+    is_open = np.ones(B, bool)
+    for _ in range(max_tries):
+        d = np.flatnonzero(is_open)
+        if not len(d):
+            break
+        attempts[d] += 1
+        u = scaled(d, c[d], n_users)
+        c[d] += 1
+        uid[d] = u                                      # (a draw that runs out keeps its last attempt's user)
+        neg = negative[d]
+        dn, un = d[neg], u[neg]
+        i = scaled(dn, c[dn], n_items)
+        c[dn] += 1
+        iid[dn] = i
+        key = un * n_items + i
+        slot = np.searchsorted(rec_keys, key)
+        taken = (slot < len(rec_keys)) & (rec_keys[np.minimum(slot, len(rec_keys) - 1)] == key) if len(rec_keys) else np.zeros(len(dn), bool)
+        is_open[dn[~taken]] = False
+        dp, up = d[~neg], u[~neg]
+        s, deg = pos_indptr[up], pos_indptr[up + 1] - pos_indptr[up]
+        has = deg > 0
+        dp, s, deg = dp[has], s[has], deg[has]
+        where = s + scaled(dp, c[dp], deg)
+        c[dp] += 1
+        at[dp], iid[dp] = where, pos_indices[where]
+        is_open[dp] = False
+    one, zero = np.float32(1), np.float32(0)
+    y = np.full(B, one, np.float32)
+    got = at >= 0
+    if values is not None:
+        v = np.asarray(values, np.float32)[at[got]]
+        y[got] = (v - np.float32(vmin)) / np.float32(vrange) if np.float32(vrange) > 0 else v
+    y[negative] = (zero - np.float32(vmin)) / np.float32(vrange) if (values is not None and np.float32(vrange) > 0) else zero
+    return uid.astype(np.int32), iid.astype(np.int32), y, attempts, is_open.copy()

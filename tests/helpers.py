@@ -55,6 +55,26 @@ def synth_history(rng, n_users, n_items, mean_deg, zipf=1.0, min_deg=0):
     return np.asarray(indptr, np.int64), (np.concatenate(idx) if idx else np.zeros(0)).astype(np.int32)
 
 
+def point_sampler_frame():
+    """The frame of the point-sampler tests (CPU oracle and GPU): 203 users, 37 items; a quarter of the users record nothing, an eighth
+    record every item, the rest each item with probability 0.3; values 1..5, a pair is a positive from 3 on.  User 0 records nothing,
+    the last user everything, and two sparse users are recorded without a positive.  Returns a dict: U, N, rec = (indptr, indices) of
+    all recorded pairs (columns ascending), pos = (indptr, indices, values float32) of the positives."""
+    rng = np.random.default_rng(1)
+    U, N = 203, 37
+    cls = rng.permutation(np.repeat([0, 1, 2], [U // 4, U // 8, U - U // 4 - U // 8]))        # 0: nothing, 1: everything, 2: sparse
+    for at, c in ((0, 0), (U - 1, 1)):                                                       # (swaps: the class sizes stay)
+        j = np.flatnonzero(cls[1:] == c)[0] + 1
+        cls[at], cls[j] = cls[j], cls[at]
+    rec = np.where(cls[:, None] == 2, rng.random((U, N)) < 0.3, cls[:, None] == 1)
+    val = rng.integers(1, 6, size=(U, N)).astype(np.float32)
+    sparse = np.flatnonzero((cls == 2) & (rec.sum(1) > 0))
+    val[sparse[0]], val[sparse[-1]] = 1.0, 2.0                                                # recorded, no positive
+    pos = rec & (val >= 3)
+    csr = lambda m: (np.concatenate([[0], np.cumsum(m.sum(1))]).astype(np.int64), np.nonzero(m)[1].astype(np.int32))
+    return {'U': U, 'N': N, 'rec': csr(rec), 'pos': csr(pos) + (val[pos],)}
+
+
 def batch_rows(indptr, indices, uids, n_items, keep_flat=None):
     """Dense targets t [B,N], keep offsets and (optionally) the kept-item lists per row."""
     B = len(uids)
