@@ -9,6 +9,8 @@ override `__call__` with explicit parameter names like the reference's classes d
 import math
 from abc import ABC, abstractmethod
 
+import numpy as np
+
 
 class RankingMetricABC(ABC):
     inputs = ()
@@ -112,3 +114,42 @@ class ReciprocalRank(RankingMetricABC):
 
     def _score(self, top, k, best):
         return 1 / (top.index(best) + 1) if best in top else 0
+
+
+# ---- predictive metrics (DRecPy/Evaluation/Metrics/regression.py): `Metric()(y_true, y_pred)` over parallel sequences of values ----
+class PredictiveMetricABC(ABC):
+    def __init__(self):
+        self.name = type(self).__name__          # the key of predictive_evaluation's result
+
+    @abstractmethod
+    def __call__(self, y_true, y_pred):
+        raise NotImplementedError
+
+
+def _errors(y_true, y_pred):
+    t, p = np.asarray(y_true, dtype=np.float64).reshape(-1), np.asarray(y_pred, dtype=np.float64).reshape(-1)
+    assert t.shape == p.shape and t.size > 0, f'a predictive metric takes parallel, non-empty values ({t.size} true, {p.size} predicted)'
+    return p - t
+
+
+class MSE(PredictiveMetricABC):
+    """Mean squared error."""
+
+    def __call__(self, y_true, y_pred):
+        e = _errors(y_true, y_pred)
+        return float((e * e).mean())
+
+
+class RMSE(PredictiveMetricABC):
+    """Root of the mean squared error."""
+
+    def __call__(self, y_true, y_pred):
+        e = _errors(y_true, y_pred)
+        return math.sqrt(float((e * e).mean()))
+
+
+class MAE(PredictiveMetricABC):
+    """Mean absolute error."""
+
+    def __call__(self, y_true, y_pred):
+        return float(np.abs(_errors(y_true, y_pred)).mean())

@@ -537,6 +537,15 @@ class CDAE(RecommenderABC):
             return super()._catalogue_ranks(uids, iids, novelty)
         return self._catalogue_ranks_fused(uids, iids, novelty)
 
+    def _predict_pairs(self, uids, iids):
+        """Predictions of many (user, item) pairs in one engine call (CdaeEngine.pair_scores: the hidden row of every distinct user
+        once, then two rows per pair — no forward over the catalogue, no [n_items] row downloaded per pair), on _recommend_batch's
+        arithmetic: a value may differ from predict()'s in the last ulp.  Any K (the pair scorer has no 256-float limit).  A subclass
+        with its own _predict keeps its arithmetic — one _predict per pair."""
+        if type(self)._predict is not CDAE._predict:
+            return super()._predict_pairs(uids, iids)
+        return self._predict_pairs_fused(uids, iids)
+
     def _all_user_items(self, uid):
         if not hasattr(self, '_user_items'):
             ds = self.interaction_dataset

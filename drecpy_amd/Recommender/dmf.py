@@ -249,6 +249,16 @@ class DMF(RecommenderABC):
         rank, score = self._catalogue_ranks_fused(uids, iids, novelty)
         return rank, np.where(rank >= 0, self._rescale_value(score), -np.inf)
 
+    def _predict_pairs(self, uids, iids):
+        """Predictions of many (user, item) pairs in one engine call (DmfEngine.pair_scores: each tower once per DISTINCT user / item
+        of the request, then two rows per pair), under _catalogue_ranks' gate and with _predict's rescaling: a subclass with its own
+        prediction hooks (ModifiedDMF) or a bound prediction scale keeps its arithmetic — one _predict per pair.  A value may differ
+        from predict()'s in the last ulp (a k-ordered fmaf chain)."""
+        if not self._fused_score_is_own(len(np.unique(uids))):
+            return super()._predict_pairs(uids, iids)
+        score, none = self._predict_pairs_fused(uids, iids)
+        return self._rescale_value(score), none
+
     def score_matrix(self, user_ids):
         """[len(user_ids), n_items] clipped cosine scores via the bf16 MFMA scorer (raw user ids in)."""
         uids = [self.interaction_dataset.user_to_uid(u) for u in user_ids]

@@ -444,6 +444,84 @@ class RecommenderABC(ABC):
                 return None
             raise
 
+    def predict_pairs(self, user_ids, item_ids, skip_errors=False):
+        """predict() for many (user, item) pairs in one call (no reference equivalent: recommender_abc.py:354-390 predicts one pair per
+        call): parallel sequences of raw ids in, np.float64 [P] out, each value what predict(user, item, skip_errors) returns — NaN
+        where it would return None under skip_errors=True (an unknown user or item, a model that cannot predict); with
+        skip_errors=False the first offending pair raises as predict() does.  A NaN the model itself predicts stays a NaN and raises
+        nothing.  One exception: for an unknown ITEM under skip_errors=True CDAE's predict() returns the user's whole row of
+        predictions (its _predict is called with iid None, as the reference's); that is no point prediction, and the value here is NaN.
+        CDAE and DMF answer from the fused pair scorer (drx_rows_pair_scores) — two rows per pair, the
+        arithmetic of recommend_batch and catalogue_ranks: a score there is a k-ordered fmaf chain, so a value may differ from
+        predict()'s in the last ulp.  (The name is not predict_batch: _predict_batch(batch_samples) is the reference's training hook.)"""
+        assert self.fitted is True, 'The model requires to be fitted before being able to make predictions.'
+        ds = self.interaction_dataset
+        user_ids, item_ids = list(user_ids), list(item_ids)
+        assert len(user_ids) == len(item_ids), f'predict_pairs takes parallel sequences ({len(user_ids)} users, {len(item_ids)} items)'
+        out = np.full(len(user_ids), np.nan, dtype=np.float64)
+        missing = np.ones(len(user_ids), dtype=bool)                  # no prediction: what predict() reports as None
+        known, uids, iids = [], [], []
+        for p, (user_id, item_id) in enumerate(zip(user_ids, item_ids)):
+            try:
+                uid, iid = ds.user_to_uid(user_id), ds.item_to_iid(item_id)
+            except Exception:
+                if skip_errors:
+                    continue
+                raise
+            if not skip_errors:
+                assert uid is not None, f'User {user_id} was not found.'
+                assert iid is not None, f'Item {item_id} was not found.'
+            if uid is None or iid is None:
+                continue
+            known.append(p)
+            uids.append(uid)
+            iids.append(iid)
+        if known:
+            try:
+                values, none = self._predict_pairs(np.asarray(uids, dtype=np.int64), np.asarray(iids, dtype=np.int64))
+            except Exception:
+                if not skip_errors:
+                    raise
+                values, none = np.full(len(known), np.nan), np.ones(len(known), dtype=bool)
+                for j, (uid, iid) in enumerate(zip(uids, iids)):       # (as predict(skip_errors=True): a pair that fails is its own loss)
+                    try:
+                        value = self._predict(uid, iid)
+                        if value is not None:
+                            values[j], none[j] = value, False
+                    except Exception:
+                        pass
+            out[np.asarray(known)], missing[np.asarray(known)] = np.where(none, np.nan, values), none
+        if not skip_errors and missing.any():
+            p = int(np.flatnonzero(missing)[0])
+            raise Exception(f'Failed to predict(user_id={user_ids[p]}, item_id={item_ids[p]}): None was returned.')
+        return out
+
+    def _predict_pairs(self, uids, iids):
+        """Hook: parallel internal ids [P] -> (np.float64 [P], bool [P]: True where the model has NO prediction — _predict's None; a
+        NaN is a prediction).  Default: one _predict per pair — the model's own arithmetic, whatever it is; an exception of _predict
+        passes through (predict_pairs decides)."""
+        out, none = np.full(len(uids), np.nan, dtype=np.float64), np.zeros(len(uids), dtype=bool)
+        for p, (uid, iid) in enumerate(zip(uids, iids)):
+            value = self._predict(int(uid), int(iid))
+            if value is None:
+                none[p] = True
+            else:
+                out[p] = value
+        return out, none
+
+    def _predict_pairs_fused(self, uids, iids, *query):
+        """What the models' _predict_pairs share, beside _recommend_batch_fused: ONE engine.pair_scores(uids, *query, iids) for all
+        pairs, sorted by user for the call (a wave's pairs then share their query row) and downloaded in request order: (np.float64
+        [P], bool [P] all False — the device scores every pair).  `query`: per-pair arrays."""
+        uids, iids = np.asarray(uids, dtype=np.int64), np.asarray(iids, dtype=np.int64)
+        order = np.argsort(uids, kind='stable')
+        rows = [np.asarray(x)[order] for x in query]
+        with self._device_lock:
+            score = self._engine.pair_scores(uids[order].astype(np.int32), *rows, iids[order].astype(np.int32)).cpu().numpy()
+        out = np.empty(len(uids), dtype=np.float64)
+        out[order] = score
+        return out, np.zeros(len(uids), dtype=bool)
+
     def recommend(self, user_id, n=None, novelty=True, interaction_threshold=None, **kwds):
         uid = self._require_user(user_id)
         ranked = self._recommend(uid, self.n_items if n is None else n, novelty, interaction_threshold)

@@ -26,6 +26,8 @@
 //
 // drx_rows_rank_items (k_rank_keys / k_rank_count / k_rank_finish, at the end of this file) answers the other question on the same walk:
 // where in the whole catalogue a GIVEN item stands for a row — a count of larger keys instead of a selection.
+// drx_rows_pair_scores (k_pair_scores, behind them) answers for given (row, item) pairs with the score alone, from the pair's two rows:
+// the same sum as one scalar fmaf chain per pair, no walk.
 #include <hip/hip_runtime.h>
 #include "drx_common.hpp"
 
@@ -1075,8 +1077,133 @@ int rankl_run(const float *table, const float *bias, int n_items, int ld, int ep
   }
 }
 
+// ---- scores of given (query row, table row) pairs and nothing else (drx_rows_pair_scores) -------------------------------------------
+// out[p] = E::score(q[q_row[p], :] . table[t_row[p], :] (+ bias[t_row[p]])): two rows per pair, no walk, no scratch.  The sum is the
+// one k_recommend / k_rank_keys build for the same rows, written out as ONE fmaf chain per pair: from 0.0f, the columns in steps of 8,
+// within a step in the order 0, 4, 1, 5, 2, 6, 3, 7 (MFMA (t, c) adds k = 8 t + c from lanes 0..31, then k = 8 t + 4 + c from lanes
+// 32..63), steps that begin behind ld skipped, and in a half-covered last step (ld % 8 == 4) the row's last float4 once more against
+// ZERO query entries (what rec_load_a's clamp and the zeroed LDS columns multiply); then the bias, then the epilogue.
+// k_pair_scores  one wave per workgroup, a lane owns a pair (the chain is sequential in k).  The rows do not reach the lanes by 64
+//                strided loads: per chunk of 32 columns (a 128-byte line of a row) 8 lanes load one pair's line as float4, 8 pairs per
+//                instruction, into registers and from there into LDS [pair][32 + 4] (the + 4 spreads a lane's float4 reads over the
+//                banks); the lane then reads its own pair's chunk.  The registers of chunk kc + 1 load while chunk kc multiplies.
+//                Pairs sorted by user give a wave one or two distinct query rows: those loads fall into the same lines (L1).
+constexpr int kPairKC = 32;                // columns of a chunk
+constexpr int kPairLs = kPairKC + 4;       // floats between two pairs' chunks in LDS
+constexpr int kPairMaxGroups = 1 << 20;    // workgroups of a launch; a workgroup strides over the pairs beyond
+
+struct PairArgs {
+  const float *table, *bias, *q;   // [n_rows][ld], [n_rows] or null, [n_q][ld]
+  const int32_t *q_row, *t_row;    // [P]
+  float *out;                      // [P]
+  int n_rows, n_q, ld;
+  int64_t P;
+};
+
+// chunk kc of the 64 rows `myrow` (one per lane, inside the array): instruction j = rows 8 j .. 8 j + 7, 8 lanes of 16 bytes per row.
+// kZeroBehind: columns behind ld are ZERO (the query side); else they repeat the row's last float4 (the table side, as rec_load_a).
+template <bool kZeroBehind>
+__device__ __forceinline__ void pair_load(const float *base, int ld, int myrow, int kc, int lane, float4 (&r)[8]) {
+  const int c = kc * kPairKC + 4 * (lane & 7);
+#pragma unroll
+  for (int j = 0; j < 8; ++j) {
+    const int row = __shfl(myrow, 8 * j + (lane >> 3), kWave);
+    float4 v = *reinterpret_cast<const float4 *>(base + (size_t)row * ld + min(c, ld - 4));   // (no branch around a load)
+    if (kZeroBehind && c >= ld) v.x = v.y = v.z = v.w = 0.f;
+    r[j] = v;
+  }
+}
+
+__device__ __forceinline__ void pair_stage(float *s, int lane, const float4 (&r)[8]) {
+#pragma unroll
+  for (int j = 0; j < 8; ++j) *reinterpret_cast<float4 *>(s + (8 * j + (lane >> 3)) * kPairLs + 4 * (lane & 7)) = r[j];
+}
+
+template <class E>
+__global__ __launch_bounds__(kWave) void k_pair_scores(PairArgs A) {
+  __shared__ __align__(16) float t_s[kWave * kPairLs], q_s[kWave * kPairLs];
+  const int lane = threadIdx.x;
+  const int nch = (A.ld + kPairKC - 1) / kPairKC;
+  for (int64_t p0 = (int64_t)blockIdx.x * kWave; p0 < A.P; p0 += (int64_t)gridDim.x * kWave) {
+    const int64_t p = p0 + lane;
+    int tr = 0, qr = 0;
+    bool valid = false;
+    if (p < A.P) {
+      const int t = A.t_row[p], u = A.q_row[p];
+      valid = (unsigned)t < (unsigned)A.n_rows && (unsigned)u < (unsigned)A.n_q;
+      if (valid) { tr = t; qr = u; }                                  // (else row 0 of both: loaded, never looked at)
+    }
+    float4 rt[8], rq[8];
+    pair_load<false>(A.table, A.ld, tr, 0, lane, rt);
+    pair_load<true>(A.q, A.ld, qr, 0, lane, rq);
+    float acc = 0.0f;
+    for (int kc = 0; kc < nch; ++kc) {
+      pair_stage(t_s, lane, rt);
+      pair_stage(q_s, lane, rq);
+      __syncthreads();
+      if (kc + 1 < nch) {
+        pair_load<false>(A.table, A.ld, tr, kc + 1, lane, rt);
+        pair_load<true>(A.q, A.ld, qr, kc + 1, lane, rq);
+      }
+      const float *a = t_s + lane * kPairLs, *b = q_s + lane * kPairLs;
+#pragma unroll
+      for (int s = 0; s < kPairKC / 8; ++s) {
+        if (kc * kPairKC + 8 * s < A.ld) {                            // wave-uniform: k steps behind the row are skipped
+          const float4 a0 = *reinterpret_cast<const float4 *>(a + 8 * s), a1 = *reinterpret_cast<const float4 *>(a + 8 * s + 4);
+          const float4 b0 = *reinterpret_cast<const float4 *>(b + 8 * s), b1 = *reinterpret_cast<const float4 *>(b + 8 * s + 4);
+          acc = fmaf(a0.x, b0.x, acc); acc = fmaf(a1.x, b1.x, acc);
+          acc = fmaf(a0.y, b0.y, acc); acc = fmaf(a1.y, b1.y, acc);
+          acc = fmaf(a0.z, b0.z, acc); acc = fmaf(a1.z, b1.z, acc);
+          acc = fmaf(a0.w, b0.w, acc); acc = fmaf(a1.w, b1.w, acc);
+        }
+      }
+      __syncthreads();
+    }
+    if (p < A.P) {
+      float sc = -INFINITY;
+      if (valid) {
+        if constexpr (E::kBias) acc += A.bias[tr];
+        sc = E::score(acc);
+        if (sc == 0.0f) sc = 0.0f;                                    // (-0.0 == 0.0, as the keys of the other entry points carry it)
+      }
+      A.out[p] = sc;
+    }
+  }
+}
+
+template <class E>
+int pair_launch(const PairArgs &A, hipStream_t st) {
+  const int64_t groups = (A.P + kWave - 1) / kWave;
+  hipLaunchKernelGGL(k_pair_scores<E>, dim3((unsigned)(groups < kPairMaxGroups ? groups : kPairMaxGroups)), dim3(kWave), 0, st, A);
+  DRX_LAUNCH_CHECK();
+  return DRX_OK;
+}
+
+int pair_run(const float *table, const float *bias, int n_rows, int ld, int epilogue, const float *q, int n_q, const int32_t *q_row,
+             const int32_t *t_row, int64_t P, float *out_score, void *stream) {
+  if (epilogue != DRX_REC_SIGMOID_BIAS && epilogue != DRX_REC_BIAS && epilogue != DRX_REC_CLIP) return DRX_EINVAL;
+  if ((epilogue == DRX_REC_CLIP) != (bias == nullptr)) return DRX_EINVAL;      // the clip has no bias, the other two need one
+  if (ld < 4 || (ld & 3) || P < 0) return DRX_EINVAL;
+  if (P == 0) return DRX_OK;
+  if (!table || !q || !q_row || !t_row || !out_score || n_rows < 1 || n_q < 1) return DRX_EINVAL;
+  PairArgs A;
+  A.table = table; A.bias = bias; A.q = q; A.q_row = q_row; A.t_row = t_row; A.out = out_score;
+  A.n_rows = n_rows; A.n_q = n_q; A.ld = ld; A.P = P;
+  hipStream_t st = (hipStream_t)stream;
+  switch (epilogue) {
+    case DRX_REC_SIGMOID_BIAS: return pair_launch<RecSigmoidBias>(A, st);
+    case DRX_REC_BIAS: return pair_launch<RecBias>(A, st);
+    default: return pair_launch<RecClip>(A, st);
+  }
+}
+
 }  // namespace
 }  // namespace drx
+
+extern "C" int drx_rows_pair_scores(const float *table, const float *bias, int32_t n_rows, int32_t ld, int32_t epilogue, const float *q,
+                                    int32_t n_q, const int32_t *q_row, const int32_t *t_row, int64_t P, float *out_score, void *stream) {
+  return drx::pair_run(table, bias, n_rows, ld, epilogue, q, n_q, q_row, t_row, P, out_score, stream);
+}
 
 extern "C" size_t drx_rows_recommend_scratch_bytes(int32_t R, int32_t n_items, int32_t ld, int32_t n) {
   return drx::rec_scratch_bytes(R, n_items, ld, n);

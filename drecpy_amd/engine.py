@@ -237,6 +237,36 @@ class RowsRecommender:
                                         ptr(sc), sc.numel(), stream_ptr(self.device)), 'drx_rows_rank_lists')
         return out_rank, out_score
 
+    # ---- scores of given (user, item) pairs and nothing else (include/drx.h drx_rows_pair_scores) --------------
+    PAIR_CHUNK_PAIRS = 1 << 20             # pairs per launch: bounds the query rows of a chunk's distinct users
+
+    def _pair_request(self, uids, items):
+        """(uid int32 [P], item int32 [P]) on the device"""
+        uid, item = self._dev_i32(uids).reshape(-1), self._dev_i32(items).reshape(-1)
+        assert uid.numel() == item.numel(), 'pair_scores takes parallel users and items'
+        return uid, item
+
+    def _rows_pair_scores(self, table, bias, ld, epilogue, uid, t_row, rows_of_users, chunk_pairs=None):
+        """`chunk_pairs` pairs at a time: the query rows of the chunk's DISTINCT users once, rows_of_users(distinct uid int32) ->
+        [n, ld] (padding columns ZERO), then one drx_rows_pair_scores against `table` [n_rows, ld] (+ `bias`) at the rows `t_row`
+        (int32 [P]; outside the table: -inf).  Returns a float32 [P] device tensor: for rows of up to 256 floats the values
+        _rows_rank_items reports for the same pairs.  No scratch.  Any pair order; sorted by user the query rows are read from the L1."""
+        L = lib()
+        P = int(uid.numel())
+        chunk = int(chunk_pairs or self.PAIR_CHUNK_PAIRS)
+        assert table.is_contiguous() and table.dim() == 2 and table.shape[1] == ld and t_row.dtype == torch.int32
+        out = torch.empty(P, dtype=torch.float32, device=self.device)
+        for lo in range(0, P, chunk):
+            u, t = uid[lo:lo + chunk], t_row[lo:lo + chunk]
+            p = int(u.numel())
+            distinct, inverse = torch.unique(u, return_inverse=True)
+            q = rows_of_users(distinct.to(torch.int32).contiguous())
+            assert q.is_contiguous() and tuple(q.shape) == (int(distinct.numel()), ld) and q.dtype == torch.float32
+            q_row = inverse.to(torch.int32).contiguous()
+            check(L.drx_rows_pair_scores(ptr(table), ptr(bias), int(table.shape[0]), ld, epilogue, ptr(q), int(q.shape[0]), ptr(q_row), ptr(t), p,
+                                         ptr(out[lo:lo + p]), stream_ptr(self.device)), 'drx_rows_pair_scores')
+        return out
+
     @staticmethod
     def _rows_per_distinct(uid, rows_of_users):
         """Query rows of the pairs `uid`, computed once per distinct user by rows_of_users(distinct uid) and gathered."""
@@ -889,6 +919,13 @@ class CdaeEngine(RowsRecommender):
             return torch.empty(0, dtype=torch.int32, device=self.device), torch.empty(0, dtype=torch.float32, device=self.device)
         return self._rows_rank_items(self.W2T, self.b2, self.ld, _lib.DRX_REC_SIGMOID_BIAS, uid, target, excl,
                                      lambda lo, u: self._rows_per_distinct(u, self._hidden_rows), chunk_rows)
+
+    def pair_scores(self, uids, items, chunk_pairs=None):
+        """float32 [P] device tensor: the score of items[p] for uids[p] and nothing else — two rows per pair, no catalogue walk —,
+        -inf for an item outside the catalogue.  Hidden rows once per distinct user of a chunk; the same table, bias and epilogue as
+        rank_items, and for rows of up to 256 floats its values; wider rows (K = 300) are answered too."""
+        uid, item = self._pair_request(uids, items)
+        return self._rows_pair_scores(self.W2T, self.b2, self.ld, _lib.DRX_REC_SIGMOID_BIAS, uid, item, self._hidden_rows, chunk_pairs)
 
     def rank_ld(self):
         return self.ld

@@ -550,6 +550,22 @@ class CaserEngine(RowsRecommender):
         return self._rows_rank_items(self.W1, self.b1, self.ld2, _lib.DRX_REC_BIAS, uid, target, excl,
                                      lambda lo, u: self._hidden_rows(u, bef[lo:lo + int(u.numel())].contiguous()), chunk_rows)
 
+    def pair_scores(self, uids, before, items, chunk_pairs=None):
+        """float32 [P] device tensor: the logit of items[p] for the (user, last L items) row (uids[p], before[p]) and nothing else, the
+        values rank_items reports; -inf for an item outside the catalogue.  One hidden row per pair, as rank_items: a pair is its
+        own query row (the shared launcher is given the pairs' positions as the rows' names)."""
+        uid, item = self._pair_request(uids, items)
+        P = int(uid.numel())
+        bef = self._dev_i32(before).reshape(P, self.L)
+        if P == 0:
+            return torch.empty(0, dtype=torch.float32, device=self.device)
+        pos = torch.arange(P, dtype=torch.int32, device=self.device)
+
+        def rows_of(d):                                                # (a chunk's distinct positions are the chunk: a slice, no gather)
+            lo = int(d[0])
+            return self._hidden_rows(uid[lo:lo + int(d.numel())], bef[lo:lo + int(d.numel())].contiguous())
+        return self._rows_pair_scores(self.W1, self.b1, self.ld2, _lib.DRX_REC_BIAS, pos, item, rows_of, chunk_pairs)
+
     def rank_ld(self):
         return self.ld2
 

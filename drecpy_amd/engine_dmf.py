@@ -638,6 +638,23 @@ class DmfEngine(RowsRecommender):
         return self._rows_rank_items(table, None, self.W, _lib.DRX_REC_CLIP, uid, target, excl,
                                      lambda lo, u: self._rows_per_distinct(u, lambda d: self._representations(0, d)), chunk_rows)
 
+    def pair_scores(self, uids, items, chunk_pairs=None):
+        """float32 [P] device tensor: max(1e-6, cosine) of every (uids[p], items[p]) — WITHOUT a bound prediction scale —, the values
+        rank_items reports; -inf for an item outside the catalogue.  The item tower runs ONCE over the DISTINCT items of the call (never
+        over the catalogue): their representations are the table, a pair's row its item's position among them; the user tower once
+        per distinct user of a chunk."""
+        uid, item = self._pair_request(uids, items)
+        if int(uid.numel()) == 0:
+            return torch.empty(0, dtype=torch.float32, device=self.device)
+        inside = (item >= 0) & (item < self.N)
+        distinct, t_row = torch.unique(torch.where(inside, item, torch.full_like(item, -1)), return_inverse=True)   # ascending: -1 first
+        outside = int(distinct[0].item() < 0)
+        distinct, t_row = distinct[outside:], (t_row - outside).to(torch.int32).contiguous()                        # (-1: no row)
+        if int(distinct.numel()) == 0:
+            return torch.full((int(uid.numel()),), float('-inf'), dtype=torch.float32, device=self.device)
+        table = self._representations(1, distinct.to(torch.int32).contiguous())
+        return self._rows_pair_scores(table, None, self.W, _lib.DRX_REC_CLIP, uid, t_row, lambda d: self._representations(0, d), chunk_pairs)
+
     def rank_ld(self):
         return self.W
 

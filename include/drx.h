@@ -864,6 +864,24 @@ int drx_rows_rank_lists(const float *table, const float *bias, int32_t n_items, 
                         const int64_t *excl_indptr, const int32_t *excl_indices,
                         int32_t *out_rank, float *out_score, void *scratch, size_t scratch_bytes, void *stream);
 
+/* ---- scores of given (query row, table row) pairs and nothing else: what predict_pairs / predictive_evaluation stand on ---------------
+ *   out_score[p] = epilogue(q[q_row[p], :] . table[t_row[p], :] (+ bias[t_row[p]]))        for p in [0, P)
+ * q_row and t_row index ROWS, not users or items: the caller passes one query row per DISTINCT user (q [n_q, ld]; no [P, ld] gather as
+ * drx_rows_rank_items needs) and may pass a table of the distinct items' rows only (DMF: the item tower never runs over the catalogue).
+ * t_row[p] outside [0, n_rows) or q_row[p] outside [0, n_q) gives -inf.  P == 0 returns DRX_OK and writes nothing; slots from P on are
+ * never written.  No scratch and no atomics: two rows per pair are read, the result is a function of the inputs alone.
+ * One serving arithmetic: for ld <= 256 a pair's score equals, as a float32 value, the out_score drx_rows_rank_items returns for the same
+ * query row and item (and so what drx_rows_recommend lists): the sum starts from 0.0f and takes the columns in steps of 8, within a
+ * step in the order 0, 4, 1, 5, 2, 6, 3, 7, one fmaf each; steps whose first column is >= ld are skipped; then the bias, then the
+ * epilogue; a score of -0.0 is written as +0.0, as the keys of the other entry points carry it.  Above ld = 256 the same chain
+ * continues (the 256-float limit of the matrix-core scorers does not exist here).
+ * Domain: ld % 4 == 0, ld >= 4, any size, else DRX_EINVAL; n_rows, n_q >= 1.  Epilogues, padding columns (ZERO in q and table) and
+ * argument errors as drx_rows_recommend: DRX_EINVAL for an unknown epilogue, a bias with DRX_REC_CLIP, no bias with the other two.
+ * Pairs sorted by q_row read their query rows from the L1; any order gives the same values. */
+int drx_rows_pair_scores(const float *table, const float *bias, int32_t n_rows, int32_t ld, int32_t epilogue,
+                         const float *q, int32_t n_q, const int32_t *q_row, const int32_t *t_row, int64_t P,
+                         float *out_score, void *stream);
+
 /* ---- stable device radix sort of (key, val) pairs (the inverted-index builder of the sparse steps; ties keep their input order).
  * Every key must be < 2^key_bits: the sort runs ceil(key_bits / digit) passes of 8-, 10- or 11-bit digits, i.e. it orders on
  * passes * digit >= key_bits bits — bits above key_bits are NOT ignored (DRX_EINVAL is not raised for them: the result is then ordered

@@ -38,6 +38,17 @@ the engine's chunks of 16 384 rows) and the engine calls, median and min of >= 2
 CDAE, K = 128, at N = 1 M items / R = 16 384 users and at the ml-1m shape (N = 3706, R = 6040); with --model the hook
 _catalogue_ranks of the fitted ml-1m-shaped model with the routing forced either way.  Writes the smallest T from which on the list
 form is faster at both shapes by more than the spread of the two series (RowsRecommender.RANK_LISTS_MIN_MEAN).
+
+    python scripts/recommend_bench.py --pairs [--model dmf] [--out profiles/pair_scores.json] [--items 1000000] [--quick]
+
+Scores of given (user, item) pairs and nothing else (pair_scores: drx_rows_pair_scores, two rows per pair) beside the only batched route
+to the same scores there was before it, rank_items(..., exclude=False) on the same pairs (a 128-item block per target and a counting
+walk of the catalogue per pair), and beside one prediction per call on 64 pairs (CDAE: the work of CDAE._predict, a forward over the
+catalogue and the row copied to the host; --model dmf: DMF._predict of the fitted model).  CDAE, K = 128, at the ml-1m shape (6040 x
+3706) and at --items; P = 4096, 65 536 and 1 048 576 pairs sorted by user, about 160 per user.  Warm-up, then repeated timed calls:
+median and min (the spread) of each series; the kernel alone (events around the library call on prepared query rows) with its
+achieved GB/s against P x (ld x 4 + 12) bytes plus the distinct query rows.  Writes where pair_scores is slower than rank_items
+(nowhere is the gate) and where it is closer than 10x.
 """
 import argparse
 import faulthandler
@@ -501,6 +512,123 @@ def ranks_model_main(a):
     write_result(res, a.out)
 
 
+def series_ms(fn, reps, warm=2):
+    """-> {device / wall: median_ms, min_ms, max_ms} of fn() -> a device tensor (or a tuple of them), the last one copied to the host"""
+    runs = []
+    for j in range(warm + reps):
+        e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+        torch.cuda.synchronize()
+        t0 = time.perf_counter()
+        e0.record()
+        out = fn()
+        e1.record()
+        (out[-1] if isinstance(out, tuple) else out).cpu()
+        wall = (time.perf_counter() - t0) * 1e3
+        if j >= warm:
+            runs.append((e0.elapsed_time(e1), wall))
+    return {name: {'median_ms': median([r[j] for r in runs]), 'min_ms': min(r[j] for r in runs), 'max_ms': max(r[j] for r in runs)}
+            for j, name in enumerate(('device', 'wall'))} | {'reps': reps}
+
+
+def pairs_of(rng, users, n_items, P, per_user=160):
+    """P pairs sorted by user (as predict_pairs hands them over): about `per_user` random items for each of P / per_user users"""
+    n_u = min(len(users), max(1, P // per_user))
+    uid = np.sort(rng.choice(users, size=n_u, replace=False)[rng.integers(0, n_u, P)])
+    return uid.astype(np.int32), rng.integers(0, n_items, P).astype(np.int32)
+
+
+def pairs_shape(a, eng, pair_scores, rank_items, kernel_of, one_prediction, users, n_items, ld):
+    """one shape: the three routes at every P; kernel_of(uid, items) -> (a function launching the library call alone, distinct query rows)"""
+    dev = eng.device
+    rng = np.random.default_rng(0)
+    out = {}
+    for P in (4096, 65536) + (() if a.quick else (1 << 20,)):
+        uid, items = pairs_of(rng, users, n_items, P)
+        d_uid, d_items = torch.as_tensor(uid).to(dev), torch.as_tensor(items).to(dev)
+        row = {'pairs': P, 'distinct_users': int(len(np.unique(uid))), 'distinct_items': int(len(np.unique(items)))}
+        with step(900):
+            row['pair_scores'] = series_ms(lambda: pair_scores(d_uid, d_items), 5 if a.quick else 20)
+            row['rank_items'] = series_ms(lambda: rank_items(d_uid, d_items), 2 if a.quick else (3 if P > 65536 else 10), warm=1)
+            row['equal_scores'] = bool(torch.equal(pair_scores(d_uid, d_items), rank_items(d_uid, d_items)[1]))
+            launch, n_q = kernel_of(d_uid, d_items)
+            burst = max(1, (1 << 20) // P)                             # back-to-back launches per event pair: a short kernel is not timed alone
+
+            def launches():
+                for _ in range(burst):
+                    launch()
+            k = spread_ms(launches, 5 if a.quick else 30)
+            k = {'median_ms': k['median_ms'] / burst, 'min_ms': k['min_ms'] / burst, 'reps': k['reps'], 'launches_per_timing': burst}
+            nbytes = P * (ld * 4 + 12) + n_q * ld * 4
+            row['kernel'] = k | {'bytes': nbytes, 'gb_per_s': nbytes / (k['median_ms'] * 1e-3) / 1e9,
+                                 'bytes_are': 'P x (ld x 4 + 12) + distinct query rows x ld x 4: a table row, two indices and a score per pair, '
+                                              'whether or not the row was already in a cache'}
+        row['rank_items_over_pair_scores'] = {s: row['rank_items'][s]['median_ms'] / row['pair_scores'][s]['median_ms'] for s in ('device', 'wall')}
+        out[str(P)] = row
+        print(P, json.dumps(row), flush=True)
+    sel = rng.integers(0, len(uid), 64)
+    with step(600):
+        for j in sel[:3]:
+            one_prediction(int(uid[j]), int(items[j]))
+        torch.cuda.synchronize()
+        t0 = time.perf_counter()
+        for j in sel:
+            one_prediction(int(uid[j]), int(items[j]))
+        out['one_prediction_per_call'] = {'pairs': 64, 'wall_ms_per_pair': (time.perf_counter() - t0) * 1e3 / 64}
+    return out
+
+
+def pairs_main(a):
+    """--pairs: pair_scores beside rank_items(exclude=False) on the same pairs and beside one prediction per call"""
+    from drecpy_amd import _lib
+    L = _lib.lib()
+    res = {'k': a.k, 'model': a.model, 'pairs_per_user': 160,
+           'timed': 'engine.pair_scores(uids, items) and engine.rank_items(uids, items, exclude=False) on the same device ids, sorted by user, '
+                    'the scores copied to the host: device = events around the call, wall = host clock to the copy; kernel = events around '
+                    'drx_rows_pair_scores alone on prepared query rows; median, min and max over the repetitions after warm-up',
+           'shapes': {}}
+    if a.model == 'cdae':
+        for name, U, N in (('ml-1m', 6040, 3706), (f'{a.items} items', a.users, a.items)):
+            with step(300):
+                eng, _, _ = cdae_engine(U, N, a.k)
+
+            def kernel_of(d_uid, d_items, eng=eng):
+                distinct, inverse = torch.unique(d_uid, return_inverse=True)
+                q, q_row = eng._hidden_rows(distinct.to(torch.int32).contiguous()), inverse.to(torch.int32).contiguous()
+                out = torch.empty(d_uid.numel(), dtype=torch.float32, device=eng.device)
+                return (lambda: _lib.check(L.drx_rows_pair_scores(
+                    _lib.ptr(eng.W2T), _lib.ptr(eng.b2), eng.n_items, eng.ld, _lib.DRX_REC_SIGMOID_BIAS, _lib.ptr(q), int(q.shape[0]), _lib.ptr(q_row),
+                    _lib.ptr(d_items), int(d_uid.numel()), _lib.ptr(out), _lib.stream_ptr(eng.device)), 'drx_rows_pair_scores')), int(q.shape[0])
+
+            def one_prediction(uid, iid, eng=eng):                    # what CDAE._predict runs for one pair
+                return eng.forward(np.array([uid], dtype=np.int32))[1][0].cpu().numpy()[iid]
+            res['shapes'][name] = {'n_users': U, 'n_items': N} | pairs_shape(
+                a, eng, eng.pair_scores, lambda u, i, eng=eng: eng.rank_items(u, i, exclude=False), kernel_of, one_prediction, np.arange(U), N, eng.ld)
+            del eng
+            torch.cuda.empty_cache()
+    else:
+        assert a.model == 'dmf', '--pairs: cdae or dmf (Caser has no point predictions)'
+        m, users = fitted_ml1m('dmf')
+        eng = m._engine
+
+        def kernel_of(d_uid, d_items):
+            distinct, inverse = torch.unique(d_uid, return_inverse=True)
+            d_it, t_row = torch.unique(d_items, return_inverse=True)
+            q, table = eng._representations(0, distinct.to(torch.int32).contiguous()), eng._representations(1, d_it.to(torch.int32).contiguous())
+            q_row, t_row = inverse.to(torch.int32).contiguous(), t_row.to(torch.int32).contiguous()
+            out = torch.empty(d_uid.numel(), dtype=torch.float32, device=eng.device)
+            return (lambda: _lib.check(L.drx_rows_pair_scores(
+                _lib.ptr(table), None, int(table.shape[0]), eng.W, _lib.DRX_REC_CLIP, _lib.ptr(q), int(q.shape[0]), _lib.ptr(q_row), _lib.ptr(t_row),
+                int(d_uid.numel()), _lib.ptr(out), _lib.stream_ptr(eng.device)), 'drx_rows_pair_scores')), int(q.shape[0])
+        res['shapes']['ml-1m'] = {'n_users': int(m.n_users), 'n_items': int(m.n_items)} | pairs_shape(
+            a, eng, eng.pair_scores, lambda u, i: eng.rank_items(u, i, exclude=False), kernel_of, m._predict, users, int(m.n_items), eng.W)
+    rows = [(name, P, r) for name, s in res['shapes'].items() for P, r in s.items() if isinstance(r, dict) and 'pair_scores' in r]
+    res['pair_scores_slower_than_rank_items_at'] = [[name, int(P)] for name, P, r in rows if min(r['rank_items_over_pair_scores'].values()) < 1.0]
+    res['closer_than_10x_at'] = [[name, int(P), r['rank_items_over_pair_scores']] for name, P, r in rows
+                                 if min(r['rank_items_over_pair_scores'].values()) < 10.0]
+    res['all_equal_scores'] = all(r['equal_scores'] for _, _, r in rows)
+    write_result(res, a.out)
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument('--out', default=None)
@@ -513,7 +641,11 @@ def main():
     ap.add_argument('--ranks', action='store_true', help='rank_items beside recommend at the same R (default --out profiles/rank_items.json)')
     ap.add_argument('--targets', default=None, help='with --ranks: T1,T2,...: the same R x T pairs through rank_items and rank_lists '
                                                     '(default --out profiles/rank_lists.json)')
+    ap.add_argument('--pairs', action='store_true', help='pair_scores beside rank_items on the same pairs (default --out profiles/pair_scores.json)')
     a = ap.parse_args()
+    if a.pairs:
+        a.out = a.out or os.path.join('profiles', 'pair_scores.json' if a.model == 'cdae' else f'pair_scores_{a.model}.json')
+        return pairs_main(a)
     if a.ranks and a.targets:
         a.out = a.out or os.path.join('profiles', 'rank_lists.json' if a.model == 'cdae' else f'rank_lists_{a.model}.json')
         return rank_lists_main(a) if a.model == 'cdae' else rank_lists_model_main(a)
