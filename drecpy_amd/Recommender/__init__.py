@@ -4,6 +4,7 @@ from .caser import Caser
 from .dmf import DMF
 from .early_stopping import EarlyStoppingRuleABC, MaxValidationValueRule
 from .trainables import TrainableLayer, TrainableModel, Variable
+from . import Baseline
 
-__all__ = ['RecommenderABC', 'CDAE', 'Caser', 'DMF', 'EarlyStoppingRuleABC', 'MaxValidationValueRule', 'Variable',
+__all__ = ['RecommenderABC', 'CDAE', 'Caser', 'DMF', 'Baseline', 'EarlyStoppingRuleABC', 'MaxValidationValueRule', 'Variable',
            'TrainableLayer', 'TrainableModel']

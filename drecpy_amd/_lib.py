@@ -25,6 +25,11 @@ class DrxError(RuntimeError):
 # epilogues of drx_rows_recommend (include/drx.h DRX_REC_*)
 DRX_REC_SIGMOID_BIAS, DRX_REC_BIAS, DRX_REC_CLIP = 0, 1, 2
 
+# drx_knn_* (include/drx.h DRX_KNN_*): similarity metrics, table types, aggregations
+KNN_METRICS = {'cosine': 0, 'adjusted_cosine': 1, 'cosine_cf': 2, 'jaccard': 3, 'msd': 4, 'pearson': 5}
+KNN_USER, KNN_ITEM = 0, 1
+KNN_AGGREGATIONS = {'mean': 0, 'weighted_mean': 1}
+
 
 class CdaeParams(C.Structure):
     _fields_ = [('n_users', C.c_int32), ('n_items', C.c_int32), ('k', C.c_int32), ('ld', C.c_int32),
@@ -283,6 +288,16 @@ SIGNATURES = {
                                       C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p]),
     'drx_rows_pair_scores': (C.c_int, [C.c_void_p, C.c_void_p, C.c_int32, C.c_int32, C.c_int32, C.c_void_p, C.c_int32, C.c_void_p, C.c_void_p,
                                        C.c_int64, C.c_void_p, C.c_void_p]),
+    'drx_knn_neighbours_scratch_bytes': (C.c_size_t, [C.c_int32, C.c_int32, C.c_int32, C.c_int32]),
+    'drx_knn_neighbours': (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_int32,
+                                     C.c_double, C.c_double, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p]),
+    'drx_knn_row_means': (C.c_int, [C.c_void_p, C.c_void_p, C.c_int64, C.c_int32, C.c_void_p, C.c_void_p]),
+    'drx_knn_score_rows_scratch_bytes': (C.c_size_t, [C.c_int32, C.c_int32, C.c_int32]),
+    'drx_knn_score_rows': (C.c_int, [C.c_int32, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64, C.c_int32, C.c_int32, C.c_void_p,
+                                     C.c_void_p, C.c_int32, C.c_void_p, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_size_t,
+                                     C.c_void_p]),
+    'drx_knn_pair_scores': (C.c_int, [C.c_int32, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64, C.c_int32, C.c_int32, C.c_void_p,
+                                      C.c_void_p, C.c_int32, C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
     'drx_idmap_scratch_bytes': (C.c_size_t, [C.c_int64]),
     'drx_idmap_build': (C.c_int, [C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p,
                                   C.c_size_t, C.c_void_p]),

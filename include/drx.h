@@ -882,6 +882,71 @@ int drx_rows_pair_scores(const float *table, const float *bias, int32_t n_rows, 
                          const float *q, int32_t n_q, const int32_t *q_row, const int32_t *t_row, int64_t P,
                          float *out_score, void *stream);
 
+/* ---- UserKNN / ItemKNN baselines (DRecPy/Recommender/Baseline: base_knn.py, similarity.py, aggregation.py) ---------------------------
+ * X is the [R, C] rating matrix in the orientation being compared (UserKNN: users x items; ItemKNN: items x users), given as a CSR:
+ * indptr int64 [R + 1], columns int32 ascending and unique per row, float values, nnz entries; an entry of value 0 or with a column
+ * outside [0, C) counts as absent, offsets are clamped into [0, nnz].  With M = (X != 0), a row pair's sums over its common columns
+ *   n = sum 1, Sxy = sum x y, Sx = sum x, Sy = sum y, Sxx = sum x^2, Syy = sum y^2          (x: the row with the SMALLER id)
+ * are fp32 products on the matrix cores (v_mfma_f32_32x32x2_f32: a k-ordered fmaf chain, exact for integer ratings below 2^24), and
+ * per row cnt, mean, full2 = sum x^2 and c2 = sum (x - mean)^2 are sequential double sums in CSR order.  The similarity is computed in
+ * double, single operations in this order (no contraction), and the pair is DROPPED where stated:
+ *   DRX_KNN_COSINE           Sxy / (sqrt(full2_x) * sqrt(full2_y))
+ *   DRX_KNN_ADJUSTED_COSINE  (((Sxy - mean_y * Sx) - mean_x * Sy) + (n * mean_x) * mean_y) / (sqrt(c2_x) * sqrt(c2_y));  denominator == 0
+ *   DRX_KNN_COSINE_CF        Sxy / (sqrt(Sxx) * sqrt(Syy));                                                              Sxy == 0
+ *   DRX_KNN_JACCARD          n / ((cnt_x + cnt_y) - n)
+ *   DRX_KNN_MSD              1 - (((Sxx + Syy) - 2 * Sxy) / (max_diff * max_diff)) / n
+ *   DRX_KNN_PEARSON          (Sxy - (Sx * Sy) / n) / (sqrt(vx) * sqrt(vy)), vx = Sxx - (Sx * Sx) / n, vy likewise;    vx <= 0 or vy <= 0
+ * always when n == 0, and when m > 0 and n < m.  Then s = s * (n / ((n + shrinkage) + 1e-6)) unless shrinkage < 0 (none), and s is
+ * rounded to float32 once.  The neighbours of row i are the k largest among the rows j != i with s > 0 in heapq.nlargest((s, j)) order
+ * (descending s, ties to the larger id): out_idx / out_sim [R, k], -1 / 0 behind the last neighbour.  sim(i, j) == sim(j, i) bit for bit.
+ * No [R, R] matrix is written; the scratch holds the dense X (R up to 128 x C up to 8 floats: the caller bounds it), the row statistics
+ * and candidate keys.  No atomics, fixed summation order: the result is a function of the inputs alone, the same for every `splits`
+ * (0: chosen to fill the chip; > 0: that many J ranges per row tile at most, for tests of the merge).
+ * Domain: 1 <= k <= 128, m >= 0, C >= 1, max_diff > 0 for DRX_KNN_MSD, else DRX_EINVAL; R == 0 returns DRX_OK and writes nothing. */
+#define DRX_KNN_COSINE          0
+#define DRX_KNN_ADJUSTED_COSINE 1
+#define DRX_KNN_COSINE_CF       2
+#define DRX_KNN_JACCARD         3
+#define DRX_KNN_MSD             4
+#define DRX_KNN_PEARSON         5
+#define DRX_KNN_USER            0   /* neighbour table over users  */
+#define DRX_KNN_ITEM            1   /* neighbour table over items  */
+#define DRX_KNN_MEAN            0   /* sum r / count               */
+#define DRX_KNN_WEIGHTED_MEAN   1   /* sum s r / sum s             */
+size_t drx_knn_neighbours_scratch_bytes(int32_t R, int32_t C, int32_t k, int32_t splits);
+int drx_knn_neighbours(const int64_t *indptr, const int32_t *indices, const float *values, int64_t nnz, int32_t R, int32_t C,
+                       int32_t metric, int32_t k, int32_t m, double shrinkage, double max_diff, int32_t splits,
+                       int32_t *out_idx, float *out_sim, void *scratch, size_t scratch_bytes, void *stream);
+
+/* out_mean[r] = the mean of ALL entries of CSR row r (a sequential double sum in CSR order / the count), 0 for an empty row: the
+ * fallback of use_averages (the user's mean for ItemKNN, the item's for UserKNN on the transposed CSR). */
+int drx_knn_row_means(const int64_t *indptr, const float *values, int64_t nnz, int32_t R, double *out_mean, void *stream);
+
+/* Predictions from a neighbour table (nb_idx / nb_sim [n_users or n_items, k] as drx_knn_neighbours writes them) and the USER-major CSR
+ * of the ratings (indptr [n_users + 1], columns ascending), whatever the type.  The terms are taken in neighbour-list order among the
+ * entries whose interaction exists — DRX_KNN_ITEM: the neighbours of the item that the user rated; DRX_KNN_USER: the neighbours of
+ * the user that rated the item — and summed in double, single operations: weighted mean num += s * r, den += s; mean num += r,
+ * den += 1; the prediction is num / den in the raw rating scale, and there is NONE where there is no term (and no fallback).
+ * drx_knn_score_rows: for the R users uid[r] every item's prediction, rounded to float32 once, out [R, n_items] (0 where none);
+ *   cand_mask (optional, drx_topk's layout: bit r * n_items + i) is in/out: the bit is cleared where the model has no prediction.
+ *   fallback (optional, DRX_KNN_ITEM only, [n_users], read at uid[r]): the row's prediction where it has no term (use_averages: the
+ *   users' means, the array drx_knn_pair_scores takes).
+ *   One workgroup per user; its row lives in LDS, or in the scratch (drx_knn_score_rows_scratch_bytes, 0 while it fits) when
+ *   n_items floats (ITEM) / 2 n_items doubles (USER) exceed 160 KiB.  R * n_items < 2^31 (drx_topk reads the matrix).
+ * drx_knn_pair_scores: the same for P given pairs, out double [P] (0 where none) and none uint8 [P]; the interaction lookup is a
+ *   binary search in the CSR row; fallback (optional) is indexed by the USER for DRX_KNN_ITEM (user means) and by the ITEM for
+ *   DRX_KNN_USER (item means).  A user or item outside the model: none.
+ * Argument errors DRX_EINVAL; R == 0 / P == 0 return DRX_OK and write nothing. */
+size_t drx_knn_score_rows_scratch_bytes(int32_t type, int32_t R, int32_t n_items);
+int drx_knn_score_rows(int32_t type, int32_t aggregation, const int64_t *indptr, const int32_t *indices, const float *values, int64_t nnz,
+                       int32_t n_users, int32_t n_items, const int32_t *nb_idx, const float *nb_sim, int32_t k,
+                       const int32_t *uid, int32_t R, const double *fallback, float *out, uint32_t *cand_mask,
+                       void *scratch, size_t scratch_bytes, void *stream);
+int drx_knn_pair_scores(int32_t type, int32_t aggregation, const int64_t *indptr, const int32_t *indices, const float *values, int64_t nnz,
+                        int32_t n_users, int32_t n_items, const int32_t *nb_idx, const float *nb_sim, int32_t k,
+                        const int32_t *uid, const int32_t *iid, int64_t P, const double *fallback, double *out, uint8_t *none,
+                        void *stream);
+
 /* ---- stable device radix sort of (key, val) pairs (the inverted-index builder of the sparse steps; ties keep their input order).
  * Every key must be < 2^key_bits: the sort runs ceil(key_bits / digit) passes of 8-, 10- or 11-bit digits, i.e. it orders on
  * passes * digit >= key_bits bits — bits above key_bits are NOT ignored (DRX_EINVAL is not raised for them: the result is then ordered
