@@ -1068,6 +1068,47 @@ int drx_cdae_sparse_prepare_hot(const DrxCdaeParams *p, const DrxHistory *hist, 
   return DRX_OK;
 }
 
+// (include/drx.h: the first two launches of a preparation — touch kernel, then the sort's counting launch or its fold — and copies of
+// what they leave, for a test to read before a sort trusts it)
+int drx_debug_prep_counts(const DrxCdaeParams *p, const DrxHistory *hist, const DrxBatch *bt, const DrxHotHead *hot, uint8_t *present,
+                          int32_t ipr, int32_t cshift, int32_t world, void *prepared, size_t prepared_bytes, uint32_t *hist_out,
+                          uint32_t *buckets_out, uint32_t *keys_out, uint32_t *vals_out, uint32_t *mask_out, int32_t *info_out,
+                          void *stream) {
+  int rc = check_params(p);
+  if (rc) return rc;
+  rc = check_batch(hist, bt);
+  if (rc || !prepared || !bt->iid || !bt->keep_off || !hist_out || !buckets_out || !keys_out || !vals_out || !info_out) return DRX_EINVAL;
+  if ((uint64_t)2 * p->n_items + p->n_users + 1 >= 0xFFFFFFFFull) return DRX_EINVAL;
+  if (hot && !hot_ok(p, hot)) return DRX_EINVAL;
+  if (present && (ipr < 1 || cshift < 0 || cshift > 30 || world < 1)) return DRX_EINVAL;
+  const int H = hot ? hot->H : 0;
+  if (H > 0 && !mask_out) return DRX_EINVAL;
+  Carver cp(prepared, prepared_bytes);
+  const PrepBufs R = prep_layout(cp, *p, bt->B, bt->n_touch_slots, H);
+  if (!cp.ok()) return DRX_ESCRATCH;
+  if (H > 0 && !hot_list_fits(R.T, *p, present != nullptr)) return DRX_EINVAL;
+  hipStream_t st = (hipStream_t)stream;
+  hot_record(prepared, 0);                                           // (no list stands in this buffer)
+  launch_touches(p, hist, bt, R, st, TouchPresence{present, WireGeo{present ? ipr : 1, present ? cshift : 0, present ? world : 1}},
+                 H > 0 ? hot->slot : nullptr, H > 0 ? hot->item : nullptr);
+  const SortRider rider{bt->keep_off, bt->B, R.order_work, R.partials, R.partial_rows};
+  const uint32_t *h = nullptr;
+  rc = sort_first_counts(R.sort_temp, R.sort_bytes, R.keys, (size_t)R.T, R.bits, true, st, rider, &h);
+  if (rc) return rc;
+  const int dbits = sort_first_digit_bits(R.bits);
+  DRX_HIP(hipMemcpyAsync(hist_out, h, sizeof(uint32_t) << dbits, hipMemcpyDeviceToDevice, st));
+  DRX_HIP(hipMemcpyAsync(buckets_out, R.order_work, 256 * sizeof(uint32_t), hipMemcpyDeviceToDevice, st));
+  DRX_HIP(hipMemcpyAsync(keys_out, R.keys, (size_t)R.T * sizeof(uint32_t), hipMemcpyDeviceToDevice, st));
+  DRX_HIP(hipMemcpyAsync(vals_out, R.vals, (size_t)R.T * sizeof(uint32_t), hipMemcpyDeviceToDevice, st));
+  if (H > 0) DRX_HIP(hipMemcpyAsync(mask_out, R.hmask, (size_t)H * R.Bw * sizeof(uint32_t), hipMemcpyDeviceToDevice, st));
+  info_out[0] = dbits;
+  info_out[1] = R.partials ? R.partial_rows : 0;
+  info_out[2] = R.T;
+  info_out[3] = DRX_PREP_ROUNDS ? touch_grid(bt->B) : (bt->B + 15) / 16;
+  DRX_LAUNCH_CHECK();
+  return DRX_OK;
+}
+
 int drx_cdae_step_sparse_hot(const DrxCdaeParams *p, const DrxOptim *opt, const DrxHistory *hist, const DrxBatch *bt,
                              const DrxHotHead *hot, int32_t loss_kind, const void *prepared, size_t prepared_bytes, void *scratch,
                              size_t scratch_bytes, float *loss_out, void *const *events, void *stream) {

@@ -184,13 +184,27 @@ struct SortRider {
   const int32_t *keep_off;
   int B;
   unsigned int *counts;      // [256], zero on entry
+  // PARTIAL COUNTS (or nullptr): the caller's own kernel — the one that wrote the keys (drx_prep.hpp k_sparse_touches_rounds) — has
+  // already counted, per workgroup, the first digit of every key that is not DRX_KEY_NONE and the degree bucket of its samples:
+  // partial_rows rows of kPartialWords words, [0, 256) the digit counts, [256, 512) the bucket counts.  The sort's first launch is
+  // then a FOLD of those rows (a handful of workgroups) instead of a pass over the keys (hundreds).  Plans whose first digit is 8
+  // bits wide and drop_none only (sort_first_digit_bits): counts of another width are refused, DRX_EINVAL.
+  const uint32_t *partials = nullptr;
+  int partial_rows = 0;
 };
+constexpr int kPartialWords = 512;
+// digit width of the first pass of a sort on end_bit bits (drx_sort.hip sort_plan)
+int sort_first_digit_bits(int end_bit);
 
 // pre_zeroed: the caller has already cleared the words sort_pairs_zero_region names (a kernel of its own that runs before the sort
 // anyway: one launch less on the stream).
 int sort_pairs_ex(void *temp, size_t temp_bytes, const uint32_t *kin, uint32_t *kout, const uint32_t *vin, uint32_t *vout, size_t n, int end_bit,
                   bool drop_none, hipStream_t stream, bool pre_zeroed = false, SortRider rider = SortRider{nullptr, 0, nullptr});
 void sort_pairs_zero_region(void *temp, size_t n, int end_bit, uint32_t **words, size_t *n_words);
+// The sort's FIRST launch alone (the counting launch, or the fold of the rider's partial counts) on a pre-zeroed temp: what a test reads
+// before a sort trusts it (drx_debug_prep_counts).  *hist = the first digit's global histogram, 2^sort_first_digit_bits words.
+int sort_first_counts(void *temp, size_t temp_bytes, const uint32_t *kin, size_t n, int end_bit, bool drop_none, hipStream_t stream,
+                      SortRider rider, const uint32_t **hist);
 
 inline int bits_for(uint64_t max_key_exclusive) {
   int b = 1;

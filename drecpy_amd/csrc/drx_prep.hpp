@@ -144,6 +144,180 @@ static __global__ __launch_bounds__(kBlock) void k_sparse_touches(int n_items, D
   }
 }
 
+// The same list BY ROUNDS on a bounded grid, with the counts its consumers need (DRX_PREP_ROUNDS=0, a variant build, keeps the kernel
+// above and the sort's counting launch).  Round r = samples 16 r .. 16 r + 15, 16 lanes per sample; a workgroup strides over the
+// rounds of the batch.  What changes against one workgroup per round:
+//   - the hot table is cleared and built ONCE per workgroup (it was 4096 builds of the same 256 entries at B = 65 536); only the mask
+//     words hm[] are per round — round r still owns half-word column r of every mask row and stores all H of them, zeros included, and
+//     whoever handles the last round writes the odd tail's zero half-word: masks, keys and vals are bit-identical to the kernel above;
+//   - what the coming rounds depend on is loaded ahead, three stages deep (the uid three rounds ahead, its keep_off / indptr / iid
+//     words two, each lane's first two items one), so that a round waits for no load of its own instead of walking the three-deep
+//     chain uid -> indptr -> indices eight times;
+//   - while it writes keys it counts the sort's first digit (8 bits) of every key that is not DRX_KEY_NONE — lane 0's two keys for the
+//     output row and the user row included — in LDS counters replicated 8 times as k_digit_histograms' (drx_sort.hip), and the
+//     degree_bucket of each of its samples; a workgroup ends by STORING its counts into row blockIdx.x of `part` (kPartialWords words:
+//     digits | buckets).  No global atomics: the histogram words and order_work are zeroed by this very launch, and an add from one
+//     workgroup could land before another's zeroing store.  The sort's first launch folds the rows (SortRider::partials).
+//     part == nullptr (a plan whose first digit is not 8 bits wide): nothing is counted, the sort counts for itself.
+#ifndef DRX_PREP_ROUNDS
+#define DRX_PREP_ROUNDS 1
+#endif
+// workgroups of the launch (-DDRX_TOUCH_GRID=n builds a variant): in the order of the sort's own grid — both run beside the training
+// kernels and ask for room on the same CUs.  A round takes one memory latency whatever is prefetched, so the launch takes about
+// rounds per workgroup x 3.5 us alone (256 / 512 / 1024 workgroups at B = 65 536: - / 30.2 / 24.4 us; one workgroup per round, the
+// kernel above: 21.2) and less of the chip the smaller it is.  The step beside it, ms, 256 / 512 / 1024 / 2048 workgroups, four
+// rounds of runs on one box: 0.3107 0.3084 0.3025 0.3038 | 0.3097 0.3075 0.3056 0.3038 | 0.3100 0.3084 0.3051 0.3062 | 0.3112 0.3082
+// 0.3052 0.3093: 1024.
+#ifndef DRX_TOUCH_GRID
+#define DRX_TOUCH_GRID 1024
+#endif
+static inline int touch_grid(int B) {
+  const int rounds = (B + kBlock / 16 - 1) / (kBlock / 16);
+  return rounds < DRX_TOUCH_GRID ? rounds : DRX_TOUCH_GRID;
+}
+
+static __global__ __launch_bounds__(kBlock) void k_sparse_touches_rounds(int n_items, DrxHistory H, DrxBatch bt, uint32_t qthr, uint32_t *keys,
+                                                                  uint32_t *vals, int T, uint8_t *solo, uint32_t *zero_a,
+                                                                  int n_zero_a, uint32_t *zero_b, int n_zero_b, uint32_t *zero_c,
+                                                                  int n_zero_c, TouchPresence pres, HotMark hot, uint32_t *part) {
+  constexpr int G = 16, SPR = kBlock / G;                          // samples per round
+  const int lane = threadIdx.x % G, grp = threadIdx.x / G;
+  const int B = bt.B, n_rounds = (B + SPR - 1) / SPR, stride = (int)gridDim.x;
+  for (int w = blockIdx.x * kBlock + threadIdx.x; w < n_zero_a; w += gridDim.x * kBlock) zero_a[w] = 0u;
+  for (int w = blockIdx.x * kBlock + threadIdx.x; w < n_zero_b; w += gridDim.x * kBlock) zero_b[w] = 0u;
+  for (int w = blockIdx.x * kBlock + threadIdx.x; w < n_zero_c; w += gridDim.x * kBlock) zero_c[w] = 0u;
+  __shared__ uint32_t hm[DRX_MAX_HOT];
+  __shared__ uint32_t dh[2048];                                    // [256 digits][8 replicas]
+  __shared__ uint32_t bh[256];
+  extern __shared__ __align__(16) int hot_table[];                // [2^tbits] items (-1: free), then [2^tbits] uint16 slots
+  const uint32_t tmask = (1u << hot.tbits) - 1u;
+  uint16_t *const hot_slot_of = reinterpret_cast<uint16_t *>(hot_table + tmask + 1);
+  if (part) {
+    for (int i = threadIdx.x; i < 2048; i += kBlock) dh[i] = 0u;
+    for (int i = threadIdx.x; i < 256; i += kBlock) bh[i] = 0u;
+  }
+  if (hot.slot) {                                                  // (workgroup-uniform)
+    for (int i = threadIdx.x; i < hot.H; i += kBlock) hm[i] = 0u;
+    if (DRX_HOT_LDS_LOOKUP) {
+      for (int i = threadIdx.x; i <= (int)tmask; i += kBlock) hot_table[i] = -1;
+      __syncthreads();
+      for (int i = threadIdx.x; i < hot.H; i += kBlock) {
+        const int it = hot.item[i];
+        uint32_t at = hot_table_home(it, hot.tbits);
+        while (atomicCAS(&hot_table[at], -1, it) != -1) at = (at + 1u) & tmask;      // (at most H of >= 4 H entries are ever taken)
+        hot_slot_of[at] = (uint16_t)i;
+      }
+    }
+  }
+  __syncthreads();
+  const uint32_t rep = threadIdx.x & 7u;
+  // The pipeline's registers, three stages deep so that a round waits for no load of its own (alone, with one stage, a round took
+  // 4.7 us: its two dependent rounds of loads, and every workgroup does eight rounds):
+  //   this round        (u, keep_off[b], keep_off[b + 1], indptr[u], indptr[u + 1], iid[b]) and each lane's first kPre items
+  //   the next round    the same words, loaded a round ago; its items are loaded while this round runs
+  //   the round after   its uid, loaded a round ago; its words are loaded while this round runs
+  //   the one behind    its uid is loaded while this round runs
+  constexpr int kPre = 2;                                          // items per lane held ahead: histories of up to 32 entries
+  struct Stage { int u, ko0, ko1, iid; int64_t s, e; };
+  const int S = stride * SPR;                                      // samples between two rounds of a workgroup
+  int r = (int)blockIdx.x;                                         // (r < n_rounds: the grid has at most n_rounds workgroups)
+  int b = r * SPR + grp;
+  Stage c{0, 0, 0, 0, 0, 0}, n1 = c;
+  int it[kPre], u2 = 0;
+  if (b < B) { c.u = bt.uid[b]; c.ko0 = bt.keep_off[b]; c.ko1 = bt.keep_off[b + 1]; c.iid = bt.iid[b]; c.s = H.indptr[c.u]; c.e = H.indptr[c.u + 1]; }
+  if (b + S < B) {
+    n1.u = bt.uid[b + S]; n1.ko0 = bt.keep_off[b + S]; n1.ko1 = bt.keep_off[b + S + 1]; n1.iid = bt.iid[b + S];
+    n1.s = H.indptr[n1.u]; n1.e = H.indptr[n1.u + 1];
+  }
+  if (b + 2 * S < B) u2 = bt.uid[b + 2 * S];
+#pragma unroll
+  for (int k = 0; k < kPre; ++k) it[k] = c.s + lane + k * G < c.e ? H.indices[c.s + lane + k * G] : 0;
+  for (; r < n_rounds; r += stride, b += S) {
+    // ---- ahead: the next round's items, the words of the round after it, the uid of the one behind (all addresses are known) ----
+    int itn[kPre], u3 = 0;
+    Stage n2{u2, 0, 0, 0, 0, 0};
+#pragma unroll
+    for (int k = 0; k < kPre; ++k) itn[k] = n1.s + lane + k * G < n1.e ? H.indices[n1.s + lane + k * G] : 0;
+    if (b + 2 * S < B) {
+      n2.ko0 = bt.keep_off[b + 2 * S]; n2.ko1 = bt.keep_off[b + 2 * S + 1]; n2.iid = bt.iid[b + 2 * S];
+      n2.s = H.indptr[u2]; n2.e = H.indptr[u2 + 1];
+    }
+    if (b + 3 * S < B) u3 = bt.uid[b + 3 * S];
+    // ---- round r ----
+    if (b < B) {
+      const int u = c.u, ko0 = c.ko0, ko1 = c.ko1;
+      const int64_t s = c.s, e = c.e;
+      if (solo && lane == 0) { solo[b] = 0; solo[B + b] = 0; }
+      if (b == B - 1)
+        for (int j = ko1 + 2 * B + lane; j < T; j += G) { keys[j] = DRX_KEY_NONE; vals[j] = 0; }      // (ko1 = keep_off[B])
+      const int base = ko0 + 2 * b;
+      const uint8_t *kp = bt.keep ? bt.keep + ko0 : nullptr;
+      auto touch = [&](uint32_t jj, int item) {
+        const bool kf = kp ? (kp[jj] != 0) : (hash_u32(bt.mask_seed, (uint32_t)b, jj) >= qthr);
+        int hs = -1;
+        if (hot.slot && kf) {
+          if (DRX_HOT_LDS_LOOKUP) {
+            for (uint32_t at = hot_table_home(item, hot.tbits);; at = (at + 1u) & tmask) {
+              const int k = hot_table[at];
+              if (k == item) hs = (int)hot_slot_of[at];
+              if (k == item || k == -1) break;
+            }
+          } else hs = (int)hot.slot[item];
+        }
+        const bool listed = kf && hs < 0;
+        keys[base + jj] = listed ? (uint32_t)item : DRX_KEY_NONE;
+        vals[base + jj] = (uint32_t)b;
+        if (part && listed) atomicAdd(&dh[(((uint32_t)item & 255u) << 3) + rep], 1u);
+        if (hs >= 0) atomicOr(&hm[hs], 1u << (b & 15));
+        if (pres.present && kf) pres.present[pres.wire(item, 0)] = 1;
+      };
+#pragma unroll
+      for (int k = 0; k < kPre; ++k)
+        if (s + lane + k * G < e) touch((uint32_t)(lane + k * G), it[k]);
+      for (int64_t j = s + lane + kPre * G; j < e; j += G) touch((uint32_t)(j - s), H.indices[j]);      // (a longer history's rest)
+      if (lane == 0) {
+        const int deg = (int)(e - s);
+        const uint32_t k_out = (uint32_t)(n_items + c.iid), k_usr = (uint32_t)(2 * n_items) + (uint32_t)u;
+        keys[base + deg] = k_out;       vals[base + deg] = (uint32_t)b;
+        if (pres.present) pres.present[pres.wire(c.iid, 1)] = 1;
+        keys[base + deg + 1] = k_usr;       vals[base + deg + 1] = (uint32_t)b;
+        if (part) {
+          atomicAdd(&dh[((k_out & 255u) << 3) + rep], 1u);
+          atomicAdd(&dh[((k_usr & 255u) << 3) + rep], 1u);
+          const int d = (ko1 - ko0) >> 2;                          // degree_bucket(keep_off, b)
+          atomicAdd(&bh[255 - (d > 255 ? 255 : d)], 1u);
+        }
+      }
+    }
+    if (hot.slot) {
+      __syncthreads();                                             // (the round's ORs are in)
+      uint16_t *const m16 = reinterpret_cast<uint16_t *>(hot.mask);      // half-word r of row i (little-endian: samples 16 r ..)
+      const size_t row = 2 * (size_t)hot.Bw;
+      const bool tail = r + 1 == n_rounds && (size_t)r + 1 < row;
+      for (int i = threadIdx.x; i < hot.H; i += kBlock) {
+        m16[(size_t)i * row + r] = (uint16_t)hm[i];
+        if (tail) m16[(size_t)i * row + r + 1] = 0;
+        hm[i] = 0u;                                                // (the same thread cleared and read it: the next round's words)
+      }
+      __syncthreads();
+    }
+    c = n1; n1 = n2; u2 = u3;
+#pragma unroll
+    for (int k = 0; k < kPre; ++k) it[k] = itn[k];
+  }
+  if (part) {
+    __syncthreads();
+    uint32_t *const mine = part + (size_t)blockIdx.x * kPartialWords;
+    for (int d = threadIdx.x; d < 256; d += kBlock) {
+      uint32_t c = 0;
+#pragma unroll
+      for (int q = 0; q < 8; ++q) c += dh[(d << 3) + q];
+      mine[d] = c;
+      mine[256 + d] = bh[d];
+    }
+  }
+}
+
 // Launch order of the forward kernel's triples: longest histories first, triples of similar length side by side (r03 phase stamps:
 // a triple lives 19 us on average but 25 us at the 90th percentile and far longer for the few users with hundreds of items; a
 // workgroup waits for its slowest triple and the launch for its last workgroups — 47 % of the chip's group slots were occupied on
@@ -346,6 +520,9 @@ struct PrepBufs {
   // the hot head (behind everything else: a list without one keeps its layout): H rows of Bw mask words
   uint32_t *hmask;
   int H, Bw;
+  // behind that: the touch kernel's partial counts, a row per workgroup (k_sparse_touches_rounds; nullptr: the sort counts for itself)
+  uint32_t *partials;
+  int partial_rows;
 };
 
 // more than 8 touches per table row on average: rows collect long runs of touches (MovieLens shapes)
@@ -457,6 +634,10 @@ static PrepBufs prep_layout(Carver &cv, const DrxCdaeParams &P, int B, int n_tou
   R.H = H;
   R.Bw = (B + 31) / 32;
   R.hmask = H > 0 ? cv.take<uint32_t>((size_t)H * R.Bw) : nullptr;
+  // 8-bit first digits only: a 10 / 11-bit plan (keys of 9 - 11, 17 - 22, 25 - 32 bits) keeps the sort's counting launch — its rows
+  // would be 1280 / 2304 words and its fold 40 / 72 workgroups
+  R.partial_rows = DRX_PREP_ROUNDS && sort_first_digit_bits(R.bits) == 8 ? touch_grid(B) : 0;
+  R.partials = R.partial_rows > 0 ? cv.take<uint32_t>((size_t)R.partial_rows * kPartialWords) : nullptr;
   return R;
 }
 
@@ -791,10 +972,30 @@ static int prepare_transposed(const DrxCdaeParams *p, const DrxHistory *hist, co
   return DRX_OK;
 }
 
+// The touch kernel's launch: the list in batch order (R.keys / R.vals), the hot mask, the zeroed words of the plan, the launch order
+// and the sort, and (DRX_PREP_ROUNDS, R.partials) the partial counts the sort's first launch folds.
+static void launch_touches(const DrxCdaeParams *p, const DrxHistory *hist, const DrxBatch *bt, const PrepBufs &R, hipStream_t st,
+                           TouchPresence pres, const int16_t *hot_slot, const int32_t *hot_item) {
+  const int gpb = kBlock / 16;
+  (void)gpb;
+  uint32_t *sort_zero = nullptr;
+  size_t sort_zero_words = 0;
+  sort_pairs_zero_region(R.sort_temp, (size_t)R.T, R.bits, &sort_zero, &sort_zero_words);
+  const HotMark hm{R.H > 0 ? hot_slot : nullptr, R.hmask, R.H, R.Bw, hot_item, hot_table_bits(R.H)};
+#if DRX_PREP_ROUNDS
+  hipLaunchKernelGGL(k_sparse_touches_rounds, dim3(touch_grid(bt->B)), dim3(kBlock), hot_table_lds_bytes(R.H), st, p->n_items, *hist, *bt,
+                     q_threshold(bt->q), R.keys, R.vals, R.T, R.solo_v, R.plan.cnt, plan_zero_words(R), R.order_work, 512,
+                     sort_zero, (int)sort_zero_words, pres, hm, R.partials);
+#else
+  hipLaunchKernelGGL(k_sparse_touches, dim3((bt->B + gpb - 1) / gpb), dim3(kBlock), hot_table_lds_bytes(R.H), st, p->n_items, *hist, *bt,
+                     q_threshold(bt->q), R.keys, R.vals, R.T, R.solo_v, R.plan.cnt, plan_zero_words(R), R.order_work, 512,
+                     sort_zero, (int)sort_zero_words, pres, hm);
+#endif
+}
+
 static int prepare_impl(const DrxCdaeParams *p, const DrxHistory *hist, const DrxBatch *bt, const PrepBufs &R, hipStream_t st,
                         bool with_marks = false, TouchPresence pres = TouchPresence{nullptr, WireGeo{1, 0, 1}},
                         const int16_t *hot_slot = nullptr, const int32_t *hot_item = nullptr) {
-  const int gpb = kBlock / 16;
   // (the transposed preparation below never builds a head)
   if (R.H > 0 && (!hot_slot || !hot_item || !hot_list_fits(R.T, *p, pres.present != nullptr))) return DRX_EINVAL;
   if (hist->t_rank && hist->t_users && hist->t_pos && hist->t_items && !pres.present && long_segments(R.T, *p)) {
@@ -818,15 +1019,11 @@ static int prepare_impl(const DrxCdaeParams *p, const DrxHistory *hist, const Dr
     }
     if (rc != kTpFallback) return rc;
   }
-  uint32_t *sort_zero = nullptr;
-  size_t sort_zero_words = 0;
-  sort_pairs_zero_region(R.sort_temp, (size_t)R.T, R.bits, &sort_zero, &sort_zero_words);
-  hipLaunchKernelGGL(k_sparse_touches, dim3((bt->B + gpb - 1) / gpb), dim3(kBlock), hot_table_lds_bytes(R.H), st, p->n_items, *hist, *bt,
-                     q_threshold(bt->q), R.keys, R.vals, R.T, R.solo_v, R.plan.cnt, plan_zero_words(R), R.order_work, 512,
-                     sort_zero, (int)sort_zero_words, pres, HotMark{R.H > 0 ? hot_slot : nullptr, R.hmask, R.H, R.Bw, hot_item, hot_table_bits(R.H)});
+  launch_touches(p, hist, bt, R, st, pres, hot_slot, hot_item);
   // the launch order (see k_degree_counts): its counts ride in the sort's first launch, its scatter in the plan + marks launch below
   const bool fused_order = with_marks && p->ld > 16;
-  const SortRider rider{fused_order ? bt->keep_off : nullptr, bt->B, R.order_work};
+  // (R.partials: the touch kernel has counted the first digit and the buckets; the sort's first launch folds its rows)
+  const SortRider rider{fused_order ? bt->keep_off : nullptr, bt->B, R.order_work, R.partials, R.partial_rows};
   // dropped inputs (DRX_KEY_NONE) take no part in the sort: its last pass writes them back behind the sorted touches
   const int rc = sort_pairs_ex(R.sort_temp, R.sort_bytes, R.keys, R.keys_s, R.vals, R.vals_s, (size_t)R.T, R.bits, true, st, true, rider);
   if (rc) return rc;

@@ -122,6 +122,35 @@ __global__ __launch_bounds__(512) void k_digit_histograms(const uint32_t *__rest
   }
 }
 
+// The first launch when the caller's own kernel has counted already (SortRider::partials): column sums of `rows` partial rows of
+// kPartialWords words.  A workgroup owns kFoldCols columns; its 256 threads are 16 row groups x 16 columns (a wave reads four 64-byte
+// runs per row), a thread has rows / 16 independent loads (32 at 512 rows) — 32 small workgroups (16 without the bucket counts) where
+// the counting launch had ~350 of 512 threads and 32 KB of LDS.  (Workgroups of 1024 threads, 16 of them, took 4.7 us alone but 34 us
+// beside the training kernels: sixteen waves that must start on ONE CU wait for room there.)  Column c < 256: the first digit's
+// histogram (a plain store: one writer); column 256 + i: ADDED to counts[i] (one writer too; zero or the caller's own on entry).
+// Integer sums: the arrays equal the counting launch's exactly.  8-bit first digits only — a 10 / 11-bit plan keeps the counting
+// launch (launch_first_counts).
+constexpr int kFoldCols = 16, kFoldThreads = 256;
+__global__ __launch_bounds__(kFoldThreads) void k_fold_counts(const uint32_t *__restrict__ partials, int rows, uint32_t *__restrict__ hist,
+                                                              unsigned int *__restrict__ counts) {
+  constexpr int RG = kFoldThreads / kFoldCols;
+  __shared__ uint32_t part[RG][kFoldCols];
+  const int col = threadIdx.x % kFoldCols, rg = threadIdx.x / kFoldCols;
+  const int c = (int)blockIdx.x * kFoldCols + col;                    // (gridDim.x * kFoldCols <= kPartialWords)
+  uint32_t sum = 0;
+#pragma unroll 8
+  for (int r = rg; r < rows; r += RG) sum += partials[(size_t)r * kPartialWords + c];
+  part[rg][col] = sum;
+  __syncthreads();
+  if (rg == 0) {
+    uint32_t tot = 0;
+#pragma unroll
+    for (int q = 0; q < RG; ++q) tot += part[q][col];
+    if (c < 256) hist[c] = tot;
+    else counts[c - 256] += tot;
+  }
+}
+
 template <int R>
 __global__ __launch_bounds__(kSortThreads) void k_onesweep_pass(const uint32_t *__restrict__ kin, const uint32_t *__restrict__ vin,
                                                                uint32_t *__restrict__ kout, uint32_t *__restrict__ vout, size_t n, int shift,
@@ -365,6 +394,44 @@ void sort_pairs_zero_region(void *temp, size_t n, int end_bit, uint32_t **words,
   *n_words = L.zero_bytes / 4;
 }
 
+int sort_first_digit_bits(int end_bit) { return sort_plan(end_bit).rbits[0]; }
+
+// The sort's first launch: the first digit's histogram into L.hist[0 .. radix) (+ the rider's bucket counts) — counted from the keys,
+// or folded from the partial counts the rider brings (every other caller of sort_pairs / sort_pairs_ex: counted).
+static int launch_first_counts(const SortPlan &P, const SortLayout &L, const uint32_t *kin, size_t n, bool drop_none, const SortRider &rider,
+                               hipStream_t stream) {
+  if (rider.partials) {
+    // counts of 8-bit digits of the keys that are not DRX_KEY_NONE: never handed to a plan of another width, or to a sort that keeps them
+    if (P.rbits[0] != 8 || !drop_none || rider.partial_rows < 1) return DRX_EINVAL;
+    const int cols = rider.keep_off ? kPartialWords : 256;
+    hipLaunchKernelGGL(k_fold_counts, dim3(cols / kFoldCols), dim3(kFoldThreads), 0, stream, rider.partials, rider.partial_rows, L.hist,
+                       rider.counts);
+    return 0;
+  }
+  int hgrid = (int)((n + 8 * 512 - 1) / (8 * 512));
+  if (hgrid > sort_grid()) hgrid = sort_grid();
+  SortPlan P1 = P;
+  P1.passes = 1;                                               // every pass counts its successor's digits while it moves the pairs
+  const int rider_blocks = rider.keep_off ? (rider.B + 511) / 512 : 0;
+  hipLaunchKernelGGL(k_digit_histograms, dim3(hgrid + rider_blocks), dim3(512), 0, stream, kin, n, P1, L.hist, drop_none ? 1 : 0, rider,
+                     rider_blocks);
+  return 0;
+}
+
+int sort_first_counts(void *temp, size_t temp_bytes, const uint32_t *kin, size_t n, int end_bit, bool drop_none, hipStream_t stream,
+                      SortRider rider, const uint32_t **hist) {
+  if (n == 0 || n >= (1u << 30)) return DRX_EINVAL;
+  const SortPlan P = sort_plan(end_bit);
+  char *t = (char *)align_up((size_t)temp, 256);
+  const SortLayout L = sort_layout(t, n, P);
+  if ((size_t)(t - (char *)temp) + L.total > temp_bytes) return DRX_ESCRATCH;
+  *hist = L.hist;
+  const int rc = launch_first_counts(P, L, kin, n, drop_none, rider, stream);
+  if (rc) return rc;
+  DRX_LAUNCH_CHECK();
+  return 0;
+}
+
 int sort_pairs_ex(void *temp, size_t temp_bytes, const uint32_t *kin, uint32_t *kout, const uint32_t *vin, uint32_t *vout, size_t n, int end_bit,
                   bool drop_none, hipStream_t stream, bool pre_zeroed, SortRider rider) {
   if (n == 0) return 0;
@@ -374,13 +441,8 @@ int sort_pairs_ex(void *temp, size_t temp_bytes, const uint32_t *kin, uint32_t *
   const SortLayout L = sort_layout(t, n, P);
   if ((size_t)(t - (char *)temp) + L.total > temp_bytes) return DRX_ESCRATCH;
   if (!pre_zeroed) DRX_HIP(hipMemsetAsync(t + L.zero_begin, 0, L.zero_bytes, stream));
-  int hgrid = (int)((n + 8 * 512 - 1) / (8 * 512));
-  if (hgrid > sort_grid()) hgrid = sort_grid();
-  SortPlan P1 = P;
-  P1.passes = 1;                                               // every pass counts its successor's digits while it moves the pairs
-  const int rider_blocks = rider.keep_off ? (rider.B + 511) / 512 : 0;
-  hipLaunchKernelGGL(k_digit_histograms, dim3(hgrid + rider_blocks), dim3(512), 0, stream, kin, n, P1, L.hist, drop_none ? 1 : 0, rider,
-                     rider_blocks);
+  const int rc1 = launch_first_counts(P, L, kin, n, drop_none, rider, stream);
+  if (rc1) return rc1;
   const uint32_t *src_k = kin, *src_v = vin;
   uint32_t *desc = L.desc;
   for (int p = 0; p < P.passes; ++p) {

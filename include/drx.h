@@ -228,6 +228,24 @@ int drx_cdae_step_sparse_hot(const DrxCdaeParams *p, const DrxOptim *opt, const 
 int32_t drx_cdae_hot_rows_for(const DrxCdaeParams *p, int32_t opt_kind, int32_t B, int32_t n_touch_slots, int32_t H);
 void drx_cdae_prep_forget(const void *prepared);
 
+/* DEBUGGING ENTRY (tests): the first two launches of a preparation on the caller's batch — the touch kernel, then the sort's first
+ * launch: its counting launch, or the fold of the per-workgroup counts the touch kernel left (8-bit first digits) — and device copies
+ * of what the sort and the launch order consume, before any sort trusts them (a wrong histogram makes the first pass scatter out of
+ * range rather than fail):
+ *   hist_out    [2048]  the first digit's histogram of the keys that are not DRX_KEY_NONE (2^info_out[0] words written)
+ *   buckets_out [256]   samples per degree bucket, bucket = 255 - min((keep_off[b + 1] - keep_off[b]) >> 2, 255)
+ *   keys_out / vals_out [n_touch_slots + 2 B]  the list in batch order: slots keep_off[b] + 2 b .. of sample b (its history, then its
+ *               output row n_items + iid, then its user row 2 n_items + uid), DRX_KEY_NONE for a dropped or hot entry and behind the batch
+ *   mask_out    [H x ceil(B / 32)]  the hot head's transposed mask (hot != NULL with H > 0)
+ *   info_out    (HOST) [4]: first digit's bits | partial-count rows folded (0: the counting launch ran) | list slots | touch workgroups
+ * hot: NULL or a head as for drx_cdae_sparse_prepare_hot.  present: NULL, or the row-sharded step's presence map (one byte per wire
+ * key of an item row, see "row-sharded multi-GPU step"; zeroed by the caller) with its geometry (items per rank, chunk shift, world).
+ * prepared: >= drx_cdae_prep_bytes_hot(p, B, n_touch_slots, H) bytes; it holds no list afterwards. */
+int drx_debug_prep_counts(const DrxCdaeParams *p, const DrxHistory *hist, const DrxBatch *bt, const DrxHotHead *hot, uint8_t *present,
+                          int32_t ipr, int32_t cshift, int32_t world, void *prepared, size_t prepared_bytes, uint32_t *hist_out,
+                          uint32_t *buckets_out, uint32_t *keys_out, uint32_t *vals_out, uint32_t *mask_out, int32_t *info_out,
+                          void *stream);
+
 /* off[0] = 0, off[b + 1] = sum_{b' <= b} (indptr[ids[b'] + 1] - indptr[ids[b']]) for device ids: the keep_off of a batch of users (DrxBatch)
  * or the touch offsets of a batch of CSR rows.  scratch: drx_point_sample_scratch_bytes(B). */
 int drx_batch_offsets(const int64_t *indptr, const int32_t *ids, int32_t B, int32_t *off, void *scratch, size_t scratch_bytes, void *stream);
