@@ -167,6 +167,8 @@ SIGNATURES = {
     'drx_debug_prep_counts': (C.c_int, [C.POINTER(CdaeParams), C.POINTER(History), C.POINTER(Batch), C.POINTER(HotHead), C.c_void_p,
                                         C.c_int32, C.c_int32, C.c_int32, C.c_void_p, C.c_size_t, C.c_void_p, C.c_void_p, C.c_void_p,
                                         C.c_void_p, C.c_void_p, C.POINTER(C.c_int32), C.c_void_p]),
+    'drx_debug_prep_result': (C.c_int, [C.POINTER(CdaeParams), C.c_int32, C.c_int32, C.c_int32, C.c_void_p, C.c_size_t, C.c_void_p,
+                                        C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
     'drx_cdae_step_sparse_hot': (C.c_int, [C.POINTER(CdaeParams), C.POINTER(Optim), C.POINTER(History), C.POINTER(Batch),
                                            C.POINTER(HotHead), C.c_int32, C.c_void_p, C.c_size_t, C.c_void_p, C.c_size_t,
                                            C.c_void_p, C.POINTER(C.c_void_p), C.c_void_p]),
@@ -338,6 +340,8 @@ SIGNATURES = {
                                                    C.c_size_t, C.c_void_p, C.c_void_p]),
     'drx_sort_pairs_temp_bytes': (C.c_size_t, [C.c_int64, C.c_int32]),
     'drx_sort_pairs': (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64, C.c_int32, C.c_void_p, C.c_size_t, C.c_void_p]),
+    'drx_debug_sort_pairs_drop': (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64, C.c_int32, C.c_int32, C.c_void_p,
+                                            C.c_size_t, C.c_void_p]),
     'drx_list_sampler_create': (C.c_void_p, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int32, C.c_int32, C.c_int32, C.c_int32,
                                              C.c_int32, C.c_int32, C.c_int64]),
     'drx_list_sampler_sample': (C.c_int, [C.c_void_p, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p,

@@ -1109,6 +1109,26 @@ int drx_debug_prep_counts(const DrxCdaeParams *p, const DrxHistory *hist, const 
   return DRX_OK;
 }
 
+// (include/drx.h: copies of what a finished preparation left in `prepared` — nothing is launched, the buffer is only read)
+int drx_debug_prep_result(const DrxCdaeParams *p, int32_t B, int32_t n_touch_slots, int32_t H, const void *prepared, size_t prepared_bytes,
+                          uint32_t *keys_s_out, uint32_t *vals_s_out, uint8_t *solo_v_out, uint8_t *solo_o_out, int32_t *order_out,
+                          void *stream) {
+  int rc = check_params(p);
+  if (rc) return rc;
+  if (B < 1 || n_touch_slots < 0 || hot_rows(p, H) < 0 || !prepared || !keys_s_out || !vals_s_out || !solo_v_out || !solo_o_out || !order_out)
+    return DRX_EINVAL;
+  Carver cp(const_cast<void *>(prepared), prepared_bytes);
+  const PrepBufs R = prep_layout(cp, *p, B, n_touch_slots, H);
+  if (!cp.ok()) return DRX_ESCRATCH;
+  hipStream_t st = (hipStream_t)stream;
+  DRX_HIP(hipMemcpyAsync(keys_s_out, R.keys_s, (size_t)R.T * sizeof(uint32_t), hipMemcpyDeviceToDevice, st));
+  DRX_HIP(hipMemcpyAsync(vals_s_out, R.vals_s, (size_t)R.T * sizeof(uint32_t), hipMemcpyDeviceToDevice, st));
+  DRX_HIP(hipMemcpyAsync(solo_v_out, R.solo_v, (size_t)B, hipMemcpyDeviceToDevice, st));
+  DRX_HIP(hipMemcpyAsync(solo_o_out, R.solo_o, (size_t)B, hipMemcpyDeviceToDevice, st));
+  DRX_HIP(hipMemcpyAsync(order_out, R.order, (size_t)B * sizeof(int32_t), hipMemcpyDeviceToDevice, st));
+  return DRX_OK;
+}
+
 int drx_cdae_step_sparse_hot(const DrxCdaeParams *p, const DrxOptim *opt, const DrxHistory *hist, const DrxBatch *bt,
                              const DrxHotHead *hot, int32_t loss_kind, const void *prepared, size_t prepared_bytes, void *scratch,
                              size_t scratch_bytes, float *loss_out, void *const *events, void *stream) {

@@ -4,8 +4,9 @@
 // Hand-written for gfx950 in the "onesweep" form (one launch per digit instead of histogram + scan + scatter launches):
 //   k_digit_histograms   one read of the keys -> the global histogram of EVERY digit position (LDS atomics, then one integer
 //                        atomic per non-empty bin and workgroup)
-//   k_onesweep_pass<R>   one launch per digit.  A tile of 4096 pairs per workgroup; tiles take their number from an atomic ticket
-//                        (so every predecessor of a running tile is itself running or done).  Per tile:
+//   k_onesweep_pass<R>   one launch per digit.  A tile of kSortTile = 8192 pairs (512 threads x 16) per workgroup; tiles take their
+//                        number from an atomic ticket (so every predecessor of a running tile is itself running or done); at most
+//                        sort_grid() = 512 workgroups, so a list of more than 512 tiles has workgroups take a second one.  Per tile:
 //                          1. every wave ranks its 64-item rows in order: lanes holding the same digit find each other with R
 //                             ballots, the lowest of them bumps the wave's private counter of that digit in LDS and hands the old
 //                             value to the others (no LDS atomics, stable by construction);
@@ -158,7 +159,7 @@ __global__ __launch_bounds__(kSortThreads) void k_onesweep_pass(const uint32_t *
                                                                int flags, uint32_t *next_hist, int next_shift) {
   constexpr int RADIX = 1 << R;
   constexpr int BPT = (RADIX + kSortThreads - 1) / kSortThreads;      // bins per thread
-  extern __shared__ __align__(16) uint32_t sort_lds[];                // onesweep_lds_bytes(R): 42 / 72 / 112 KB for R = 8 / 10 / 11
+  extern __shared__ __align__(16) uint32_t sort_lds[];                // onesweep_lds_bytes(R): 83 968 / 114 688 / 155 648 bytes for R = 8 / 10 / 11
   uint32_t (*whist)[RADIX] = reinterpret_cast<uint32_t (*)[RADIX]>(sort_lds);   // [waves][RADIX] per-wave digit counters, then offsets
   uint32_t *gbase = sort_lds + kSortWaves * RADIX;  // where LDS slot i of digit d goes: gbase[d] + i
   uint32_t *lstart = gbase + RADIX;                 // start of digit d's run inside the tile
@@ -205,7 +206,7 @@ __global__ __launch_bounds__(kSortThreads) void k_onesweep_pass(const uint32_t *
   const size_t base = (size_t)tile * kSortTile;
   const int tile_n = (int)((n_in - base) < (size_t)kSortTile ? (n_in - base) : (size_t)kSortTile);
 
-  // ---- 1. load + rank (wave w owns items [w*512, w*512+512) of the tile, row `it` = 64 consecutive items) ----
+  // ---- 1. load + rank (wave w owns items [w*1024, w*1024+1024) of the tile — 64 * kSortIPT —, row `it` = 64 consecutive items) ----
   uint32_t key[kSortIPT], val[kSortIPT], pre[kSortIPT];
 #pragma unroll
   for (int it = 0; it < kSortIPT; ++it) {
@@ -369,7 +370,14 @@ __global__ __launch_bounds__(kSortThreads) void k_onesweep_pass(const uint32_t *
 #endif
 inline int sort_grid() { return DRX_SORT_GRID; }
 
-inline size_t onesweep_lds_bytes(int r) { return ((size_t)(kSortWaves + 2) * ((size_t)1 << r) + 2 * (size_t)kSortTile + 2048) * 4; }
+// dynamic LDS of a pass: whist [waves][radix], gbase and lstart [radix], skey and sval [tile], nh [2048] — with tiles of 8192 pairs
+// 83 968 / 114 688 / 155 648 bytes for R = 8 / 10 / 11: the 11-bit digit is within 8 KB of what a workgroup can have
+constexpr size_t onesweep_lds_bytes(int r) { return ((size_t)(kSortWaves + 2) * ((size_t)1 << r) + 2 * (size_t)kSortTile + 2048) * 4; }
+// the kernel's own __shared__ words beside it: s_tile, s_tile_valid, wl[waves], wg[waves]
+constexpr size_t kSortStaticLds = (2 + 2 * (size_t)kSortWaves) * 4;
+constexpr size_t kSortLdsLimit = 160 * 1024;                             // LDS of a workgroup on gfx950
+static_assert(onesweep_lds_bytes(11) + kSortStaticLds <= kSortLdsLimit,
+              "k_onesweep_pass<11>: tile (DRX_SORT_THREADS x DRX_SORT_IPT) + counters do not fit a workgroup's LDS");
 
 template <int R>
 static int launch_pass(const uint32_t *sk, const uint32_t *sv, uint32_t *dk, uint32_t *dv, size_t n, int shift, const uint32_t *gh, uint32_t *ticket,
@@ -481,5 +489,20 @@ int drx_sort_pairs(const uint32_t *keys_in, uint32_t *keys_out, const uint32_t *
                    void *temp, size_t temp_bytes, void *stream) {
   if (n < 0 || key_bits < 1 || key_bits > 32 || (n > 0 && (!keys_in || !keys_out || !vals_in || !vals_out || !temp))) return DRX_EINVAL;
   return drx::sort_pairs(temp, temp_bytes, keys_in, keys_out, vals_in, vals_out, (size_t)n, key_bits, (hipStream_t)stream);
+}
+// (include/drx.h: the sort as the preparation calls it — DRX_KEY_NONE pairs dropped, no rider — with the caller's or its own zeroing)
+int drx_debug_sort_pairs_drop(const uint32_t *keys_in, uint32_t *keys_out, const uint32_t *vals_in, uint32_t *vals_out, int64_t n,
+                              int32_t key_bits, int32_t pre_zeroed, void *temp, size_t temp_bytes, void *stream) {
+  if (n < 0 || key_bits < 1 || key_bits > 32 || (n > 0 && (!keys_in || !keys_out || !vals_in || !vals_out || !temp))) return DRX_EINVAL;
+  hipStream_t st = (hipStream_t)stream;
+  if (pre_zeroed && n > 0 && n < (1ll << 30)) {
+    // exactly the words sort_pairs_zero_region names, cleared the way a caller's own kernel would have
+    uint32_t *words = nullptr;
+    size_t n_words = 0;
+    drx::sort_pairs_zero_region(temp, (size_t)n, key_bits, &words, &n_words);
+    if ((size_t)((char *)(words + n_words) - (char *)temp) > temp_bytes) return DRX_ESCRATCH;      // (the sort would refuse as well)
+    DRX_HIP(hipMemsetAsync(words, 0, n_words * sizeof(uint32_t), st));
+  }
+  return drx::sort_pairs_ex(temp, temp_bytes, keys_in, keys_out, vals_in, vals_out, (size_t)n, key_bits, true, st, pre_zeroed != 0);
 }
 }

@@ -246,6 +246,19 @@ int drx_debug_prep_counts(const DrxCdaeParams *p, const DrxHistory *hist, const 
                           uint32_t *buckets_out, uint32_t *keys_out, uint32_t *vals_out, uint32_t *mask_out, int32_t *info_out,
                           void *stream);
 
+/* DEBUGGING ENTRY (tests): device copies of what a finished preparation — drx_cdae_sparse_prepare / _hot of a batch of B samples and
+ * n_touch_slots slots, with a head of H rows (0: none) — left in `prepared`, laid out as the step reads it; nothing is launched:
+ *   keys_s_out / vals_s_out [n_touch_slots + 2 B]  the sorted list: the touches that are not DRX_KEY_NONE ordered by key, the touches of a
+ *               key in a fixed order (sorted: samples ascending; through the history's transpose: user by user, samples ascending inside
+ *               a user), the key of a V / W2T row's sole touch blanked to DRX_KEY_NONE where marks are made (ld > 16), its sample kept;
+ *               DRX_KEY_NONE behind the list
+ *   solo_v_out / solo_o_out [B]  1: sample b is the only one of the batch that touches its V row / its W2T row
+ *   order_out   [B]     the forward kernel's launch order: a permutation of the samples, degree buckets ascending
+ * prepared: the buffer the preparation wrote, same p, B, n_touch_slots and H. */
+int drx_debug_prep_result(const DrxCdaeParams *p, int32_t B, int32_t n_touch_slots, int32_t H, const void *prepared, size_t prepared_bytes,
+                          uint32_t *keys_s_out, uint32_t *vals_s_out, uint8_t *solo_v_out, uint8_t *solo_o_out, int32_t *order_out,
+                          void *stream);
+
 /* off[0] = 0, off[b + 1] = sum_{b' <= b} (indptr[ids[b'] + 1] - indptr[ids[b']]) for device ids: the keep_off of a batch of users (DrxBatch)
  * or the touch offsets of a batch of CSR rows.  scratch: drx_point_sample_scratch_bytes(B). */
 int drx_batch_offsets(const int64_t *indptr, const int32_t *ids, int32_t B, int32_t *off, void *scratch, size_t scratch_bytes, void *stream);
@@ -972,6 +985,13 @@ int drx_knn_pair_scores(int32_t type, int32_t aggregation, const int64_t *indptr
 size_t drx_sort_pairs_temp_bytes(int64_t n, int32_t key_bits);
 int drx_sort_pairs(const uint32_t *keys_in, uint32_t *keys_out, const uint32_t *vals_in, uint32_t *vals_out, int64_t n, int32_t key_bits,
                    void *temp, size_t temp_bytes, void *stream);
+/* DEBUGGING ENTRY (tests): the sort as a preparation calls it — pairs whose key is DRX_KEY_NONE take no part: keys_out = the other
+ * pairs sorted, then DRX_KEY_NONE up to n; vals_out is written for the sorted pairs only (the words behind them keep what they held).
+ * Every other key must be < 2^key_bits (key_bits = 32: <= 0xFFFFFFFE).  pre_zeroed != 0: the sort is told that its caller has cleared
+ * the counters and tile words of `temp` (the library's preparations do that in a kernel of their own); this entry clears exactly
+ * that range first, with one memset, and nothing else of `temp`.  Arguments and return codes as drx_sort_pairs. */
+int drx_debug_sort_pairs_drop(const uint32_t *keys_in, uint32_t *keys_out, const uint32_t *vals_in, uint32_t *vals_out, int64_t n,
+                              int32_t key_bits, int32_t pre_zeroed, void *temp, size_t temp_bytes, void *stream);
 
 /* ---- raw -> internal id map (mem_dataset.py:309-330) --------------------------------------
  * codes[r] = rank of first appearance of raw[r] (int64 raw ids), bit-exact.

@@ -98,37 +98,6 @@ def test_masked_topk_packs_rows_that_share_words(n, k):
     assert (idx[1] == -1).all()                        # the row without a candidate: no entry
 
 
-@pytest.mark.parametrize('n,bits', [(1, 1), (63, 9), (64, 10), (4096, 18), (4097, 18), (100_003, 25), (1_440_000, 25), (300_000, 27), (70_000, 32),
-                                    (200_000, 12), (500_000, 16), (33_000, 8)])      # narrow keys over many tiles: one- and two-pass plans
-def test_sort_pairs_is_a_stable_sort(n, bits):
-    """drx_sort_pairs (the inverted-index builder of the sparse steps) against torch's stable sort: heavy duplicates (Zipf-like
-    keys), padding keys 0xFFFFFFFF, sizes around tile and wave borders, only the low `bits` bits order the pairs."""
-    import ctypes as C
-    import torch
-    from drecpy_amd import _lib
-    L = _lib.lib()
-    g = torch.Generator(device='cuda'); g.manual_seed(n + bits)
-    hi = (1 << bits) - 1
-    u = torch.rand(n, generator=g, device='cuda', dtype=torch.float64)
-    keys64 = (u ** 6 * hi).to(torch.int64)                                 # skewed: many duplicates of small keys
-    if bits == 25 or bits == 32:
-        pad = torch.rand(n, generator=g, device='cuda') < 0.15
-        keys64 = torch.where(pad, torch.full_like(keys64, 0xFFFFFFFF), keys64)
-    keys64 = keys64 & 0xFFFFFFFF
-    keys = (keys64 - ((keys64 >> 31) << 32)).to(torch.int32)               # uint32 bit pattern in an int32 tensor
-    vals = torch.arange(n, device='cuda', dtype=torch.int32)
-    ko, vo = torch.empty_like(keys), torch.empty_like(vals)
-    need = L.drx_sort_pairs_temp_bytes(n, bits)
-    tmp = torch.empty(need, dtype=torch.uint8, device='cuda')
-    _lib.check(L.drx_sort_pairs(_lib.ptr(keys), _lib.ptr(ko), _lib.ptr(vals), _lib.ptr(vo), n, bits, _lib.ptr(tmp), need,
-                                _lib.stream_ptr(torch.device('cuda'))), 'drx_sort_pairs')
-    torch.cuda.synchronize()
-    low = keys64 & hi                                                       # only the low `bits` bits order the pairs
-    want = torch.sort(low, stable=True)
-    assert torch.equal(vo.long(), want.indices)
-    assert torch.equal(ko.long() & 0xFFFFFFFF, keys64[want.indices])
-
-
 @pytest.mark.parametrize('T,n_rows,ld,indexed', [(1, 5, 4, False), (700, 300, 52, False), (6144, 3706, 100, False),
                                                   (2560, 3706, 52, True), (40_000, 3706, 64, True), (200_000, 50_000, 128, True),
                                                   (70, 9, 300, True)])

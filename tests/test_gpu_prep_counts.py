@@ -13,7 +13,7 @@ import numpy as np
 import pytest
 import torch
 
-from helpers import hash_u32, q_threshold
+from prep_oracle import _expect, _wire      # (the statement of the unsorted list: shared with tests/test_gpu_prep_list.py)
 
 NONE = 0xFFFFFFFF
 _cache = {}
@@ -47,41 +47,6 @@ def _engine(U, N, mean_deg, seed=0):
         eng.set_history(indptr, indices, with_transpose=False)
         _cache[key] = eng
     return _cache[key]
-
-
-def _wire(item, is_out, ipr, cshift, world):
-    o = item // ipr
-    l = 2 * (item - o * ipr) + is_out
-    return (((l >> cshift) * world + o) << cshift) | (l & ((1 << cshift) - 1))
-
-
-def _expect(indptr, indices, N, uid, iid, seed, q, keep, slot_of, H, slack):
-    B = len(uid)
-    deg = (indptr[uid + 1] - indptr[uid]).astype(np.int64)
-    keep_off = np.concatenate([[0], np.cumsum(deg)])
-    tot = int(keep_off[-1])
-    T = tot + slack + 2 * B
-    row = np.repeat(np.arange(B), deg)
-    j = np.arange(tot) - keep_off[row]
-    items = indices[indptr[uid][row] + j].astype(np.int64)
-    kf = (keep[:tot] != 0) if keep is not None else (hash_u32(seed, row, j) >= q_threshold(q))
-    slot = slot_of[items] if H else np.full(tot, -1)
-    listed = kf & (slot < 0)
-    keys = np.full(T, NONE, dtype=np.uint32)
-    vals = np.zeros(T, dtype=np.uint32)
-    pos = keep_off[row] + 2 * row + j
-    keys[pos] = np.where(listed, items, NONE)
-    vals[pos] = row
-    b = np.arange(B)
-    at = keep_off[:-1] + 2 * b + deg
-    keys[at], vals[at] = N + iid, b
-    keys[at + 1], vals[at + 1] = 2 * N + uid, b
-    Bw = (B + 31) // 32
-    mask = np.zeros((max(H, 1), Bw), dtype=np.uint32)
-    hot = kf & (slot >= 0)
-    np.bitwise_or.at(mask, (slot[hot], row[hot] // 32), (np.uint32(1) << (row[hot] % 32).astype(np.uint32)))
-    buckets = np.bincount(255 - np.minimum(deg >> 2, 255), minlength=256)
-    return dict(T=T, keys=keys, vals=vals, mask=mask[:H], buckets=buckets, kept_items=items[kf], deg=deg)
 
 
 def _check(U, N, B, mean_deg=12, H=0, explicit_keep=False, presence=None, q=0.2, seed=77, slack=37, uid_fix=True):
