@@ -162,27 +162,35 @@ class CDAE(RecommenderABC):
         return [self.W, self.W_, self.V, self.b, self.b_]
 
     def _configure_optimizer(self):
-        """Reference mode trains with Keras Adam (the default registered by fit(), or an optimizers.Adam passed as `optimizer=`);
-        sampled mode with the constructor's `sparse_optimizer` unless `optimizer=` forces another kind."""
+        """Reference mode trains with the registered optimizer's dense rule — Keras Adam by default, or an optimizers.Adam / Adagrad /
+        SGD / RMSprop passed as `optimizer=`; sampled mode with the constructor's `sparse_optimizer` unless `optimizer=` forces another
+        of ITS kinds (adagrad / adam / rowwise_adagrad: the sparse step has no SGD or RMSprop)."""
+        from ..optimizers import N_SLOTS
         o, e = self.optimizer, self._engine
+        kind = getattr(o, 'kind', None)
+        if getattr(self, '_dist_model', None) is not None:
+            if self._optimizer_forced:
+                raise Exception('optimizer= cannot be forced on a sharded fit() (layout="rows" or "columns"): choose the sparse rule with '
+                                'CDAE(sparse_optimizer=...) — adagrad, adam or rowwise_adagrad')
+            return
         if self.mode == 'reference':
-            if getattr(o, 'kind', None) != 'adam':
-                raise Exception(f'CDAE mode="reference" is the reference step: Keras Adam only (got {o!r}); Adagrad variants exist in mode="sampled"')
-            kind = 'adam'
+            if kind not in N_SLOTS or kind == 'rowwise_adagrad':
+                raise Exception(f'CDAE mode="reference" trains with the dense rules adam, adagrad, sgd, rmsprop (got {o!r}); '
+                                f'rowwise_adagrad exists in mode="sampled"')
         else:
             if not self._optimizer_forced:
                 return
-            kind = o.kind
-        if getattr(self, '_dist_model', None) is not None:
-            if self._optimizer_forced:
-                raise Exception('optimizer= cannot be forced on a column-sharded fit(): choose it with CDAE(sparse_optimizer=...)')
-            return
+            if kind not in ('adam', 'adagrad', 'rowwise_adagrad'):
+                raise Exception(f'CDAE mode="sampled" has no sparse {kind} step (got {o!r}): choose CDAE(sparse_optimizer=...) among '
+                                f"'adagrad', 'adam', 'rowwise_adagrad', or train with mode=\"reference\", whose dense step takes sgd and rmsprop")
         if kind == 'adam':
-            same = e.s2 is not None and (e.lr, e.beta1, e.beta2, e.opt_eps) == (o.learning_rate, o.beta_1, o.beta_2, o.epsilon)
+            same = e.s2 is not None and e.opt_kind == 0 and (e.lr, e.beta1, e.beta2, e.opt_eps) == (o.learning_rate, o.beta_1, o.beta_2, o.epsilon)
             if not same:                                   # (the slots _pre_fit allocated are kept when nothing differs)
                 e.init_optimizer('adam', o.learning_rate, e.reg_rate, o.beta_1, o.beta_2, o.epsilon)
-        else:
+        elif kind in ('adagrad', 'rowwise_adagrad'):
             e.init_optimizer(kind, o.learning_rate, e.reg_rate, eps=o.epsilon, initial_accumulator=o.initial_accumulator_value)
+        else:
+            e.init_optimizer(kind, o.learning_rate, e.reg_rate, eps=getattr(o, 'epsilon', None), momentum=o.momentum, rho=getattr(o, 'rho', 0.9))
 
     # ---- cdae.py:34-45 ---------------------------------------------------------------------------
     def _pre_fit(self, learning_rate, neg_ratio, reg_rate, **kwds):

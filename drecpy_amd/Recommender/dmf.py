@@ -128,10 +128,9 @@ class DMF(RecommenderABC):
 
     def _configure_optimizer(self):
         o = self.optimizer
-        if getattr(o, 'kind', None) != 'adam':
-            raise Exception(f'DMF trains with Keras Adam only (dense update of both towers); got {o!r}')
-        e = self._engine
-        e.lr, e.beta1, e.beta2, e.eps = o.learning_rate, o.beta_1, o.beta_2, o.epsilon
+        if getattr(o, 'kind', None) not in ('adam', 'adagrad', 'sgd', 'momentum', 'nesterov', 'rmsprop', 'rmsprop_momentum'):
+            raise Exception(f'DMF trains with the dense rules adam, adagrad, sgd, rmsprop (dense update of both towers); got {o!r}')
+        self._engine.set_optimizer(o)
 
     def _keras_init(self, rng):
         p = {}

@@ -97,6 +97,10 @@ class CsrAdamTable(C.Structure):                        # include/drx.h DrxCsrAd
                [(n, C.c_void_p) for n in ('p', 'm', 'v', 'p_s', 'm_s', 'v_s')] + [(n, C.c_float) for n in ('alpha', 'alpha_s', 'l2_coef')]
 
 
+class OptRule(C.Structure):                             # include/drx.h DrxOptRule
+    _fields_ = [('kind', C.c_int32), ('lr', C.c_float), ('mu', C.c_float), ('mu2', C.c_float), ('eps', C.c_float)]
+
+
 class CsrList(C.Structure):                             # include/drx.h DrxCsrList
     _fields_ = [('keys', C.c_void_p), ('T', C.c_int32), ('n_rows', C.c_int32), ('row_ptr', C.c_void_p), ('order', C.c_void_p)]
 
@@ -121,7 +125,7 @@ class DmfArgs(C.Structure):
 
 class DmfK0Update(C.Structure):
     _fields_ = [(n, C.c_void_p) for n in ('K0u', 'm_u', 'v_u', 'K0i', 'm_i', 'v_i')] + [('n_items', C.c_int32), ('n_users', C.c_int32)] + \
-               [(n, C.c_float) for n in ('alpha_u', 'alpha_i', 'l2_coef', 'beta1', 'beta2', 'eps')] + [('row_order', C.c_void_p), ('n_long', C.c_int32)]
+               [(n, C.c_float) for n in ('alpha_u', 'alpha_i', 'l2_coef', 'beta1', 'beta2', 'eps')] + [('row_order', C.c_void_p), ('n_long', C.c_int32), ('opt_kind', C.c_int32)]
 
 
 class Optim(C.Structure):
@@ -264,6 +268,18 @@ SIGNATURES = {
     'drx_rows_csr_adam_outer': (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int32, C.c_int32, C.c_int32, C.c_void_p,
                                           C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_float, C.c_float, C.c_float,
                                           C.c_float, C.c_float, C.c_float, C.c_void_p]),
+    'drx_opt_dense': (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64, C.POINTER(OptRule), C.c_float, C.c_void_p]),
+    'drx_opt_segments': (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.POINTER(AdamSegments), C.POINTER(OptRule), C.c_void_p]),
+    'drx_rows_csr_opt': (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int32, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p,
+                                   C.c_void_p, C.c_void_p, C.c_void_p, C.c_float, C.c_float, C.c_float, C.POINTER(OptRule), C.c_void_p]),
+    'drx_rows_csr_opt_outer': (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int32, C.c_int32, C.c_int32, C.c_void_p,
+                                         C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_float, C.c_float, C.c_float,
+                                         C.POINTER(OptRule), C.c_void_p]),
+    'drx_rows_csr_opt_multi': (C.c_int, [C.POINTER(CsrAdamTable), C.c_int32, C.POINTER(OptRule), C.c_void_p]),
+    'drx_caser_step_small_opt': (C.c_int, [C.POINTER(CaserDims), C.POINTER(CaserArgs), C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p,
+                                           C.POINTER(AdamSegments), C.POINTER(OptRule), C.c_void_p]),
+    'drx_dmf_step_small_opt': (C.c_int, [C.POINTER(DmfDims), C.POINTER(DmfArgs), C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p,
+                                         C.POINTER(AdamSegments), C.POINTER(OptRule), C.c_void_p]),
     'drx_dmf_work_order_device': (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int32, C.c_void_p, C.c_int32,
                                             C.c_void_p, C.c_void_p, C.c_void_p]),
     'drx_dmf_work_order': (C.c_int32, [C.c_void_p, C.c_int32, C.c_void_p, C.c_int32, C.c_int32, C.c_void_p, C.c_int32, C.c_void_p,

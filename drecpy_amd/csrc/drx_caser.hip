@@ -8,6 +8,7 @@
 // weights in LDS (channel-fastest, [s][f][c]: every lane reads its own column).  Through r04 the same wave-per-sample program also did
 // the backward pass (HISTORY.md).
 #include "drx_caser_tile.hpp"
+#include "drx_opt.hpp"
 
 
 namespace drx {
@@ -151,9 +152,10 @@ __global__ __launch_bounds__(1024) void k_sum_partials(const float *__restrict__
 
 // k_sum_partials with the small weights' Keras Adam behind it: the thread that has column j's sum applies l2 + Adam of j's segment
 // (one launch instead of two; same operations in the same order as k_sum_partials + k_adam_segments).
-__global__ __launch_bounds__(1024) void k_sum_partials_adam(const float *__restrict__ part, int n_rows, int n, const float *__restrict__ tail,
-                                                            float *__restrict__ out, float *p, float *m, float *v, DrxAdamSegments sg,
-                                                            float b1, float b2, float eps) {
+// (kind: the dense rule, at run time — a small launch; m / v of a rule without that slot are NULL and are not touched)
+__global__ __launch_bounds__(1024) void k_sum_partials_opt(const float *__restrict__ part, int n_rows, int n, const float *__restrict__ tail,
+                                                           float *__restrict__ out, float *p, float *m, float *v, DrxAdamSegments sg,
+                                                           int kind, float b1, float b2, float eps) {
   __shared__ float red[16][64];
   const int c = threadIdx.x & 63, q = threadIdx.x >> 6;
   const int j = blockIdx.x * 64 + c;
@@ -172,24 +174,31 @@ __global__ __launch_bounds__(1024) void k_sum_partials_adam(const float *__restr
       for (int k = 0; k < sg.n; ++k)
         if (j >= sg.start[k] && j < sg.start[k] + sg.len[k]) s = k;
       if (s >= 0) {                                  // (padding entries of a bias segment belong to no segment: left alone)
-        const OptScalars o{DRX_OPT_ADAM, 0.f, 0.f, b1, b2, eps, sg.alpha[s]};
-        float pp = p[j], mm = m[j], vv = v[j];
-        opt_update1(o, fmaf(sg.l2_coef[s], pp, t), pp, mm, vv);
-        p[j] = pp; m[j] = mm; v[j] = vv;
+        const OptScalars o{kind, sg.alpha[s], 0.f, b1, b2, eps, sg.alpha[s]};
+        const bool h1 = opt_has_s1(kind), h2 = opt_has_s2(kind);
+        float pp = p[j], mm = h1 ? m[j] : 0.f, vv = h2 ? v[j] : 0.f;
+        opt_update_dense<-1>(o, fmaf(sg.l2_coef[s], pp, t), pp, mm, vv);
+        p[j] = pp;
+        if (h1) m[j] = mm;
+        if (h2) v[j] = vv;
       }
     }
   }
 }
 
-__global__ __launch_bounds__(kBlock) void k_adam_segments(float *p, float *m, float *v, const float *g, DrxAdamSegments sg, float b1,
-                                                          float b2, float eps) {
+// (the rule at run time: a small launch; m / v of a rule without that slot are NULL and are not touched)
+__global__ __launch_bounds__(kBlock) void k_opt_segments(float *p, float *m, float *v, const float *g, DrxAdamSegments sg, int kind, float b1,
+                                                         float b2, float eps) {
+  const bool h1 = opt_has_s1(kind), h2 = opt_has_s2(kind);
   for (int s = 0; s < sg.n; ++s) {
-    OptScalars o{DRX_OPT_ADAM, 0.f, 0.f, b1, b2, eps, sg.alpha[s]};
+    OptScalars o{kind, sg.alpha[s], 0.f, b1, b2, eps, sg.alpha[s]};
     for (int i = blockIdx.x * kBlock + threadIdx.x; i < sg.len[s]; i += gridDim.x * kBlock) {
       const int k = sg.start[s] + i;
-      float pp = p[k], mm = m[k], vv = v[k];
-      opt_update1(o, fmaf(sg.l2_coef[s], pp, g[k]), pp, mm, vv);
-      p[k] = pp; m[k] = mm; v[k] = vv;
+      float pp = p[k], mm = h1 ? m[k] : 0.f, vv = h2 ? v[k] : 0.f;
+      opt_update_dense<-1>(o, fmaf(sg.l2_coef[s], pp, g[k]), pp, mm, vv);
+      p[k] = pp;
+      if (h1) m[k] = mm;
+      if (h2) v[k] = vv;
     }
   }
 }
@@ -277,17 +286,27 @@ int drx_caser_fwd_bwd(const DrxCaserDims *D, const DrxCaserArgs *A, float *gsw_o
   return DRX_OK;
 }
 
-int drx_caser_step_small(const DrxCaserDims *D, const DrxCaserArgs *A, float *gsw_out, float *sw, float *sw_m, float *sw_v,
-                         const DrxAdamSegments *sg, float beta1, float beta2, float eps, void *stream) {
-  if (!sw || !sw_m || !sw_v || !sg || sg->n < 1 || sg->n > DRX_MAX_SEGMENTS || (A && sw != A->sw)) return DRX_EINVAL;
+int drx_caser_step_small_opt(const DrxCaserDims *D, const DrxCaserArgs *A, float *gsw_out, float *sw, float *sw_m, float *sw_v,
+                             const DrxAdamSegments *sg, const DrxOptRule *rule, void *stream) {
+  if (!sw || !rule || !opt_dense_kind(rule->kind) || !opt_slots_ok(rule->kind, sw_m, sw_v) || !sg || sg->n < 1 || sg->n > DRX_MAX_SEGMENTS ||
+      (A && sw != A->sw))
+    return DRX_EINVAL;
+  if (!opt_has_s1(rule->kind)) sw_m = nullptr;
+  if (!opt_has_s2(rule->kind)) sw_v = nullptr;
   hipStream_t st = (hipStream_t)stream;
   int grid = 0;
   const int rc = launch_caser_tile(D, A, gsw_out, st, &grid);
   if (rc) return rc;
-  hipLaunchKernelGGL(k_sum_partials_adam, dim3((D->n_small + 64) / 64), dim3(1024), 0, st, A->gsw_part, grid, D->n_small,
-                     A->loss_part, gsw_out, sw, sw_m, sw_v, *sg, beta1, beta2, eps);
+  hipLaunchKernelGGL(k_sum_partials_opt, dim3((D->n_small + 64) / 64), dim3(1024), 0, st, A->gsw_part, grid, D->n_small,
+                     A->loss_part, gsw_out, sw, sw_m, sw_v, *sg, rule->kind, rule->mu, rule->mu2, rule->eps);
   DRX_LAUNCH_CHECK();
   return DRX_OK;
+}
+
+int drx_caser_step_small(const DrxCaserDims *D, const DrxCaserArgs *A, float *gsw_out, float *sw, float *sw_m, float *sw_v,
+                         const DrxAdamSegments *sg, float beta1, float beta2, float eps, void *stream) {
+  const DrxOptRule rule{DRX_OPT_ADAM, 0.f, beta1, beta2, eps};
+  return drx_caser_step_small_opt(D, A, gsw_out, sw, sw_m, sw_v, sg, &rule, stream);
 }
 
 int drx_caser_hidden(const DrxCaserDims *D, const DrxCaserArgs *A, void *stream) {
@@ -304,12 +323,21 @@ int drx_caser_hidden(const DrxCaserDims *D, const DrxCaserArgs *A, void *stream)
   return DRX_OK;
 }
 
-int drx_adam_segments(float *p, float *m, float *v, const float *g, const DrxAdamSegments *sg, float beta1, float beta2, float eps,
-                      void *stream) {
-  if (!p || !m || !v || !g || !sg || sg->n < 1 || sg->n > DRX_MAX_SEGMENTS) return DRX_EINVAL;
-  hipLaunchKernelGGL(k_adam_segments, dim3(64), dim3(kBlock), 0, (hipStream_t)stream, p, m, v, g, *sg, beta1, beta2, eps);
+int drx_opt_segments(float *p, float *s1, float *s2, const float *g, const DrxAdamSegments *sg, const DrxOptRule *rule, void *stream) {
+  if (!p || !g || !sg || sg->n < 1 || sg->n > DRX_MAX_SEGMENTS || !rule || !opt_dense_kind(rule->kind) || !opt_slots_ok(rule->kind, s1, s2))
+    return DRX_EINVAL;
+  if (!opt_has_s1(rule->kind)) s1 = nullptr;
+  if (!opt_has_s2(rule->kind)) s2 = nullptr;
+  hipLaunchKernelGGL(k_opt_segments, dim3(64), dim3(kBlock), 0, (hipStream_t)stream, p, s1, s2, g, *sg, rule->kind, rule->mu, rule->mu2,
+                     rule->eps);
   DRX_LAUNCH_CHECK();
   return DRX_OK;
+}
+
+int drx_adam_segments(float *p, float *m, float *v, const float *g, const DrxAdamSegments *sg, float beta1, float beta2, float eps,
+                      void *stream) {
+  const DrxOptRule rule{DRX_OPT_ADAM, 0.f, beta1, beta2, eps};
+  return drx_opt_segments(p, m, v, g, sg, &rule, stream);
 }
 
 }  // extern "C"

@@ -7,6 +7,7 @@
 // DRecPy/Recommender/recommender_abc.py:190-204,328-334 (see include/drx.h for the per-entry mapping).
 #include "drx_common.hpp"
 #include "drx_rows.hpp"
+#include "drx_opt.hpp"
 #include "drx_cdae_host.hpp"
 
 namespace drx {
@@ -98,7 +99,9 @@ struct OutDenseArgs {
   int loss_kind;
 };
 
-template <int G, int J, bool WANT_LOSS>
+// KIND (here and in k_out_dense_tile, k_in_sweep): < 0 — Adam or Adagrad, opt.kind deciding at run time as ever; >= 0 — one of the other
+// dense rules, known at compile time (csrc/drx_opt.hpp)
+template <int G, int J, bool WANT_LOSS, int KIND>
 __global__ __launch_bounds__(kBlock) void k_out_dense(DrxCdaeParams P, DrxOptim opt, OutDenseArgs A) {
   extern __shared__ __align__(16) float lds[];
   constexpr int R = kBlock / G;
@@ -196,13 +199,14 @@ __global__ __launch_bounds__(kBlock) void k_out_dense(DrxCdaeParams P, DrxOptim 
           }
         }
         if (sb + 1 == A.n_sub) {
-          reg_acc += row_update<G, J>(oW, P.W2T, opt.s1[1], opt.s2[1], (size_t)n, ld, lane, w, gw);
+          reg_acc += row_update_rule<G, J, KIND>(oW, P.W2T, opt.s1[1], opt.s2[1], (size_t)n, ld, lane, w, gw);
           if (lane == 0) {
-            float pb = bias, m = opt.s1[4][n], v = oB.kind == DRX_OPT_ADAM ? opt.s2[4][n] : 0.f;
+            float pb = bias, m = rule_has_s1<KIND>(oB) ? opt.s1[4][n] : 0.f, v = rule_has_s2<KIND>(oB) ? opt.s2[4][n] : 0.f;
             OptScalars ob = oB; ob.rb = 0.f;
-            opt_update1(ob, gb2, pb, m, v);
-            P.b2[n] = pb; opt.s1[4][n] = m;
-            if (oB.kind == DRX_OPT_ADAM) opt.s2[4][n] = v;
+            opt_update_rule<KIND>(ob, gb2, pb, m, v);
+            P.b2[n] = pb;
+            if (rule_has_s1<KIND>(oB)) opt.s1[4][n] = m;
+            if (rule_has_s2<KIND>(oB)) opt.s2[4][n] = v;
           }
         }
       }
@@ -231,7 +235,7 @@ __host__ __device__ inline size_t out_tile_lds_floats(int B, int ld) {
   return (size_t)B * (ld + 4) + (size_t)B * ld + (size_t)kTileR * (ld + 4) + (size_t)B * kTileR + 2 * kTileR;
 }
 
-template <bool WANT_LOSS>
+template <bool WANT_LOSS, int KIND>
 __global__ __launch_bounds__(kBlock) void k_out_dense_tile(DrxCdaeParams P, DrxOptim opt, OutDenseArgs A) {
   constexpr int R = kTileR;
   extern __shared__ __align__(16) float lds[];
@@ -314,15 +318,17 @@ __global__ __launch_bounds__(kBlock) void k_out_dense_tile(DrxCdaeParams P, DrxO
       for (int b = 0; b < B; ++b) f4_fma(g, dz_s[b * R + r], reinterpret_cast<const float4 *>(h_s + (size_t)b * ldp)[c]);
       float4 p = reinterpret_cast<const float4 *>(w_s + (size_t)r * ldp)[c];
       float4 *pw = reinterpret_cast<float4 *>(P.W2T + (size_t)n * ld) + c;
-      float4 *p1 = reinterpret_cast<float4 *>(opt.s1[1] + (size_t)n * ld) + c;
-      float4 *p2 = oW.kind == DRX_OPT_ADAM ? reinterpret_cast<float4 *>(opt.s2[1] + (size_t)n * ld) + c : nullptr;
-      float4 m = *p1, v = p2 ? *p2 : f4_zero();
+      const bool h1 = rule_has_s1<KIND>(oW);         // (KIND < 0: a constant true)
+      float4 *p1 = h1 ? reinterpret_cast<float4 *>(opt.s1[1] + (size_t)n * ld) + c : nullptr;
+      float4 *p2 = rule_has_s2<KIND>(oW) ? reinterpret_cast<float4 *>(opt.s2[1] + (size_t)n * ld) + c : nullptr;
+      float4 m = h1 ? *p1 : f4_zero(), v = p2 ? *p2 : f4_zero();
       reg_acc += f4_dot(p, p);
-      opt_update1(oW, fmaf(oW.rb, p.x, g.x), p.x, m.x, v.x);
-      opt_update1(oW, fmaf(oW.rb, p.y, g.y), p.y, m.y, v.y);
-      opt_update1(oW, fmaf(oW.rb, p.z, g.z), p.z, m.z, v.z);
-      opt_update1(oW, fmaf(oW.rb, p.w, g.w), p.w, m.w, v.w);
-      *pw = p; *p1 = m;
+      opt_update_rule<KIND>(oW, fmaf(oW.rb, p.x, g.x), p.x, m.x, v.x);
+      opt_update_rule<KIND>(oW, fmaf(oW.rb, p.y, g.y), p.y, m.y, v.y);
+      opt_update_rule<KIND>(oW, fmaf(oW.rb, p.z, g.z), p.z, m.z, v.z);
+      opt_update_rule<KIND>(oW, fmaf(oW.rb, p.w, g.w), p.w, m.w, v.w);
+      *pw = p;
+      if (h1) *p1 = m;
       if (p2) *p2 = v;
     }
     if (threadIdx.x >= kBlock - R) {             // the last R threads (idle in B for every supported width): the unit's bias
@@ -330,11 +336,12 @@ __global__ __launch_bounds__(kBlock) void k_out_dense_tile(DrxCdaeParams P, DrxO
       if (n < P.n_items) {
         float gb2 = 0.f;
         for (int b = 0; b < B; ++b) gb2 += dz_s[b * R + r];
-        float pb = bias_s[r], m = opt.s1[4][n], v = oB.kind == DRX_OPT_ADAM ? opt.s2[4][n] : 0.f;
+        float pb = bias_s[r], m = rule_has_s1<KIND>(oB) ? opt.s1[4][n] : 0.f, v = rule_has_s2<KIND>(oB) ? opt.s2[4][n] : 0.f;
         OptScalars ob = oB; ob.rb = 0.f;
-        opt_update1(ob, gb2, pb, m, v);
-        P.b2[n] = pb; opt.s1[4][n] = m;
-        if (oB.kind == DRX_OPT_ADAM) opt.s2[4][n] = v;
+        opt_update_rule<KIND>(ob, gb2, pb, m, v);
+        P.b2[n] = pb;
+        if (rule_has_s1<KIND>(oB)) opt.s1[4][n] = m;
+        if (rule_has_s2<KIND>(oB)) opt.s2[4][n] = v;
       }
     }
   }
@@ -401,7 +408,7 @@ struct DensePrefetch {          // n16 16-byte words from src (pinned host memor
   size_t n16;
 };
 
-template <int G, int J>
+template <int G, int J, int KIND>
 __global__ __launch_bounds__(kBlock) void k_in_sweep(DrxCdaeParams P, DrxOptim opt, int B, float scale, DenseAux aux,
                                                      const float *__restrict__ dz1, float *reg_part, DensePrefetch pf) {
   __shared__ float red[kBlock / 64];
@@ -435,7 +442,7 @@ __global__ __launch_bounds__(kBlock) void k_in_sweep(DrxCdaeParams P, DrxOptim o
       load_row<G, J>(P.b, 0, ld, lane, w);
       OptScalars o = opt_for(opt, 3, B);
       o.rb = 0.f;
-      row_update<G, J>(o, P.b, opt.s1[3], opt.s2[3], 0, ld, lane, w, g);
+      row_update_rule<G, J, KIND>(o, P.b, opt.s1[3], opt.s2[3], 0, ld, lane, w, g);
     }
     if (threadIdx.x == 0) reg_part[blockIdx.x] = 0.f;
     return;
@@ -465,10 +472,10 @@ __global__ __launch_bounds__(kBlock) void k_in_sweep(DrxCdaeParams P, DrxOptim o
 #pragma unroll
       for (int j = 0; j < J; ++j) { g[j].x *= scale; g[j].y *= scale; g[j].z *= scale; g[j].w *= scale; }
       load_row<G, J>(P.W, rr, ld, lane, w);
-      reg_acc += row_update<G, J>(oW, P.W, opt.s1[0], opt.s2[0], rr, ld, lane, w, g);
+      reg_acc += row_update_rule<G, J, KIND>(oW, P.W, opt.s1[0], opt.s2[0], rr, ld, lane, w, g);
     } else {
       load_row<G, J>(P.V, rr, ld, lane, w);
-      reg_acc += row_update<G, J>(oV, P.V, opt.s1[2], opt.s2[2], rr, ld, lane, w, g);
+      reg_acc += row_update_rule<G, J, KIND>(oV, P.V, opt.s1[2], opt.s2[2], rr, ld, lane, w, g);
     }
   }
   float rsum = block_sum(reg_acc, red);
@@ -606,9 +613,9 @@ static int step_dense_impl(const DrxCdaeParams *p, const DrxOptim *opt, const Dr
   if (rc) return rc;
   rc = check_batch(hist, bt);
   if (rc || !opt || !scratch) return DRX_EINVAL;
-  if (opt->kind != DRX_OPT_ADAM && opt->kind != DRX_OPT_ADAGRAD) return DRX_EINVAL;
+  if (!opt_dense_kind(opt->kind)) return DRX_EINVAL;
   for (int i = 0; i < 5; ++i)
-    if (!opt->s1[i] || (opt->kind == DRX_OPT_ADAM && !opt->s2[i])) return DRX_EINVAL;
+    if (!opt_slots_ok(opt->kind, opt->s1[i], opt->s2[i])) return DRX_EINVAL;
   hipStream_t st = (hipStream_t)stream;
   Carver cv(scratch, scratch_bytes);
   // DRX_DENSE_AUX_CLEAN: the caller vouches that the batch-membership arrays in `scratch` are all zero — true for zero-initialised
@@ -628,6 +635,8 @@ static int step_dense_impl(const DrxCdaeParams *p, const DrxOptim *opt, const Dr
   A.gbuf = L.gbuf; A.gb2buf = L.gb2buf; A.dh_slab = L.dh_slab; A.loss_part = L.loss_part; A.reg_part = L.reg_part1;
   A.loss_kind = loss_kind;
   const int total_rows = p->n_items + p->n_users;
+  return dispatch_opt_kind_keep_adam(opt->kind, [&](auto kc) -> int {
+  constexpr int KIND = decltype(kc)::value;
   return dispatch_geom(p->ld, [&](auto g) -> int {
     constexpr int G = decltype(g)::G, J = decltype(g)::J;
     constexpr int gpb = kBlock / G;
@@ -642,8 +651,8 @@ static int step_dense_impl(const DrxCdaeParams *p, const DrxOptim *opt, const Dr
     else
       hipLaunchKernelGGL((k_hidden_fwd<G, J, 1>), dim3((bt->B + gpb - 1) / gpb), dim3(kBlock), 0, st, *p, *hist, *bt, scale, qthr, L.h,
                          aux);
-    const OutDenseKernel out = L.tile_path ? (loss_out ? k_out_dense_tile<true> : k_out_dense_tile<false>)
-                                           : (loss_out ? k_out_dense<G, J, true> : k_out_dense<G, J, false>);
+    const OutDenseKernel out = L.tile_path ? (loss_out ? k_out_dense_tile<true, KIND> : k_out_dense_tile<false, KIND>)
+                                           : (loss_out ? k_out_dense<G, J, true, KIND> : k_out_dense<G, J, false, KIND>);
     const int orc = launch_out_dense(out, L, *p, *opt, A, st);
     if (orc) return orc;
     if (bt->B <= kFewRows && L.out_grid > 16 * gpb)          // many partial slabs per row: 1024 threads fold them
@@ -654,12 +663,13 @@ static int step_dense_impl(const DrxCdaeParams *p, const DrxOptim *opt, const Dr
                          L.dh_slab, L.h, L.dz1);
     int sweep = (total_rows + gpb - 1) / gpb;
     if (sweep > kSweepGrid) sweep = kSweepGrid;
-    hipLaunchKernelGGL((k_in_sweep<G, J>), dim3(sweep + 1), dim3(kBlock), 0, st, *p, *opt, bt->B, scale, aux, L.dz1, L.reg_part2, pf);
+    hipLaunchKernelGGL((k_in_sweep<G, J, KIND>), dim3(sweep + 1), dim3(kBlock), 0, st, *p, *opt, bt->B, scale, aux, L.dz1, L.reg_part2, pf);
     if (loss_out)
       hipLaunchKernelGGL(k_loss_final, dim3(1), dim3(64), 0, st, L.loss_part, L.out_grid, L.reg_part1, L.out_grid, L.reg_part2, sweep + 1,
                          0.5f * opt->reg_rate / (float)bt->B, loss_out);
     DRX_LAUNCH_CHECK();
     return DRX_OK;
+  });
   });
 }
 

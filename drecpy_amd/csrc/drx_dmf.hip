@@ -9,6 +9,7 @@
 // leaves as (row key, sample, coefficient) touches + one dz0 row per sample for drx_scatter_rows.
 #include "drx_common.hpp"
 #include "drx_rows.hpp"
+#include "drx_opt.hpp"
 
 namespace drx {
 
@@ -363,6 +364,9 @@ struct K0Tables {
 // A workgroup per row left four fifths of its lanes idle on the average row (193 entries against 1024 per round) and kept a CU at 8 rows
 // in flight; a wave per row keeps 32.  Same walk, the wave's own 256 entries per round, no cross-wave combine.
 constexpr int kK0WaveMax = 1024;
+// KIND (here and in k_dmf_k0_update): the update rule, a dense DRX_OPT_* known at compile time; U.m / U.v of a rule without that slot are
+// NULL and are neither read nor written (csrc/drx_opt.hpp)
+template <int KIND>
 __device__ __forceinline__ void k0_update_wave_row(const DrxDmfDims &D, const DrxDmfArgs &A, const K0Tables &U, int row, int (*hd)[64],
                                                    float (*hc)[64]) {
   const int k = threadIdx.x & 63, w = threadIdx.x >> 6, r = k >> 4, c = k & 15;
@@ -381,8 +385,8 @@ __device__ __forceinline__ void k0_update_wave_row(const DrxDmfDims &D, const Dr
   const size_t at = (size_t)n * ld0 + 4 * c;
   if (upd) {
     p = *reinterpret_cast<const float4 *>(U.K0[tw] + at);
-    m = *reinterpret_cast<const float4 *>(U.m[tw] + at);
-    v = *reinterpret_cast<const float4 *>(U.v[tw] + at);
+    if (opt_has_s1(KIND)) m = *reinterpret_cast<const float4 *>(U.m[tw] + at);
+    if (opt_has_s2(KIND)) v = *reinterpret_cast<const float4 *>(U.v[tw] + at);
   }
   const int64_t s = ip[n], e = ip[n + 1];
   float4 acc = f4_zero();
@@ -438,17 +442,18 @@ __device__ __forceinline__ void k0_update_wave_row(const DrxDmfDims &D, const Dr
   acc.x += __shfl_xor(acc.x, 16); acc.y += __shfl_xor(acc.y, 16); acc.z += __shfl_xor(acc.z, 16); acc.w += __shfl_xor(acc.w, 16);
   acc.x += __shfl_xor(acc.x, 32); acc.y += __shfl_xor(acc.y, 32); acc.z += __shfl_xor(acc.z, 32); acc.w += __shfl_xor(acc.w, 32);
   if (upd) {
-    const OptScalars o{DRX_OPT_ADAM, 0.f, 0.f, U.b1, U.b2, U.eps, U.alpha[tw]};
-    opt_update1(o, fmaf(U.l2c, p.x, acc.x), p.x, m.x, v.x);
-    opt_update1(o, fmaf(U.l2c, p.y, acc.y), p.y, m.y, v.y);
-    opt_update1(o, fmaf(U.l2c, p.z, acc.z), p.z, m.z, v.z);
-    opt_update1(o, fmaf(U.l2c, p.w, acc.w), p.w, m.w, v.w);
+    const OptScalars o{KIND, U.alpha[tw], 0.f, U.b1, U.b2, U.eps, U.alpha[tw]};
+    opt_update_dense<KIND>(o, fmaf(U.l2c, p.x, acc.x), p.x, m.x, v.x);
+    opt_update_dense<KIND>(o, fmaf(U.l2c, p.y, acc.y), p.y, m.y, v.y);
+    opt_update_dense<KIND>(o, fmaf(U.l2c, p.z, acc.z), p.z, m.z, v.z);
+    opt_update_dense<KIND>(o, fmaf(U.l2c, p.w, acc.w), p.w, m.w, v.w);
     *reinterpret_cast<float4 *>(U.K0[tw] + at) = p;
-    *reinterpret_cast<float4 *>(U.m[tw] + at) = m;
-    *reinterpret_cast<float4 *>(U.v[tw] + at) = v;
+    if (opt_has_s1(KIND)) *reinterpret_cast<float4 *>(U.m[tw] + at) = m;
+    if (opt_has_s2(KIND)) *reinterpret_cast<float4 *>(U.v[tw] + at) = v;
   }
 }
 
+template <int KIND>
 __global__ __launch_bounds__(256) void k_dmf_k0_update(DrxDmfDims D, DrxDmfArgs A, K0Tables U) {
   __shared__ int hd[4][64];
   __shared__ float hc[4][64];
@@ -456,7 +461,7 @@ __global__ __launch_bounds__(256) void k_dmf_k0_update(DrxDmfDims D, DrxDmfArgs 
   const int k = threadIdx.x & 63, w = threadIdx.x >> 6, r = k >> 4, c = k & 15;
   if (U.order && (int)blockIdx.x >= U.n_long) {      // a workgroup of four short rows, a wave each (whole waves leave: no barrier in there)
     const int i = U.n_long + ((int)blockIdx.x - U.n_long) * 4 + w;
-    if (i < U.rows[0] + U.rows[1]) k0_update_wave_row(D, A, U, U.order[i], hd, hc);
+    if (i < U.rows[0] + U.rows[1]) k0_update_wave_row<KIND>(D, A, U, U.order[i], hd, hc);
     return;
   }
   const int row = U.order ? U.order[blockIdx.x] : (int)blockIdx.x;
@@ -475,8 +480,8 @@ __global__ __launch_bounds__(256) void k_dmf_k0_update(DrxDmfDims D, DrxDmfArgs 
   const size_t at = (size_t)n * ld0 + 4 * c;
   if (upd) {                                         // (issued before the scan: the row is not written by anyone else)
     p = *reinterpret_cast<const float4 *>(U.K0[tw] + at);
-    m = *reinterpret_cast<const float4 *>(U.m[tw] + at);
-    v = *reinterpret_cast<const float4 *>(U.v[tw] + at);
+    if (opt_has_s1(KIND)) m = *reinterpret_cast<const float4 *>(U.m[tw] + at);
+    if (opt_has_s2(KIND)) v = *reinterpret_cast<const float4 *>(U.v[tw] + at);
   }
   const int64_t s = ip[n], e = ip[n + 1];
   float4 acc = f4_zero();
@@ -537,14 +542,14 @@ __global__ __launch_bounds__(256) void k_dmf_k0_update(DrxDmfDims D, DrxDmfArgs 
   if (upd) {
     float4 g = part[0][c];
     f4_add(g, part[1][c]); f4_add(g, part[2][c]); f4_add(g, part[3][c]);
-    const OptScalars o{DRX_OPT_ADAM, 0.f, 0.f, U.b1, U.b2, U.eps, U.alpha[tw]};
-    opt_update1(o, fmaf(U.l2c, p.x, g.x), p.x, m.x, v.x);
-    opt_update1(o, fmaf(U.l2c, p.y, g.y), p.y, m.y, v.y);
-    opt_update1(o, fmaf(U.l2c, p.z, g.z), p.z, m.z, v.z);
-    opt_update1(o, fmaf(U.l2c, p.w, g.w), p.w, m.w, v.w);
+    const OptScalars o{KIND, U.alpha[tw], 0.f, U.b1, U.b2, U.eps, U.alpha[tw]};
+    opt_update_dense<KIND>(o, fmaf(U.l2c, p.x, g.x), p.x, m.x, v.x);
+    opt_update_dense<KIND>(o, fmaf(U.l2c, p.y, g.y), p.y, m.y, v.y);
+    opt_update_dense<KIND>(o, fmaf(U.l2c, p.z, g.z), p.z, m.z, v.z);
+    opt_update_dense<KIND>(o, fmaf(U.l2c, p.w, g.w), p.w, m.w, v.w);
     *reinterpret_cast<float4 *>(U.K0[tw] + at) = p;
-    *reinterpret_cast<float4 *>(U.m[tw] + at) = m;
-    *reinterpret_cast<float4 *>(U.v[tw] + at) = v;
+    if (opt_has_s1(KIND)) *reinterpret_cast<float4 *>(U.m[tw] + at) = m;
+    if (opt_has_s2(KIND)) *reinterpret_cast<float4 *>(U.v[tw] + at) = v;
   }
 }
 
@@ -892,11 +897,12 @@ __global__ __launch_bounds__(1024) void k_sum_partials2(const float *__restrict_
   }
 }
 
-// k_sum_partials2 with the small weights' Keras Adam behind it (as drx_caser.hip's k_sum_partials_adam): the thread that has column j's
-// sum applies l2 + Adam of j's segment — one launch instead of two, the same operations in the same order.
-__global__ __launch_bounds__(1024) void k_sum_partials2_adam(const float *__restrict__ part, int n_rows, int n, const float *__restrict__ tail,
-                                                             float *__restrict__ out, float *p, float *m, float *v, DrxAdamSegments sg,
-                                                             float b1, float b2, float eps) {
+// k_sum_partials2 with the small weights' update behind it (as drx_caser.hip's k_sum_partials_opt): the thread that has column j's
+// sum applies l2 + the rule of j's segment — one launch instead of two, the same operations in the same order.
+// (kind: the dense rule, at run time — a small launch; m / v of a rule without that slot are NULL and are not touched)
+__global__ __launch_bounds__(1024) void k_sum_partials2_opt(const float *__restrict__ part, int n_rows, int n, const float *__restrict__ tail,
+                                                            float *__restrict__ out, float *p, float *m, float *v, DrxAdamSegments sg,
+                                                            int kind, float b1, float b2, float eps) {
   __shared__ float red[16][64];
   const int c = threadIdx.x & 63, q = threadIdx.x >> 6;
   const int j = blockIdx.x * 64 + c;
@@ -915,10 +921,13 @@ __global__ __launch_bounds__(1024) void k_sum_partials2_adam(const float *__rest
       for (int k = 0; k < sg.n; ++k)
         if (j >= sg.start[k] && j < sg.start[k] + sg.len[k]) sgi = k;
       if (sgi >= 0) {
-        const OptScalars o{DRX_OPT_ADAM, 0.f, 0.f, b1, b2, eps, sg.alpha[sgi]};
-        float pp = p[j], mm = m[j], vv = v[j];
-        opt_update1(o, fmaf(sg.l2_coef[sgi], pp, t), pp, mm, vv);
-        p[j] = pp; m[j] = mm; v[j] = vv;
+        const OptScalars o{kind, sg.alpha[sgi], 0.f, b1, b2, eps, sg.alpha[sgi]};
+        const bool h1 = opt_has_s1(kind), h2 = opt_has_s2(kind);
+        float pp = p[j], mm = h1 ? m[j] : 0.f, vv = h2 ? v[j] : 0.f;
+        opt_update_dense<-1>(o, fmaf(sg.l2_coef[sgi], pp, t), pp, mm, vv);
+        p[j] = pp;
+        if (h1) m[j] = mm;
+        if (h2) v[j] = vv;
       }
     }
   }
@@ -1180,22 +1189,32 @@ size_t drx_dmf_work_bytes(int32_t B) {
 }
 
 static int dmf_fwd_bwd_impl(const DrxDmfDims *D, const DrxDmfArgs *A, float *gsw_out, float *sw, float *sw_m, float *sw_v,
-                            const DrxAdamSegments *sg, float beta1, float beta2, float eps, void *stream);
+                            const DrxAdamSegments *sg, const DrxOptRule *rule, void *stream);
 
 int drx_dmf_fwd_bwd(const DrxDmfDims *D, const DrxDmfArgs *A, float *gsw_out, void *stream) {
-  return dmf_fwd_bwd_impl(D, A, gsw_out, nullptr, nullptr, nullptr, nullptr, 0.f, 0.f, 0.f, stream);
+  return dmf_fwd_bwd_impl(D, A, gsw_out, nullptr, nullptr, nullptr, nullptr, nullptr, stream);
 }
 
 // drx_dmf_fwd_bwd with the small weights' Keras Adam in the launch that sums the chunks' partial gradients (drx_adam_segments' work; the
 // first-layer update — drx_dmf_k0_update — reads none of `sw` and may follow)
+int drx_dmf_step_small_opt(const DrxDmfDims *D, const DrxDmfArgs *A, float *gsw_out, float *sw, float *sw_m, float *sw_v,
+                           const DrxAdamSegments *sg, const DrxOptRule *rule, void *stream) {
+  if (!sw || !rule || !opt_dense_kind(rule->kind) || !opt_slots_ok(rule->kind, sw_m, sw_v) || !sg || sg->n < 1 || sg->n > DRX_MAX_SEGMENTS ||
+      (A && sw != A->sw))
+    return DRX_EINVAL;
+  if (!opt_has_s1(rule->kind)) sw_m = nullptr;
+  if (!opt_has_s2(rule->kind)) sw_v = nullptr;
+  return dmf_fwd_bwd_impl(D, A, gsw_out, sw, sw_m, sw_v, sg, rule, stream);
+}
+
 int drx_dmf_step_small(const DrxDmfDims *D, const DrxDmfArgs *A, float *gsw_out, float *sw, float *sw_m, float *sw_v,
                        const DrxAdamSegments *sg, float beta1, float beta2, float eps, void *stream) {
-  if (!sw || !sw_m || !sw_v || !sg || sg->n < 1 || sg->n > DRX_MAX_SEGMENTS || (A && sw != A->sw)) return DRX_EINVAL;
-  return dmf_fwd_bwd_impl(D, A, gsw_out, sw, sw_m, sw_v, sg, beta1, beta2, eps, stream);
+  const DrxOptRule rule{DRX_OPT_ADAM, 0.f, beta1, beta2, eps};
+  return drx_dmf_step_small_opt(D, A, gsw_out, sw, sw_m, sw_v, sg, &rule, stream);
 }
 
 static int dmf_fwd_bwd_impl(const DrxDmfDims *D, const DrxDmfArgs *A, float *gsw_out, float *sw, float *sw_m, float *sw_v,
-                            const DrxAdamSegments *sg, float beta1, float beta2, float eps, void *stream) {
+                            const DrxAdamSegments *sg, const DrxOptRule *rule, void *stream) {
   int rc = check_dims(D);
   if (rc) return rc;
   if (!A || !A->K0u || !A->K0i || !A->sw || !A->u_indptr || !A->u_indices || !A->u_values || !A->i_indptr || !A->i_indices ||
@@ -1251,8 +1270,8 @@ static int dmf_fwd_bwd_impl(const DrxDmfDims *D, const DrxDmfArgs *A, float *gsw
   hipLaunchKernelGGL(k_dmf_dzsum, dim3((items + 3) / 4 < 2048 ? (items + 3) / 4 : 2048), dim3(256), 0, st, *D, *A, W);
   hipLaunchKernelGGL(k_dmf_wgrad, dim3((D->n_small + 1 + 255) / 256, chunks), dim3(256), 0, st, *D, *A, chunk, W);
   if (sg)
-    hipLaunchKernelGGL(k_sum_partials2_adam, dim3((D->n_small + 64) / 64), dim3(1024), 0, st, A->gsw_part, chunks, D->n_small,
-                       A->loss_part, gsw_out, sw, sw_m, sw_v, *sg, beta1, beta2, eps);
+    hipLaunchKernelGGL(k_sum_partials2_opt, dim3((D->n_small + 64) / 64), dim3(1024), 0, st, A->gsw_part, chunks, D->n_small,
+                       A->loss_part, gsw_out, sw, sw_m, sw_v, *sg, rule->kind, rule->mu, rule->mu2, rule->eps);
   else
     hipLaunchKernelGGL(k_sum_partials2, dim3((D->n_small + 64) / 64), dim3(1024), 0, st, A->gsw_part, chunks, D->n_small,
                        A->loss_part, gsw_out);
@@ -1276,13 +1295,17 @@ int drx_dmf_k0_update(const DrxDmfDims *D, const DrxDmfArgs *A, const DrxDmfK0Up
   if (!A || !up || !A->u_indptr || !A->u_indices || !A->u_values || !A->i_indptr || !A->i_indices || !A->i_values || !A->dz0u ||
       !A->dz0i || !A->map_u || !A->map_i || !A->rho_u || !A->rho_i || A->stamp == 0 || up->n_items < 1 || up->n_users < 1)
     return DRX_EINVAL;
-  if (!up->K0u || !up->K0i || !up->m_u || !up->m_i || !up->v_u || !up->v_i) return DRX_EINVAL;
-  if (D->ld0[0] > 64 || D->ld0[1] > 64) return DRX_EINVAL;      // (a quarter-wave per dz0 row; wider first layers: touches + drx_scatter_rows)
-  if (((uintptr_t)up->K0u | (uintptr_t)up->K0i | (uintptr_t)up->m_u | (uintptr_t)up->m_i | (uintptr_t)up->v_u | (uintptr_t)up->v_i |
-       (uintptr_t)A->dz0u | (uintptr_t)A->dz0i) & 15)
+  const int kind = up->opt_kind;
+  if (!opt_dense_kind(kind) || !up->K0u || !up->K0i || !opt_slots_ok(kind, up->m_u, up->v_u) || !opt_slots_ok(kind, up->m_i, up->v_i))
     return DRX_EINVAL;
+  if (D->ld0[0] > 64 || D->ld0[1] > 64) return DRX_EINVAL;      // (a quarter-wave per dz0 row; wider first layers: touches + drx_scatter_rows)
   K0Tables U{{up->K0u, up->K0i}, {up->m_u, up->m_i}, {up->v_u, up->v_i}, {up->n_items, up->n_users}, {up->alpha_u, up->alpha_i},
              up->l2_coef, up->beta1, up->beta2, up->eps, up->row_order, 0};
+  if (!opt_has_s1(kind)) U.m[0] = U.m[1] = nullptr;
+  if (!opt_has_s2(kind)) U.v[0] = U.v[1] = nullptr;
+  if (((uintptr_t)up->K0u | (uintptr_t)up->K0i | (uintptr_t)U.m[0] | (uintptr_t)U.m[1] | (uintptr_t)U.v[0] | (uintptr_t)U.v[1] |
+       (uintptr_t)A->dz0u | (uintptr_t)A->dz0i) & 15)
+    return DRX_EINVAL;
   const int rows = up->n_items + up->n_users;
   int grid = rows;
   if (up->row_order) {                               // the order's first n_long rows: a workgroup each; the others a wave each
@@ -1290,9 +1313,11 @@ int drx_dmf_k0_update(const DrxDmfDims *D, const DrxDmfArgs *A, const DrxDmfK0Up
     U.n_long = up->n_long;
     grid = up->n_long + (rows - up->n_long + 3) / 4;
   }
-  hipLaunchKernelGGL(k_dmf_k0_update, dim3((unsigned)grid), dim3(256), 0, (hipStream_t)stream, *D, *A, U);
-  DRX_LAUNCH_CHECK();
-  return DRX_OK;
+  return dispatch_opt_kind(kind, [&](auto kc) -> int {
+    hipLaunchKernelGGL(k_dmf_k0_update<decltype(kc)::value>, dim3((unsigned)grid), dim3(256), 0, (hipStream_t)stream, *D, *A, U);
+    DRX_LAUNCH_CHECK();
+    return DRX_OK;
+  });
 }
 
 int drx_dmf_predict(const DrxDmfDims *D, const DrxDmfArgs *A, void *stream) {

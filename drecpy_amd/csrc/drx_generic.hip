@@ -1,39 +1,46 @@
 // Model-independent pieces of the reference-mode ("dense Keras Adam") steps of DMF and Caser:
-//   drx_adam_dense   : fused L2 + Keras-Adam sweep over a flat parameter array (replaces one
-//                      optimizer.apply_gradients of recommender_abc.py:328-334): p, m, v read once / written once
+//   drx_opt_dense    : fused L2 + one dense update rule (drx.h DrxOptRule; csrc/drx_opt.hpp) over a flat parameter array (SURVEY.md H4;
+//                      replaces one optimizer.apply_gradients of recommender_abc.py:328-334): p and the rule's slots read once /
+//                      written once; drx_adam_dense is this with the Adam rule
 //   drx_scatter_rows : deterministic scatter-add of per-touch gradient rows into a dense gradient table
 //                      (what tape.gradient does for tf.nn.embedding_lookup / Keras Embedding inputs): stable sort of
 //                      the touches by destination row + the segmented reduction of drx_segreduce.hpp
 //   drx_rows_dot     : scores[b, n] = x_b . T[n] (+ bias[n]) for all rows n (all-item scoring of _rank)
 #include "drx_common.hpp"
 #include "drx_rows.hpp"
+#include "drx_opt.hpp"
 #include "drx_segreduce.hpp"
 
 namespace drx {
 
-__global__ __launch_bounds__(kBlock) void k_adam_dense(float *__restrict__ p, float *__restrict__ m, float *__restrict__ v,
-                                                       const float *__restrict__ g, size_t n, float alpha, float l2c, float b1,
-                                                       float b2, float eps) {
+// One dense rule (o.kind at run time: a small launch) over a flat array; s1 / s2 of a rule without them are NULL and are not touched.
+__global__ __launch_bounds__(kBlock) void k_opt_dense(float *__restrict__ p, float *__restrict__ m, float *__restrict__ v,
+                                                      const float *__restrict__ g, size_t n, OptScalars o, float l2c) {
   const size_t n4 = n / 4;
+  const bool h1 = opt_has_s1(o.kind), h2 = opt_has_s2(o.kind);
   for (size_t i = blockIdx.x * (size_t)kBlock + threadIdx.x; i < n4; i += (size_t)gridDim.x * kBlock) {
-    float4 pp = reinterpret_cast<float4 *>(p)[i], mm = reinterpret_cast<float4 *>(m)[i], vv = reinterpret_cast<float4 *>(v)[i];
+    float4 pp = reinterpret_cast<float4 *>(p)[i], mm = h1 ? reinterpret_cast<float4 *>(m)[i] : f4_zero(),
+           vv = h2 ? reinterpret_cast<float4 *>(v)[i] : f4_zero();
     float4 gg = g ? reinterpret_cast<const float4 *>(g)[i] : f4_zero();
-    OptScalars o{DRX_OPT_ADAM, 0.f, 0.f, b1, b2, eps, alpha};
-    opt_update1(o, fmaf(l2c, pp.x, gg.x), pp.x, mm.x, vv.x);
-    opt_update1(o, fmaf(l2c, pp.y, gg.y), pp.y, mm.y, vv.y);
-    opt_update1(o, fmaf(l2c, pp.z, gg.z), pp.z, mm.z, vv.z);
-    opt_update1(o, fmaf(l2c, pp.w, gg.w), pp.w, mm.w, vv.w);
-    reinterpret_cast<float4 *>(p)[i] = pp; reinterpret_cast<float4 *>(m)[i] = mm; reinterpret_cast<float4 *>(v)[i] = vv;
+    opt_update_dense<-1>(o, fmaf(l2c, pp.x, gg.x), pp.x, mm.x, vv.x);
+    opt_update_dense<-1>(o, fmaf(l2c, pp.y, gg.y), pp.y, mm.y, vv.y);
+    opt_update_dense<-1>(o, fmaf(l2c, pp.z, gg.z), pp.z, mm.z, vv.z);
+    opt_update_dense<-1>(o, fmaf(l2c, pp.w, gg.w), pp.w, mm.w, vv.w);
+    reinterpret_cast<float4 *>(p)[i] = pp;
+    if (h1) reinterpret_cast<float4 *>(m)[i] = mm;
+    if (h2) reinterpret_cast<float4 *>(v)[i] = vv;
   }
   if (blockIdx.x == 0 && threadIdx.x < (n & 3)) {
     const size_t i = n4 * 4 + threadIdx.x;
-    float pp = p[i], mm = m[i], vv = v[i];
-    OptScalars o{DRX_OPT_ADAM, 0.f, 0.f, b1, b2, eps, alpha};
-    opt_update1(o, fmaf(l2c, pp, g ? g[i] : 0.f), pp, mm, vv);
-    p[i] = pp; m[i] = mm; v[i] = vv;
+    float pp = p[i], mm = h1 ? m[i] : 0.f, vv = h2 ? v[i] : 0.f;
+    opt_update_dense<-1>(o, fmaf(l2c, pp, g ? g[i] : 0.f), pp, mm, vv);
+    p[i] = pp;
+    if (h1) m[i] = mm;
+    if (h2) v[i] = vv;
   }
 }
 
+// (drx_rows_csr_opt and its forms; drx_rows_csr_adam* are these with the Adam rule.)
 // A table whose gradient is a sum of lookup rows AND whose optimizer is dense (Keras Adam on an Embedding / Dense kernel: the
 // moments of every row decay every step): gradient and update in one pass over the table, from the lookups grouped by row on the
 // host (drx_batch_csr: counting sort, lookups of a row in batch order).  One group of G lanes per row:
@@ -44,15 +51,18 @@ __global__ __launch_bounds__(kBlock) void k_adam_dense(float *__restrict__ p, fl
 // blk of n_blk: this workgroup's share of the table's rows (a launch of its own, or a table's part of drx_rows_csr_adam_multi's).
 constexpr int kCsrSplit = 64;     // lookups from which a row's sum is split over the groups of its workgroup
 
-template <int G, int J, bool OUTER>
-__device__ __forceinline__ void rows_csr_adam_body(const int32_t *__restrict__ ptr, const int32_t *__restrict__ order,
-                                                   const float *__restrict__ src, const float *__restrict__ src_s, int ld, int n_rows,
-                                                   float *p, float *m, float *v, float *ps, float *ms, float *vs, float alpha,
-                                                   float alpha_s, float l2c, float b1, float b2, float eps, int group, int blk, int n_blk,
-                                                   float *part /* LDS [kBlock / G][4 * G * J] */, float *part_s /* LDS [kBlock / G] */,
-                                                   int *cnt /* LDS [kBlock / G] */) {
+// KIND: the rule, at compile time (b1 / b2: DrxOptRule's mu / mu2; alpha / alpha_s: the step sizes).  m / v (ms / vs) of a rule without that
+// slot are NULL: never loaded, never stored.  KIND = DRX_OPT_ADAM is the kernel this was before the other rules came.
+template <int G, int J, bool OUTER, int KIND>
+__device__ __forceinline__ void rows_csr_body(const int32_t *__restrict__ ptr, const int32_t *__restrict__ order,
+                                              const float *__restrict__ src, const float *__restrict__ src_s, int ld, int n_rows,
+                                              float *p, float *m, float *v, float *ps, float *ms, float *vs, float alpha,
+                                              float alpha_s, float l2c, float b1, float b2, float eps, int group, int blk, int n_blk,
+                                              float *part /* LDS [kBlock / G][4 * G * J] */, float *part_s /* LDS [kBlock / G] */,
+                                              int *cnt /* LDS [kBlock / G] */) {
   const int lane = threadIdx.x % G, gid = threadIdx.x / G;
   constexpr int gpb = kBlock / G;
+  constexpr bool H1 = opt_has_s1(KIND), H2 = opt_has_s2(KIND);
   // g, gs += the gradient rows / scalars of the lookups [qa, qb) of the list, in list order, four rows in flight
   auto sum_range = [&](int qa, int qb, float4 (&g)[J], float &gs) __attribute__((always_inline)) {
     int q = qa;
@@ -85,9 +95,9 @@ __device__ __forceinline__ void rows_csr_adam_body(const int32_t *__restrict__ p
       }
     }
   };
-  // l2 + Keras Adam of table row `row` (and of its scalar) with the gradient g / gs
+  // l2 + the rule's update of table row `row` (and of its scalar) with the gradient g / gs
   auto apply = [&](int row, const float4 (&w)[J], float4 (&mm)[J], float4 (&vv)[J], const float4 (&g)[J], float gs) __attribute__((always_inline)) {
-    const OptScalars o{DRX_OPT_ADAM, 0.f, 0.f, b1, b2, eps, alpha};
+    const OptScalars o{KIND, alpha, 0.f, b1, b2, eps, alpha};
     float4 *pr = reinterpret_cast<float4 *>(p + (size_t)row * ld), *mr = reinterpret_cast<float4 *>(m + (size_t)row * ld),
            *vr = reinterpret_cast<float4 *>(v + (size_t)row * ld);
 #pragma unroll
@@ -95,18 +105,31 @@ __device__ __forceinline__ void rows_csr_adam_body(const int32_t *__restrict__ p
       const int c = lane + j * G;
       if (4 * c < ld) {
         float4 ww = w[j];
-        opt_update1(o, fmaf(l2c, ww.x, g[j].x), ww.x, mm[j].x, vv[j].x);
-        opt_update1(o, fmaf(l2c, ww.y, g[j].y), ww.y, mm[j].y, vv[j].y);
-        opt_update1(o, fmaf(l2c, ww.z, g[j].z), ww.z, mm[j].z, vv[j].z);
-        opt_update1(o, fmaf(l2c, ww.w, g[j].w), ww.w, mm[j].w, vv[j].w);
-        pr[c] = ww; mr[c] = mm[j]; vr[c] = vv[j];
+        opt_update_dense<KIND>(o, fmaf(l2c, ww.x, g[j].x), ww.x, mm[j].x, vv[j].x);
+        opt_update_dense<KIND>(o, fmaf(l2c, ww.y, g[j].y), ww.y, mm[j].y, vv[j].y);
+        opt_update_dense<KIND>(o, fmaf(l2c, ww.z, g[j].z), ww.z, mm[j].z, vv[j].z);
+        opt_update_dense<KIND>(o, fmaf(l2c, ww.w, g[j].w), ww.w, mm[j].w, vv[j].w);
+        pr[c] = ww;
+        if (H1) mr[c] = mm[j];
+        if (H2) vr[c] = vv[j];
       }
     }
     if (ps && lane == 0) {
-      const OptScalars os{DRX_OPT_ADAM, 0.f, 0.f, b1, b2, eps, alpha_s};
-      float pp = ps[row], pm = ms[row], pv = vs[row];
-      opt_update1(os, gs, pp, pm, pv);
-      ps[row] = pp; ms[row] = pm; vs[row] = pv;
+      const OptScalars os{KIND, alpha_s, 0.f, b1, b2, eps, alpha_s};
+      float pp = ps[row], pm = H1 ? ms[row] : 0.f, pv = H2 ? vs[row] : 0.f;
+      opt_update_dense<KIND>(os, gs, pp, pm, pv);
+      ps[row] = pp;
+      if (H1) ms[row] = pm;
+      if (H2) vs[row] = pv;
+    }
+  };
+  auto load_slots = [&](int row, float4 (&mm)[J], float4 (&vv)[J]) __attribute__((always_inline)) {
+    if (H1) load_row<G, J>(m, (size_t)row, ld, lane, mm);
+    if (H2) load_row<G, J>(v, (size_t)row, ld, lane, vv);
+#pragma unroll
+    for (int j = 0; j < J; ++j) {
+      if (!H1) mm[j] = f4_zero();
+      if (!H2) vv[j] = f4_zero();
     }
   };
   // A workgroup takes gpb rows at a time, a group each.  A row named by kCsrSplit lookups or more (a popular item: thousands at a
@@ -121,8 +144,7 @@ __device__ __forceinline__ void rows_csr_adam_body(const int32_t *__restrict__ p
     if (valid && q1 - q0 < kCsrSplit) {
       float4 w[J], mm[J], vv[J], g[J];
       load_row<G, J>(p, (size_t)row, ld, lane, w);
-      load_row<G, J>(m, (size_t)row, ld, lane, mm);
-      load_row<G, J>(v, (size_t)row, ld, lane, vv);
+      load_slots(row, mm, vv);
       float gs = 0.f;
 #pragma unroll
       for (int j = 0; j < J; ++j) g[j] = f4_zero();
@@ -146,8 +168,7 @@ __device__ __forceinline__ void rows_csr_adam_body(const int32_t *__restrict__ p
       if (gid == 0) {
         float4 w[J], mm[J], vv[J];
         load_row<G, J>(p, (size_t)hrow, ld, lane, w);
-        load_row<G, J>(m, (size_t)hrow, ld, lane, mm);
-        load_row<G, J>(v, (size_t)hrow, ld, lane, vv);
+        load_slots(hrow, mm, vv);
         gs = part_s[0];
         for (int kk = 1; kk < gpb; ++kk) {
           gs += part_s[kk];
@@ -162,22 +183,23 @@ __device__ __forceinline__ void rows_csr_adam_body(const int32_t *__restrict__ p
   }
 }
 
-template <int G, int J, bool OUTER>
-__global__ __launch_bounds__(kBlock) void k_rows_csr_adam(const int32_t *__restrict__ ptr, const int32_t *__restrict__ order,
-                                                          const float *__restrict__ src, const float *__restrict__ src_s, int ld,
-                                                          int n_rows, float *p, float *m, float *v, float *ps, float *ms, float *vs,
-                                                          float alpha, float alpha_s, float l2c, float b1, float b2, float eps, int group) {
+template <int G, int J, bool OUTER, int KIND>
+__global__ __launch_bounds__(kBlock) void k_rows_csr_opt(const int32_t *__restrict__ ptr, const int32_t *__restrict__ order,
+                                                         const float *__restrict__ src, const float *__restrict__ src_s, int ld,
+                                                         int n_rows, float *p, float *m, float *v, float *ps, float *ms, float *vs,
+                                                         float alpha, float alpha_s, float l2c, float b1, float b2, float eps, int group) {
   __shared__ __align__(16) float part[(kBlock / G) * 4 * G * J];
   __shared__ float part_s[kBlock / G];
   __shared__ int cnt[kBlock / G];
-  rows_csr_adam_body<G, J, OUTER>(ptr, order, src, src_s, ld, n_rows, p, m, v, ps, ms, vs, alpha, alpha_s, l2c, b1, b2, eps, group,
-                                  (int)blockIdx.x, (int)gridDim.x, part, part_s, cnt);
+  rows_csr_body<G, J, OUTER, KIND>(ptr, order, src, src_s, ld, n_rows, p, m, v, ps, ms, vs, alpha, alpha_s, l2c, b1, b2, eps, group,
+                                   (int)blockIdx.x, (int)gridDim.x, part, part_s, cnt);
 }
 
 // Several tables in one launch (Caser's three lookup tables: three launches of a few microseconds of work each spent most of their
 // time starting and draining): consecutive ranges of workgroups take a table each.
 struct CsrMulti { DrxCsrAdamTable t[DRX_MAX_CSR_TABLES]; int blocks[DRX_MAX_CSR_TABLES]; int n; };
-__global__ __launch_bounds__(kBlock) void k_rows_csr_adam_multi(CsrMulti M, float b1, float b2, float eps) {
+template <int KIND>
+__global__ __launch_bounds__(kBlock) void k_rows_csr_opt_multi(CsrMulti M, float b1, float b2, float eps) {
   int blk = blockIdx.x, ti = 0;
   while (ti + 1 < M.n && blk >= M.blocks[ti]) { blk -= M.blocks[ti]; ++ti; }
   const DrxCsrAdamTable &T = M.t[ti];
@@ -186,8 +208,8 @@ __global__ __launch_bounds__(kBlock) void k_rows_csr_adam_multi(CsrMulti M, floa
   __shared__ float part_s[kBlock / 4];
   __shared__ int cnt[kBlock / 4];
 #define BODY(G, OUTER)                                                                                                             \
-  rows_csr_adam_body<G, 1, OUTER>(T.row_ptr, T.order, T.src, T.scale, T.ld, T.n_rows, T.p, T.m, T.v, T.p_s, T.m_s, T.v_s, T.alpha,    \
-                                  T.alpha_s, T.l2_coef, b1, b2, eps, T.group, blk, nb, part, part_s, cnt)
+  rows_csr_body<G, 1, OUTER, KIND>(T.row_ptr, T.order, T.src, T.scale, T.ld, T.n_rows, T.p, T.m, T.v, T.p_s, T.m_s, T.v_s, T.alpha,   \
+                                   T.alpha_s, T.l2_coef, b1, b2, eps, T.group, blk, nb, part, part_s, cnt)
 #define GEOM(OUTER)                                         \
   do {                                                      \
     if (T.ld <= 16) BODY(4, OUTER);                         \
@@ -405,52 +427,81 @@ int drx_copy_f4_variant(void *dst, const void *src, size_t n_bytes, int32_t vari
 #endif
 int drx_copy_f4(void *dst, const void *src, size_t n_bytes, void *stream) { return drx_copy_f4_variant(dst, src, n_bytes, DRX_COPY_VARIANT, stream); }
 
-int drx_adam_dense(float *p, float *m, float *v, const float *g, int64_t n, float alpha, float l2_coef, float beta1, float beta2,
-                   float eps, void *stream) {
-  if (!p || !m || !v || n < 1) return DRX_EINVAL;
-  if (((uintptr_t)p | (uintptr_t)m | (uintptr_t)v | (uintptr_t)g) & 15) return DRX_EINVAL;
+int drx_opt_dense(float *p, float *s1, float *s2, const float *g, int64_t n, const DrxOptRule *rule, float l2_coef, void *stream) {
+  if (!p || !rule || n < 1 || !opt_dense_kind(rule->kind) || !opt_slots_ok(rule->kind, s1, s2)) return DRX_EINVAL;
+  if (!opt_has_s1(rule->kind)) s1 = nullptr;
+  if (!opt_has_s2(rule->kind)) s2 = nullptr;
+  if (((uintptr_t)p | (uintptr_t)s1 | (uintptr_t)s2 | (uintptr_t)g) & 15) return DRX_EINVAL;
   int blocks = (int)std::min<int64_t>((n / 4 + kBlock - 1) / kBlock + 1, 4096);
-  hipLaunchKernelGGL(k_adam_dense, dim3(blocks), dim3(kBlock), 0, (hipStream_t)stream, p, m, v, g, (size_t)n, alpha, l2_coef,
-                     beta1, beta2, eps);
+  const OptScalars o{rule->kind, rule->lr, 0.f, rule->mu, rule->mu2, rule->eps, rule->lr};
+  hipLaunchKernelGGL(k_opt_dense, dim3(blocks), dim3(kBlock), 0, (hipStream_t)stream, p, s1, s2, g, (size_t)n, o, l2_coef);
   DRX_LAUNCH_CHECK();
   return DRX_OK;
 }
 
-// the two entry points below: lookups' rows as they are / as scale[o] * src[o / group]
-static int rows_csr_adam(const int32_t *row_ptr, const int32_t *order, const float *src, const float *src_s, int32_t group, int32_t ld,
-                         int32_t n_rows, float *p, float *m, float *v, float *p_s, float *m_s, float *v_s, float alpha, float alpha_s,
-                         float l2_coef, float beta1, float beta2, float eps, void *stream) {
-  if (!row_ptr || !order || !src || !p || !m || !v || n_rows < 1 || ld < 4 || (ld & 3) || ld > DRX_MAX_K) return DRX_EINVAL;
-  if ((p_s != nullptr) != (src_s != nullptr) || (p_s && (!m_s || !v_s))) return DRX_EINVAL;
+int drx_adam_dense(float *p, float *m, float *v, const float *g, int64_t n, float alpha, float l2_coef, float beta1, float beta2,
+                   float eps, void *stream) {
+  const DrxOptRule rule{DRX_OPT_ADAM, alpha, beta1, beta2, eps};
+  return drx_opt_dense(p, m, v, g, n, &rule, l2_coef, stream);
+}
+
+// the entry points below: lookups' rows as they are / as scale[o] * src[o / group]
+static int rows_csr_opt(const int32_t *row_ptr, const int32_t *order, const float *src, const float *src_s, int32_t group, int32_t ld,
+                        int32_t n_rows, float *p, float *m, float *v, float *p_s, float *m_s, float *v_s, float alpha, float alpha_s,
+                        float l2_coef, const DrxOptRule *rule, void *stream) {
+  if (!rule || !opt_dense_kind(rule->kind)) return DRX_EINVAL;
+  const int kind = rule->kind;
+  if (!row_ptr || !order || !src || !p || !opt_slots_ok(kind, m, v) || n_rows < 1 || ld < 4 || (ld & 3) || ld > DRX_MAX_K) return DRX_EINVAL;
+  if ((p_s != nullptr) != (src_s != nullptr) || (p_s && !opt_slots_ok(kind, m_s, v_s))) return DRX_EINVAL;
+  if (!opt_has_s1(kind)) m = m_s = nullptr;
+  if (!opt_has_s2(kind)) v = v_s = nullptr;
   if (((uintptr_t)src | (uintptr_t)p | (uintptr_t)m | (uintptr_t)v) & 15) return DRX_EINVAL;
   hipStream_t st = (hipStream_t)stream;
-  return dispatch_geom(ld, [&](auto g) -> int {
-    constexpr int G = decltype(g)::G, J = decltype(g)::J;
-    constexpr int gpb = kBlock / G;
-    int blocks = (n_rows + gpb - 1) / gpb;
-    if (blocks > 8192) blocks = 8192;
-    if (group > 0)
-      hipLaunchKernelGGL((k_rows_csr_adam<G, J, true>), dim3(blocks), dim3(kBlock), 0, st, row_ptr, order, src, src_s, ld, n_rows, p, m, v,
-                         p_s, m_s, v_s, alpha, alpha_s, l2_coef, beta1, beta2, eps, group);
-    else
-      hipLaunchKernelGGL((k_rows_csr_adam<G, J, false>), dim3(blocks), dim3(kBlock), 0, st, row_ptr, order, src, src_s, ld, n_rows, p, m, v,
-                         p_s, m_s, v_s, alpha, alpha_s, l2_coef, beta1, beta2, eps, 1);
-    DRX_LAUNCH_CHECK();
-    return DRX_OK;
+  const float b1 = rule->mu, b2 = rule->mu2, eps = rule->eps;
+  return dispatch_opt_kind(kind, [&](auto kc) -> int {
+    constexpr int KIND = decltype(kc)::value;
+    return dispatch_geom(ld, [&](auto g) -> int {
+      constexpr int G = decltype(g)::G, J = decltype(g)::J;
+      constexpr int gpb = kBlock / G;
+      int blocks = (n_rows + gpb - 1) / gpb;
+      if (blocks > 8192) blocks = 8192;
+      if (group > 0)
+        hipLaunchKernelGGL((k_rows_csr_opt<G, J, true, KIND>), dim3(blocks), dim3(kBlock), 0, st, row_ptr, order, src, src_s, ld, n_rows, p, m,
+                           v, p_s, m_s, v_s, alpha, alpha_s, l2_coef, b1, b2, eps, group);
+      else
+        hipLaunchKernelGGL((k_rows_csr_opt<G, J, false, KIND>), dim3(blocks), dim3(kBlock), 0, st, row_ptr, order, src, src_s, ld, n_rows, p, m,
+                           v, p_s, m_s, v_s, alpha, alpha_s, l2_coef, b1, b2, eps, 1);
+      DRX_LAUNCH_CHECK();
+      return DRX_OK;
+    });
   });
+}
+
+int drx_rows_csr_opt(const int32_t *row_ptr, const int32_t *order, const float *src, const float *src_s, int32_t ld, int32_t n_rows,
+                     float *p, float *s1, float *s2, float *p_s, float *s1_s, float *s2_s, float alpha, float alpha_s, float l2_coef,
+                     const DrxOptRule *rule, void *stream) {
+  return rows_csr_opt(row_ptr, order, src, src_s, 0, ld, n_rows, p, s1, s2, p_s, s1_s, s2_s, alpha, alpha_s, l2_coef, rule, stream);
+}
+
+int drx_rows_csr_opt_outer(const int32_t *row_ptr, const int32_t *order, const float *scale, const float *src, int32_t group, int32_t ld,
+                           int32_t n_rows, float *p, float *s1, float *s2, float *p_s, float *s1_s, float *s2_s, float alpha,
+                           float alpha_s, float l2_coef, const DrxOptRule *rule, void *stream) {
+  if (!scale || group < 1 || !p_s) return DRX_EINVAL;
+  return rows_csr_opt(row_ptr, order, src, scale, group, ld, n_rows, p, s1, s2, p_s, s1_s, s2_s, alpha, alpha_s, l2_coef, rule, stream);
 }
 
 int drx_rows_csr_adam(const int32_t *row_ptr, const int32_t *order, const float *src, const float *src_s, int32_t ld, int32_t n_rows,
                       float *p, float *m, float *v, float *p_s, float *m_s, float *v_s, float alpha, float alpha_s, float l2_coef,
                       float beta1, float beta2, float eps, void *stream) {
-  return rows_csr_adam(row_ptr, order, src, src_s, 0, ld, n_rows, p, m, v, p_s, m_s, v_s, alpha, alpha_s, l2_coef, beta1, beta2, eps, stream);
+  const DrxOptRule rule{DRX_OPT_ADAM, alpha, beta1, beta2, eps};
+  return drx_rows_csr_opt(row_ptr, order, src, src_s, ld, n_rows, p, m, v, p_s, m_s, v_s, alpha, alpha_s, l2_coef, &rule, stream);
 }
 
 int drx_rows_csr_adam_outer(const int32_t *row_ptr, const int32_t *order, const float *scale, const float *src, int32_t group, int32_t ld,
                             int32_t n_rows, float *p, float *m, float *v, float *p_s, float *m_s, float *v_s, float alpha, float alpha_s,
                             float l2_coef, float beta1, float beta2, float eps, void *stream) {
-  if (!scale || group < 1 || !p_s) return DRX_EINVAL;
-  return rows_csr_adam(row_ptr, order, src, scale, group, ld, n_rows, p, m, v, p_s, m_s, v_s, alpha, alpha_s, l2_coef, beta1, beta2, eps, stream);
+  const DrxOptRule rule{DRX_OPT_ADAM, alpha, beta1, beta2, eps};
+  return drx_rows_csr_opt_outer(row_ptr, order, scale, src, group, ld, n_rows, p, m, v, p_s, m_s, v_s, alpha, alpha_s, l2_coef, &rule, stream);
 }
 
 // ---- drx_batch_csr on the device: the lookups of several key lists grouped by the table row they name -----------------------------
@@ -545,16 +596,20 @@ int drx_batch_csr_device(const DrxCsrList *lists, int32_t n_lists, void *scratch
   return DRX_OK;
 }
 
-int drx_rows_csr_adam_multi(const DrxCsrAdamTable *tables, int32_t n_tables, float beta1, float beta2, float eps, void *stream) {
-  if (!tables || n_tables < 1 || n_tables > DRX_MAX_CSR_TABLES) return DRX_EINVAL;
+int drx_rows_csr_opt_multi(const DrxCsrAdamTable *tables, int32_t n_tables, const DrxOptRule *rule, void *stream) {
+  if (!tables || n_tables < 1 || n_tables > DRX_MAX_CSR_TABLES || !rule || !opt_dense_kind(rule->kind)) return DRX_EINVAL;
+  const int kind = rule->kind;
   CsrMulti M;
   M.n = n_tables;
   int total = 0;
   for (int i = 0; i < n_tables; ++i) {
-    const DrxCsrAdamTable &T = tables[i];
-    if (!T.row_ptr || !T.order || !T.src || !T.p || !T.m || !T.v || T.n_rows < 1 || T.ld < 4 || (T.ld & 3) || T.ld > 256 || T.group < 0)
+    DrxCsrAdamTable T = tables[i];
+    if (!T.row_ptr || !T.order || !T.src || !T.p || !opt_slots_ok(kind, T.m, T.v) || T.n_rows < 1 || T.ld < 4 || (T.ld & 3) || T.ld > 256 ||
+        T.group < 0)
       return DRX_EINVAL;
-    if ((T.p_s != nullptr) != (T.scale != nullptr) || (T.p_s && (!T.m_s || !T.v_s)) || (T.group > 0 && !T.scale)) return DRX_EINVAL;
+    if ((T.p_s != nullptr) != (T.scale != nullptr) || (T.p_s && !opt_slots_ok(kind, T.m_s, T.v_s)) || (T.group > 0 && !T.scale)) return DRX_EINVAL;
+    if (!opt_has_s1(kind)) T.m = T.m_s = nullptr;
+    if (!opt_has_s2(kind)) T.v = T.v_s = nullptr;
     if (((uintptr_t)T.src | (uintptr_t)T.p | (uintptr_t)T.m | (uintptr_t)T.v) & 15) return DRX_EINVAL;
     const int gpb = kBlock / pick_geom(T.ld).G;
     int blocks = (T.n_rows + gpb - 1) / gpb;
@@ -563,9 +618,17 @@ int drx_rows_csr_adam_multi(const DrxCsrAdamTable *tables, int32_t n_tables, flo
     M.blocks[i] = blocks;
     total += blocks;
   }
-  hipLaunchKernelGGL(k_rows_csr_adam_multi, dim3(total), dim3(kBlock), 0, (hipStream_t)stream, M, beta1, beta2, eps);
-  DRX_LAUNCH_CHECK();
-  return DRX_OK;
+  return dispatch_opt_kind(kind, [&](auto kc) -> int {
+    hipLaunchKernelGGL(k_rows_csr_opt_multi<decltype(kc)::value>, dim3(total), dim3(kBlock), 0, (hipStream_t)stream, M, rule->mu, rule->mu2,
+                       rule->eps);
+    DRX_LAUNCH_CHECK();
+    return DRX_OK;
+  });
+}
+
+int drx_rows_csr_adam_multi(const DrxCsrAdamTable *tables, int32_t n_tables, float beta1, float beta2, float eps, void *stream) {
+  const DrxOptRule rule{DRX_OPT_ADAM, 0.f, beta1, beta2, eps};
+  return drx_rows_csr_opt_multi(tables, n_tables, &rule, stream);
 }
 
 size_t drx_scatter_scratch_bytes(int32_t ld, int32_t n_touches, int32_t n_rows) {

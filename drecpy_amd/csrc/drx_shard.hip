@@ -921,6 +921,7 @@ int drx_shard_apply(const DrxCdaeParams *p, const DrxOptim *opt, const DrxShard 
   int rc = check_local_params(p, sh);
   if (rc) return rc;
   if (!opt || n < 1 || b_norm < 1 || !recv_counts || !recv_keys || !grad_recv || !table) return DRX_EINVAL;
+  if (opt->kind != DRX_OPT_ADAM && opt->kind != DRX_OPT_ADAGRAD && opt->kind != DRX_OPT_ROWWISE_ADAGRAD) return DRX_EINVAL;
   if (n_segments < sh->world || n_segments % sh->world || n_segments > sh->world * DRX_MAX_MICRO) return DRX_EINVAL;
   SegOff so{};
   const ShardGeo g = geo_of(*sh, p->ld);

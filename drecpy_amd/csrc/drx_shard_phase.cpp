@@ -179,6 +179,7 @@ int drx_shard_phase_tail(const DrxCdaeParams *p, const DrxOptim *opt, const DrxS
                          DrxShardExchange *next, int32_t b_norm, float *loss_out, void *stream) {
   Geo g;
   if (!p || !opt || !comm || check_x(x) || !x->grad_send || !x->grad_recv || geo_of(sh, p->ld, g)) return DRX_EINVAL;
+  if (opt->kind != DRX_OPT_ADAM && opt->kind != DRX_OPT_ADAGRAD && opt->kind != DRX_OPT_ROWWISE_ADAGRAD) return DRX_EINVAL;   // (before anything is sent)
   if (next && (check_x(next) || !next->rows_cache || !next->rows_send)) return DRX_EINVAL;
   Geo::Chunk s[DRX_MAX_CHUNKS], r[DRX_MAX_CHUNKS];
   for (int c = 0; c < g.chunks; ++c) {

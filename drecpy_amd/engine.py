@@ -465,35 +465,38 @@ class CdaeEngine(RowsRecommender):
         return _lib.HotHead(H, ptr(self._hot_slot) if H else None, ptr(self._hot_item) if H else None)
 
     # ---- optimizer --------------------------------------------------------------------------
-    def init_optimizer(self, kind, lr, reg_rate, beta1=ADAM_B1, beta2=ADAM_B2, eps=None, initial_accumulator=ADAGRAD_INIT):
+    def init_optimizer(self, kind, lr, reg_rate, beta1=ADAM_B1, beta2=ADAM_B2, eps=None, initial_accumulator=ADAGRAD_INIT, momentum=0.0,
+                       rho=0.9):
         """kind: 'adam' (Keras Adam, reference default recommender_abc.py:153), 'adagrad', or — sampled mode only —
-        'rowwise_adagrad' (one accumulator per table row: acc += mean_k(g^2); an engine extension, oracle/cdae_oracle.py).
-        The hyper-parameters default to tf.keras's; drecpy_amd.optimizers objects passed to fit(optimizer=...) set them."""
-        if kind not in ('adam', 'adagrad', 'rowwise_adagrad'):
-            raise _lib.DrxError(f'unknown optimizer "{kind}" (adam, adagrad, rowwise_adagrad)')
-        self.opt_kind = {'adam': _lib.OPT_ADAM, 'adagrad': _lib.OPT_ADAGRAD, 'rowwise_adagrad': _lib.OPT_ROWWISE_ADAGRAD}[kind]
+        'rowwise_adagrad' (one accumulator per table row: acc += mean_k(g^2); an engine extension, oracle/cdae_oracle.py), or —
+        dense (reference-mode) steps only — 'sgd', 'momentum', 'nesterov', 'rmsprop', 'rmsprop_momentum' (include/drx.h DrxOptRule;
+        `momentum` and `rho` are theirs).  Only the slots the rule has are allocated: none for 'sgd', s1 alone for all but 'adam' and
+        'rmsprop_momentum'.  The hyper-parameters default to tf.keras's; drecpy_amd.optimizers objects passed to fit(optimizer=...) set them."""
+        from .optimizers import KINDS, N_SLOTS
+        if kind not in KINDS:
+            raise _lib.DrxError(f'unknown optimizer "{kind}" ({", ".join(KINDS)})')
+        self.opt_kind = KINDS[kind]
         self.lr, self.reg_rate = float(lr), float(reg_rate)
+        if kind in ('sgd', 'momentum', 'nesterov', 'rmsprop', 'rmsprop_momentum'):
+            beta1, beta2 = momentum, rho                 # (DrxOptim: beta1 carries the momentum, beta2 rho)
         self.beta1, self.beta2 = float(beta1), float(beta2)
         self.opt_eps = float(eps) if eps is not None else (ADAM_EPS if kind == 'adam' else ADAGRAD_EPS)
         self._optim_struct = self._alpha_tab = None
-        if kind == 'adam':
-            self.s1 = [torch.zeros_like(t) for t in self.tables()]
-            self.s2 = [torch.zeros_like(t) for t in self.tables()]
-        else:
-            self.s1 = [torch.full_like(t, float(initial_accumulator)) for t in self.tables()]
-            self.s2 = None
+        init = float(initial_accumulator) if kind in ('adagrad', 'rowwise_adagrad') else 0.0
+        self.s1 = [torch.full_like(t, init) for t in self.tables()] if N_SLOTS[kind] >= 1 else None
+        self.s2 = [torch.zeros_like(t) for t in self.tables()] if N_SLOTS[kind] >= 2 else None
 
     def _optim(self, alphas):
         # the struct is kept between steps (the slot tensors live as long as the optimizer): only the five lr_t change
         o = getattr(self, '_optim_struct', None)
-        if o is None or self._optim_for is not self.s1:
+        if o is None or self._optim_for is not self.s1:          # (init_optimizer drops the struct: a rule without slots has s1 None)
             o = Optim()
             o.kind = self.opt_kind
             o.lr, o.reg_rate = self.lr, self.reg_rate
             o.beta1, o.beta2 = self.beta1, self.beta2
             o.eps = self.opt_eps
             for j in range(5):
-                o.s1[j] = self.s1[j].data_ptr()
+                o.s1[j] = self.s1[j].data_ptr() if self.s1 is not None else 0
                 o.s2[j] = self.s2[j].data_ptr() if self.s2 is not None else 0
             self._optim_struct, self._optim_for = o, self.s1
         o.alpha[0], o.alpha[1], o.alpha[2], o.alpha[3], o.alpha[4] = alphas
@@ -513,6 +516,8 @@ class CdaeEngine(RowsRecommender):
     def _alpha_table(self, first_step, n_steps):
         """float32 [n_steps, 5]: lr_t of dense steps first_step .. first_step + n_steps - 1."""
         f = np.float32
+        if self.opt_kind != _lib.OPT_ADAM:           # (no other rule has a bias correction: DrxOptim.alpha goes unread)
+            return np.full((n_steps, 5), self.lr, dtype=np.float32)
         t = (5 * first_step + 1 + np.arange(5 * n_steps)).astype(np.float32)
         tab = f(self.lr) * np.sqrt(f(1.0) - np.power(f(self.beta2), t)) / (f(1.0) - np.power(f(self.beta1), t))
         return np.ascontiguousarray(tab.astype(np.float32).reshape(-1, 5))

@@ -60,6 +60,7 @@ class DmfEngine(RowsRecommender):
         self.scale_var = None
         self.broadcast_targets = False
         self.beta1, self.beta2, self.eps = ADAM_B1, ADAM_B2, ADAM_EPS
+        self.opt_kind, self._slot_init = 'adam', 0.0        # (set_optimizer: another dense rule of optimizers.py)
         z = dict(dtype=torch.float32, device=self.device)
         self.K0u = torch.zeros(n_items, D.ld0[0], **z)
         self.K0i = torch.zeros(n_users, D.ld0[1], **z)
@@ -99,7 +100,9 @@ class DmfEngine(RowsRecommender):
         self.D.off_scale = self._scale_slot
         self.scale_var = variable
         self.broadcast_targets = bool(broadcast_targets)
-        self.state['sw'][0].zero_(); self.state['sw'][1].zero_()
+        for slot in self.state['sw']:
+            if slot is not None:
+                slot.fill_(self._slot_init)
 
     def tensors(self):
         return {'K0u': self.K0u, 'K0i': self.K0i, 'sw': self.sw}
@@ -153,12 +156,50 @@ class DmfEngine(RowsRecommender):
             p['extra_w'] = c(self.sw[self._scale_slot:self._scale_slot + 1])
         return p
 
+    def set_optimizer(self, opt):
+        """The update rule of every dense step from a drecpy_amd.optimizers object (Adam, Adagrad, SGD, RMSprop): its kind and
+        hyper-parameters, and slots of that rule alone — none for plain SGD, s1 for all but Adam and RMSprop with momentum (Adagrad's at
+        its accumulator value).  beta1 / beta2 carry include/drx.h DrxOptRule's mu / mu2.  Slots that already fit the rule are kept."""
+        from .optimizers import KINDS, N_SLOTS
+        kind = opt.kind
+        if kind not in KINDS or kind == 'rowwise_adagrad':
+            raise _lib.DrxError(f'no dense update rule "{kind}"')
+        mu, mu2 = opt._mus()
+        self.lr, self.beta1, self.beta2, self.eps = opt.learning_rate, mu, mu2, getattr(opt, 'epsilon', 0.0)
+        if kind == self.opt_kind and getattr(opt, 'slot_init', 0.0) == self._slot_init:
+            return
+        self.opt_kind, self._slot_init = kind, float(getattr(opt, 'slot_init', 0.0))
+        n = N_SLOTS[kind]
+        self.state = {name: tuple(torch.full_like(t, self._slot_init) if i < n else None for i in range(2)) for name, t in self.tensors().items()}
+
+    def _rule(self, step_size=0.0):
+        """include/drx.h DrxOptRule of the engine's rule (step_size: where the entry point has none per variable)"""
+        key = (self.opt_kind, step_size, self.beta1, self.beta2, self.eps)
+        c = self.__dict__.get('_rule_cache')
+        if c is None or c[0] != key:                     # (one struct per setting: the steps pass it by reference)
+            from .optimizers import KINDS
+            c = self._rule_cache = (key, _lib.OptRule(KINDS[self.opt_kind], step_size, self.beta1, self.beta2, self.eps))
+        return c[1]
+
+    def _step_sizes(self, step_idx, applies):
+        """the step size of each apply of step `step_idx`: Keras Adam's lr_t of its counter; the learning rate under every other rule"""
+        if self.opt_kind != 'adam':
+            return [self.lr if j is not None else 0.0 for j in applies[1:]]
+        return [self.adam_alpha(self.lr, applies[0] * step_idx + j + 1, self.beta1, self.beta2) if j is not None else 0.0 for j in applies[1:]]
+
     def snapshot(self):
-        return {'p': {n: t.clone() for n, t in self.tensors().items()}}
+        """Device copies of the parameters and of the slots the rule has (used by _store_epoch_weights / _revert_weights)."""
+        return {'p': {n: t.clone() for n, t in self.tensors().items()},
+                's': {n: tuple(None if t is None else t.clone() for t in st) for n, st in self.state.items()}}
 
     def restore(self, snap, with_optimizer=False):
         for n, t in self.tensors().items():
             t.copy_(snap['p'][n])
+        if with_optimizer and 's' in snap:
+            for n, st in self.state.items():
+                for dst, src in zip(st, snap['s'][n]):
+                    if dst is not None and src is not None:
+                        dst.copy_(src)
 
     def _base_args(self, uid, iid):
         A = DmfArgs()
@@ -472,7 +513,7 @@ class DmfEngine(RowsRecommender):
         if applies is None:
             applies = (3, 1, 2, 0) if self.scale_var is not None else (2, 0, 1, None)
         n_app = applies[0]
-        alpha = [self.adam_alpha(self.lr, n_app * step_idx + j + 1, self.beta1, self.beta2) if j is not None else 0.0 for j in applies[1:]]
+        alpha = self._step_sizes(step_idx, applies)
         l2c = 2.0 * self.reg
         sg = AdamSegments()
         sg.n = len(self.seg)
@@ -486,12 +527,14 @@ class DmfEngine(RowsRecommender):
         # forward / backward with the small weights' Keras Adam in the launch that sums their partial gradients (r06: drx_dmf_step_small
         # — one launch less than drx_dmf_fwd_bwd + drx_adam_segments; gsw still holds the gradient and, last, the loss sum; the
         # first-layer update below reads none of the small weights)
-        check(L_.drx_dmf_step_small(C.byref(self.D), C.byref(A), ptr(gsw), ptr(self.sw), ptr(m), ptr(v), C.byref(sg), self.beta1, self.beta2,
-                                    self.eps, stream), 'drx_dmf_step_small')
+        rule = self._rule()
+        check(L_.drx_dmf_step_small_opt(C.byref(self.D), C.byref(A), ptr(gsw), ptr(self.sw), ptr(m), ptr(v), C.byref(sg), C.byref(rule), stream),
+              'drx_dmf_step_small_opt')
         if scan:
             up = DmfK0Update()
             (mu, vu), (mi, vi) = self.state['K0u'], self.state['K0i']
-            up.K0u, up.m_u, up.v_u, up.K0i, up.m_i, up.v_i = (t.data_ptr() for t in (self.K0u, mu, vu, self.K0i, mi, vi))
+            up.K0u, up.m_u, up.v_u, up.K0i, up.m_i, up.v_i = (t.data_ptr() if t is not None else None for t in (self.K0u, mu, vu, self.K0i, mi, vi))
+            up.opt_kind = rule.kind
             up.n_items, up.n_users = self.N, self.U
             up.row_order, up.n_long = self._k0_order.data_ptr(), self._k0_long
             up.alpha_u, up.alpha_i, up.l2_coef, up.beta1, up.beta2, up.eps = alpha[0], alpha[1], l2c, self.beta1, self.beta2, self.eps
@@ -503,20 +546,21 @@ class DmfEngine(RowsRecommender):
             for name, tw in (('K0u', 0), ('K0i', 1)):
                 p = self.tensors()[name]
                 m, v = self.state[name]
-                check(L_.drx_adam_dense(ptr(p), ptr(m), ptr(v), ptr(self._g[name]), p.numel(), alpha[tw], l2c, self.beta1, self.beta2,
-                                        self.eps, stream), 'drx_adam_dense')
+                check(L_.drx_opt_dense(ptr(p), ptr(m), ptr(v), ptr(self._g[name]), p.numel(), C.byref(self._rule(alpha[tw])), l2c, stream),
+                      'drx_opt_dense')
         wanted_host = None if on_device else self.__dict__.get('_stage', {}).pop('cache_wanted', None)
         if (not on_device) and scan and wanted_host is not None and not want_loss:
             sg_tw = [(i, tw) for i, (_, _, _, _, tw) in enumerate(self.seg)] + ([(len(self.seg), 2)] if self.scale_var is not None else [])
             self._stage['cache'][wanted_host[0]] = {
                 'B': B, 'base': wanted_host[1], 'applies': tuple(applies), 'key': self._step_cache_key(), 'A': A, 'up': up, 'sg': sg, 'gsw': ptr(gsw),
                 'D': C.byref(self.D), 'Aref': C.byref(A), 'upref': C.byref(up), 'sgref': C.byref(sg), 'sg_tw': sg_tw, 'sw': ptr(self.sw),
-                'm': ptr(m), 'v': ptr(v), 'keep': (gsw, gpart, lpart, dz0u, dz0i)}
+                'm': ptr(m), 'v': ptr(v), 'rule': rule, 'ruleref': C.byref(rule), 'keep': (gsw, gpart, lpart, dz0u, dz0i)}
         if on_device and scan and prep['device'].pop('step_cache_wanted', False):
             sg_tw = [(i, tw) for i, (_, _, _, _, tw) in enumerate(self.seg)] + ([(len(self.seg), 2)] if self.scale_var is not None else [])
             prep['device']['step_cache'] = {
                 'applies': tuple(applies), 'key': self._step_cache_key(), 'A': A, 'up': up, 'sg': sg, 'gsw': ptr(gsw), 'D': C.byref(self.D),
                 'Aref': C.byref(A), 'upref': C.byref(up), 'sgref': C.byref(sg), 'sg_tw': sg_tw, 'sw': ptr(self.sw), 'm': ptr(m), 'v': ptr(v),
+                'rule': rule, 'ruleref': C.byref(rule),
                 'keep': (gsw, gpart, lpart, dz0u, dz0i)}
         if want_loss:
             return float((gsw[-1] + reg_loss).item())
@@ -543,13 +587,12 @@ class DmfEngine(RowsRecommender):
         self._stamp += 1
         A.stamp = self._stamp
         n_app = applies[0]
-        alpha = [self.adam_alpha(self.lr, n_app * step_idx + j + 1, self.beta1, self.beta2) if j is not None else 0.0 for j in applies[1:]]
+        alpha = self._step_sizes(step_idx, applies)
         for i, tw in c['sg_tw']:
             sg.alpha[i] = alpha[tw]
         # (the small weights' Adam in the launch that sums their partial gradients: drx_dmf_step_small — one launch less than
         # drx_dmf_fwd_bwd + drx_adam_segments, the same bits; the first-layer update reads none of them)
-        check(L_.drx_dmf_step_small(c['D'], c['Aref'], gsw, c['sw'], c['m'], c['v'], c['sgref'], self.beta1, self.beta2, self.eps, stream),
-              'drx_dmf_step_small')
+        check(L_.drx_dmf_step_small_opt(c['D'], c['Aref'], gsw, c['sw'], c['m'], c['v'], c['sgref'], c['ruleref'], stream), 'drx_dmf_step_small_opt')
         up.alpha_u, up.alpha_i = alpha[0], alpha[1]
         check(L_.drx_dmf_k0_update(c['D'], c['Aref'], c['upref'], stream), 'drx_dmf_k0_update')
 
@@ -558,7 +601,8 @@ class DmfEngine(RowsRecommender):
         would replace, and the scalars baked into the structs"""
         w = getattr(self, '_work', None)
         return (self.K0u.data_ptr(), self.sw.data_ptr(), self._maps[0].data_ptr(), self._rho[0].data_ptr(), self.csr[0].data_ptr(),
-                self.state['sw'][0].data_ptr(), self.state['K0u'][0].data_ptr(), self._k0_order.data_ptr(), self._k0_long,
+                self.opt_kind, tuple(s.data_ptr() if s is not None else 0 for n in ('sw', 'K0u') for s in self.state[n]), self._k0_order.data_ptr(),
+                self._k0_long,
                 w.data_ptr() if w is not None else 0, id(self.D), self.D.off_scale, self.first_layer_update, self.reg, self.beta1, self.beta2,
                 self.eps, self.broadcast_targets, self.scale_var is not None, getattr(self, '_step_bufs', (None,))[0])
 

@@ -45,8 +45,31 @@ enum { DRX_TARGETS_REFERENCE = 0, DRX_TARGETS_PER_ROW = 1 };   /* (B,B,N) broadc
  * scratch, or scratch last used by a COMPLETED dense step of the same batch size: consumers clear what they read) -> no memset */
 #define DRX_DENSE_AUX_CLEAN 0x100
 enum { DRX_OPT_ADAM = 0, DRX_OPT_ADAGRAD = 1,
-       DRX_OPT_ROWWISE_ADAGRAD = 2   /* sampled mode only: ONE accumulator per table row, kept in the first float of the row's slot
-                                        (s1[var][row * ld]): acc += mean_k(g^2), p -= lr * g / (sqrt(acc) + eps); b and b2 per element */ };
+       DRX_OPT_ROWWISE_ADAGRAD = 2,  /* sampled mode only: ONE accumulator per table row, kept in the first float of the row's slot
+                                        (s1[var][row * ld]): acc += mean_k(g^2), p -= lr * g / (sqrt(acc) + eps); b and b2 per element */
+       /* DENSE updates only (drx_opt_*, drx_rows_csr_opt*, drx_cdae_step_dense / drx_cdae_fit_dense): every sparse / sharded entry point
+        * returns DRX_EINVAL for them.  g = data gradient + l2 * p; fp32, one operation at a time, in this order (Keras optimizer_v2): */
+       DRX_OPT_SGD = 3,              /* no slot:      p -= lr * g */
+       DRX_OPT_MOMENTUM = 4,         /* s1 = accumulator (init 0): s1 = s1 * mu - g * lr;  p += s1 */
+       DRX_OPT_NESTEROV = 5,         /* s1 as above:  s1 = s1 * mu - g * lr;  p += s1 * mu - g * lr */
+       DRX_OPT_RMSPROP = 6,          /* s1 = rms (init 0): s1 += (g * g - s1) * (1 - rho);  p -= lr * g / (sqrt(s1) + eps) */
+       DRX_OPT_RMSPROP_MOMENTUM = 7  /* s1 as above, s2 = mom (init 0): s2 = s2 * mu + (g * lr) / sqrt(s1 + eps);  p -= s2 */ };
+
+/* One update rule for the dense entry points.  Which hyper-parameters and slots a kind reads (an absent slot is passed as NULL and is
+ * neither read nor written):
+ *   kind                      lr                 mu        mu2      eps   s1            s2
+ *   DRX_OPT_ADAM              Keras lr_t         beta_1    beta_2   yes   m             v
+ *   DRX_OPT_ADAGRAD           learning rate      -         -        yes   accumulator   -
+ *   DRX_OPT_SGD               learning rate      -         -        -     -             -
+ *   DRX_OPT_MOMENTUM/NESTEROV learning rate      momentum  -        -     accumulator   -
+ *   DRX_OPT_RMSPROP           learning rate      -         rho      yes   rms           -
+ *   DRX_OPT_RMSPROP_MOMENTUM  learning rate      momentum  rho      yes   rms           mom
+ * Entry points with a step size per variable (DrxAdamSegments::alpha, DrxCsrAdamTable::alpha / alpha_s) take it from there (Adam: the
+ * variable's lr_t; the other kinds: the learning rate) and ignore `lr`.  DRX_OPT_ROWWISE_ADAGRAD is not a dense rule: DRX_EINVAL. */
+typedef struct DrxOptRule {
+  int32_t kind;             /* DRX_OPT_* */
+  float lr, mu, mu2, eps;
+} DrxOptRule;
 
 /* CDAE parameters (cdae.py:34-41) and optimizer slots of the same shapes.
  * Adam uses s1 = m, s2 = v; Adagrad uses s1 = accumulator (s2 unused, may be NULL). */
@@ -119,6 +142,10 @@ typedef struct DrxOptim {
   int32_t kind;             /* DRX_OPT_* */
   float lr, reg_rate;       /* reg is applied as reg_rate / B (cdae.py:82) */
   float beta1, beta2, eps;  /* Adam: .9 .999 1e-7 (Keras); Adagrad: eps 1e-7 */
+  /* Per kind (the new kinds: drx_cdae_step_dense / drx_cdae_fit_dense only; DrxOptRule's table has the arithmetic):
+   *   ADAM              beta1, beta2, eps, alpha[]; s1 = m, s2 = v          ADAGRAD / ROWWISE_ADAGRAD  lr, eps; s1 (s2 may be NULL)
+   *   SGD               lr; no slot (s1, s2 may be NULL)                   MOMENTUM / NESTEROV        lr, beta1 = momentum; s1
+   *   RMSPROP           lr, beta2 = rho, eps; s1                           RMSPROP_MOMENTUM           lr, beta1 = momentum, beta2 = rho, eps; s1, s2 */
   /* Keras-Adam lr_t = lr*sqrt(1-b2^t)/(1-b1^t) per variable in registration order W, W_, V, b, b_
    * (recommender_abc.py:328-334 advances the counter once per variable: t = 5*step + j + 1). */
   float alpha[5];
@@ -583,6 +610,23 @@ typedef struct DrxCsrAdamTable {
   float alpha, alpha_s, l2_coef;
 } DrxCsrAdamTable;
 int drx_rows_csr_adam_multi(const DrxCsrAdamTable *tables, int32_t n_tables, float beta1, float beta2, float eps, void *stream);
+/* The dense family with the update rule as an argument (DrxOptRule above): the `_adam` entry points are these with
+ * {DRX_OPT_ADAM, alpha, beta1, beta2, eps}, bit for bit.  s1 / s2 (and s1_s / s2_s, DrxCsrAdamTable's m / v / m_s / v_s) are the slots the
+ * rule has; one the rule lacks is passed as NULL and never dereferenced, one it has must be there (DRX_EINVAL).  Every row / element is
+ * updated every step, also a table row no lookup names (g = l2_coef * p: its accumulators decay or advance as in Keras's dense
+ * apply).  Nothing is launched when DRX_EINVAL is returned.
+ *   drx_opt_dense          drx_adam_dense's sweep; step size rule->lr
+ *   drx_rows_csr_opt       drx_rows_csr_adam; step sizes alpha / alpha_s
+ *   drx_rows_csr_opt_outer drx_rows_csr_adam_outer
+ *   drx_rows_csr_opt_multi drx_rows_csr_adam_multi; one rule for all tables of the call, step sizes from the tables */
+int drx_opt_dense(float *p, float *s1, float *s2, const float *g, int64_t n, const DrxOptRule *rule, float l2_coef, void *stream);
+int drx_rows_csr_opt(const int32_t *row_ptr, const int32_t *order, const float *src, const float *src_s, int32_t ld, int32_t n_rows,
+                     float *p, float *s1, float *s2, float *p_s, float *s1_s, float *s2_s, float alpha, float alpha_s, float l2_coef,
+                     const DrxOptRule *rule, void *stream);
+int drx_rows_csr_opt_outer(const int32_t *row_ptr, const int32_t *order, const float *scale, const float *src, int32_t group, int32_t ld,
+                           int32_t n_rows, float *p, float *s1, float *s2, float *p_s, float *s1_s, float *s2_s, float alpha,
+                           float alpha_s, float l2_coef, const DrxOptRule *rule, void *stream);
+int drx_rows_csr_opt_multi(const DrxCsrAdamTable *tables, int32_t n_tables, const DrxOptRule *rule, void *stream);
 /* host: first[c] = first position of code c in codes[0..n), -1 when absent; returns the number of distinct codes (Dataset.unique on
  * dense integer code columns, mem_dataset.py's drop_duplicates, without a sort) */
 int64_t drx_first_occurrence(const int64_t *codes, int64_t n, int64_t n_codes, int64_t *first);
@@ -623,6 +667,9 @@ typedef struct DrxAdamSegments {
 } DrxAdamSegments;
 int drx_adam_segments(float *p, float *m, float *v, const float *g, const DrxAdamSegments *sg, float beta1, float beta2, float eps,
                       void *stream);
+/* The same under any dense rule (DrxOptRule; step size per segment from sg->alpha, rule->lr ignored); s1 / s2: the slots the rule has,
+ * NULL where it has none.  drx_adam_segments is this with {DRX_OPT_ADAM, -, beta1, beta2, eps}. */
+int drx_opt_segments(float *p, float *s1, float *s2, const float *g, const DrxAdamSegments *sg, const DrxOptRule *rule, void *stream);
 
 /* ---- Caser (DRecPy/Recommender/caser.py) ------------------------------------------------------------------------
  * Tables: item_emb [N, ld], user_emb [U, ld] (caser.py:47-50), W1 [N, ld2] = dense_1_W rows (first d columns meet
@@ -664,6 +711,10 @@ int drx_caser_fwd_bwd(const DrxCaserDims *D, const DrxCaserArgs *A, float *gsw_o
  * place once the training kernel has read them). */
 int drx_caser_step_small(const DrxCaserDims *D, const DrxCaserArgs *A, float *gsw_out, float *sw, float *sw_m, float *sw_v,
                          const DrxAdamSegments *sg, float beta1, float beta2, float eps, void *stream);
+/* The same under any dense rule (DrxOptRule; drx_opt_segments' arithmetic, step size per segment from sg->alpha): sw_s1 / sw_s2 are the
+ * slots the rule has, NULL where it has none.  drx_caser_step_small is this with {DRX_OPT_ADAM, -, beta1, beta2, eps}. */
+int drx_caser_step_small_opt(const DrxCaserDims *D, const DrxCaserArgs *A, float *gsw_out, float *sw, float *sw_s1, float *sw_s2,
+                             const DrxAdamSegments *sg, const DrxOptRule *rule, void *stream);
 /* inference hidden state cat_out[b] = [dense_0 output | user embedding] (caser.py:97-115 with training=False) */
 int drx_caser_hidden(const DrxCaserDims *D, const DrxCaserArgs *A, void *stream);
 
@@ -780,6 +831,10 @@ int drx_dmf_fwd_bwd(const DrxDmfDims *D, const DrxDmfArgs *A, float *gsw_out, vo
  * partial gradients: one launch less per step (r06; drx_dmf_k0_update reads none of `sw` and may follow). */
 int drx_dmf_step_small(const DrxDmfDims *D, const DrxDmfArgs *A, float *gsw_out, float *sw, float *sw_m, float *sw_v,
                        const DrxAdamSegments *sg, float beta1, float beta2, float eps, void *stream);
+/* The same under any dense rule (DrxOptRule; drx_opt_segments' arithmetic, step size per segment from sg->alpha): sw_s1 / sw_s2 are the
+ * slots the rule has, NULL where it has none.  drx_dmf_step_small is this with {DRX_OPT_ADAM, -, beta1, beta2, eps}. */
+int drx_dmf_step_small_opt(const DrxDmfDims *D, const DrxDmfArgs *A, float *gsw_out, float *sw, float *sw_s1, float *sw_s2,
+                           const DrxAdamSegments *sg, const DrxOptRule *rule, void *stream);
 int drx_dmf_predict(const DrxDmfDims *D, const DrxDmfArgs *A, void *stream);
 /* The update of the first-layer kernels (tf.keras Dense kernels [N, f0] of user_nn / [U, f0] of item_nn, dmf.py:44-60) after
  * drx_dmf_fwd_bwd ran with the id maps: gradient (+ l2_coef * K0, dmf.py:101-103) and dense Keras Adam in one pass over both tables —
@@ -788,7 +843,7 @@ int drx_dmf_predict(const DrxDmfDims *D, const DrxDmfArgs *A, void *stream);
  * u_* and map_i.  Cost per step: one walk over all non-zeros (8 bytes each) — pays while nnz is within ~64x the batch's touches;
  * beyond that use the touches + drx_scatter_rows + drx_adam_dense. */
 typedef struct DrxDmfK0Update {
-  float *K0u, *m_u, *v_u;    /* [n_items, ld0[0]] kernel, Adam moments */
+  float *K0u, *m_u, *v_u;    /* [n_items, ld0[0]] kernel, Adam moments (another rule: its slots s1, s2; NULL where it has none) */
   float *K0i, *m_i, *v_i;    /* [n_users, ld0[1]] */
   int32_t n_items, n_users;
   float alpha_u, alpha_i;    /* Keras-Adam lr_t of the apply_gradients call each kernel belongs to */
@@ -798,6 +853,9 @@ typedef struct DrxDmfK0Update {
    * workgroup each — every row whose walk is longer than 1024 entries must be among them —, the others a WAVE each, four per workgroup. */
   const int32_t *row_order;
   int32_t n_long;
+  /* the update rule, a dense DRX_OPT_* (0 = DRX_OPT_ADAM: a zero-initialised field is the update this was).  Another rule reads alpha_u /
+   * alpha_i as its learning rate, beta1 as DrxOptRule's mu (momentum), beta2 as mu2 (rho), and the slots it has in m_* (s1) and v_* (s2). */
+  int32_t opt_kind;
 } DrxDmfK0Update;
 int drx_dmf_k0_update(const DrxDmfDims *D, const DrxDmfArgs *A, const DrxDmfK0Update *up, void *stream);
 /* all-pairs cosine scores on the matrix cores: out[u, n] = max(1e-6, ru[u,:kdim] . ri[n,:kdim]) with bf16 operands /
