@@ -141,8 +141,21 @@ class BaseKNN(RecommenderABC, ABC):
         return [[(float(v), int(i)) for v, i in zip(vr, ir) if i >= 0] for vr, ir in zip(val, idx)]
 
     def _recommend_batch(self, uids, n, novelty):
-        """Top-n of the whole catalogue for many users, in chunks whose prediction matrix stays within a budget; excluded under
-        novelty: the rows of _exclusion_csr (every (uid, iid) row of the frame)."""
+        """Top-n of the whole catalogue for many users.  n <= KnnEngine.FUSED_MAX_N: ONE KnnEngine.recommend (drx_knn_recommend:
+        predictions, exclusions and selection in the workgroup that holds the user's row), the predictions and
+        the order of recommend() bit for bit.  A longer list (n=None), or an engine with fused = False: the score-matrix route."""
+        eng = self._engine
+        if not (eng.fused and 1 <= int(n) <= eng.FUSED_MAX_N):
+            return self._recommend_batch_by_matrix(uids, n, novelty)
+        with self._device_lock:
+            self._upload_exclusions(novelty)
+            idx, val = eng.recommend(np.asarray(uids, np.int32), int(n), self.aggregation, self.use_averages, exclude=bool(novelty),
+                                     chunk_bytes=_MATRIX_CHUNK_BYTES)
+            return idx.cpu().numpy().astype(np.int64), val.cpu().numpy().astype(np.float64)
+
+    def _recommend_batch_by_matrix(self, uids, n, novelty):
+        """The same in chunks whose prediction matrix stays within a budget; excluded under novelty: the rows of _exclusion_csr
+        (every (uid, iid) row of the frame)."""
         idx = np.full((len(uids), n), -1, dtype=np.int64)
         val = np.full((len(uids), n), -np.inf, dtype=np.float64)
         per = self._engine.matrix_chunk_users(max(self.n_items, 1), _MATRIX_CHUNK_BYTES)
@@ -157,3 +170,22 @@ class BaseKNN(RecommenderABC, ABC):
                 for j, (score, iid) in enumerate(ranked):
                     idx[lo + r, j], val[lo + r, j] = iid, score
         return idx, val
+
+    def _catalogue_ranks(self, uids, iids, novelty):
+        """The pairs grouped by user (one row a user, however many items) and ONE KnnEngine.rank_lists (drx_knn_rank_lists: the ranks
+        counted on the user's row where it lies); the positions and values of recommend()'s list bit for bit.  The device ignores a
+        target's own exclusion: an excluded pair is set to -1 / -inf here, as an unknown item (iid -1) comes back."""
+        eng = self._engine
+        if not eng.fused:
+            return super()._catalogue_ranks(uids, iids, novelty)
+        uids, iids = np.asarray(uids, dtype=np.int64), np.asarray(iids, dtype=np.int64)
+        with self._device_lock:
+            self._upload_exclusions(novelty)
+            order, starts, indptr = self._grouped_pairs(uids, iids, len(uids) + 1)
+            r, s = eng.rank_lists(uids[order[starts]].astype(np.int32), indptr, iids[order].astype(np.int32), self.aggregation,
+                                  self.use_averages, exclude=bool(novelty), chunk_bytes=_MATRIX_CHUNK_BYTES)
+            rank, score = np.empty(len(uids), np.int64), np.empty(len(uids), np.float64)
+            rank[order], score[order] = r.cpu().numpy(), s.cpu().numpy()
+            if novelty:
+                self._unlist_excluded(uids, iids, rank, score)
+        return rank, score

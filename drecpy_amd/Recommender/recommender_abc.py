@@ -584,8 +584,7 @@ class RecommenderABC(ABC):
         downloaded as (idx int64 [R, n], val float32 [R, n]), -1 / -inf from column n_items on."""
         with self._device_lock:
             eng = self._engine
-            if novelty and getattr(eng, '_excl', None) is None:
-                eng.set_exclusions(*self._exclusion_csr())
+            self._upload_exclusions(novelty)
             idx, val = eng.recommend(np.asarray(uids, dtype=np.int32), *query, min(int(n), self.n_items), exclude=bool(novelty))
             idx, val = idx.cpu().numpy().astype(np.int64), val.cpu().numpy()
         pad = n - idx.shape[1]
@@ -602,7 +601,8 @@ class RecommenderABC(ABC):
         a -1).  What full-catalogue HR@k / NDCG@k / MRR need, for any k, without lists (recommendation_evaluation(batched='ranks')).
         CDAE, DMF and Caser answer from the fused scorer-counter: users with several pairs through its list
         form (drx_rows_rank_lists: one catalogue walk per user and group of its items), scattered pairs through its pair form
-        (drx_rows_rank_items: one query row and one walk per pair); both give the same bits."""
+        (drx_rows_rank_items: one query row and one walk per pair); both give the same bits.  UserKNN and ItemKNN count on the user's
+        prediction row in its workgroup (drx_knn_rank_lists): recommend()'s positions and values bit for bit."""
         assert self.fitted is True, 'The model requires to be fitted before being able to make predictions.'
         uids = np.fromiter((self._require_user(user) for user in user_ids), dtype=np.int64)
         to_iid = self.interaction_dataset.item_to_iid
@@ -637,8 +637,7 @@ class RecommenderABC(ABC):
         uids, iids = np.asarray(uids, dtype=np.int64), np.asarray(iids, dtype=np.int64)
         with self._device_lock:
             eng = self._engine
-            if novelty and getattr(eng, '_excl', None) is None:
-                eng.set_exclusions(*self._exclusion_csr())
+            self._upload_exclusions(novelty)
             group = eng.rank_lists_group(eng.rank_ld())
             if group > 0 and len(uids) >= eng.RANK_LISTS_MIN_MEAN * len(np.unique(uids)):
                 order, starts, indptr = self._grouped_pairs(uids, iids, group)
@@ -650,13 +649,22 @@ class RecommenderABC(ABC):
                 rank, score = eng.rank_items(uids.astype(np.int32), *query, iids.astype(np.int32), exclude=bool(novelty))
                 rank, score = rank.cpu().numpy().astype(np.int64), score.cpu().numpy().astype(np.float64)
             if novelty:
-                _, _, ip, ix = eng._excl
-                cells = np.repeat(np.arange(len(ip) - 1, dtype=np.int64), np.diff(ip)) * self.n_items + ix      # ascending: rows, then columns
-                wanted = uids * self.n_items + iids
-                at = np.minimum(np.searchsorted(cells, wanted), max(len(cells) - 1, 0))
-                excluded = (cells[at] == wanted) if len(cells) else np.zeros(len(wanted), bool)
-                rank[excluded & (iids >= 0)], score[excluded & (iids >= 0)] = -1, -np.inf
+                self._unlist_excluded(uids, iids, rank, score)
         return rank, score
+
+    def _upload_exclusions(self, novelty):
+        """_exclusion_csr on the device, once per engine (again after load(): _restore_engine builds a new one)"""
+        if novelty and getattr(self._engine, '_excl', None) is None:
+            self._engine.set_exclusions(*self._exclusion_csr())
+
+    def _unlist_excluded(self, uids, iids, rank, score):
+        """-1 / -inf into rank / score at the pairs that lie in the engine's exclusion CSR (the device ranks a target as if listed)"""
+        _, _, ip, ix = self._engine._excl
+        cells = np.repeat(np.arange(len(ip) - 1, dtype=np.int64), np.diff(ip)) * self.n_items + ix      # ascending: rows, then columns
+        wanted = uids * self.n_items + iids
+        at = np.minimum(np.searchsorted(cells, wanted), max(len(cells) - 1, 0))
+        excluded = (cells[at] == wanted) if len(cells) else np.zeros(len(wanted), bool)
+        rank[excluded & (iids >= 0)], score[excluded & (iids >= 0)] = -1, -np.inf
 
     @staticmethod
     def _grouped_pairs(uids, iids, group):

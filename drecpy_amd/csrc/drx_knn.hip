@@ -451,14 +451,10 @@ __device__ __forceinline__ void knn_clear_bit(uint32_t *mask, size_t flat) {
 
 // ItemKNN: the user's ratings as a row [n_items] (NaN = none) in LDS, or in the scratch when it does not fit; a lane takes an item and
 // walks its neighbours.
-__global__ __launch_bounds__(kBlock) void k_knn_score_item(KnnModel Mo, const int32_t *__restrict__ uid, const double *__restrict__ fallback,
-                                                           float *__restrict__ out, uint32_t *mask, float *rows) {
-  extern __shared__ __align__(16) float knn_lds_f[];
-  const int r = blockIdx.x, N = Mo.n_items;
-  float *row = rows ? rows + (size_t)r * N : knn_lds_f;
+__device__ __forceinline__ void knn_item_ratings(const KnnModel &Mo, int u, float *row) {
+  const int N = Mo.n_items;
   for (int i = threadIdx.x; i < N; i += kBlock) row[i] = __uint_as_float(0x7FC00000u);
   __syncthreads();
-  const int u = uid[r];
   if ((unsigned)u < (unsigned)Mo.n_users) {
     int64_t lo, hi;
     knn_row(Mo.indptr, Mo.nnz, u, lo, hi);
@@ -468,34 +464,48 @@ __global__ __launch_bounds__(kBlock) void k_knn_score_item(KnnModel Mo, const in
     }
   }
   __syncthreads();
+}
+
+// the prediction of item i from the ratings row (0 and false where there is none)
+__device__ __forceinline__ bool knn_item_predict(const KnnModel &Mo, const float *row, int u, int i, const double *__restrict__ fallback,
+                                                 float &pred) {
+  const int N = Mo.n_items;
+  double num = 0.0, den = 0.0;
+  for (int t = 0; t < Mo.k; ++t) {
+    const int j = Mo.nb_idx[(size_t)i * Mo.k + t];
+    if (j < 0) break;
+    if (j >= N) continue;
+    const float v = row[j];
+    if (v != v) continue;
+    knn_term(Mo.agg, (double)Mo.nb_sim[(size_t)i * Mo.k + t], (double)v, num, den);
+  }
+  pred = 0.0f;
+  if (den > 0.0) pred = (float)(num / den);
+  else if (fallback && (unsigned)u < (unsigned)Mo.n_users) pred = (float)fallback[u];
+  else return false;
+  return true;
+}
+
+__global__ __launch_bounds__(kBlock) void k_knn_score_item(KnnModel Mo, const int32_t *__restrict__ uid, const double *__restrict__ fallback,
+                                                           float *__restrict__ out, uint32_t *mask, float *rows) {
+  extern __shared__ __align__(16) float knn_lds_f[];
+  const int r = blockIdx.x, N = Mo.n_items;
+  float *row = rows ? rows + (size_t)r * N : knn_lds_f;
+  const int u = uid[r];
+  knn_item_ratings(Mo, u, row);
   for (int i = threadIdx.x; i < N; i += kBlock) {
-    double num = 0.0, den = 0.0;
-    for (int t = 0; t < Mo.k; ++t) {
-      const int j = Mo.nb_idx[(size_t)i * Mo.k + t];
-      if (j < 0) break;
-      if (j >= N) continue;
-      const float v = row[j];
-      if (v != v) continue;
-      knn_term(Mo.agg, (double)Mo.nb_sim[(size_t)i * Mo.k + t], (double)v, num, den);
-    }
-    float pred = 0.0f;
-    if (den > 0.0) pred = (float)(num / den);
-    else if (fallback && (unsigned)u < (unsigned)Mo.n_users) pred = (float)fallback[u];
-    else knn_clear_bit(mask, (size_t)r * N + i);
+    float pred;
+    if (!knn_item_predict(Mo, row, u, i, fallback, pred)) knn_clear_bit(mask, (size_t)r * N + i);
     out[(size_t)r * N + i] = pred;
   }
 }
 
 // UserKNN: the sums of every item [n_items][2] doubles in LDS (or the scratch); the neighbours' CSR rows one after another, a lane per
 // entry — a row's columns are distinct, so no two lanes meet.
-__global__ __launch_bounds__(kBlock) void k_knn_score_user(KnnModel Mo, const int32_t *__restrict__ uid, float *__restrict__ out, uint32_t *mask,
-                                                           double *rows) {
-  extern __shared__ __align__(16) double knn_lds_d[];
-  const int r = blockIdx.x, N = Mo.n_items;
-  double *acc = rows ? rows + (size_t)r * 2 * N : knn_lds_d;
+__device__ __forceinline__ void knn_user_sums(const KnnModel &Mo, int u, double *acc) {
+  const int N = Mo.n_items;
   for (int i = threadIdx.x; i < 2 * N; i += kBlock) acc[i] = 0.0;
   __syncthreads();
-  const int u = uid[r];
   if ((unsigned)u < (unsigned)Mo.n_users) {
     for (int t = 0; t < Mo.k; ++t) {
       const int v = Mo.nb_idx[(size_t)u * Mo.k + t];                  // (uniform over the workgroup)
@@ -511,11 +521,25 @@ __global__ __launch_bounds__(kBlock) void k_knn_score_user(KnnModel Mo, const in
       __syncthreads();
     }
   }
+}
+
+__device__ __forceinline__ bool knn_user_predict(const double *acc, int i, float &pred) {
+  const double num = acc[2 * i], den = acc[2 * i + 1];
+  pred = 0.0f;
+  if (!(den > 0.0)) return false;
+  pred = (float)(num / den);
+  return true;
+}
+
+__global__ __launch_bounds__(kBlock) void k_knn_score_user(KnnModel Mo, const int32_t *__restrict__ uid, float *__restrict__ out, uint32_t *mask,
+                                                           double *rows) {
+  extern __shared__ __align__(16) double knn_lds_d[];
+  const int r = blockIdx.x, N = Mo.n_items;
+  double *acc = rows ? rows + (size_t)r * 2 * N : knn_lds_d;
+  knn_user_sums(Mo, uid[r], acc);
   for (int i = threadIdx.x; i < N; i += kBlock) {
-    const double num = acc[2 * i], den = acc[2 * i + 1];
-    float pred = 0.0f;
-    if (den > 0.0) pred = (float)(num / den);
-    else knn_clear_bit(mask, (size_t)r * N + i);
+    float pred;
+    if (!knn_user_predict(acc, i, pred)) knn_clear_bit(mask, (size_t)r * N + i);
     out[(size_t)r * N + i] = pred;
   }
 }
@@ -574,6 +598,189 @@ size_t knn_row_bytes(int type, int n_items) { return (size_t)n_items * (type == 
 size_t knn_score_scratch_bytes(int type, int R, int n_items) {
   if (R < 1 || n_items < 1 || knn_row_bytes(type, n_items) <= kKnnLdsBytes) return 0;
   return align_up((size_t)R * knn_row_bytes(type, n_items), 256) + 256;
+}
+
+// ---- top-n and catalogue ranks where the row lies: no score matrix ----------------------------------------------------------------
+// One workgroup per request row, as the score kernels, and their arithmetic (knn_item_predict / knn_user_predict).  The working row
+// ends as KEYS: uint32 [n_items], the ordered bits of an item's float32 prediction, 0 where it has none (no float orders to 0).
+//   ItemKNN   float ratings [n_items] | uint32 keys [n_items]                                     8 bytes an item
+//   UserKNN   double sums [n_items][2], packed down IN PLACE to uint32 keys [n_items]            16 bytes an item
+// in LDS while the row and the selection's kKnnFusedTail bytes fit kKnnLdsBytes, else in the scratch (one row per request row).
+// An item's full key is (bits << 32 | item): unique, so "the n best" and "how many are ahead" have one answer, ties to the larger id.
+constexpr size_t kKnnFusedTail = 64;      // [2][waves] wave maxima of k_knn_recommend, behind the row
+constexpr int kKnnMaxTopN = 128;
+constexpr int kKnnRankGroup = 4;          // targets a wave counts in one walk of the row
+
+size_t knn_fused_row_bytes(int type, int n_items) { return (size_t)n_items * (type == DRX_KNN_USER ? 2 * sizeof(double) : 2 * sizeof(float)); }
+bool knn_fused_in_lds(int type, int n_items) { return knn_fused_row_bytes(type, n_items) + kKnnFusedTail <= kKnnLdsBytes; }
+size_t knn_fused_scratch_bytes(int type, int R, int n_items) {
+  if (R < 1 || n_items < 1 || knn_fused_in_lds(type, n_items)) return 0;
+  return align_up((size_t)R * knn_fused_row_bytes(type, n_items), 256) + 256;
+}
+
+__device__ __forceinline__ u64 knn_full_key(uint32_t bits, int i) { return bits ? ((u64)bits << 32) | (unsigned)i : 0ull; }
+
+// The keys of user u's row in the working area ws (all threads; ends on a barrier).
+template <int TYPE>
+__device__ __forceinline__ uint32_t *knn_row_keys(const KnnModel &Mo, int u, const double *__restrict__ fallback, void *ws) {
+  const int N = Mo.n_items;
+  if constexpr (TYPE == DRX_KNN_ITEM) {
+    float *row = (float *)ws;
+    uint32_t *keys = (uint32_t *)(row + N);
+    knn_item_ratings(Mo, u, row);
+    for (int i = threadIdx.x; i < N; i += kBlock) {
+      float pred;
+      keys[i] = knn_item_predict(Mo, row, u, i, fallback, pred) ? knn_ordered_bits(pred) : 0u;
+    }
+    __syncthreads();
+    return keys;
+  } else {
+    double *acc = (double *)ws;
+    uint32_t *keys = (uint32_t *)ws;
+    knn_user_sums(Mo, u, acc);
+    // key i lands on the sums of item i / 4, which this or an earlier round has read: a barrier between a round's reads and its writes
+    for (int base = 0; base < N; base += kBlock) {
+      const int i = base + (int)threadIdx.x;
+      uint32_t key = 0u;
+      float pred;
+      if (i < N && knn_user_predict(acc, i, pred)) key = knn_ordered_bits(pred);
+      __syncthreads();
+      if (i < N) keys[i] = key;
+    }
+    __syncthreads();
+    return keys;
+  }
+}
+
+// the exclusion row of user u, empty without a CSR or for a user outside the model
+__device__ __forceinline__ void knn_excl_row(const int64_t *__restrict__ excl_indptr, int u, int n_users, int64_t &lo, int64_t &hi) {
+  lo = hi = 0;
+  if (!excl_indptr || (unsigned)u >= (unsigned)n_users) return;
+  lo = excl_indptr[u];
+  hi = excl_indptr[u + 1];
+}
+
+struct KnnFused {
+  const int32_t *uid;
+  const double *fallback;
+  const int64_t *excl_indptr;
+  const int32_t *excl_indices;
+  unsigned char *rows;           // the working rows in the scratch, nullptr: LDS
+  size_t row_bytes;
+};
+
+// The n best by rounds: every thread holds the largest full key of its own items (i = thread, thread + 256, ...) below the last key
+// taken; a round is one maximum over the workgroup (shuffles within a wave, one LDS word a wave, one barrier), and only the thread
+// whose key was taken looks through its items again.
+template <int TYPE>
+__global__ __launch_bounds__(kBlock) void k_knn_recommend(KnnModel Mo, KnnFused F, int n, int32_t *__restrict__ out_idx, float *__restrict__ out_val) {
+  extern __shared__ __align__(16) unsigned char knn_lds_fused[];
+  const int r = blockIdx.x, N = Mo.n_items, tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+  constexpr int kWaves = kBlock / kWave;
+  u64 *wmax = (u64 *)(knn_lds_fused + (F.rows ? 0 : F.row_bytes));
+  const int u = F.uid[r];
+  uint32_t *keys = knn_row_keys<TYPE>(Mo, u, F.fallback, F.rows ? (void *)(F.rows + (size_t)r * F.row_bytes) : (void *)knn_lds_fused);
+  int64_t xlo, xhi;
+  knn_excl_row(F.excl_indptr, u, Mo.n_users, xlo, xhi);
+  for (int64_t p = xlo + tid; p < xhi; p += kBlock) {
+    const int c = F.excl_indices[p];
+    if ((unsigned)c < (unsigned)N) keys[c] = 0u;
+  }
+  __syncthreads();
+  auto best_below = [&](u64 below) {
+    u64 best = 0ull;
+    for (int i = tid; i < N; i += kBlock) {
+      const u64 key = knn_full_key(keys[i], i);
+      if (key < below && key > best) best = key;
+    }
+    return best;
+  };
+  u64 cand = best_below(~0ull);
+  int32_t *oi = out_idx + (size_t)r * n;
+  float *ov = out_val + (size_t)r * n;
+  for (int j = 0; j < n; ++j) {
+    u64 m = cand;
+#pragma unroll
+    for (int s = kWave / 2; s >= 1; s >>= 1) {
+      const u64 o = __shfl_xor(m, s, kWave);
+      m = o > m ? o : m;
+    }
+    u64 *slot = wmax + (j & 1) * kWaves;                              // (two sets: a round's words are read while the next one's are written)
+    if (lane == 0) slot[wave] = m;
+    __syncthreads();
+    u64 best = slot[0];
+#pragma unroll
+    for (int w = 1; w < kWaves; ++w) best = slot[w] > best ? slot[w] : best;
+    if (best == 0ull) {                                               // (uniform) no eligible item is left
+      for (int t = j + tid; t < n; t += kBlock) { oi[t] = -1; ov[t] = -INFINITY; }
+      break;
+    }
+    if (tid == 0) { oi[j] = (int32_t)(best & 0xFFFFFFFFull); ov[j] = knn_score_of(best); }
+    if (cand == best) cand = best_below(best);
+  }
+}
+
+// Ranks by counting: a wave takes kKnnRankGroup targets of the row at a time and walks the keys once for them; the exclusion row is
+// taken off afterwards (the items in it that are ahead), which leaves the target's own exclusion out of it.  No barrier after the keys.
+template <int TYPE>
+__global__ __launch_bounds__(kBlock) void k_knn_rank_lists(KnnModel Mo, KnnFused F, const int64_t *__restrict__ target_indptr,
+                                                           const int32_t *__restrict__ targets, int64_t P, int32_t *__restrict__ out_rank,
+                                                           float *__restrict__ out_score) {
+  extern __shared__ __align__(16) unsigned char knn_lds_fused[];
+  const int r = blockIdx.x, N = Mo.n_items, tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+  const int64_t tlo = min(max(target_indptr[r], (int64_t)0), P), thi = min(max(target_indptr[r + 1], tlo), P);
+  if (tlo >= thi) return;                                             // (uniform: before any barrier)
+  const int u = F.uid[r];
+  const uint32_t *keys = knn_row_keys<TYPE>(Mo, u, F.fallback, F.rows ? (void *)(F.rows + (size_t)r * F.row_bytes) : (void *)knn_lds_fused);
+  int64_t xlo, xhi;
+  knn_excl_row(F.excl_indptr, u, Mo.n_users, xlo, xhi);
+  constexpr int G = kKnnRankGroup;
+  for (int64_t g = tlo + (int64_t)wave * G; g < thi; g += (int64_t)(kBlock / kWave) * G) {
+    u64 tk[G];
+    int cnt[G];
+#pragma unroll
+    for (int j = 0; j < G; ++j) {
+      const int t = g + j < thi ? targets[g + j] : -1;
+      const u64 key = (unsigned)t < (unsigned)N ? knn_full_key(keys[t], t) : 0ull;
+      tk[j] = key ? key : ~0ull;                                      // (nothing is ahead of ~0: no prediction, no rank)
+      cnt[j] = 0;
+    }
+    for (int i = lane; i < N; i += kWave) {
+      const u64 key = knn_full_key(keys[i], i);
+#pragma unroll
+      for (int j = 0; j < G; ++j) cnt[j] += key > tk[j] ? 1 : 0;
+    }
+    for (int64_t p = xlo + lane; p < xhi; p += kWave) {
+      const int c = F.excl_indices[p];
+      const u64 key = (unsigned)c < (unsigned)N ? knn_full_key(keys[c], c) : 0ull;
+#pragma unroll
+      for (int j = 0; j < G; ++j) cnt[j] -= key > tk[j] ? 1 : 0;
+    }
+#pragma unroll
+    for (int j = 0; j < G; ++j) {
+#pragma unroll
+      for (int s = kWave / 2; s >= 1; s >>= 1) cnt[j] += __shfl_xor(cnt[j], s, kWave);
+      if (lane == j && g + j < thi) {
+        const bool has = tk[j] != ~0ull;
+        out_rank[g + j] = has ? cnt[j] : -1;
+        out_score[g + j] = has ? knn_score_of(tk[j]) : -INFINITY;
+      }
+    }
+  }
+}
+
+// what both entry points check before they launch, and where the working rows of R request rows lie
+int knn_fused_args(const KnnModel &Mo, const int32_t *uid, int R, const double *fallback, const int64_t *excl_indptr, const int32_t *excl_indices,
+                   void *scratch, size_t scratch_bytes, KnnFused &F, size_t &lds) {
+  if (!knn_model_ok(Mo) || R < 0 || (fallback && Mo.type != DRX_KNN_ITEM) || (!excl_indptr != !excl_indices)) return DRX_EINVAL;
+  if (R > 0 && !uid) return DRX_EINVAL;
+  const size_t need = knn_fused_scratch_bytes(Mo.type, R, Mo.n_items);
+  if (need && (!scratch || scratch_bytes < need)) return DRX_ESCRATCH;
+  F.uid = uid; F.fallback = fallback; F.excl_indptr = excl_indptr; F.excl_indices = excl_indices;
+  F.rows = need ? (unsigned char *)scratch : nullptr;
+  F.row_bytes = knn_fused_row_bytes(Mo.type, Mo.n_items);
+  lds = need ? 0 : F.row_bytes;
+  return DRX_OK;
 }
 
 }  // namespace
@@ -641,6 +848,73 @@ extern "C" int drx_knn_pair_scores(int32_t type, int32_t aggregation, const int6
   if (groups > 0x7FFFFFFFll) return DRX_EINVAL;
   hipLaunchKernelGGL(drx::k_knn_pair_scores, dim3((unsigned)groups), dim3(drx::kBlock), 0, (hipStream_t)stream, Mo, uid, iid, P, fallback, out,
                      none);
+  DRX_LAUNCH_CHECK();
+  return DRX_OK;
+}
+
+extern "C" size_t drx_knn_recommend_scratch_bytes(int32_t type, int32_t R, int32_t n_items, int32_t n) {
+  if (n < 1 || n > drx::kKnnMaxTopN) return 0;
+  return drx::knn_fused_scratch_bytes(type, R, n_items);
+}
+
+extern "C" int drx_knn_recommend(int32_t type, int32_t aggregation, const int64_t *indptr, const int32_t *indices, const float *values,
+                                 int64_t nnz, int32_t n_users, int32_t n_items, const int32_t *nb_idx, const float *nb_sim, int32_t k,
+                                 const int32_t *uid, int32_t R, int32_t n, const double *fallback, const int64_t *excl_indptr,
+                                 const int32_t *excl_indices, int32_t *out_idx, float *out_val, void *scratch, size_t scratch_bytes,
+                                 void *stream) {
+  drx::KnnModel Mo{indptr, indices, values, nnz, n_users, n_items, nb_idx, nb_sim, k, type, aggregation};
+  if (n < 1) return DRX_EINVAL;
+  if (n > drx::kKnnMaxTopN) return DRX_ENOTIMPL;
+  if (R > 0 && (!out_idx || !out_val)) return DRX_EINVAL;
+  drx::KnnFused F;
+  size_t lds;
+  const int rc = drx::knn_fused_args(Mo, uid, R, fallback, excl_indptr, excl_indices, scratch, scratch_bytes, F, lds);
+  if (rc != DRX_OK || R == 0) return rc;
+  hipStream_t st = (hipStream_t)stream;
+  lds += drx::kKnnFusedTail;
+  if (type == DRX_KNN_ITEM) {
+    DRX_HIP(hipFuncSetAttribute((const void *)drx::k_knn_recommend<DRX_KNN_ITEM>, hipFuncAttributeMaxDynamicSharedMemorySize,
+                                (int)drx::kKnnLdsBytes));
+    hipLaunchKernelGGL(drx::k_knn_recommend<DRX_KNN_ITEM>, dim3(R), dim3(drx::kBlock), lds, st, Mo, F, n, out_idx, out_val);
+  } else {
+    DRX_HIP(hipFuncSetAttribute((const void *)drx::k_knn_recommend<DRX_KNN_USER>, hipFuncAttributeMaxDynamicSharedMemorySize,
+                                (int)drx::kKnnLdsBytes));
+    hipLaunchKernelGGL(drx::k_knn_recommend<DRX_KNN_USER>, dim3(R), dim3(drx::kBlock), lds, st, Mo, F, n, out_idx, out_val);
+  }
+  DRX_LAUNCH_CHECK();
+  return DRX_OK;
+}
+
+extern "C" size_t drx_knn_rank_lists_scratch_bytes(int32_t type, int32_t R, int64_t P, int32_t n_items) {
+  if (P < 1) return 0;
+  return drx::knn_fused_scratch_bytes(type, R, n_items);
+}
+
+extern "C" int drx_knn_rank_lists(int32_t type, int32_t aggregation, const int64_t *indptr, const int32_t *indices, const float *values,
+                                  int64_t nnz, int32_t n_users, int32_t n_items, const int32_t *nb_idx, const float *nb_sim, int32_t k,
+                                  const int32_t *uid, int32_t R, const int64_t *target_indptr, const int32_t *targets, int64_t P,
+                                  const double *fallback, const int64_t *excl_indptr, const int32_t *excl_indices, int32_t *out_rank,
+                                  float *out_score, void *scratch, size_t scratch_bytes, void *stream) {
+  drx::KnnModel Mo{indptr, indices, values, nnz, n_users, n_items, nb_idx, nb_sim, k, type, aggregation};
+  if (R < 0 || P < 0) return DRX_EINVAL;
+  const bool work = R > 0 && P > 0;
+  if (work && (!target_indptr || !targets || !out_rank || !out_score)) return DRX_EINVAL;
+  drx::KnnFused F;
+  size_t lds;
+  const int rc = drx::knn_fused_args(Mo, uid, work ? R : 0, fallback, excl_indptr, excl_indices, scratch, scratch_bytes, F, lds);
+  if (rc != DRX_OK || !work) return rc;
+  hipStream_t st = (hipStream_t)stream;
+  if (type == DRX_KNN_ITEM) {
+    DRX_HIP(hipFuncSetAttribute((const void *)drx::k_knn_rank_lists<DRX_KNN_ITEM>, hipFuncAttributeMaxDynamicSharedMemorySize,
+                                (int)drx::kKnnLdsBytes));
+    hipLaunchKernelGGL(drx::k_knn_rank_lists<DRX_KNN_ITEM>, dim3(R), dim3(drx::kBlock), lds, st, Mo, F, target_indptr, targets, P, out_rank,
+                       out_score);
+  } else {
+    DRX_HIP(hipFuncSetAttribute((const void *)drx::k_knn_rank_lists<DRX_KNN_USER>, hipFuncAttributeMaxDynamicSharedMemorySize,
+                                (int)drx::kKnnLdsBytes));
+    hipLaunchKernelGGL(drx::k_knn_rank_lists<DRX_KNN_USER>, dim3(R), dim3(drx::kBlock), lds, st, Mo, F, target_indptr, targets, P, out_rank,
+                       out_score);
+  }
   DRX_LAUNCH_CHECK();
   return DRX_OK;
 }

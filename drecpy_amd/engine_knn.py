@@ -14,6 +14,8 @@ from .engine import RowsRecommender, pack_mask_bits
 class KnnEngine(RowsRecommender):
     DENSE_BUDGET_BYTES = 8 << 30        # the dense fp32 matrix drx_knn_neighbours stages in its scratch
     MAX_K = 128                         # the kernel's domain
+    FUSED_MAX_N = 128                   # the longest list drx_knn_recommend selects (a longer one: score_rows + topk)
+    SCRATCH_CHUNK_BYTES = 1 << 30       # rows past LDS: the working rows of one launch of the fused kernels stay within this
 
     def __init__(self, n_users, n_items, kind, device='cuda:0'):
         assert kind in ('user', 'item'), kind
@@ -22,6 +24,7 @@ class KnnEngine(RowsRecommender):
         self.device = torch.device(device)
         self.k = None
         self.nb_idx = self.nb_sim = None
+        self.fused = True               # False: recommend_batch / catalogue_ranks of the public classes keep the score-matrix route
 
     # ---- the ratings ---------------------------------------------------------------------------------------------------------------
     def _upload_csr(self, csr, n_rows):
@@ -121,3 +124,62 @@ class KnnEngine(RowsRecommender):
         check(lib().drx_knn_pair_scores(*self._model_args(aggregation), ptr(uid), ptr(iid), P, ptr(fb), ptr(out), ptr(none),
                                         stream_ptr(self.device)), 'drx_knn_pair_scores')
         return out, none
+
+    # ---- top-n and catalogue ranks without the score matrix (include/drx.h drx_knn_recommend / drx_knn_rank_lists) -----------------------
+    def _fallback(self, use_averages):
+        return self.user_mean if use_averages and self.kind == 'item' else None
+
+    def _fused_scratch(self, need):
+        sc = getattr(self, '_fused_sc', None)
+        if need and (sc is None or sc.numel() < need):
+            self._fused_sc = None
+            sc = self._fused_sc = torch.empty(need, dtype=torch.uint8, device=self.device)
+        return sc if need else None
+
+    def recommend(self, uids, n, aggregation, use_averages=False, exclude=None, chunk_bytes=None):
+        """(idx int32 [R, n], val float32 [R, n]) on the device: per user the n <= FUSED_MAX_N best items the model has a prediction
+        for, drx_topk's order, -1 / -inf behind the last; exclude: without the user's row of set_exclusions().  One launch while a
+        working row fits LDS; past it `chunk_bytes` (SCRATCH_CHUNK_BYTES) of working rows at a time."""
+        uid, n, excl, out_idx, out_val = self._recommend_request(uids, n, exclude)
+        R = int(uid.numel())
+        L = lib()
+        if not 1 <= n <= self.FUSED_MAX_N:
+            raise _lib.DrxError(f'drx_knn_recommend: n = {n} lies outside the fused domain 1..{self.FUSED_MAX_N}')
+        per = self._fused_chunk(int(L.drx_knn_recommend_scratch_bytes(self.type, 1, self.n_items, n)), R, chunk_bytes)
+        fb = self._fallback(use_averages)
+        for lo in range(0, R, per):
+            r = min(per, R - lo)
+            need = int(L.drx_knn_recommend_scratch_bytes(self.type, r, self.n_items, n))
+            sc = self._fused_scratch(need)
+            check(L.drx_knn_recommend(*self._model_args(aggregation), ptr(uid[lo:lo + r]), r, n, ptr(fb), ptr(excl[0]) if excl else None,
+                                      ptr(excl[1]) if excl else None, ptr(out_idx[lo:lo + r]), ptr(out_val[lo:lo + r]), ptr(sc), need,
+                                      stream_ptr(self.device)), 'drx_knn_recommend')
+        return out_idx, out_val
+
+    def _fused_chunk(self, one_row_bytes, R, chunk_bytes):
+        """rows per launch: all of them while the kernels need no scratch"""
+        if one_row_bytes == 0:
+            return max(R, 1)
+        return max(1, int(chunk_bytes or self.SCRATCH_CHUNK_BYTES) // one_row_bytes)
+
+    def rank_lists(self, uids, indptr, targets, aggregation, use_averages=False, exclude=None, chunk_bytes=None):
+        """(rank int32 [P], score float32 [P]) on the device, parallel to `targets`: row r (user uids[r]) owns targets[indptr[r] :
+        indptr[r + 1]]; the rank is the number of eligible items ahead of the target in recommend()'s order with n unbounded, -1 / -inf
+        for a target outside the catalogue or without a prediction.  A target's own exclusion is ignored."""
+        uid, ip, d_ip, tg, excl = self._rank_lists_request(uids, indptr, targets, exclude)
+        R, P = int(uid.numel()), int(tg.numel())
+        out_rank = torch.empty(P, dtype=torch.int32, device=self.device)
+        out_score = torch.empty(P, dtype=torch.float32, device=self.device)
+        if R == 0 or P == 0:
+            return out_rank, out_score
+        L = lib()
+        per = self._fused_chunk(int(L.drx_knn_rank_lists_scratch_bytes(self.type, 1, P, self.n_items)), R, chunk_bytes)
+        fb = self._fallback(use_averages)
+        for lo in range(0, R, per):
+            r = min(per, R - lo)
+            need = int(L.drx_knn_rank_lists_scratch_bytes(self.type, r, P, self.n_items))
+            sc = self._fused_scratch(need)
+            check(L.drx_knn_rank_lists(*self._model_args(aggregation), ptr(uid[lo:lo + r]), r, ptr(d_ip[lo:]), ptr(tg), P, ptr(fb),
+                                       ptr(excl[0]) if excl else None, ptr(excl[1]) if excl else None, ptr(out_rank), ptr(out_score),
+                                       ptr(sc), need, stream_ptr(self.device)), 'drx_knn_rank_lists')
+        return out_rank, out_score

@@ -1036,6 +1036,41 @@ int drx_knn_pair_scores(int32_t type, int32_t aggregation, const int64_t *indptr
                         const int32_t *uid, const int32_t *iid, int64_t P, const double *fallback, double *out, uint8_t *none,
                         void *stream);
 
+/* Top-n and catalogue ranks from the same predictions WITHOUT the [R, n_items] matrix of drx_knn_score_rows and without a candidate
+ * mask: the model arguments, uid [R] and fallback (DRX_KNN_ITEM only, else DRX_EINVAL) as drx_knn_score_rows takes them, the optional
+ * exclusion CSR over users (excl_indptr [n_users + 1] / excl_indices, columns ascending and unique; both NULL = none) as
+ * drx_rows_recommend takes it.  The prediction of (r, i) is drx_knn_score_rows' value bit for bit (the same device code: the same terms
+ * in the same order, double, one rounding to float32).  An item is ELIGIBLE for row r when it has a prediction (a term, or the
+ * fallback) and is not in the exclusion row of uid[r]; a uid[r] outside [0, n_users) has no eligible item.  Order is drx_topk's:
+ * descending prediction, ties to the larger item index (key = ordered float bits << 32 | item, -0.0 carried as +0.0).
+ * drx_knn_recommend: out_idx / out_val [R, n] = the n best eligible items of each row, -1 / -inf behind the last one.  Domain
+ *   1 <= n <= 128; a larger n returns DRX_ENOTIMPL (scratch bytes 0) and the caller keeps drx_knn_score_rows + drx_topk.
+ * drx_knn_rank_lists: row r owns targets[target_indptr[r] .. target_indptr[r + 1]) (target_indptr a DEVICE pointer to R + 1 offsets,
+ *   clamped into [0, P]; P is given, nothing is read back), in any order, duplicates allowed, possibly empty.  For a target t of row r
+ *     out_rank  = #{ i != t, i eligible for r, (prediction_i, i) > (prediction_t, t) }      out_score = t's prediction
+ *   — the position t has in drx_knn_recommend's list for that row with n unbounded.  The target's own exclusion is ignored (the
+ *   caller decides what an excluded target means).  A target outside [0, n_items), a target without a prediction and a uid outside
+ *   the model give -1 / -inf.  P == 0 or R == 0 returns DRX_OK and writes nothing; slots from P on are never written.
+ * One workgroup per row.  Its working row — DRX_KNN_ITEM: the user's ratings and the prediction keys, 8 bytes an item; DRX_KNN_USER:
+ * the [n_items][2] double sums, overwritten in place by the keys, 16 bytes an item — lives in LDS while it fits 160 KiB less 64 bytes
+ * (n_items <= 20472 / 10236; scratch bytes 0), beyond that in the scratch (R rows of that size, the only thing of size [R, n_items]
+ * ever written).  The exclusion row is applied in the workgroup; the selection takes n rounds of "the largest key below the last
+ * one", the ranks one counting walk of the row per 4 targets.  No atomics, every order fixed: the result is a function of the
+ * inputs alone, the same for every request order and chunking.  Argument errors DRX_EINVAL (also NULL outputs with work to do, one
+ * half of the exclusion CSR without the other), a short scratch DRX_ESCRATCH. */
+size_t drx_knn_recommend_scratch_bytes(int32_t type, int32_t R, int32_t n_items, int32_t n);
+int drx_knn_recommend(int32_t type, int32_t aggregation, const int64_t *indptr, const int32_t *indices, const float *values, int64_t nnz,
+                      int32_t n_users, int32_t n_items, const int32_t *nb_idx, const float *nb_sim, int32_t k,
+                      const int32_t *uid, int32_t R, int32_t n, const double *fallback,
+                      const int64_t *excl_indptr, const int32_t *excl_indices,
+                      int32_t *out_idx, float *out_val, void *scratch, size_t scratch_bytes, void *stream);
+size_t drx_knn_rank_lists_scratch_bytes(int32_t type, int32_t R, int64_t P, int32_t n_items);
+int drx_knn_rank_lists(int32_t type, int32_t aggregation, const int64_t *indptr, const int32_t *indices, const float *values, int64_t nnz,
+                       int32_t n_users, int32_t n_items, const int32_t *nb_idx, const float *nb_sim, int32_t k,
+                       const int32_t *uid, int32_t R, const int64_t *target_indptr, const int32_t *targets, int64_t P,
+                       const double *fallback, const int64_t *excl_indptr, const int32_t *excl_indices,
+                       int32_t *out_rank, float *out_score, void *scratch, size_t scratch_bytes, void *stream);
+
 /* ---- stable device radix sort of (key, val) pairs (the inverted-index builder of the sparse steps; ties keep their input order).
  * Every key must be < 2^key_bits: the sort runs ceil(key_bits / digit) passes of 8-, 10- or 11-bit digits, i.e. it orders on
  * passes * digit >= key_bits bits — bits above key_bits are NOT ignored (DRX_EINVAL is not raised for them: the result is then ordered
