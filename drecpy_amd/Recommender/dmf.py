@@ -102,16 +102,13 @@ class DMF(RecommenderABC):
         from ..engine import run_ahead_stream
         self._dev_side = run_ahead_stream(self._engine.device, 0)          # (the process-wide pool: a stream with a hardware queue of its own)
         self._dev_side.wait_stream(torch.cuda.current_stream(self._engine.device))       # the frame uploaded a moment ago
-        self._dev_done = {}                          # ring slot -> event recorded behind the step that read it
         self._sampler_kind = 'device PointSampler (drx_point_sample_valued, counter-based; throughput mode)'
 
     def _draw_device(self, batch_size):
-        """The next batch, drawn and prepared on the side stream (it waits only for the step that last read the ring slot it writes)."""
+        """The next batch, drawn and prepared on the side stream (which the engine makes wait only for the step that last read the ring
+        slot it writes)."""
         import torch
         eng = self._engine
-        k = eng._dev_i % 3
-        if k in self._dev_done:
-            self._dev_side.wait_event(self._dev_done[k])
         self._dev_draws += 1
         seed = (int(self.seed) if self.seed is not None else 0) * 1000003 + self._dev_draws
         from ..engine import _on_stream                 # (`with torch.cuda.stream(...)` without most of its Python layers)
@@ -119,7 +116,6 @@ class DMF(RecommenderABC):
             prep = eng.prepare_batch_device(batch_size, self._neg_ratio, seed)
             prep['ready'] = torch.cuda.Event()
             prep['ready'].record(self._dev_side)
-        prep['slot'] = k
         return prep
 
     def _fused_trainables(self):
@@ -163,16 +159,9 @@ class DMF(RecommenderABC):
         if isinstance(batch_samples, tuple) and len(batch_samples) == 2 and batch_samples[0] == 'device-batch':
             import torch
             prep = batch_samples[1]
-            main = torch.cuda.current_stream(e.device)
-            main.wait_event(prep['ready'])
-            applies = (len(self._apply_order()), self._apply_position(e.user_nn), self._apply_position(e.item_nn),
-                       self._apply_position(e.scale_var) if e.scale_var is not None else None)
-            out = e.step(step, prep, want_loss=want_loss, applies=applies)
-            ev = torch.cuda.Event()
-            ev.record(main)
-            self._dev_done[prep['slot']] = ev
-            return out
-        prep = batch_samples[3] if len(batch_samples) > 3 else e.prepare_batch(*batch_samples[:3])
+            torch.cuda.current_stream(e.device).wait_event(prep['ready'])
+        else:
+            prep = batch_samples[3] if len(batch_samples) > 3 else e.prepare_batch(*batch_samples[:3])
         # one apply_gradients per registered item, in registration-list order (recommender_abc.py:194-196,328-334)
         applies = (len(self._apply_order()), self._apply_position(e.user_nn), self._apply_position(e.item_nn),
                    self._apply_position(e.scale_var) if e.scale_var is not None else None)

@@ -42,7 +42,7 @@ _LOG_FORMAT = '[%(asctime)s] (%(levelname)s) %(name)s: %(message)s'
 _UNPICKLED = ('_engine', '_logger', '_file_logger', '_device_lock', '_sampler', '_mask_rng', '_mask_rngs', '_drawahead', '_L', 'epoch_weights', '_pipeline', '_pending',
               '_host_pool', '_dist_model', 'optimizer', 'trainable_vars', 'trainable_weights', 'trainable_layers', 'trainable_models',
               '_extra_weight', 'W', 'W_', 'V', 'b', 'b_', 'user_nn', 'item_nn', '_layers',
-              '_ahead', '_dev_side', '_dev_next', '_dev_done')             # (run-ahead state of fit(device_sampler=True): streams, events, device batches)
+              '_ahead', '_dev_side', '_dev_next')             # (run-ahead state of fit(device_sampler=True): streams, events, device batches)
 
 
 def _make_logger(name, handler):

@@ -530,42 +530,25 @@ class CdaeEngine(RowsRecommender):
             return a.to(self.device, dtype).contiguous()
         return torch.as_tensor(np.ascontiguousarray(a)).to(self.device, dtype)
 
-    _STAGE_SLOTS = 4
-
     def _make_batch_staged(self, uid, iid, y, keep_off, keep, q, mask_seed, n_touch_slots):
-        """Host (numpy) batch -> device in ONE asynchronous copy: the arrays are packed into a pinned staging buffer (a ring
-        of _STAGE_SLOTS, so the host can run ahead of the device) and land in one device buffer that the Batch points into."""
+        """Host (numpy) batch -> device in ONE asynchronous copy (_staging.StagedUpload: a pinned ring, so the host can run ahead of
+        the device): the arrays land in one device buffer that the Batch points into."""
         B = len(uid)
-        parts = [('uid', np.ascontiguousarray(uid, dtype=np.int32)), ('keep_off', np.ascontiguousarray(keep_off, dtype=np.int32))]
+        parts = {'uid': np.ascontiguousarray(uid, dtype=np.int32), 'keep_off': np.ascontiguousarray(keep_off, dtype=np.int32)}
         if iid is not None:
-            parts.append(('iid', np.ascontiguousarray(iid, dtype=np.int32)))
+            parts['iid'] = np.ascontiguousarray(iid, dtype=np.int32)
         if y is not None:
-            parts.append(('y', np.ascontiguousarray(y, dtype=np.float32)))
+            parts['y'] = np.ascontiguousarray(y, dtype=np.float32)
         if keep is not None:
             k8 = np.ascontiguousarray(keep, dtype=np.uint8)
-            parts.append(('keep', k8 if k8.size else np.zeros(1, np.uint8)))
-        offs, total = {}, 0
-        for name, a in parts:
-            offs[name] = total
-            total += (a.nbytes + 15) & ~15
-        st = self.__dict__.setdefault('_stage', {'i': 0, 'host': [None] * self._STAGE_SLOTS, 'ev': [None] * self._STAGE_SLOTS})
-        k = st['i'] % self._STAGE_SLOTS
-        st['i'] += 1
-        if st['host'][k] is None or st['host'][k].numel() < total:
-            st['host'][k] = torch.empty(int(total * 1.5) + 4096, dtype=torch.uint8, pin_memory=True)
-            st['ev'][k] = None
-        if st['ev'][k] is not None:
-            st['ev'][k].synchronize()                 # the copy that last read this pinned slot (4 batches ago) has finished
-        hv = st['host'][k].numpy()
-        for name, a in parts:
-            hv[offs[name]:offs[name] + a.nbytes] = a.view(np.uint8).reshape(-1)
-        dev = torch.empty(total, dtype=torch.uint8, device=self.device)      # owned by the batch (the keep-alive tuple)
-        dev.copy_(st['host'][k][:total], non_blocking=True)
-        st['ev'][k] = torch.cuda.Event()
-        st['ev'][k].record(torch.cuda.current_stream(self.device))
+            parts['keep'] = k8 if k8.size else np.zeros(1, np.uint8)
+        if getattr(self, '_stage', None) is None:
+            from ._staging import StagedUpload
+            self._stage = StagedUpload(self.device)
+        dev, offs = self._stage.pack(list(parts.values()))      # dev: owned by the batch (the keep-alive tuple)
         base = dev.data_ptr()
-        at = lambda name: (base + offs[name]) if name in offs else None
-        bt = Batch(B, at('uid'), at('iid'), at('y'), at('keep_off'), at('keep'), int(mask_seed) & (2 ** 64 - 1), float(q),
+        at = {name: base + o for name, o in zip(parts, offs)}
+        bt = Batch(B, at['uid'], at.get('iid'), at.get('y'), at['keep_off'], at.get('keep'), int(mask_seed) & (2 ** 64 - 1), float(q),
                    int(n_touch_slots), self._batch_flags(n_touch_slots))
         return bt, (dev,)
 

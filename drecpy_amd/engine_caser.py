@@ -16,10 +16,12 @@ import torch
 
 from . import _lib
 from ._lib import AdamSegments, CaserArgs, CaserDims, check, lib, ptr, stream_ptr
-from .engine import ADAM_B1, ADAM_B2, ADAM_EPS, RowsRecommender, _round_up
+from ._staging import StagedUpload
+from .engine import _round_up
+from .engine_dense import DenseEngine, aligned_offsets
 
 
-class CaserEngine(RowsRecommender):
+class CaserEngine(DenseEngine):
     ACTIVATIONS = {'relu': 0, 'tanh': 1, 'sigmoid': 2, 'linear': 3, None: 3}
 
     def __init__(self, n_users, n_items, L=5, T=3, neg_ratio=3, d=50, n_v=4, n_h=16, device='cuda:0', act_h='relu', act_mlp='relu'):
@@ -62,7 +64,7 @@ class CaserEngine(RowsRecommender):
         self.W1 = torch.zeros(n_items, self.ld2, **z)
         self.b1 = torch.zeros(n_items, **z)
         self.sw = torch.zeros(off, **z)
-        self.state = {n: (torch.zeros_like(t), torch.zeros_like(t)) for n, t in self.tensors().items()}
+        self._init_optimizer_state()
         # the dense gradient tables of the scatters live in ONE buffer, zeroed by one kernel per step
         scat = [n for n in ('item_emb', 'W1', 'b1', 'user_emb') if n in self.tensors()]
         sizes = [(self.tensors()[n].numel() + 63) // 64 * 64 for n in scat]
@@ -76,8 +78,8 @@ class CaserEngine(RowsRecommender):
                 self._grads[n] = torch.zeros_like(t)
         self._scratch = None
         self.lr, self.reg = 1e-3, 1e-3
-        self.beta1, self.beta2, self.eps = ADAM_B1, ADAM_B2, ADAM_EPS
-        self.opt_kind, self._slot_init = 'adam', 0.0        # (set_optimizer: another dense rule of optimizers.py)
+        self._stage = StagedUpload(self.device)             # host batches: one asynchronous upload each
+        self._seg_layers = [layer for (_, _, _, _, layer) in self.seg]      # (whose step size a segment of the small weights takes)
         from .Recommender.trainables import TrainableLayer
         # the 6 + L Keras layers caser.py:47-70 registers, in that order (= the order of the per-step Adam applies)
         seg_views = lambda j: [self.sw[st:st + n] for _, st, n, _, layer in self.seg if layer == j]
@@ -130,45 +132,6 @@ class CaserEngine(RowsRecommender):
                 p[name] = c(self.sw[start:start + n])
         return p
 
-    def set_optimizer(self, opt):
-        """The update rule of every dense step from a drecpy_amd.optimizers object (Adam, Adagrad, SGD, RMSprop): its kind and
-        hyper-parameters, and slots of that rule alone — none for plain SGD, s1 for all but Adam and RMSprop with momentum (Adagrad's at
-        its accumulator value).  beta1 / beta2 carry include/drx.h DrxOptRule's mu / mu2.  Slots that already fit the rule are kept."""
-        from .optimizers import KINDS, N_SLOTS
-        kind = opt.kind
-        if kind not in KINDS or kind == 'rowwise_adagrad':
-            raise _lib.DrxError(f'no dense update rule "{kind}"')
-        mu, mu2 = opt._mus()
-        self.lr, self.beta1, self.beta2, self.eps = opt.learning_rate, mu, mu2, getattr(opt, 'epsilon', 0.0)
-        if kind == self.opt_kind and getattr(opt, 'slot_init', 0.0) == self._slot_init:
-            return
-        self.opt_kind, self._slot_init = kind, float(getattr(opt, 'slot_init', 0.0))
-        n = N_SLOTS[kind]
-        self.state = {name: tuple(torch.full_like(t, self._slot_init) if i < n else None for i in range(2)) for name, t in self.tensors().items()}
-
-    def _rule(self, step_size=0.0):
-        """include/drx.h DrxOptRule of the engine's rule (step_size: where the entry point has none per variable)"""
-        key = (self.opt_kind, step_size, self.beta1, self.beta2, self.eps)
-        c = self.__dict__.get('_rule_cache')
-        if c is None or c[0] != key:                     # (one struct per setting: the steps pass it by reference)
-            from .optimizers import KINDS
-            c = self._rule_cache = (key, _lib.OptRule(KINDS[self.opt_kind], step_size, self.beta1, self.beta2, self.eps))
-        return c[1]
-
-    def snapshot(self):
-        """Device copies of the parameters and of the slots the rule has (used by _store_epoch_weights / _revert_weights)."""
-        return {'p': {n: t.clone() for n, t in self.tensors().items()},
-                's': {n: tuple(None if t is None else t.clone() for t in st) for n, st in self.state.items()}}
-
-    def restore(self, snap, with_optimizer=False):
-        for n, t in self.tensors().items():
-            t.copy_(snap['p'][n])
-        if with_optimizer and 's' in snap:
-            for n, st in self.state.items():
-                for dst, src in zip(st, snap['s'][n]):
-                    if dst is not None and src is not None:
-                        dst.copy_(src)
-
     # ---- helpers --------------------------------------------------------------------------------------------------
     def _scatter(self, keys, T, src, ld, n_rows, out, src_s=None, out_s=None, stream=None):
         """keys / src / src_s / out / out_s: device addresses.  `out` (and `out_s`) must already be zero: step() clears the whole
@@ -196,14 +159,11 @@ class CaserEngine(RowsRecommender):
         t = (self.n_layers * step_idx + 1 + np.arange(self.n_layers)).astype(np.float32)
         return (f(self.lr) * np.sqrt(f(1.0) - np.power(f(self.beta2), t)) / (f(1.0) - np.power(f(self.beta1), t))).astype(np.float32).tolist()
 
-    def _args(self, uid, before, after=None, keep=None, rate=0.0, mask_seed=0):
+    def _args(self, uid, before, B, after=None):
+        """DrxCaserArgs with the parameters and the B windows' ids at the device addresses uid / before / after"""
         A = CaserArgs()
         A.item_emb, A.user_emb, A.W1, A.b1, A.sw = (t.data_ptr() for t in (self.item_emb, self.user_emb, self.W1, self.b1, self.sw))
-        A.uid, A.before = uid.data_ptr(), before.data_ptr()
-        A.after = after.data_ptr() if after is not None else None
-        A.keep = keep.data_ptr() if keep is not None else None
-        A.rate, A.B = float(rate), int(uid.numel())
-        A.mask_seed = int(mask_seed) & (2 ** 64 - 1)
+        A.uid, A.before, A.after, A.B = uid, before, after, int(B)
         return A
 
     # how the four lookup tables (user / item embeddings, dense_1_W + dense_1_b) are updated: 'csr' = drx_rows_csr_adam, gradient and
@@ -214,163 +174,73 @@ class CaserEngine(RowsRecommender):
     # batches already on the device: group their lookups by table row on the device (True) or take the scatter + dense-Adam update
     device_csr = True
 
-    def prepare_device_batch(self, uid, bef, aft):
-        """A batch that is already on the device, its lookups grouped by table row on the CURRENT stream (which may be a run-ahead
-        stream: nothing here depends on the parameters) — what step() takes in place of (uids, before, after).  The three slots of the
-        ring are reused only behind the step that last read them (an event recorded by that step on ITS stream)."""
-        uid, bef, aft = self._dev_i32(uid), self._dev_i32(bef), self._dev_i32(aft)
-        prep = {'uid': uid, 'before': bef, 'after': aft, 'B': uid.numel()}
-        prep['csr_dev'] = self._csr_on_device(uid, bef, aft, prep)
-        return prep
-
-    # ---- the same with the batch's id tensors OWNED by the ring (Caser.fit(device_sampler=True): the sampler writes into them) ----------
-    # Everything a draw and a step hand to the library is then the same from visit to visit of a slot: the argument structs are built
-    # once per slot (at 4096 windows the host's Python, not the 79 us of training kernels, bounded the step: r06,
-    # profiles/r06_caser_host_profile.txt).
-    def device_slot(self, B):
-        """The next ring slot for a batch of B windows drawn on the device: {'uid', 'before', 'after'} int32 tensors to fill on the CURRENT
-        stream (which has been made to wait for the step that last read the slot), then group_slot(slot)."""
-        st = self.__dict__.setdefault('_dev_slots', {})
+    # ---- batches that are already on the device: rings of three slots ---------------------------------------------------------------
+    # A slot holds the lookups of one batch grouped by table row (drx_batch_csr_device: row_ptr / order of the three lists in one buffer)
+    # and the event `free` of the step that last read it, recorded by that step on ITS stream: the slot is filled again only behind it.
+    # Ring '_dev_csr' (prepare_device_batch) is handed the id tensors of every batch; ring '_dev_slots' (device_slot / group_slot:
+    # Caser.fit(device_sampler=True), the sampler writes into them) OWNS them — everything a draw and a step hand to the library is
+    # then the same from visit to visit of a slot, and the step's call is built once per slot (at 4096 windows the host's Python, not
+    # the 79 us of training kernels, bounded the step: profiles/r06_caser_host_profile.txt).
+    def _ring_slot(self, ring, B, ids=None):
+        """The next slot of `ring` for a batch of B windows, on the CURRENT stream (which may be a run-ahead stream: nothing here depends
+        on the parameters).  ids: the batch's (uid, before, after) int32 device tensors, or None for a ring that owns them."""
+        st = self.__dict__.setdefault(ring, {})
         if st.get('B') != B:
             i32 = dict(dtype=torch.int32, device=self.device)
-            sizes = (self.N + 1, B * self.L, self.N + 1, B * self.Tp, self.U + 1, B)       # ptrE, ordE, ptrW, ordW, ptrU, ordU
-            offs, total = [], 0
-            for n in sizes:
-                offs.append(total)
-                total += (4 * n + 15) & ~15
+            offs, total = aligned_offsets([4 * n for n in (self.N + 1, B * self.L, self.N + 1, B * self.Tp, self.U + 1, B)])
             st.clear()
-            st.update({'B': B, 'i': 0, 'slots': []})
+            st.update({'B': B, 'i': 0, 'scratch': None, 'slots': []})
             for k in range(3):
-                sl = {'k': k, 'B': B, 'uid': torch.empty(B, **i32), 'before': torch.empty(B, self.L, **i32),
-                      'after': torch.empty(B, self.Tp, **i32), 'buf': torch.empty(total, dtype=torch.uint8, device=self.device), 'free': None}
-                base = sl['buf'].data_ptr()
-                ls = (_lib.CsrList * 3)()
-                for l, (keys, T, n_rows, kp_, ko_) in zip(ls, ((sl['before'], B * self.L, self.N, 0, 1), (sl['after'], B * self.Tp, self.N, 2, 3),
-                                                            (sl['uid'], B, self.U, 4, 5))):
-                    l.keys, l.T, l.n_rows, l.row_ptr, l.order = keys.data_ptr(), T, n_rows, base + offs[kp_], base + offs[ko_]
-                sl['lists'] = ls
-                sl['csr_dev'] = [base + o for o in offs]
+                sl = {'k': k, 'B': B, 'buf': torch.empty(total, dtype=torch.uint8, device=self.device), 'free': None, 'own_ids': ids is None}
+                sl['csr_dev'] = [sl['buf'].data_ptr() + o for o in offs]                   # ptrE, ordE, ptrW, ordW, ptrU, ordU
+                if ids is None:
+                    self._slot_ids(sl, torch.empty(B, **i32), torch.empty(B, self.L, **i32), torch.empty(B, self.Tp, **i32))
                 st['slots'].append(sl)
-            need = int(lib().drx_batch_csr_device_bytes(st['slots'][0]['lists'], 3))
-            if need <= 0:
-                raise _lib.DrxError('drx_batch_csr_device_bytes: invalid lists')
-            st['scratch'] = torch.empty(need, dtype=torch.uint8, device=self.device)
-            st['scratch_args'] = (st['scratch'].data_ptr(), st['scratch'].numel())
         sl = st['slots'][st['i'] % 3]
         st['i'] += 1
         if sl['free'] is not None:
             torch.cuda.current_stream(self.device).wait_event(sl['free'])
             sl['free'] = None
+        if ids is not None:
+            self._slot_ids(sl, *ids)               # (the tensors stay alive with the slot: beyond the step that reads them)
         return sl
 
-    def group_slot(self, sl):
-        """the lookups of a filled slot grouped by table row (drx_batch_csr_device) on the current stream; returns what step() takes"""
-        check(lib().drx_batch_csr_device(sl['lists'], 3, *self._dev_slots['scratch_args'], stream_ptr(self.device)), 'drx_batch_csr_device')
-        return sl
-
-    def _step_slot(self, step_idx, sl, keep, rate, mask_seed):
-        """step() on a ring slot (no loss wanted): the argument structs of the slot's earlier visit with this step's scalars"""
-        L_ = lib()
+    def _slot_ids(self, sl, uid, bef, aft):
+        """the id tensors of the slot's batch and the three lists drx_batch_csr_device groups: item lookups, target lookups, users"""
         B = sl['B']
-        c = sl.get('step')
-        n_dE, n_dW1, n_dPu = B * self.L * self.ld, B * self.ld2, B * self.ld
-        wk = getattr(self, '_step_bufs', None)
-        if wk is None or wk[0] != (B, True):               # (the work buffers of a batch size, shared with the general path)
-            z = dict(dtype=torch.float32, device=self.device)
-            grid = L_.drx_caser_grid(C.byref(self.D), B)
-            rows = torch.zeros(n_dE + n_dW1 + n_dPu, **z)
-            wk = self._step_bufs = ((B, True), rows, torch.empty(B * self.Tp, **z), torch.empty(grid, self.D.n_small, **z), torch.empty(grid, **z),
-                                    torch.empty(self.D.n_small + 1, **z))
-        key = (self.item_emb.data_ptr(), self.sw.data_ptr(), self.opt_kind,
-               tuple(s.data_ptr() if s is not None else 0 for n in ('sw', 'W1') for s in self.state[n]), self.reg, self.beta1,
-               self.beta2, self.eps, id(self.D), id(wk))
-        if c is None or c['key'] != key:
-            _, rows, db1, gpart, lpart, gsw = wk
-            base = rows.data_ptr()
-            p_dE, p_dW1, p_dPu = base, base + 4 * n_dE, base + 4 * (n_dE + n_dW1)
-            A = CaserArgs()
-            A.item_emb, A.user_emb, A.W1, A.b1, A.sw = (t.data_ptr() for t in (self.item_emb, self.user_emb, self.W1, self.b1, self.sw))
-            A.uid, A.before, A.after = sl['uid'].data_ptr(), sl['before'].data_ptr(), sl['after'].data_ptr()
-            A.B = int(B)
-            A.dE, A.db1, A.dPu, A.gsw_part, A.loss_part = p_dE, db1.data_ptr(), p_dPu, gpart.data_ptr(), lpart.data_ptr()
-            A.dW1, A.cat_out = None, p_dW1
-            l2c = 2.0 * self.reg
-            sg = AdamSegments()
-            sg.n = len(self.seg)
-            for i, (_, start, n, regd, layer) in enumerate(self.seg):
-                sg.start[i], sg.len[i], sg.l2_coef[i] = start, n, (l2c if regd else 0.0)
-            ptrE, ordE, ptrW, ordW, ptrU, ordU = sl['csr_dev']
-            st_ = self.state
-            tabs = (_lib.CsrAdamTable * 3)()
-            for t, (rp, od, src, scale, group, ld, n_rows, name, sname) in zip(tabs, (
-                    (ptrU, ordU, p_dPu, None, 0, self.ld, self.U, 'user_emb', None),
-                    (ptrE, ordE, p_dE, None, 0, self.ld, self.N, 'item_emb', None),
-                    (ptrW, ordW, p_dW1, db1.data_ptr(), self.Tp, self.ld2, self.N, 'W1', 'b1'))):
-                t.row_ptr, t.order, t.src, t.scale, t.group, t.ld, t.n_rows = rp, od, src, scale, group, ld, n_rows
-                t.p, (t.m, t.v) = getattr(self, name).data_ptr(), (x.data_ptr() if x is not None else None for x in st_[name])
-                if sname is not None:
-                    t.p_s, (t.m_s, t.v_s) = getattr(self, sname).data_ptr(), (x.data_ptr() if x is not None else None for x in st_[sname])
-                t.l2_coef = l2c
-            m, v = self.state['sw']
-            rule = self._rule()
-            c = sl['step'] = {'key': key, 'A': A, 'sg': sg, 'tabs': tabs, 'keep': wk, 'rule': rule,
-                              'small': (C.byref(self.D), C.byref(A), gsw.data_ptr(), self.sw.data_ptr(), _lib.ptr(m), _lib.ptr(v), C.byref(sg),
-                                        C.byref(rule)),
-                              'layers': [layer for (_, _, _, _, layer) in self.seg]}
-        A, sg, tabs = c['A'], c['sg'], c['tabs']
-        kp = None
-        if keep is not None:
-            kp = torch.as_tensor(np.ascontiguousarray(keep, dtype=np.uint8)).to(self.device) if not torch.is_tensor(keep) \
-                else keep.to(self.device, torch.uint8).contiguous()
-        A.keep = kp.data_ptr() if kp is not None else None
-        A.rate = float(rate)
-        A.mask_seed = int(mask_seed) & (2 ** 64 - 1)
-        alpha = self._alphas(step_idx)
-        for i, layer in enumerate(c['layers']):
-            sg.alpha[i] = alpha[layer]
-        tabs[0].alpha, tabs[1].alpha, tabs[2].alpha, tabs[2].alpha_s = alpha[0], alpha[1], alpha[4 + self.L], alpha[5 + self.L]
-        stream = stream_ptr(self.device)
-        check(L_.drx_caser_step_small_opt(*c['small'], stream), 'drx_caser_step_small_opt')
-        check(L_.drx_rows_csr_opt_multi(tabs, 3, C.byref(c['rule']), stream), 'drx_rows_csr_opt_multi')
-        ev = torch.cuda.Event()
-        ev.record(torch.cuda.current_stream(self.device))
-        sl['free'] = ev
-        return None
-
-    def _csr_on_device(self, uid, bef, aft, prep=None):
-        B = uid.numel()
-        sizes = (self.N + 1, B * self.L, self.N + 1, B * self.Tp, self.U + 1, B)           # ptrE, ordE, ptrW, ordW, ptrU, ordU
-        offs, total = [], 0
-        for n in sizes:
-            offs.append(total)
-            total += (4 * n + 15) & ~15
-        st = self.__dict__.setdefault('_dev_csr', {})
-        if st.get('key') != (B, total):
-            st['key'] = (B, total)
-            st['ring'] = [torch.empty(total, dtype=torch.uint8, device=self.device) for _ in range(3)]
-            st['free'] = [None] * 3                        # recorded by the step that read the slot, on its stream
-            st['i'] = 0
-            st['scratch'] = None
-        k = st['i'] % 3
-        buf = st['ring'][k]
-        st['i'] += 1
-        if st['free'][k] is not None:
-            torch.cuda.current_stream(self.device).wait_event(st['free'][k])
-            st['free'][k] = None
-        if prep is not None:
-            prep['slot'] = k
-        base = buf.data_ptr()
+        ptrE, ordE, ptrW, ordW, ptrU, ordU = sl['csr_dev']
         ls = (_lib.CsrList * 3)()
-        for l, (keys, T, n_rows, kp_, ko_) in zip(ls, ((bef, B * self.L, self.N, 0, 1), (aft, B * self.Tp, self.N, 2, 3), (uid, B, self.U, 4, 5))):
-            l.keys, l.T, l.n_rows, l.row_ptr, l.order = keys.data_ptr(), T, n_rows, base + offs[kp_], base + offs[ko_]
+        for l, (keys, T, n_rows, rp, od) in zip(ls, ((bef, B * self.L, self.N, ptrE, ordE), (aft, B * self.Tp, self.N, ptrW, ordW),
+                                                    (uid, B, self.U, ptrU, ordU))):
+            l.keys, l.T, l.n_rows, l.row_ptr, l.order = keys.data_ptr(), T, n_rows, rp, od
+        sl.update(uid=uid, before=bef, after=aft, lists=ls)
+
+    def _group(self, ring, sl):
+        """the lookups of a filled slot grouped by table row (drx_batch_csr_device: one stable sort for the three lists) on the current
+        stream; returns the slot: what step() takes"""
+        st = self.__dict__[ring]
         if st['scratch'] is None:
-            need = int(lib().drx_batch_csr_device_bytes(ls, 3))
+            need = int(lib().drx_batch_csr_device_bytes(sl['lists'], 3))
             if need <= 0:
                 raise _lib.DrxError('drx_batch_csr_device_bytes: invalid lists')
             st['scratch'] = torch.empty(need, dtype=torch.uint8, device=self.device)
-        check(lib().drx_batch_csr_device(ls, 3, st['scratch'].data_ptr(), st['scratch'].numel(), stream_ptr(self.device)), 'drx_batch_csr_device')
-        st['keep'] = (uid, bef, aft)                       # (alive until the next step has been queued behind this one)
-        return [base + o for o in offs]
+            st['scratch_args'] = (st['scratch'].data_ptr(), st['scratch'].numel())
+        check(lib().drx_batch_csr_device(sl['lists'], 3, *st['scratch_args'], stream_ptr(self.device)), 'drx_batch_csr_device')
+        return sl
+
+    def prepare_device_batch(self, uid, bef, aft):
+        """A batch that is already on the device, its lookups grouped by table row on the CURRENT stream — what step() takes in place of
+        (uids, before, after)."""
+        uid, bef, aft = self._dev_i32(uid), self._dev_i32(bef), self._dev_i32(aft)
+        return self._group('_dev_csr', self._ring_slot('_dev_csr', uid.numel(), (uid, bef, aft)))
+
+    def device_slot(self, B):
+        """The next ring slot for a batch of B windows drawn on the device: {'uid', 'before', 'after'} int32 tensors to fill on the CURRENT
+        stream (which has been made to wait for the step that last read the slot), then group_slot(slot)."""
+        return self._ring_slot('_dev_slots', B)
+
+    def group_slot(self, sl):
+        return self._group('_dev_slots', sl)
 
     def prepare_batch(self, uids, before, after):
         """Host half of a step (Caser.fit() runs it on the sampler's worker thread): the batch as int32 arrays plus, for each of the
@@ -378,10 +248,7 @@ class CaserEngine(RowsRecommender):
         B = len(uids)
         L_ = lib()
         sizes = (B, B * self.L, B * self.Tp, self.N + 1, B * self.L, self.N + 1, B * self.Tp, self.U + 1, B)
-        offs, total = [], 0
-        for n in sizes:
-            offs.append(total)
-            total += (4 * n + 15) & ~15
+        offs, total = aligned_offsets([4 * n for n in sizes])
         buf = np.empty(total, np.uint8)
         view = lambda k: buf[offs[k]:offs[k] + 4 * sizes[k]].view(np.int32)
         view(0)[:] = uids
@@ -392,82 +259,20 @@ class CaserEngine(RowsRecommender):
             check(L_.drx_batch_csr(base + offs[keys], T, n_rows, base + offs[kp], base + offs[ko]), 'drx_batch_csr')
         return {'buf': buf, 'offs': offs, 'B': B}
 
-    def _upload(self, buf):
-        st = self.__dict__.setdefault('_ring', {'i': 0, 'host': [None] * 4, 'ev': [None] * 4})
-        total = buf.nbytes
-        k = st['i'] % 4
-        st['i'] += 1
-        if st['host'][k] is None or st['host'][k].numel() < total:
-            st['host'][k] = torch.empty(int(total * 1.5) + 4096, dtype=torch.uint8, pin_memory=True)
-            st['ev'][k] = torch.cuda.Event()
-        else:
-            st['ev'][k].synchronize()                 # the copy that last read this pinned slot has finished
-        st['host'][k].numpy()[:total] = buf
-        dev = torch.empty(total, dtype=torch.uint8, device=self.device)
-        dev.copy_(st['host'][k][:total], non_blocking=True)
-        st['ev'][k].record(torch.cuda.current_stream(self.device))
-        return dev
-
     # ---- one training step ---------------------------------------------------------------------------------------
-    def step(self, step_idx, uids, before=None, after=None, keep=None, rate=0.0, want_loss=False, mask_seed=0):
-        """uids, before, after: the batch (arrays or device tensors) — or `uids` = what prepare_batch returned for it.
-        keep: explicit dropout keep mask [B, n_v + L*n_h] or None; with None and rate > 0 the kernel evaluates the counter-based
-        mask drx_hash_u32(mask_seed, b, j) >= rate * 2^32 itself (no 344 K host random numbers per batch of 4096)."""
-        L_ = lib()
-        csr = None
-        slot = None
-        if isinstance(uids, dict) and 'lists' in uids:             # a ring slot (device_slot / group_slot)
-            if not want_loss and self.table_update == 'csr':
-                return self._step_slot(step_idx, uids, keep, rate, mask_seed)
-            sl = uids                                               # (with the loss: the general path below, on the slot's tensors)
-            uids = {'uid': sl['uid'], 'before': sl['before'], 'after': sl['after'], 'B': sl['B'], 'csr_dev': sl['csr_dev'], 'ring_slot': sl}
-        if isinstance(uids, dict) and 'csr_dev' in uids:           # prepare_device_batch: ids and grouped lookups already on the device
-            prep = uids
-            uid, bef, aft, B, csr, slot = prep['uid'], prep['before'], prep['after'], prep['B'], prep['csr_dev'], prep.get('slot')
-            uid_p, bef_p, aft_p = uid.data_ptr(), bef.data_ptr(), aft.data_ptr()
-            kp = None
-            if keep is not None:
-                kp = torch.as_tensor(np.ascontiguousarray(keep, dtype=np.uint8)).to(self.device) if not torch.is_tensor(keep) \
-                    else keep.to(self.device, torch.uint8).contiguous()
-        elif isinstance(uids, dict) or (self.table_update == 'csr' and not any(torch.is_tensor(a) for a in (uids, before, after))):
-            prep = uids if isinstance(uids, dict) else self.prepare_batch(uids, before, after)
-            dev = self._upload(prep['buf'])
-            B = prep['B']
-            pb = [dev.data_ptr() + o for o in prep['offs']]
-            uid_p, bef_p, aft_p = pb[0], pb[1], pb[2]
-            csr = pb[3:]
-            kp = None
-            if keep is not None:
-                kp = torch.as_tensor(np.ascontiguousarray(keep, dtype=np.uint8)).to(self.device, non_blocking=True) if not torch.is_tensor(keep) \
-                    else keep.to(self.device, torch.uint8).contiguous()
-        else:
-            if any(torch.is_tensor(a) for a in (uids, before, after, keep)):
-                uid, bef, aft = self._dev_i32(uids), self._dev_i32(before), self._dev_i32(after)
-                kp = None
-                if keep is not None:
-                    kp = torch.as_tensor(np.ascontiguousarray(keep, dtype=np.uint8)).to(self.device) if not torch.is_tensor(keep) \
-                        else keep.to(self.device, torch.uint8).contiguous()
-                if self.table_update == 'csr' and self.device_csr:
-                    # a batch that is already on the device (Caser.fit(device_sampler=True)): the lookups are grouped by table row THERE
-                    # (drx_batch_csr_device: one stable sort for the three lists) and the step takes the same two launches as a host batch
-                    csr = self._csr_on_device(uid, bef, aft)
-            else:                                          # host batch: one asynchronous copy for all of it
-                if getattr(self, '_stage', None) is None:
-                    from ._staging import StagedUpload
-                    self._stage = StagedUpload(self.device)
-                arrays = [np.ascontiguousarray(uids, dtype=np.int32), np.ascontiguousarray(before, dtype=np.int32),
-                          np.ascontiguousarray(after, dtype=np.int32)]
-                if keep is not None:
-                    arrays.append(np.ascontiguousarray(keep, dtype=np.uint8))
-                _owner, views = self._stage(arrays)
-                uid, bef, aft = views[:3]
-                kp = views[3] if keep is not None else None
-            B = uid.numel()
-            assert bef.shape == (B, self.L) and aft.shape == (B, self.Tp)
-            uid_p, bef_p, aft_p = uid.data_ptr(), bef.data_ptr(), aft.data_ptr()
+    def _call_key(self):
+        """what the cached call of a ring slot depends on besides the slot: the tensors a set_params / optimizer change would replace,
+        the scalars baked into the structs and the work buffers"""
+        return (self.item_emb.data_ptr(), self.sw.data_ptr(), self.opt_kind,
+                tuple(s.data_ptr() if s is not None else 0 for n in ('sw', 'W1') for s in self.state[n]), self.reg, self.beta1,
+                self.beta2, self.eps, id(self.D), id(self.__dict__.get('_step_bufs')))
+
+    def _build_call(self, ids, csr, B):
+        """Everything the library calls of one step take, for B windows whose (uid, before, after) ids lie at the device addresses `ids`:
+        the argument structs and the work buffers.  csr: the six addresses of the lookups grouped by table row (ptrE, ordE, ptrW, ordW,
+        ptrU, ordU) for the 'csr' update of the tables, None for the 'scatter' update.  What changes from step to step (the dropout
+        mask, the step sizes) is left to _launch."""
         z = dict(dtype=torch.float32, device=self.device)
-        stream = stream_ptr(self.device)
-        grid = L_.drx_caser_grid(C.byref(self.D), B)
         # dense_1's gradient rows are outer products, score gradient x [dense_0 output | user row]: with the 'csr' update the kernel writes
         # the B hidden rows and drx_rows_csr_adam_outer forms the B * Tp rows where it sums them (19.7 MB less to write and to read back
         # per step of 4096); the 'scatter' update takes them written out
@@ -476,72 +281,128 @@ class CaserEngine(RowsRecommender):
         # device work buffers of a batch size: steps run in order on one stream, so they are reused from step to step
         wk = getattr(self, '_step_bufs', None)
         if wk is None or wk[0] != (B, outer):
+            grid = lib().drx_caser_grid(C.byref(self.D), B)
             rows = torch.zeros(n_dE + n_dW1 + n_dPu, **z)    # the padding columns of the gradient rows stay zero: the kernel never writes them
             wk = self._step_bufs = ((B, outer), rows, torch.empty(B * self.Tp, **z), torch.empty(grid, self.D.n_small, **z), torch.empty(grid, **z),
                                     torch.empty(self.D.n_small + 1, **z))
         _, rows, db1, gpart, lpart, gsw = wk
         base = rows.data_ptr()
         p_dE, p_dW1, p_dPu = base, base + 4 * n_dE, base + 4 * (n_dE + n_dW1)       # (p_dW1: the rows, or the B hidden rows)
-        A = CaserArgs()
-        A.item_emb, A.user_emb, A.W1, A.b1, A.sw = (t.data_ptr() for t in (self.item_emb, self.user_emb, self.W1, self.b1, self.sw))
-        A.uid, A.before, A.after = uid_p, bef_p, aft_p
-        A.keep = kp.data_ptr() if kp is not None else None
-        A.rate, A.B = float(rate), int(B)
-        A.mask_seed = int(mask_seed) & (2 ** 64 - 1)
+        A = self._args(*ids[:2], B, ids[2])
         A.dE, A.db1, A.dPu, A.gsw_part, A.loss_part = p_dE, db1.data_ptr(), p_dPu, gpart.data_ptr(), lpart.data_ptr()
         A.dW1, A.cat_out = (None, p_dW1) if outer else (p_dW1, None)
+        l2c = 2.0 * self.reg
+        sg = AdamSegments()
+        sg.n = len(self.seg)
+        for i, (_, start, n, regd, _) in enumerate(self.seg):
+            sg.start[i], sg.len[i], sg.l2_coef[i] = start, n, (l2c if regd else 0.0)
+        tabs = None
+        if outer:
+            # the three lookup tables (+ dense_1_b) in one launch: gradient rows summed per table row, l2, the update rule
+            ptrE, ordE, ptrW, ordW, ptrU, ordU = csr
+            tabs = (_lib.CsrAdamTable * 3)()
+            for t, (rp, od, src, scale, group, ld, n_rows, name, sname) in zip(tabs, (
+                    (ptrU, ordU, p_dPu, None, 0, self.ld, self.U, 'user_emb', None),
+                    (ptrE, ordE, p_dE, None, 0, self.ld, self.N, 'item_emb', None),
+                    (ptrW, ordW, p_dW1, db1.data_ptr(), self.Tp, self.ld2, self.N, 'W1', 'b1'))):
+                t.row_ptr, t.order, t.src, t.scale, t.group, t.ld, t.n_rows = rp, od, src, scale, group, ld, n_rows
+                t.p, (t.m, t.v) = getattr(self, name).data_ptr(), (x.data_ptr() if x is not None else None for x in self.state[name])
+                if sname is not None:
+                    t.p_s, (t.m_s, t.v_s) = getattr(self, sname).data_ptr(), (x.data_ptr() if x is not None else None for x in self.state[sname])
+                t.l2_coef = l2c
+        m, v = self.state['sw']
+        rule = self._rule()
+        return {'A': A, 'sg': sg, 'tabs': tabs, 'bufs': wk, 'rule': rule,
+                'small': (C.byref(self.D), C.byref(A), gsw.data_ptr(), self.sw.data_ptr(), ptr(m), ptr(v), C.byref(sg), C.byref(rule)),
+                'scatter': None if outer else (ids, (p_dE, p_dW1, p_dPu, db1.data_ptr()), l2c)}
+
+    def _launch(self, c, step_idx, kp, rate, mask_seed, want_loss, slot=None):
+        """The library calls of one step from a built call, with this step's dropout (kp: uint8 device keep mask or None), step sizes
+        and, if wanted, loss.  slot: the ring slot the batch lies in — its `free` event is recorded behind the step's last launch."""
+        L_ = lib()
+        A, sg, tabs = c['A'], c['sg'], c['tabs']
+        A.keep = kp.data_ptr() if kp is not None else None
+        A.rate = float(rate)
+        A.mask_seed = int(mask_seed) & (2 ** 64 - 1)
         reg_loss = None
         if want_loss:                                   # Keras l2(reg) on the pre-update weights
             sq = _lib.sumsq([self.user_emb, self.item_emb, self.W1] + [self.sw[start:start + n] for _, start, n, regd, _ in self.seg if regd])
             reg_loss = self.reg * sq
         alpha = self._alphas(step_idx)
-        l2c = 2.0 * self.reg
-        sg = AdamSegments()
-        sg.n = len(self.seg)
-        for i, (_, start, n, regd, layer) in enumerate(self.seg):
-            sg.start[i], sg.len[i], sg.alpha[i], sg.l2_coef[i] = start, n, alpha[layer], (l2c if regd else 0.0)
-        m, v = self.state['sw']
-        # forward / backward, then the small weights' Adam in the launch that sums the workgroups' partial gradients
-        rule = self._rule()
-        check(L_.drx_caser_step_small_opt(C.byref(self.D), C.byref(A), gsw.data_ptr(), self.sw.data_ptr(), _lib.ptr(m), _lib.ptr(v), C.byref(sg),
-                                          C.byref(rule), stream), 'drx_caser_step_small_opt')
-        if csr is not None:
-            # the three lookup tables (+ dense_1_b) in one launch: gradient rows summed per table row, l2, Keras Adam
-            ptrE, ordE, ptrW, ordW, ptrU, ordU = csr
-            st_ = self.state
-            tabs = (_lib.CsrAdamTable * 3)()
-            for t, (rp, od, src, scale, group, ld, n_rows, name, a, sname, a_s) in zip(tabs, (
-                    (ptrU, ordU, p_dPu, None, 0, self.ld, self.U, 'user_emb', alpha[0], None, 0.0),
-                    (ptrE, ordE, p_dE, None, 0, self.ld, self.N, 'item_emb', alpha[1], None, 0.0),
-                    (ptrW, ordW, p_dW1, db1.data_ptr(), self.Tp, self.ld2, self.N, 'W1', alpha[4 + self.L], 'b1', alpha[5 + self.L]))):
-                t.row_ptr, t.order, t.src, t.scale, t.group, t.ld, t.n_rows = rp, od, src, scale, group, ld, n_rows
-                t.p, (t.m, t.v) = getattr(self, name).data_ptr(), (x.data_ptr() if x is not None else None for x in st_[name])
-                if sname is not None:
-                    t.p_s, (t.m_s, t.v_s) = getattr(self, sname).data_ptr(), (x.data_ptr() if x is not None else None for x in st_[sname])
-                t.alpha, t.alpha_s, t.l2_coef = a, a_s, l2c
-            check(L_.drx_rows_csr_opt_multi(tabs, 3, C.byref(rule), stream), 'drx_rows_csr_opt_multi')
-            if slot is not None:                            # (the ring slot of a device-prepared batch may be rebuilt behind this point)
-                ev = torch.cuda.Event()
-                ev.record(torch.cuda.current_stream(self.device))
-                self._dev_csr['free'][slot] = ev
-            if isinstance(uids, dict) and uids.get('ring_slot') is not None:
-                ev = torch.cuda.Event()
-                ev.record(torch.cuda.current_stream(self.device))
-                uids['ring_slot']['free'] = ev
+        for i, layer in enumerate(self._seg_layers):
+            sg.alpha[i] = alpha[layer]
+        stream = stream_ptr(self.device)
+        # forward / backward, then the small weights' update in the launch that sums the workgroups' partial gradients
+        check(L_.drx_caser_step_small_opt(*c['small'], stream), 'drx_caser_step_small_opt')
+        if tabs is not None:
+            tabs[0].alpha, tabs[1].alpha, tabs[2].alpha, tabs[2].alpha_s = alpha[0], alpha[1], alpha[4 + self.L], alpha[5 + self.L]
+            check(L_.drx_rows_csr_opt_multi(tabs, 3, c['small'][7], stream), 'drx_rows_csr_opt_multi')
         else:
+            B, g = A.B, self._grads
+            (uid_p, bef_p, aft_p), (p_dE, p_dW1, p_dPu, p_db1), l2c = c['scatter']
             self._grad_arena.zero_()
-            g = self._grads
             self._scatter(bef_p, B * self.L, p_dE, self.ld, self.N, g['item_emb'].data_ptr(), stream=stream)
-            self._scatter(aft_p, B * self.Tp, p_dW1, self.ld2, self.N, g['W1'].data_ptr(), src_s=db1.data_ptr(), out_s=g['b1'].data_ptr(),
-                          stream=stream)
+            self._scatter(aft_p, B * self.Tp, p_dW1, self.ld2, self.N, g['W1'].data_ptr(), src_s=p_db1, out_s=g['b1'].data_ptr(), stream=stream)
             self._scatter(uid_p, B, p_dPu, self.ld, self.U, g['user_emb'].data_ptr(), stream=stream)
             self._adam('user_emb', g['user_emb'], alpha[0], l2c, stream)
             self._adam('item_emb', g['item_emb'], alpha[1], l2c, stream)
             self._adam('W1', g['W1'], alpha[4 + self.L], l2c, stream)
             self._adam('b1', g['b1'], alpha[5 + self.L], 0.0, stream)
+        if slot is not None:                            # (the ring slot may be filled again behind this point: _ring_slot waits for it)
+            slot['free'] = torch.cuda.Event()
+            slot['free'].record(torch.cuda.current_stream(self.device))
         if want_loss:
-            return float((gsw[-1] + reg_loss).item())
+            return float((c['bufs'][5][-1] + reg_loss).item())
         return None
+
+    def _step_slot(self, step_idx, sl, keep, rate, mask_seed, want_loss):
+        """step() on a ring slot.  A slot that owns its id tensors keeps the call of its earlier visit (the 'csr' update, no loss
+        wanted): only this step's scalars are set."""
+        csr = sl['csr_dev'] if self.table_update == 'csr' else None
+        cached = sl['own_ids'] and csr is not None and not want_loss
+        c = sl.get('step') if cached else None
+        if c is None or c['key'] != self._call_key():
+            c = self._build_call((sl['uid'].data_ptr(), sl['before'].data_ptr(), sl['after'].data_ptr()), csr, sl['B'])
+            if cached:
+                c['key'] = self._call_key()                 # (now: it names the work buffers _build_call may have made)
+                sl['step'] = c
+        return self._launch(c, step_idx, self._keep_mask(keep), rate, mask_seed, want_loss, sl)
+
+    def step(self, step_idx, uids, before=None, after=None, keep=None, rate=0.0, want_loss=False, mask_seed=0):
+        """uids, before, after: the batch (arrays or device tensors) — or `uids` = what prepare_batch, prepare_device_batch or group_slot
+        returned for it.
+        keep: explicit dropout keep mask [B, n_v + L*n_h] or None; with None and rate > 0 the kernel evaluates the counter-based
+        mask drx_hash_u32(mask_seed, b, j) >= rate * 2^32 itself (no 344 K host random numbers per batch of 4096)."""
+        if isinstance(uids, dict) and 'csr_dev' in uids:           # a ring slot: ids and grouped lookups already on the device
+            return self._step_slot(step_idx, uids, keep, rate, mask_seed, want_loss)
+        tensors = not isinstance(uids, dict) and any(torch.is_tensor(a) for a in (uids, before, after))
+        if isinstance(uids, dict) or (self.table_update == 'csr' and not tensors):
+            # a host batch with its lookups grouped by row on the host: one asynchronous copy for all of it
+            prep = uids if isinstance(uids, dict) else self.prepare_batch(uids, before, after)
+            alive = self._stage.upload(prep['buf'])
+            B = prep['B']
+            pb = [alive.data_ptr() + o for o in prep['offs']]
+            ids, csr, kp = pb[:3], pb[3:], self._keep_mask(keep, non_blocking=True)
+        elif tensors or torch.is_tensor(keep):
+            uid, bef, aft = self._dev_i32(uids), self._dev_i32(before), self._dev_i32(after)
+            B = uid.numel()
+            assert bef.shape == (B, self.L) and aft.shape == (B, self.Tp)
+            if self.table_update == 'csr' and self.device_csr:
+                # a batch that is already on the device (Caser.fit(device_sampler=True)): the lookups are grouped by table row THERE
+                # and the step takes the same two launches as a host batch
+                return self._step_slot(step_idx, self.prepare_device_batch(uid, bef, aft), keep, rate, mask_seed, want_loss)
+            ids, csr, kp = (uid.data_ptr(), bef.data_ptr(), aft.data_ptr()), None, self._keep_mask(keep)
+        else:                                              # host arrays, 'scatter' update: one asynchronous copy for all of them
+            arrays = [np.ascontiguousarray(uids, dtype=np.int32), np.ascontiguousarray(before, dtype=np.int32),
+                      np.ascontiguousarray(after, dtype=np.int32)]
+            if keep is not None:
+                arrays.append(np.ascontiguousarray(keep, dtype=np.uint8))
+            alive, views = self._stage(arrays)
+            uid, bef, aft = views[:3]
+            B = uid.numel()
+            assert bef.shape == (B, self.L) and aft.shape == (B, self.Tp)
+            ids, csr, kp = (uid.data_ptr(), bef.data_ptr(), aft.data_ptr()), None, views[3] if keep is not None else None
+        return self._launch(self._build_call(ids, csr, B), step_idx, kp, rate, mask_seed, want_loss)
 
     # ---- inference: scores of ALL items for each (user, last-L-items) row (caser.py:128-137) --------------------
     def scores_all(self, uids, before):
@@ -557,7 +418,7 @@ class CaserEngine(RowsRecommender):
     def _hidden_rows(self, uid, bef):
         """[B, ld2] rows [dense_0 output | user row] of drx_caser_hidden; zeros (not torch.empty) behind 2 d: the scorer multiplies them"""
         cat = torch.zeros(int(uid.numel()), self.ld2, dtype=torch.float32, device=self.device)
-        A = self._args(uid, bef)
+        A = self._args(uid.data_ptr(), bef.data_ptr(), uid.numel())
         A.cat_out = cat.data_ptr()
         check(lib().drx_caser_hidden(C.byref(self.D), C.byref(A), stream_ptr(self.device)), 'drx_caser_hidden')
         return cat

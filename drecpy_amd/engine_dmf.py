@@ -20,10 +20,12 @@ import torch
 
 from . import _lib
 from ._lib import AdamSegments, DmfArgs, DmfDims, DmfK0Update, check, lib, ptr, stream_ptr
-from .engine import ADAM_B1, ADAM_B2, ADAM_EPS, RowsRecommender, _round_up
+from ._staging import StagedUpload
+from .engine import _round_up
+from .engine_dense import DenseEngine, aligned_offsets
 
 
-class DmfEngine(RowsRecommender):
+class DmfEngine(DenseEngine):
     def __init__(self, n_users, n_items, user_factors=(64, 32), item_factors=(64, 32), l2_norm_vectors=True, device='cuda:0'):
         if not torch.cuda.is_available():
             raise _lib.DrxError('drecpy_amd needs a ROCm GPU (MI355X); there is no CPU fallback.')
@@ -59,13 +61,11 @@ class DmfEngine(RowsRecommender):
         self.D = D
         self.scale_var = None
         self.broadcast_targets = False
-        self.beta1, self.beta2, self.eps = ADAM_B1, ADAM_B2, ADAM_EPS
-        self.opt_kind, self._slot_init = 'adam', 0.0        # (set_optimizer: another dense rule of optimizers.py)
         z = dict(dtype=torch.float32, device=self.device)
         self.K0u = torch.zeros(n_items, D.ld0[0], **z)
         self.K0i = torch.zeros(n_users, D.ld0[1], **z)
         self.sw = torch.zeros(off, **z)
-        self.state = {n: (torch.zeros_like(t), torch.zeros_like(t)) for n, t in self.tensors().items()}
+        self._init_optimizer_state()
         nu, ni = self.K0u.numel(), self.K0i.numel()
         self._g_arena = torch.zeros(nu + ni, **z)            # both dense gradient tables: one buffer, one fill per step
         self._g = {'K0u': self._g_arena[:nu].view(self.K0u.shape), 'K0i': self._g_arena[nu:].view(self.K0i.shape)}
@@ -76,6 +76,8 @@ class DmfEngine(RowsRecommender):
         self.first_layer_update = 'scan'
         self._maps = (torch.zeros(n_users, dtype=torch.int64, device=self.device), torch.zeros(n_items, dtype=torch.int64, device=self.device))
         self._stamp = 0
+        self._stage = StagedUpload(self.device)             # host-prepared batches: one upload each, into device buffers the ring keeps
+        self._dev_ring, self._dev_i = {}, 0                 # device-prepared batches: (B, k) -> ring slot (prepare_batch_device)
         from .Recommender.trainables import TrainableModel
         # what DMF._pre_fit registers (dmf.py:60): the two Sequential towers, each one apply_gradients per step
         self.user_nn = TrainableModel('user_nn', lambda: self._tower_weights(0))
@@ -156,62 +158,20 @@ class DmfEngine(RowsRecommender):
             p['extra_w'] = c(self.sw[self._scale_slot:self._scale_slot + 1])
         return p
 
-    def set_optimizer(self, opt):
-        """The update rule of every dense step from a drecpy_amd.optimizers object (Adam, Adagrad, SGD, RMSprop): its kind and
-        hyper-parameters, and slots of that rule alone — none for plain SGD, s1 for all but Adam and RMSprop with momentum (Adagrad's at
-        its accumulator value).  beta1 / beta2 carry include/drx.h DrxOptRule's mu / mu2.  Slots that already fit the rule are kept."""
-        from .optimizers import KINDS, N_SLOTS
-        kind = opt.kind
-        if kind not in KINDS or kind == 'rowwise_adagrad':
-            raise _lib.DrxError(f'no dense update rule "{kind}"')
-        mu, mu2 = opt._mus()
-        self.lr, self.beta1, self.beta2, self.eps = opt.learning_rate, mu, mu2, getattr(opt, 'epsilon', 0.0)
-        if kind == self.opt_kind and getattr(opt, 'slot_init', 0.0) == self._slot_init:
-            return
-        self.opt_kind, self._slot_init = kind, float(getattr(opt, 'slot_init', 0.0))
-        n = N_SLOTS[kind]
-        self.state = {name: tuple(torch.full_like(t, self._slot_init) if i < n else None for i in range(2)) for name, t in self.tensors().items()}
-
-    def _rule(self, step_size=0.0):
-        """include/drx.h DrxOptRule of the engine's rule (step_size: where the entry point has none per variable)"""
-        key = (self.opt_kind, step_size, self.beta1, self.beta2, self.eps)
-        c = self.__dict__.get('_rule_cache')
-        if c is None or c[0] != key:                     # (one struct per setting: the steps pass it by reference)
-            from .optimizers import KINDS
-            c = self._rule_cache = (key, _lib.OptRule(KINDS[self.opt_kind], step_size, self.beta1, self.beta2, self.eps))
-        return c[1]
-
     def _step_sizes(self, step_idx, applies):
         """the step size of each apply of step `step_idx`: Keras Adam's lr_t of its counter; the learning rate under every other rule"""
         if self.opt_kind != 'adam':
             return [self.lr if j is not None else 0.0 for j in applies[1:]]
         return [self.adam_alpha(self.lr, applies[0] * step_idx + j + 1, self.beta1, self.beta2) if j is not None else 0.0 for j in applies[1:]]
 
-    def snapshot(self):
-        """Device copies of the parameters and of the slots the rule has (used by _store_epoch_weights / _revert_weights)."""
-        return {'p': {n: t.clone() for n, t in self.tensors().items()},
-                's': {n: tuple(None if t is None else t.clone() for t in st) for n, st in self.state.items()}}
-
-    def restore(self, snap, with_optimizer=False):
-        for n, t in self.tensors().items():
-            t.copy_(snap['p'][n])
-        if with_optimizer and 's' in snap:
-            for n, st in self.state.items():
-                for dst, src in zip(st, snap['s'][n]):
-                    if dst is not None and src is not None:
-                        dst.copy_(src)
-
-    def _base_args(self, uid, iid):
+    def _base_args(self, uid, iid, B):
+        """DrxDmfArgs with the parameters, both orientations of the matrix and the B (user, item) ids at the addresses uid / iid"""
         A = DmfArgs()
         A.K0u, A.K0i, A.sw = self.K0u.data_ptr(), self.K0i.data_ptr(), self.sw.data_ptr()
         A.u_indptr, A.u_indices, A.u_values = (t.data_ptr() for t in self.csr)
         A.i_indptr, A.i_indices, A.i_values = (t.data_ptr() for t in self.csc)
-        A.uid, A.iid, A.B = uid.data_ptr(), iid.data_ptr(), int(uid.numel())
+        A.uid, A.iid, A.B = uid, iid, int(B)
         return A
-
-    def _offsets(self, ids, indptr):
-        off = _lib.batch_offsets(indptr, ids if ids.dtype == torch.int32 else ids.to(torch.int32))
-        return off, int(off[-1].item())
 
     def _scatter(self, keys, T, src, src_index, coef, ld, n_rows, out):
         """`out` must already be zero (step() clears the gradient arena once)."""
@@ -230,10 +190,7 @@ class DmfEngine(RowsRecommender):
     @staticmethod
     def _batch_layout(B):
         lens = (B, B, B, B + 1, B + 1, B, B, B + 1, B + 1, B, B, 2 * B + DmfEngine._ORDER_EXTRA, 2 * B)
-        offs, total = [], 0
-        for n in lens:
-            offs.append(total)
-            total += (4 * n + 15) & ~15
+        offs, total = aligned_offsets([4 * n for n in lens])
         return offs, lens, total
 
     @staticmethod
@@ -286,8 +243,6 @@ class DmfEngine(RowsRecommender):
         y32[:] = y
         off_u = buf[at['off_u']:at['off_u'] + 4 * (nd[0] + 1)].view(np.int32)
         off_i = buf[at['off_i']:at['off_i'] + 4 * (nd[1] + 1)].view(np.int32)
-        # the gather's work items, LONGEST row / column first (include/drx.h DrxDmfArgs::work_order): a popular item's column has
-        # thousands of non-zeros and is the launch's critical path when its workgroup happens to start late
         # the gather's work items: longest rows / columns first, long ones cut into segments of _seg_len non-zeros (include/drx.h
         # DrxDmfArgs::work_order; uncut when the segments would not fit the list or their partial rows _zpart: host_work_list)
         i32 = lambda name: buf[at[name]:at[name] + 4 * lens[self._BATCH_ARRAYS.index(name)]].view(np.int32)
@@ -315,7 +270,7 @@ class DmfEngine(RowsRecommender):
     host_step_cache = True
 
     # device-prepared batches: the gather's work list (longest rows first, long ones cut into segments) built on the device too — False:
-    # one work item per distinct id in their own order, as through r05 (52.6 against 28 us for the gather at B = 4096)
+    # one work item per distinct id in their own order (52.6 against 28 us for the gather at B = 4096)
     device_work_order = True
 
     def _device_seg_len(self):
@@ -324,18 +279,13 @@ class DmfEngine(RowsRecommender):
         nnz2 = int(self.csr[1].numel()) + int(self.csc[1].numel())
         return max(int(self._seg_len), -(-nnz2 // self._ORDER_EXTRA))
 
-    def _ensure_dev_ring(self):
-        if not hasattr(self, '_dev_ring'):
-            self._dev_ring, self._dev_i = {}, 0
-
     def prepare_batch_device(self, B, neg_ratio, seed, triples=None):
         """One batch drawn by the device PointSampler (drx_point_sample_valued: the reference sampler's distribution, a counter-based
         stream) and prepared there (drx_dmf_batch_distinct_device) on the CURRENT stream — DMF.fit() runs it one step ahead on a side
-        stream.  Returns what step() takes in place of prepare_batch()'s host arrays.  A ring of 3 buffers per batch size: the
-        caller keeps at most two batches in flight.  triples: (uid, iid, y) device tensors to prepare INSTEAD of drawing (tests)."""
+        stream.  Returns what step() takes in place of prepare_batch()'s host arrays.  A ring of 3 slots per batch size: the stream
+        first waits for the step that last read the slot (the slot's `free` event, recorded by step() on ITS stream).  triples: (uid, iid, y) device tensors to prepare INSTEAD of drawing (tests)."""
         from ._lib import History
         L_ = lib()
-        self._ensure_dev_ring()
         k = self._dev_i % 3
         self._dev_i += 1
         slot = self._dev_ring.get((B, k))
@@ -348,11 +298,15 @@ class DmfEngine(RowsRecommender):
                 'nd': torch.empty(2, **i32), 'y_mean': torch.empty(1, dtype=torch.float32, device=self.device),
                 'scratch': torch.empty(need, dtype=torch.uint8, device=self.device),
                 # the gather's work list built on the device (drx_dmf_work_order_device): entries, zseg per work index, {entries, partial rows}
-                'order': torch.empty(2 * B + self._ORDER_EXTRA, **i32), 'zseg': torch.empty(2 * B, **i32), 'nw': torch.zeros(2, **i32)}
+                'order': torch.empty(2 * B + self._ORDER_EXTRA, **i32), 'zseg': torch.empty(2 * B, **i32), 'nw': torch.zeros(2, **i32),
+                'free': None}
+        if slot['free'] is not None:
+            torch.cuda.current_stream(self.device).wait_event(slot['free'])
+            slot['free'] = None
         st = stream_ptr(self.device)
         uid, iid = slot['ids'][0], slot['ids'][1]
         # everything but the seed and the stream is the same from call to call on a slot: the arguments are built once (at B = 256 the
-        # host, not the device, bounds fit(device_sampler=True): r06, profiles/r06_dmf_host_profile_B256.txt)
+        # host, not the device, bounds fit(device_sampler=True): profiles/r06_dmf_host_profile_B256.txt)
         call = slot.get('call')
         pos, rec = getattr(self, '_pos', None), getattr(self, '_rec', None)          # (set_sampler_frame; absent when only `triples` are prepared)
         if call is None or call['pos'] is not pos or call['rec'] is not rec:
@@ -382,219 +336,172 @@ class DmfEngine(RowsRecommender):
             check(L_.drx_dmf_work_order_device(*wo[1], st), 'drx_dmf_work_order_device')
         return {'device': slot, 'B': B}
 
-    def _upload_batch(self, prepared):
-        """Host batch -> device in one asynchronous copy from a pinned ring (so the host can run ahead of the device); returns the
-        device buffer and the addresses of the arrays in it."""
-        st = self.__dict__.setdefault('_stage', {'i': 0, 'host': [None] * 4, 'ev': [None] * 4, 'dev': [None] * 4, 'cache': [None] * 4})
-        buf = prepared['buf']
-        total = buf.nbytes
-        k = st['i'] % 4
-        st['i'] += 1
-        if st['host'][k] is None or st['host'][k].numel() < total:
-            st['host'][k] = torch.empty(int(total * 1.5) + 4096, dtype=torch.uint8, pin_memory=True)
-            st['ev'][k] = torch.cuda.Event()
-            # the device side of the slot is kept too (r06): steps run in order on one stream, so a copy into it is queued behind the
-            # step that last read it — and a slot's addresses stay the same from visit to visit (the step's argument structs are cached)
-            st['dev'][k] = torch.empty(st['host'][k].numel(), dtype=torch.uint8, device=self.device)
-            st['cache'][k] = None
-        else:
-            st['ev'][k].synchronize()                 # the copy that last read this pinned slot has finished
-        st['host'][k].numpy()[:total] = buf
-        dev = st['dev'][k]
-        dev[:total].copy_(st['host'][k][:total], non_blocking=True)
-        st['ev'][k].record(torch.cuda.current_stream(self.device))
-        base = dev.data_ptr()
-        prepared['stage_slot'] = k
-        return dev, [base + o for o in prepared['offs']]
+    def _zpart_ptr(self):
+        """the partial rows of the work items of cut rows / columns: one buffer, steps run in order on one stream"""
+        zp = getattr(self, '_zpart', None)
+        if zp is None:
+            zp = self._zpart = torch.empty(self._ORDER_EXTRA + 8, self.W, dtype=torch.float32, device=self.device)
+        return zp.data_ptr()
 
-    def step(self, step_idx, uids, iids=None, y=None, want_loss=False, applies=None):
-        """uids, iids, y: the batch (arrays or tensors) — or `uids` = what prepare_batch returned for it.
-        applies = (n, j_user, j_item, j_scale): number of apply_gradients calls per step and the positions of user_nn, item_nn
-        and the prediction scale among them (the registration order, recommender_abc.py:194-196); default: the reference DMF's
-        (2, 0, 1), or (3, 1, 2, 0) with a bound scale."""
+    def _where(self, prep, slot):
+        """Where the batch of a step is: the DrxDmfArgs fields that name it, the touches of both sides (scatter update) and whether its
+        counts come from the host with every batch.  slot: the ring slot it lies in — of the upload ring (13 arrays in the slot's
+        device buffer; n_du, n_di, n_work, seg_len and y_mean are this batch's: _launch sets them) or of the device ring (8 rows,
+        the counts, the batch mean and the work list are read on the device; the host's n_du / n_di only size the launches)."""
+        B = prep['B']
+        if prep.get('device') is None:
+            base = slot['dev'].data_ptr()
+            f = dict(zip(self._BATCH_ARRAYS, (base + o for o in prep['offs'])))
+            f['uid'], f['iid'], f['work_order'], f['zpart'] = f.pop('du'), f.pop('di'), f.pop('order'), self._zpart_ptr()
+            return {'B': B, 'host': True, 'fields': f, 'touches': (prep['Tu'], prep['Ti'])}
+        a = slot['arr']
+        f = dict(zip(('uid', 'iid', 'inv_u', 'inv_i', 'gptr_u', 'gptr_i', 'grows_u', 'grows_i'), (a[r].data_ptr() for r in range(8))))
+        f.update(y=slot['y'].data_ptr(), n_du=B, n_di=B, nd_dev=slot['nd'].data_ptr(), y_mean_dev=slot['y_mean'].data_ptr())
+        if self.device_work_order and 'order' in slot:
+            f.update(work_order=slot['order'].data_ptr(), n_work=slot['order'].numel(), seg_len=self._device_seg_len(),
+                     zseg=slot['zseg'].data_ptr(), zpart=self._zpart_ptr(), n_work_dev=slot['nw'].data_ptr())
+        return {'B': B, 'host': False, 'fields': f, 'touches': (0, 0)}
+
+    def _build_call(self, where, applies):
+        """Everything the library calls of one step take, for a batch at `where`: the argument structs, the work buffers and what keeps
+        them alive.  What changes from step to step (the stamp, the step sizes, a host batch's counts) is left to _launch."""
         L_ = lib()
-        if isinstance(uids, dict) and uids.get('device') is not None and not want_loss:
-            done = self._step_device_cached(L_, step_idx, uids, applies)
-            if done:
-                return None
+        B, (Tu, Ti) = where['B'], where['touches']
         z = dict(dtype=torch.float32, device=self.device)
         i32 = dict(dtype=torch.int32, device=self.device)
-        if not isinstance(uids, dict):
-            if torch.is_tensor(uids) or torch.is_tensor(iids) or torch.is_tensor(y):
-                c = lambda a: a.detach().cpu().numpy() if torch.is_tensor(a) else np.asarray(a)
-                uids, iids, y = c(uids), c(iids), c(y)
-            uids = self.prepare_batch(uids, iids, y)
-        prep = uids
-        on_device = prep.get('device') is not None
-        if on_device:                       # drawn and prepared on the device: the distinct counts and the batch mean live there
-            if self.first_layer_update != 'scan':
-                raise _lib.DrxError('device-prepared DMF batches need the scan update of the first-layer kernels (set_interactions chose '
-                                    '"scatter": more than SCAN_MAX_NNZ interactions)')
-            sl = prep['device']
-            a = sl['arr']
-            p_du, p_di, p_invu, p_invi, p_gpu, p_gpi, p_gru, p_gri = (a[r].data_ptr() for r in range(8))
-            p_y, p_offu, p_offi = sl['y'].data_ptr(), 0, 0
-            B, Tu, Ti = prep['B'], 0, 0
-            n_du = n_di = B                 # upper bounds: they size the launches; the kernels read nd_dev
-        else:
-            alive, ptrs = self._upload_batch(prep)
-            if not want_loss and self.first_layer_update == 'scan' and self.host_step_cache:
-                c = self._stage['cache'][prep['stage_slot']]
-                if applies is None:
-                    applies = (3, 1, 2, 0) if self.scale_var is not None else (2, 0, 1, None)
-                if c is not None and c['B'] == prep['B'] and c['base'] == alive.data_ptr() and c['applies'] == tuple(applies) \
-                        and c['key'] == self._step_cache_key():
-                    A = c['A']                              # the slot's struct with this batch's scalars
-                    A.n_du, A.n_di, A.n_work, A.seg_len = prep['n_du'], prep['n_di'], prep['n_work'], prep['seg_len']
-                    if A.target_mode == 1:
-                        A.y_mean = prep['y_mean']
-                    self._launch_cached(L_, c, step_idx, tuple(applies))
-                    return None
-                self._stage['cache_wanted'] = (prep['stage_slot'], alive.data_ptr())
-            p_du, p_di, p_y, p_offu, p_offi, p_invu, p_invi, p_gpu, p_gpi, p_gru, p_gri, p_order, p_zseg = ptrs
-            B, Tu, Ti = prep['B'], prep['Tu'], prep['Ti']
-            n_du, n_di = prep['n_du'], prep['n_di']
         ld0u, ld0i = self.D.ld0[0], self.D.ld0[1]
-        stream = stream_ptr(self.device)
-        grid = L_.drx_dmf_grid(B)
         # device work buffers of a batch size: steps run in order on one stream, so they are reused from step to step
         wk = getattr(self, '_step_bufs', None)
         if wk is None or wk[0] != B:
+            grid = L_.drx_dmf_grid(B)
             wk = self._step_bufs = (B, torch.empty(B, ld0u, **z), torch.empty(B, ld0i, **z), torch.empty(grid, self.D.n_small, **z),
                                     torch.empty(grid, **z), torch.empty(self.D.n_small + 1, **z))
         _, dz0u, dz0i, gpart, lpart, gsw = wk
-        scan = self.first_layer_update == 'scan'
-        if not scan:
-            tk_u, ts_u, tc_u = torch.empty(max(Tu, 1), **i32), torch.empty(max(Tu, 1), **i32), torch.empty(max(Tu, 1), **z)
-            tk_i, ts_i, tc_i = torch.empty(max(Ti, 1), **i32), torch.empty(max(Ti, 1), **i32), torch.empty(max(Ti, 1), **z)
-        A = DmfArgs()
-        A.K0u, A.K0i, A.sw = self.K0u.data_ptr(), self.K0i.data_ptr(), self.sw.data_ptr()
-        A.u_indptr, A.u_indices, A.u_values = (t.data_ptr() for t in self.csr)
-        A.i_indptr, A.i_indices, A.i_values = (t.data_ptr() for t in self.csc)
-        A.uid, A.iid, A.B = p_du, p_di, int(B)
-        A.y, A.off_u, A.off_i = p_y, p_offu, p_offi
-        A.inv_u, A.inv_i, A.gptr_u, A.gptr_i, A.grows_u, A.grows_i = p_invu, p_invi, p_gpu, p_gpi, p_gru, p_gri
-        A.n_du, A.n_di = n_du, n_di
-        if not on_device:
-            A.work_order, A.n_work, A.seg_len, A.zseg = p_order, prep['n_work'], prep['seg_len'], p_zseg
-            zp = getattr(self, '_zpart', None)
-            if zp is None:
-                zp = self._zpart = torch.empty(self._ORDER_EXTRA + 8, self.W, dtype=torch.float32, device=self.device)
-            A.zpart = zp.data_ptr()
-        if on_device:
-            A.nd_dev, A.y_mean_dev = prep['device']['nd'].data_ptr(), prep['device']['y_mean'].data_ptr()
-            if self.device_work_order and 'order' in prep['device']:
-                sl_ = prep['device']
-                zp = getattr(self, '_zpart', None)
-                if zp is None:
-                    zp = self._zpart = torch.empty(self._ORDER_EXTRA + 8, self.W, dtype=torch.float32, device=self.device)
-                A.work_order, A.n_work, A.seg_len = sl_['order'].data_ptr(), sl_['order'].numel(), self._device_seg_len()
-                A.zseg, A.zpart, A.n_work_dev = sl_['zseg'].data_ptr(), zp.data_ptr(), sl_['nw'].data_ptr()
+        f = where['fields']
+        A = self._base_args(f['uid'], f['iid'], B)
+        for name, value in f.items():
+            setattr(A, name, value)
         if self.broadcast_targets and self.scale_var is not None:
-            A.target_mode = 1
-            A.y_mean = 0.0 if on_device else prep['y_mean']
+            A.target_mode = 1                               # (y_mean: a host batch's from _launch, a device batch's at y_mean_dev)
         A.dz0u, A.dz0i = dz0u.data_ptr(), dz0i.data_ptr()
         A.rho_u, A.rho_i = self._rho[0].data_ptr(), self._rho[1].data_ptr()
-        if scan:
-            self._stamp += 1
-            A.map_u, A.map_i, A.stamp = self._maps[0].data_ptr(), self._maps[1].data_ptr(), self._stamp
-        else:
-            A.tkeys_u, A.tsrc_u, A.tcoef_u = tk_u.data_ptr(), ts_u.data_ptr(), tc_u.data_ptr()
-            A.tkeys_i, A.tsrc_i, A.tcoef_i = tk_i.data_ptr(), ts_i.data_ptr(), tc_i.data_ptr()
         A.gsw_part, A.loss_part = gpart.data_ptr(), lpart.data_ptr()
         need = L_.drx_dmf_work_bytes(B)
         if getattr(self, '_work', None) is None or self._work.numel() < need:
             self._work = torch.empty(int(need) + 1024, dtype=torch.uint8, device=self.device)
         A.work = self._work.data_ptr()
-        reg_loss = None
-        if want_loss:
-            sq = _lib.sumsq([self.K0u, self.K0i] + [self.sw[start:start + n] for _, start, n, regd, _ in self.seg if regd])
-            reg_loss = self.reg * sq
-        if applies is None:
-            applies = (3, 1, 2, 0) if self.scale_var is not None else (2, 0, 1, None)
-        n_app = applies[0]
-        alpha = self._step_sizes(step_idx, applies)
         l2c = 2.0 * self.reg
         sg = AdamSegments()
         sg.n = len(self.seg)
+        sg_tw = []                                          # (segment, index of its step size): _launch fills sg.alpha
         for i, (_, start, n, regd, tw) in enumerate(self.seg):
-            sg.start[i], sg.len[i], sg.alpha[i], sg.l2_coef[i] = start, n, alpha[tw], (l2c if regd else 0.0)
+            sg.start[i], sg.len[i], sg.l2_coef[i] = start, n, (l2c if regd else 0.0)
+            sg_tw.append((i, tw))
         if self.scale_var is not None:                     # the registered scalar: its own lr_t, no regulariser
             i = sg.n
             sg.n += 1
-            sg.start[i], sg.len[i], sg.alpha[i], sg.l2_coef[i] = self._scale_slot, 1, alpha[2], 0.0
+            sg.start[i], sg.len[i], sg.l2_coef[i] = self._scale_slot, 1, 0.0
+            sg_tw.append((i, 2))
         m, v = self.state['sw']
-        # forward / backward with the small weights' Keras Adam in the launch that sums their partial gradients (r06: drx_dmf_step_small
-        # — one launch less than drx_dmf_fwd_bwd + drx_adam_segments; gsw still holds the gradient and, last, the loss sum; the
-        # first-layer update below reads none of the small weights)
         rule = self._rule()
-        check(L_.drx_dmf_step_small_opt(C.byref(self.D), C.byref(A), ptr(gsw), ptr(self.sw), ptr(m), ptr(v), C.byref(sg), C.byref(rule), stream),
-              'drx_dmf_step_small_opt')
-        if scan:
+        up = scatter = None
+        if self.first_layer_update == 'scan':
             up = DmfK0Update()
             (mu, vu), (mi, vi) = self.state['K0u'], self.state['K0i']
             up.K0u, up.m_u, up.v_u, up.K0i, up.m_i, up.v_i = (t.data_ptr() if t is not None else None for t in (self.K0u, mu, vu, self.K0i, mi, vi))
             up.opt_kind = rule.kind
             up.n_items, up.n_users = self.N, self.U
             up.row_order, up.n_long = self._k0_order.data_ptr(), self._k0_long
-            up.alpha_u, up.alpha_i, up.l2_coef, up.beta1, up.beta2, up.eps = alpha[0], alpha[1], l2c, self.beta1, self.beta2, self.eps
-            check(L_.drx_dmf_k0_update(C.byref(self.D), C.byref(A), C.byref(up), stream), 'drx_dmf_k0_update')
+            up.l2_coef, up.beta1, up.beta2, up.eps = l2c, self.beta1, self.beta2, self.eps
+            A.map_u, A.map_i = self._maps[0].data_ptr(), self._maps[1].data_ptr()
         else:
-            self._g_arena.zero_()
-            self._scatter(tk_u, Tu, dz0u, ts_u, tc_u, ld0u, self.N, self._g['K0u'])
-            self._scatter(tk_i, Ti, dz0i, ts_i, tc_i, ld0i, self.U, self._g['K0i'])
-            for name, tw in (('K0u', 0), ('K0i', 1)):
-                p = self.tensors()[name]
-                m, v = self.state[name]
-                check(L_.drx_opt_dense(ptr(p), ptr(m), ptr(v), ptr(self._g[name]), p.numel(), C.byref(self._rule(alpha[tw])), l2c, stream),
-                      'drx_opt_dense')
-        wanted_host = None if on_device else self.__dict__.get('_stage', {}).pop('cache_wanted', None)
-        if (not on_device) and scan and wanted_host is not None and not want_loss:
-            sg_tw = [(i, tw) for i, (_, _, _, _, tw) in enumerate(self.seg)] + ([(len(self.seg), 2)] if self.scale_var is not None else [])
-            self._stage['cache'][wanted_host[0]] = {
-                'B': B, 'base': wanted_host[1], 'applies': tuple(applies), 'key': self._step_cache_key(), 'A': A, 'up': up, 'sg': sg, 'gsw': ptr(gsw),
-                'D': C.byref(self.D), 'Aref': C.byref(A), 'upref': C.byref(up), 'sgref': C.byref(sg), 'sg_tw': sg_tw, 'sw': ptr(self.sw),
-                'm': ptr(m), 'v': ptr(v), 'rule': rule, 'ruleref': C.byref(rule), 'keep': (gsw, gpart, lpart, dz0u, dz0i)}
-        if on_device and scan and prep['device'].pop('step_cache_wanted', False):
-            sg_tw = [(i, tw) for i, (_, _, _, _, tw) in enumerate(self.seg)] + ([(len(self.seg), 2)] if self.scale_var is not None else [])
-            prep['device']['step_cache'] = {
-                'applies': tuple(applies), 'key': self._step_cache_key(), 'A': A, 'up': up, 'sg': sg, 'gsw': ptr(gsw), 'D': C.byref(self.D),
-                'Aref': C.byref(A), 'upref': C.byref(up), 'sgref': C.byref(sg), 'sg_tw': sg_tw, 'sw': ptr(self.sw), 'm': ptr(m), 'v': ptr(v),
-                'rule': rule, 'ruleref': C.byref(rule),
-                'keep': (gsw, gpart, lpart, dz0u, dz0i)}
-        if want_loss:
-            return float((gsw[-1] + reg_loss).item())
-        return None
+            tk_u, ts_u, tc_u = torch.empty(max(Tu, 1), **i32), torch.empty(max(Tu, 1), **i32), torch.empty(max(Tu, 1), **z)
+            tk_i, ts_i, tc_i = torch.empty(max(Ti, 1), **i32), torch.empty(max(Ti, 1), **i32), torch.empty(max(Ti, 1), **z)
+            A.tkeys_u, A.tsrc_u, A.tcoef_u = tk_u.data_ptr(), ts_u.data_ptr(), tc_u.data_ptr()
+            A.tkeys_i, A.tsrc_i, A.tcoef_i = tk_i.data_ptr(), ts_i.data_ptr(), tc_i.data_ptr()
+            scatter = ((tk_u, Tu, dz0u, ts_u, tc_u, ld0u, self.N, 'K0u'), (tk_i, Ti, dz0i, ts_i, tc_i, ld0i, self.U, 'K0i'))
+        return {'B': B, 'applies': applies, 'host': where['host'], 'A': A, 'up': up, 'sg': sg, 'sg_tw': sg_tw,
+                'rule': rule, 'l2c': l2c, 'scatter': scatter, 'gsw': gsw, 'upref': C.byref(up) if up is not None else None,
+                'small': (C.byref(self.D), C.byref(A), ptr(gsw), ptr(self.sw), ptr(m), ptr(v), C.byref(sg), C.byref(rule)),
+                'keep': (gpart, lpart, dz0u, dz0i)}
 
-    def _step_device_cached(self, L_, step_idx, prep, applies):
-        """step() for a device-prepared batch whose argument structs were built by an earlier step on the same ring slot: only the stamp
-        and the learning rates change from step to step (fit(device_sampler=True) at B = 256 is bound by the host's Python, not by the
-        75 us of kernels).  False when there is no valid cache for the slot: the caller takes the general path, which fills it."""
-        sl = prep['device']
-        c = sl.get('step_cache')
-        if applies is None:
-            applies = (3, 1, 2, 0) if self.scale_var is not None else (2, 0, 1, None)
-        if c is None or c['applies'] != applies or c['key'] != self._step_cache_key():
-            sl['step_cache_wanted'] = True
-            return False
-        self._launch_cached(L_, c, step_idx, applies)
-        return True
+    def _cached_call(self, slot, B, applies):
+        """the call an earlier step built for the ring slot, if it still holds (fit() at B = 256 is bound by the host's Python, not by the
+        75 us of kernels: the structs are built once per slot); else None"""
+        c = slot.get('step')
+        if c is None or c['B'] != B or c['applies'] != applies or c['key'] != self._step_cache_key():
+            return None
+        return c
 
-    def _launch_cached(self, L_, c, step_idx, applies):
-        """the three library calls of a scan-update step from cached argument structs: stamp and learning rates refreshed"""
-        A, up, sg, gsw = c['A'], c['up'], c['sg'], c['gsw']
+    def _launch(self, c, step_idx, prep):
+        """The library calls of one step from a built call: stamp and step sizes refreshed, and a host batch's own counts."""
+        L_ = lib()
+        A, up, sg = c['A'], c['up'], c['sg']
         stream = stream_ptr(self.device)
-        self._stamp += 1
-        A.stamp = self._stamp
-        n_app = applies[0]
-        alpha = self._step_sizes(step_idx, applies)
+        if c['host']:
+            A.n_du, A.n_di, A.n_work, A.seg_len = prep['n_du'], prep['n_di'], prep['n_work'], prep['seg_len']
+            if A.target_mode == 1:
+                A.y_mean = prep['y_mean']
+        alpha = self._step_sizes(step_idx, c['applies'])
         for i, tw in c['sg_tw']:
             sg.alpha[i] = alpha[tw]
-        # (the small weights' Adam in the launch that sums their partial gradients: drx_dmf_step_small — one launch less than
-        # drx_dmf_fwd_bwd + drx_adam_segments, the same bits; the first-layer update reads none of them)
-        check(L_.drx_dmf_step_small_opt(c['D'], c['Aref'], gsw, c['sw'], c['m'], c['v'], c['sgref'], c['ruleref'], stream), 'drx_dmf_step_small_opt')
-        up.alpha_u, up.alpha_i = alpha[0], alpha[1]
-        check(L_.drx_dmf_k0_update(c['D'], c['Aref'], c['upref'], stream), 'drx_dmf_k0_update')
+        if up is not None:
+            self._stamp += 1
+            A.stamp = self._stamp
+        # forward / backward with the small weights' update in the launch that sums their partial gradients (one launch less than
+        # drx_dmf_fwd_bwd + drx_adam_segments, the same bits; gsw still holds the gradient and, last, the loss sum; the first-layer
+        # update below reads none of the small weights)
+        check(L_.drx_dmf_step_small_opt(*c['small'], stream), 'drx_dmf_step_small_opt')
+        if up is not None:
+            up.alpha_u, up.alpha_i = alpha[0], alpha[1]
+            check(L_.drx_dmf_k0_update(c['small'][0], c['small'][1], c['upref'], stream), 'drx_dmf_k0_update')
+            return
+        self._g_arena.zero_()
+        for keys, T, src, src_index, coef, ld, n_rows, name in c['scatter']:
+            self._scatter(keys, T, src, src_index, coef, ld, n_rows, self._g[name])
+        for tw, name in enumerate(('K0u', 'K0i')):
+            p = self.tensors()[name]
+            m, v = self.state[name]
+            check(L_.drx_opt_dense(ptr(p), ptr(m), ptr(v), ptr(self._g[name]), p.numel(), C.byref(self._rule(alpha[tw])), c['l2c'], stream),
+                  'drx_opt_dense')
+
+    def step(self, step_idx, uids, iids=None, y=None, want_loss=False, applies=None):
+        """uids, iids, y: the batch (arrays or tensors) — or `uids` = what prepare_batch / prepare_batch_device returned for it.
+        applies = (n, j_user, j_item, j_scale): number of apply_gradients calls per step and the positions of user_nn, item_nn
+        and the prediction scale among them (the registration order, recommender_abc.py:194-196); default: the reference DMF's
+        (2, 0, 1), or (3, 1, 2, 0) with a bound scale."""
+        applies = tuple(applies) if applies is not None else (3, 1, 2, 0) if self.scale_var is not None else (2, 0, 1, None)
+        if not isinstance(uids, dict):
+            if torch.is_tensor(uids) or torch.is_tensor(iids) or torch.is_tensor(y):
+                c = lambda a: a.detach().cpu().numpy() if torch.is_tensor(a) else np.asarray(a)
+                uids, iids, y = c(uids), c(iids), c(y)
+            uids = self.prepare_batch(uids, iids, y)
+        prep = uids
+        scan = self.first_layer_update == 'scan'
+        dev_slot = prep.get('device')
+        if dev_slot is not None:            # drawn and prepared on the device: the distinct counts and the batch mean live there
+            if not scan:
+                raise _lib.DrxError('device-prepared DMF batches need the scan update of the first-layer kernels (set_interactions chose '
+                                    '"scatter": more than SCAN_MAX_NNZ interactions)')
+            slot, cached = dev_slot, not want_loss
+        else:                               # one asynchronous copy into the device buffer of a slot of the upload ring
+            slot, cached = self._stage.upload_kept(prep['buf']), not want_loss and scan and self.host_step_cache
+        call = self._cached_call(slot, prep['B'], applies) if cached else None
+        if call is None:
+            call = self._build_call(self._where(prep, slot), applies)
+            if cached:
+                call['key'] = self._step_cache_key()        # (now: it names the work buffers _build_call may have made)
+                slot['step'] = call
+        reg_loss = None
+        if want_loss:                       # Keras l2(reg) on the pre-update weights
+            reg_loss = self.reg * _lib.sumsq([self.K0u, self.K0i] + [self.sw[start:start + n] for _, start, n, regd, _ in self.seg if regd])
+        self._launch(call, step_idx, prep)
+        if dev_slot is not None:            # (the ring slot may be drawn into again behind this point: prepare_batch_device waits for it)
+            dev_slot['free'] = torch.cuda.Event()
+            dev_slot['free'].record(torch.cuda.current_stream(self.device))
+        if want_loss:
+            return float((call['gsw'][-1] + reg_loss).item())
+        return None
 
     def _step_cache_key(self):
         """what a cached argument struct depends on besides its ring slot: the tensors a set_params / set_interactions / optimizer change
@@ -612,7 +519,7 @@ class DmfEngine(RowsRecommender):
         uid, iid = self._dev_i32(uids), self._dev_i32(iids)
         B = uid.numel()
         pred = torch.empty(B, dtype=torch.float32, device=self.device)
-        A = self._base_args(uid, iid)
+        A = self._base_args(uid.data_ptr(), iid.data_ptr(), B)
         A.pred_out = pred.data_ptr()
         ru = ri = None
         if want_reps:
@@ -649,7 +556,7 @@ class DmfEngine(RowsRecommender):
         B = int(ids.numel())
         other = torch.zeros(B, dtype=torch.int32, device=self.device)       # (a pair needs a partner: id 0 of the other side, unused)
         rep = torch.empty(B, self.W, dtype=torch.float32, device=self.device)
-        A = self._base_args(ids, other) if tower == 0 else self._base_args(other, ids)
+        A = self._base_args(ids.data_ptr(), other.data_ptr(), B) if tower == 0 else self._base_args(other.data_ptr(), ids.data_ptr(), B)
         if tower == 0:
             A.rep_u_out = rep.data_ptr()
         else:

@@ -566,7 +566,7 @@ def test_a_batch_on_the_device_takes_the_same_step_as_the_same_batch_from_the_ho
 
 def test_ring_slots_with_cached_argument_structs_take_the_same_steps(monkeypatch):
     """Caser.fit(device_sampler=True) fills ring slots the engine owns (device_slot / group_slot) and steps on them with argument structs
-    built once per slot (_step_slot): the same parameters, bit for bit, as the same draws through prepare_device_batch and the general
+    built once per slot (_step_slot / _build_call): the same parameters, bit for bit, as the same draws through prepare_device_batch and the general
     step — over more steps than the ring has slots, with dropout, a learning-rate change in between."""
     import torch
     from drecpy_amd.engine_caser import CaserEngine
@@ -598,6 +598,47 @@ def test_ring_slots_with_cached_argument_structs_take_the_same_steps(monkeypatch
     a, b = engs[0].get_params(), engs[1].get_params()
     engs[1].step(10, engs[1].prepare_device_batch(*(engs[0]._dev_slots['slots'][(engs[0]._dev_slots['i'] - 1) % 3][k] for k in ('uid', 'before', 'after'))),
                  rate=0.5, mask_seed=5, want_loss=True)
+    a, b = engs[0].get_params(), engs[1].get_params()
+    for k in a:
+        assert np.array_equal(a[k], b[k]), k
+
+
+def test_a_step_with_the_scatter_update_hands_its_ring_slot_back():
+    """table_update = 'scatter' on a device_slot / group_slot slot and on a prepare_device_batch batch: the step records the `free` event
+    of the slot it read in either ring (every exit of a step that consumed a slot does), and takes the scatter update — the same
+    parameters, bit for bit, as the same two steps given as plain device tensors."""
+    import torch
+    from drecpy_amd.engine_caser import CaserEngine
+    d, L, n_v, n_h, T, neg, B, U, N = 50, 5, 4, 16, 3, 3, 300, 70, 120
+    rng = np.random.default_rng(11)
+    p = ca.init_params(rng, U, N, L, d, n_v, n_h, np.float64)
+    engs = []
+    for _ in range(2):
+        e = CaserEngine(U, N, L, T, neg, d, n_v, n_h)
+        e.set_params(p)
+        e.lr, e.reg = 5e-3, 1e-4
+        e.table_update = 'scatter'
+        engs.append(e)
+    dev = engs[0].device
+    t = lambda a: torch.as_tensor(np.ascontiguousarray(a, dtype=np.int32)).to(dev)
+    slots = []
+    for step in range(2):
+        uids, before, after = t(rng.integers(0, U, size=B)), t(rng.zipf(1.5, size=(B, L)) % N), t(rng.integers(0, N, size=(B, T + T * neg)))
+        if step == 0:
+            sl = engs[0].device_slot(B)
+            sl['uid'].copy_(uids); sl['before'].copy_(before); sl['after'].copy_(after)
+            sl = engs[0].group_slot(sl)
+        else:
+            sl = engs[0].prepare_device_batch(uids, before, after)
+        assert sl['free'] is None
+        engs[0].step(step, sl, rate=0.5, mask_seed=31 + step)
+        slots.append(sl)
+        engs[1].step(step, uids, before, after, rate=0.5, mask_seed=31 + step)
+    assert slots[0] is engs[0]._dev_slots['slots'][0] and slots[1] is engs[0]._dev_csr['slots'][0]
+    torch.cuda.synchronize()
+    for sl in slots:
+        assert isinstance(sl['free'], torch.cuda.Event) and sl['free'].query()
+    assert '_dev_csr' not in engs[1].__dict__ and '_dev_slots' not in engs[1].__dict__      # (plain tensors, scatter update: no ring)
     a, b = engs[0].get_params(), engs[1].get_params()
     for k in a:
         assert np.array_equal(a[k], b[k]), k

@@ -439,7 +439,7 @@ def test_a_step_on_a_device_prepared_batch_equals_the_host_prepared_one(modified
 @pytest.mark.parametrize('modified', [False, True])
 def test_the_cached_argument_structs_of_device_batches_change_nothing(modified, monkeypatch):
     """Steps on device-prepared batches reuse the argument structs an earlier step built for the same ring slot (only the stamp and the
-    learning rates are refreshed: DmfEngine._step_device_cached): the same parameters, bit for bit, as with the cache off — over more steps
+    learning rates are refreshed: DmfEngine._cached_call / _launch): the same parameters, bit for bit, as with the cache off — over more steps
     than the ring has slots, with a learning-rate change and a set_params (which replaces nothing the cache points to) in between."""
     import torch
     from drecpy_amd.engine_dmf import DmfEngine
@@ -457,15 +457,15 @@ def test_the_cached_argument_structs_of_device_batches_change_nothing(modified, 
         e.set_params(p)
         e.lr, e.reg = 2e-3, 1e-3
         engs.append(e)
-    monkeypatch.setattr(engs[1], '_step_device_cached', lambda *a, **k: False)          # the general path every time
+    monkeypatch.setattr(engs[1], '_cached_call', lambda *a, **k: None)                  # the general path every time: built anew
     hits = [0]
-    inner = engs[0]._step_device_cached
+    inner = engs[0]._cached_call
 
     def counted(*a, **k):
         r = inner(*a, **k)
-        hits[0] += bool(r)
+        hits[0] += r is not None
         return r
-    monkeypatch.setattr(engs[0], '_step_device_cached', counted)
+    monkeypatch.setattr(engs[0], '_cached_call', counted)
     for step in range(11):
         u = rng.integers(0, U, size=B).astype(np.int32)
         i = rng.integers(0, N // 3, size=B).astype(np.int32)
@@ -671,7 +671,50 @@ def test_the_cached_argument_structs_of_host_batches_change_nothing(modified):
         want_loss = step == 10
         la = [e.step(step, u, i, y, want_loss=want_loss) for e in engs]
         assert la[0] == la[1]
-    assert sum(c is not None for c in engs[0]._stage['cache']) == 4 and all(c is None for c in engs[1]._stage['cache'])
+    assert sum('step' in k for k in engs[0]._stage.kept) == 4 and not any('step' in k for k in engs[1]._stage.kept)
+    ga, gb = engs[0].get_params(), engs[1].get_params()
+    for k in ga:
+        assert np.array_equal(ga[k], gb[k]), k
+
+
+def test_a_device_ring_slot_is_handed_back_by_the_step_that_read_it():
+    """Four consecutive prepare_batch_device + step on the current stream, one more than the ring has slots: the step that read a slot
+    records the slot's `free` event, and the prepare that comes round to the slot waits for it (and clears it).  The parameters equal
+    those of an engine fed the same triples through host step(u, i, y) bit for bit — the tolerance of
+    test_a_step_on_a_device_prepared_batch_equals_the_host_prepared_one."""
+    import torch
+    from drecpy_amd.engine_dmf import DmfEngine
+    rng = np.random.default_rng(37)
+    U, N, B = 150, 90, 180
+    csr, csc, _ = _problem(rng, U, N, 2800)
+    p = dm.init_params(rng, U, N, (32, 16), (24, 16), np.float64)
+    engs = []
+    for _ in range(2):
+        e = DmfEngine(U, N, (32, 16), (24, 16), True)
+        e.set_interactions(csr, csc)
+        e.set_params(p)
+        e.lr, e.reg = 2e-3, 1e-3
+        engs.append(e)
+    first = ev = None
+    for step in range(4):
+        u = rng.integers(0, U, size=B).astype(np.int32)
+        i = rng.integers(0, N // 3, size=B).astype(np.int32)
+        y = rng.random(B).astype(np.float32)
+        if step == 3:                                # before the fourth prepare: the first slot still carries the first step's event
+            assert isinstance(first['free'], torch.cuda.Event) and first['free'] is ev
+        prep = engs[0].prepare_batch_device(B, 0, 0, triples=[torch.as_tensor(a).cuda() for a in (u, i, y)])
+        if step == 0:
+            first = prep['device']
+            assert first['free'] is None
+        if step == 3:
+            assert prep['device'] is first and first['free'] is None        # (waited for, then cleared)
+        engs[0].step(step, prep)
+        if step == 0:
+            ev = first['free']
+            assert isinstance(ev, torch.cuda.Event)
+        engs[1].step(step, u, i, y)
+    torch.cuda.synchronize()
+    assert ev.query() and first['free'] is not ev and first['free'].query()
     ga, gb = engs[0].get_params(), engs[1].get_params()
     for k in ga:
         assert np.array_equal(ga[k], gb[k]), k
