@@ -251,16 +251,21 @@ class Caser(RecommenderABC):
         eng = self._engine
         if type(self)._rank is not Caser._rank or len(uids) < self.RECOMMEND_MIN_FUSED_USERS or not eng.recommend_is_fused(eng.ld2, min(int(n), self.n_items)):
             return super()._recommend_batch(uids, n, novelty)
-        self._user_sequence(0)                                            # (builds _seq_ptr / _seq_items)
-        full = (self._seq_ptr[uids + 1] - self._seq_ptr[uids]) >= self.L
+        full, before = self._last_items(uids)
         idx = np.full((len(uids), n), -1, dtype=np.int64)
         val = np.full((len(uids), n), -np.inf, dtype=np.float64)
         if not full.all():
             idx[~full], val[~full] = super()._recommend_batch(uids[~full], n, novelty)
         if full.any():
-            before = np.stack([self._user_sequence(x)[-self.L:] for x in uids[full]])
             idx[full], val[full] = self._recommend_batch_fused(uids[full], n, novelty, before)
         return idx, val
+
+    def _last_items(self, uids):
+        """(full bool [len(uids)]: the user's sequence is at least L long — a fused query row needs L items —; before [full.sum(), L]:
+        the last L items of those users, or None where there is none)"""
+        self._user_sequence(0)                                            # (builds _seq_ptr / _seq_items)
+        full = (self._seq_ptr[uids + 1] - self._seq_ptr[uids]) >= self.L
+        return full, np.stack([self._user_sequence(x)[-self.L:] for x in uids[full]]) if full.any() else None
 
     def _catalogue_ranks(self, uids, iids, novelty):
         """Catalogue ranks of many (user, item) pairs in one engine call (CaserEngine.rank_items), under _recommend_batch's gates,
@@ -269,14 +274,12 @@ class Caser(RecommenderABC):
         eng = self._engine
         if type(self)._rank is not Caser._rank or not eng.rank_is_fused(eng.ld2):
             return super()._catalogue_ranks(uids, iids, novelty)
-        self._user_sequence(0)                                            # (builds _seq_ptr / _seq_items)
-        full = (self._seq_ptr[uids + 1] - self._seq_ptr[uids]) >= self.L
+        full, before = self._last_items(uids)
         ranks = np.full(len(uids), -1, dtype=np.int64)
         scores = np.full(len(uids), -np.inf, dtype=np.float64)
         if not full.all():
             ranks[~full], scores[~full] = super()._catalogue_ranks(uids[~full], iids[~full], novelty)
         if full.any():
-            before = np.stack([self._user_sequence(x)[-self.L:] for x in uids[full]])
             ranks[full], scores[full] = self._catalogue_ranks_fused(uids[full], iids[full], novelty, before)
         return ranks, scores
 

@@ -16,14 +16,10 @@ import torch
 
 from . import _lib
 from ._lib import Batch, CdaeParams, History, Optim, check, lib, ptr, stream_ptr
+from .engine_rows import ADAM_B1, ADAM_B2, ADAM_EPS, RowsRecommender, _round_up, pack_mask_bits    # noqa: F401 (this module's importers take them from here too)
 
 VAR_ORDER = ('W', 'W2T', 'V', 'b', 'b2')      # registration order W, W_, V, b, b_ (cdae.py:43)
-ADAM_B1, ADAM_B2, ADAM_EPS = 0.9, 0.999, 1e-7  # tf.keras.optimizers.Adam defaults
 ADAGRAD_INIT, ADAGRAD_EPS = 0.1, 1e-7         # tf.keras.optimizers.Adagrad defaults
-
-
-def _round_up(x, m):
-    return (x + m - 1) // m * m
 
 
 def _forget_prepared(addr):
@@ -31,247 +27,6 @@ def _forget_prepared(addr):
         lib().drx_cdae_prep_forget(addr)
     except Exception:           # (interpreter shutdown)
         pass
-
-
-def pack_mask_bits(mask_bool):
-    """bool [R,n] (numpy) -> uint32 words; bit (i & 31) of word (i >> 5) is flat element i."""
-    flat = np.asarray(mask_bool, dtype=bool).ravel()
-    pad = (-len(flat)) % 32
-    if pad:
-        flat = np.concatenate([flat, np.zeros(pad, bool)])
-    return np.packbits(flat, bitorder='little').view(np.uint32).copy()
-
-
-class RowsRecommender:
-    """What the engines of all models share.  The model-independent half of recommend(): the exclusion CSR on the device and the
-    chunked launch of the fused scorer-selector (include/drx.h drx_rows_recommend) — an engine brings n_users,
-    n_items, device, the table (+ bias), the epilogue and a function that computes the query rows of a chunk of users.  And the
-    score-matrix route of rank(), ranking_evaluation and requests outside the fused domain: drx_topk under a host candidate mask."""
-    RECOMMEND_CHUNK_USERS = 16384          # users per launch of the fused path: bounds its scratch (candidate keys only)
-
-    @staticmethod
-    def adam_alpha(lr, t, beta1=ADAM_B1, beta2=ADAM_B2):
-        """Keras-Adam lr_t for the 1-based step t, in fp32 like optimizer_v2/adam.py."""
-        f = np.float32
-        return float(f(lr) * np.sqrt(f(1.0) - np.power(f(beta2), f(t))) / (f(1.0) - np.power(f(beta1), f(t))))
-
-    def _dev_i32(self, a):
-        if torch.is_tensor(a):
-            return a.to(self.device, torch.int32).contiguous()
-        return torch.as_tensor(np.ascontiguousarray(a, dtype=np.int32)).to(self.device)
-
-    def topk(self, scores, k, cand_mask=None):
-        """Row-wise top-k with heapq.nlargest((score, iid)) ordering (cdae.py:103)."""
-        scores = scores.contiguous()
-        R, n = scores.shape
-        out_idx = torch.empty(R, k, dtype=torch.int32, device=self.device)
-        out_val = torch.empty(R, k, dtype=torch.float32, device=self.device)
-        sb = lib().drx_topk_scratch_bytes_k(R, n, k)
-        sc = torch.empty(sb, dtype=torch.uint8, device=self.device) if sb else None
-        check(lib().drx_topk(ptr(scores), ptr(cand_mask), R, n, k, ptr(out_idx), ptr(out_val), ptr(sc), sb,
-                             stream_ptr(self.device)), 'drx_topk')
-        return out_idx, out_val
-
-    def masked_topk(self, scores, cand, k):
-        """topk among the candidates `cand`, a host bool array [R, n_items]: -1 / -inf behind a row's last candidate."""
-        return self.topk(scores, k, torch.as_tensor(pack_mask_bits(cand).view(np.int32)).to(self.device))
-
-    @staticmethod
-    def matrix_chunk_users(n_items, budget_bytes):
-        """Users per chunk of the score-matrix route: their fp32 [R, n_items] matrix within `budget_bytes`, and R * n_items < 2^31
-        (the index range of drx_topk's long rows)."""
-        return max(1, min(budget_bytes // (4 * n_items), ((1 << 31) - 1) // n_items))
-
-    def set_exclusions(self, indptr, indices):
-        """CSR over users (columns ascending and unique) of the items recommend() never returns for a user; None = none."""
-        if indptr is None:
-            self._excl = None
-            return
-        ip = np.ascontiguousarray(indptr, dtype=np.int64)
-        ix = np.ascontiguousarray(indices, dtype=np.int32)
-        assert len(ip) == self.n_users + 1 and int(ip[-1]) == len(ix)
-        d_ip = torch.as_tensor(ip).to(self.device)
-        d_ix = torch.as_tensor(ix if len(ix) else np.zeros(1, np.int32)).to(self.device)
-        self._excl = (d_ip, d_ix, ip, ix)
-
-    def _exclusion_mask(self, host_uids):
-        """The rows of set_exclusions() as a host candidate mask, bool [len(host_uids), n_items]: False at a user's excluded items."""
-        _, _, ip, ix = self._excl
-        cand = np.ones((len(host_uids), self.n_items), dtype=bool)
-        for j, x in enumerate(host_uids):
-            cand[j, ix[ip[x]:ip[x + 1]]] = False
-        return cand
-
-    def recommend_is_fused(self, ld, n):
-        """Whether rows of `ld` floats and lists of n lie in the fused domain (else drx_rows_recommend answers DRX_ENOTIMPL)."""
-        return int(lib().drx_rows_recommend_scratch_bytes(1, self.n_items, int(ld), int(n))) > 0
-
-    def _recommend_request(self, uids, n, exclude):
-        """(uid int32 on the device, n, the exclusion CSR or None, out_idx int32 [R, n], out_val float32 [R, n])"""
-        uid = self._dev_i32(uids)
-        R, n = int(uid.numel()), int(n)
-        assert n >= 1
-        excl = getattr(self, '_excl', None) if exclude is None or exclude is True else None
-        assert not (exclude is True and excl is None), 'recommend(exclude=True) needs set_exclusions()'
-        out_idx = torch.empty(R, n, dtype=torch.int32, device=self.device)
-        out_val = torch.empty(R, n, dtype=torch.float32, device=self.device)
-        return uid, n, excl, out_idx, out_val
-
-    def _rows_recommend(self, table, bias, ld, epilogue, uid, n, excl, rows_of, out_idx, out_val, chunk_users=None):
-        """`chunk_users` users at a time: rows_of(lo, uid[lo:lo + r]) -> their [r, ld] query rows (padding columns ZERO), then one
-        drx_rows_recommend against `table` [n_items, ld] (+ `bias`) into out_idx / out_val [lo:lo + r].  The scratch is kept."""
-        L = lib()
-        R = int(uid.numel())
-        chunk = int(chunk_users or self.RECOMMEND_CHUNK_USERS)
-        assert table.is_contiguous() and tuple(table.shape) == (self.n_items, ld)
-        for lo in range(0, R, chunk):
-            u = uid[lo:lo + chunk]
-            r = int(u.numel())
-            q = rows_of(lo, u)
-            assert q.is_contiguous() and tuple(q.shape) == (r, ld) and q.dtype == torch.float32
-            need = int(L.drx_rows_recommend_scratch_bytes(r, self.n_items, ld, n))
-            sc = getattr(self, '_rec_scratch', None)
-            if sc is None or sc.numel() < need:
-                self._rec_scratch = None
-                sc = self._rec_scratch = torch.empty(need, dtype=torch.uint8, device=self.device)
-            check(L.drx_rows_recommend(ptr(table), ptr(bias), self.n_items, ld, epilogue, ptr(q), ptr(u), r, n,
-                                       ptr(excl[0]) if excl else None, ptr(excl[1]) if excl else None, ptr(out_idx[lo:lo + r]),
-                                       ptr(out_val[lo:lo + r]), ptr(sc), sc.numel(), stream_ptr(self.device)), 'drx_rows_recommend')
-        return out_idx, out_val
-
-    # ---- catalogue ranks of given (user, item) pairs (include/drx.h drx_rows_rank_items; DESIGN.md section 3.5) ----------------------
-    def rank_is_fused(self, ld):
-        """Whether rows of `ld` floats lie in the fused domain of drx_rows_rank_items (else it answers DRX_ENOTIMPL)."""
-        return int(lib().drx_rows_rank_items_scratch_bytes(1, self.n_items, int(ld))) > 0
-
-    def _rank_request(self, uids, items, exclude):
-        """(uid int32 [P], target int32 [P] on the device, the exclusion CSR or None)"""
-        uid, target = self._dev_i32(uids).reshape(-1), self._dev_i32(items).reshape(-1)
-        assert uid.numel() == target.numel(), 'rank_items takes parallel users and items'
-        excl = getattr(self, '_excl', None) if exclude is None or exclude is True else None
-        assert not (exclude is True and excl is None), 'rank_items(exclude=True) needs set_exclusions()'
-        return uid, target, excl
-
-    def _rows_rank_items(self, table, bias, ld, epilogue, uid, target, excl, rows_of, chunk_rows=None):
-        """The chunked launch beside _rows_recommend: `chunk_rows` (user, item) rows at a time, rows_of(lo, uid[lo:lo + r]) -> their
-        [r, ld] query rows (padding columns ZERO), then one drx_rows_rank_items against `table` [n_items, ld] (+ `bias`).  Returns
-        device tensors (rank int32 [P]: the number of eligible items ahead of the target, -1 for a target outside the catalogue;
-        score float32 [P]).  The scratch is kept."""
-        L = lib()
-        P = int(uid.numel())
-        chunk = int(chunk_rows or self.RECOMMEND_CHUNK_USERS)
-        assert table.is_contiguous() and tuple(table.shape) == (self.n_items, ld)
-        out_rank = torch.empty(P, dtype=torch.int32, device=self.device)
-        out_score = torch.empty(P, dtype=torch.float32, device=self.device)
-        for lo in range(0, P, chunk):
-            u, t = uid[lo:lo + chunk], target[lo:lo + chunk]
-            r = int(u.numel())
-            q = rows_of(lo, u)
-            assert q.is_contiguous() and tuple(q.shape) == (r, ld) and q.dtype == torch.float32
-            need = int(L.drx_rows_rank_items_scratch_bytes(r, self.n_items, ld))
-            sc = getattr(self, '_rank_scratch', None)
-            if sc is None or sc.numel() < need:
-                self._rank_scratch = None
-                sc = self._rank_scratch = torch.empty(need, dtype=torch.uint8, device=self.device)
-            check(L.drx_rows_rank_items(ptr(table), ptr(bias), self.n_items, ld, epilogue, ptr(q), ptr(u), ptr(t), r,
-                                        ptr(excl[0]) if excl else None, ptr(excl[1]) if excl else None, ptr(out_rank[lo:lo + r]),
-                                        ptr(out_score[lo:lo + r]), ptr(sc), sc.numel(), stream_ptr(self.device)), 'drx_rows_rank_items')
-        return out_rank, out_score
-
-    # ---- the same for rows that own a LIST of targets (include/drx.h drx_rows_rank_lists): one counting walk per row, not per pair ----
-    # pairs are grouped per user when there are at least this many per distinct user (RecommenderABC._catalogue_ranks_fused;
-    # DESIGN.md section 3.5 has the measurement behind the value)
-    RANK_LISTS_MIN_MEAN = 2.0
-
-    def rank_ld(self):
-        """The width of this engine's query rows in the fused scorer (what rank_is_fused / rank_lists_group are asked about)."""
-        raise NotImplementedError
-
-    def rank_lists_group(self, ld):
-        """G: the targets of one row that drx_rows_rank_lists counts in ONE walk at rows of `ld` floats (a longer row walks again for
-        every further G); 0 outside the fused domain."""
-        return int(lib().drx_rows_rank_lists_group(int(ld)))
-
-    def _rank_lists_request(self, uids, indptr, items, exclude):
-        """(uid int32 [R] on the device, the offsets int64 [R + 1] on the host and on the device, targets int32 [P] on the device,
-        the exclusion CSR or None)"""
-        uid, targets = self._dev_i32(uids).reshape(-1), self._dev_i32(items).reshape(-1)
-        ip = indptr.cpu().numpy() if torch.is_tensor(indptr) else np.asarray(indptr)
-        ip = np.ascontiguousarray(ip, dtype=np.int64).reshape(-1)
-        assert len(ip) == uid.numel() + 1 and ip[0] == 0 and ip[-1] == targets.numel() and (np.diff(ip) >= 0).all(), \
-            'rank_lists takes CSR offsets [R + 1] over the items: 0 first, ascending, len(items) last'
-        excl = getattr(self, '_excl', None) if exclude is None or exclude is True else None
-        assert not (exclude is True and excl is None), 'rank_lists(exclude=True) needs set_exclusions()'
-        return uid, ip, torch.as_tensor(ip).to(self.device), targets, excl
-
-    def _rows_rank_lists(self, table, bias, ld, epilogue, uid, indptr, targets, excl, rows_of, chunk_rows=None):
-        """The chunked launch beside _rows_rank_items for rows that own lists: `indptr` = (host, device) int64 [R + 1] offsets of row
-        r's ascending targets in `targets` [P].  `chunk_rows` rows at a time: rows_of(lo, uid[lo:lo + r]) -> their [r, ld] query rows
-        (padding columns ZERO), then one drx_rows_rank_lists at the offsets from `lo` on (they are absolute: outputs land in place).
-        Returns device tensors (rank int32 [P], score float32 [P]) parallel to `targets`, -1 / -inf for a target outside the
-        catalogue.  The scratch is kept."""
-        L = lib()
-        ip, d_ip = indptr
-        R, P = int(uid.numel()), int(targets.numel())
-        chunk = int(chunk_rows or self.RECOMMEND_CHUNK_USERS)
-        assert table.is_contiguous() and tuple(table.shape) == (self.n_items, ld)
-        out_rank = torch.empty(P, dtype=torch.int32, device=self.device)
-        out_score = torch.empty(P, dtype=torch.float32, device=self.device)
-        for lo in range(0, R, chunk):
-            u = uid[lo:lo + chunk]
-            r = int(u.numel())
-            p = int(ip[lo + r] - ip[lo])
-            if p == 0:
-                continue
-            q = rows_of(lo, u)
-            assert q.is_contiguous() and tuple(q.shape) == (r, ld) and q.dtype == torch.float32
-            need = int(L.drx_rows_rank_lists_scratch_bytes(r, p, self.n_items, ld))
-            if need == 0:
-                raise _lib.DrxError(f'drx_rows_rank_lists: rows of {ld} floats lie outside the fused domain (rank_is_fused tells)')
-            sc = getattr(self, '_rank_scratch', None)
-            if sc is None or sc.numel() < need:
-                self._rank_scratch = None
-                sc = self._rank_scratch = torch.empty(need, dtype=torch.uint8, device=self.device)
-            check(L.drx_rows_rank_lists(ptr(table), ptr(bias), self.n_items, ld, epilogue, ptr(q), ptr(u), r, ptr(d_ip[lo:]), ptr(targets),
-                                        ptr(excl[0]) if excl else None, ptr(excl[1]) if excl else None, ptr(out_rank), ptr(out_score),
-                                        ptr(sc), sc.numel(), stream_ptr(self.device)), 'drx_rows_rank_lists')
-        return out_rank, out_score
-
-    # ---- scores of given (user, item) pairs and nothing else (include/drx.h drx_rows_pair_scores; DESIGN.md section 3.5) --------------
-    PAIR_CHUNK_PAIRS = 1 << 20             # pairs per launch: bounds the query rows of a chunk's distinct users
-
-    def _pair_request(self, uids, items):
-        """(uid int32 [P], item int32 [P]) on the device"""
-        uid, item = self._dev_i32(uids).reshape(-1), self._dev_i32(items).reshape(-1)
-        assert uid.numel() == item.numel(), 'pair_scores takes parallel users and items'
-        return uid, item
-
-    def _rows_pair_scores(self, table, bias, ld, epilogue, uid, t_row, rows_of_users, chunk_pairs=None):
-        """`chunk_pairs` pairs at a time: the query rows of the chunk's DISTINCT users once, rows_of_users(distinct uid int32) ->
-        [n, ld] (padding columns ZERO), then one drx_rows_pair_scores against `table` [n_rows, ld] (+ `bias`) at the rows `t_row`
-        (int32 [P]; outside the table: -inf).  Returns a float32 [P] device tensor: for rows of up to 256 floats the values
-        _rows_rank_items reports for the same pairs.  No scratch.  Any pair order; sorted by user the query rows are read from the L1."""
-        L = lib()
-        P = int(uid.numel())
-        chunk = int(chunk_pairs or self.PAIR_CHUNK_PAIRS)
-        assert table.is_contiguous() and table.dim() == 2 and table.shape[1] == ld and t_row.dtype == torch.int32
-        out = torch.empty(P, dtype=torch.float32, device=self.device)
-        for lo in range(0, P, chunk):
-            u, t = uid[lo:lo + chunk], t_row[lo:lo + chunk]
-            p = int(u.numel())
-            distinct, inverse = torch.unique(u, return_inverse=True)
-            q = rows_of_users(distinct.to(torch.int32).contiguous())
-            assert q.is_contiguous() and tuple(q.shape) == (int(distinct.numel()), ld) and q.dtype == torch.float32
-            q_row = inverse.to(torch.int32).contiguous()
-            check(L.drx_rows_pair_scores(ptr(table), ptr(bias), int(table.shape[0]), ld, epilogue, ptr(q), int(q.shape[0]), ptr(q_row), ptr(t), p,
-                                         ptr(out[lo:lo + p]), stream_ptr(self.device)), 'drx_rows_pair_scores')
-        return out
-
-    @staticmethod
-    def _rows_per_distinct(uid, rows_of_users):
-        """Query rows of the pairs `uid`, computed once per distinct user by rows_of_users(distinct uid) and gathered."""
-        distinct, inverse = torch.unique(uid, return_inverse=True)
-        return rows_of_users(distinct.to(torch.int32).contiguous())[inverse].contiguous()
 
 
 class CdaeEngine(RowsRecommender):
@@ -882,52 +637,21 @@ class CdaeEngine(RowsRecommender):
               'drx_cdae_forward')
         return h
 
-    def recommend(self, uids, n, exclude=None, chunk_users=None):
-        """(idx int32 [R, n], val float32 [R, n]) device tensors: the n best items of every user by (score, item) descending, -1 / -inf
-        behind the last eligible one.  exclude: None = the rows of set_exclusions() where one was given, False = nothing excluded.
-        The hidden rows come from forward(); scores and selection from the fused scorer-selector (RowsRecommender), `chunk_users` users
-        at a time — or, outside its domain (n > 128, rows wider than 256 floats) and below RECOMMEND_MIN_FUSED_USERS users, from
-        forward + drx_topk."""
-        uid, n, excl, out_idx, out_val = self._recommend_request(uids, n, exclude)
-        R = int(uid.numel())
-        if R == 0:
-            return out_idx, out_val
-        if not (R >= self.RECOMMEND_MIN_FUSED_USERS and self.recommend_is_fused(self.ld, n)):
-            return self._recommend_by_matrix(uid, n, excl, out_idx, out_val)
-        return self._rows_recommend(self.W2T, self.b2, self.ld, _lib.DRX_REC_SIGMOID_BIAS, uid, n, excl, lambda lo, u: self._hidden_rows(u),
-                                    out_idx, out_val, chunk_users)
-
-    def rank_items(self, uids, items, exclude=None, chunk_rows=None):
-        """(rank int32 [P], score float32 [P]) device tensors for the parallel users / items: the position of items[p] in the list
-        recommend(uids[p], n = unbounded, exclude) would give — whatever the item's own exclusion —, and its score; -1 / -inf for an
-        item outside the catalogue.  One row per pair: a user with T items costs T rows.  Hidden rows once per distinct user; the same
-        table, bias and epilogue as recommend().  Rows wider than 256 floats: DrxError (rank_is_fused tells)."""
-        uid, target, excl = self._rank_request(uids, items, exclude)
-        if int(uid.numel()) == 0:
-            return torch.empty(0, dtype=torch.int32, device=self.device), torch.empty(0, dtype=torch.float32, device=self.device)
-        return self._rows_rank_items(self.W2T, self.b2, self.ld, _lib.DRX_REC_SIGMOID_BIAS, uid, target, excl,
-                                     lambda lo, u: self._rows_per_distinct(u, self._hidden_rows), chunk_rows)
-
-    def pair_scores(self, uids, items, chunk_pairs=None):
-        """float32 [P] device tensor: the score of items[p] for uids[p] and nothing else — two rows per pair, no catalogue walk —,
-        -inf for an item outside the catalogue.  Hidden rows once per distinct user of a chunk; the same table, bias and epilogue as
-        rank_items, and for rows of up to 256 floats its values; wider rows (K = 300) are answered too."""
-        uid, item = self._pair_request(uids, items)
-        return self._rows_pair_scores(self.W2T, self.b2, self.ld, _lib.DRX_REC_SIGMOID_BIAS, uid, item, self._hidden_rows, chunk_pairs)
+    # what the four calls of RowsRecommender score against: sigmoid(hidden row . W2T row + b2), the hidden rows of forward() — a
+    # user's alone, so made once per distinct user of a chunk
+    EPILOGUE = _lib.DRX_REC_SIGMOID_BIAS
+    _query_rows = _hidden_rows
 
     def rank_ld(self):
         return self.ld
 
-    def rank_lists(self, uids, indptr, items, exclude=None, chunk_rows=None):
-        """rank_items for rows that own several items: row r = user uids[r] with the ASCENDING items[indptr[r]:indptr[r + 1]] (CSR
-        offsets [R + 1]; a row may be empty, a user may own several rows).  (rank int32 [P], score float32 [P]) device tensors
-        parallel to `items`, bit for bit what rank_items gives for the pairs — at one catalogue walk per rank_lists_group(ld) items
-        of a row instead of one per item."""
-        uid, ip, d_ip, targets, excl = self._rank_lists_request(uids, indptr, items, exclude)
-        if int(targets.numel()) == 0:
-            return torch.empty(0, dtype=torch.int32, device=self.device), torch.empty(0, dtype=torch.float32, device=self.device)
-        return self._rows_rank_lists(self.W2T, self.b2, self.ld, _lib.DRX_REC_SIGMOID_BIAS, uid, (ip, d_ip), targets, excl,
-                                     lambda lo, u: self._rows_per_distinct(u, self._hidden_rows), chunk_rows)
+    def _score_table(self, items=None):
+        return self.W2T, self.b2
+
+    def _recommend_fused(self, R, n):
+        """Outside the fused domain (n > 128, rows wider than 256 floats) and below RECOMMEND_MIN_FUSED_USERS users recommend() takes
+        forward + drx_topk (_recommend_by_matrix)."""
+        return R >= self.RECOMMEND_MIN_FUSED_USERS and self.recommend_is_fused(self.ld, n)
 
     def _recommend_by_matrix(self, uid, n, excl, out_idx, out_val):
         """The score-matrix route: forward + host-built candidate mask + drx_topk, in chunks of users."""

@@ -17,8 +17,8 @@ import torch
 from . import _lib
 from ._lib import AdamSegments, CaserArgs, CaserDims, check, lib, ptr, stream_ptr
 from ._staging import StagedUpload
-from .engine import _round_up
 from .engine_dense import DenseEngine, aligned_offsets
+from .engine_rows import _round_up
 
 
 class CaserEngine(DenseEngine):
@@ -423,59 +423,18 @@ class CaserEngine(DenseEngine):
         check(lib().drx_caser_hidden(C.byref(self.D), C.byref(A), stream_ptr(self.device)), 'drx_caser_hidden')
         return cat
 
-    def recommend(self, uids, before, n, exclude=None, chunk_users=None):
-        """(idx int32 [R, n], val float32 [R, n]) device tensors: the n best items of every (user, last L items) row by (logit, item)
-        descending — the values scores_all / _rank give —, -1 / -inf behind the last eligible one.  exclude as CdaeEngine.recommend.
-        The hidden rows of all requested users come from one drx_caser_hidden per chunk; scores and selection from the fused
-        scorer-selector.  Outside its domain (n > 128): DrxError — Caser._recommend_batch asks recommend_is_fused first."""
-        uid, n, excl, out_idx, out_val = self._recommend_request(uids, n, exclude)
-        R = int(uid.numel())
-        if R == 0:
-            return out_idx, out_val
-        bef = self._dev_i32(before).reshape(R, self.L)
-        return self._rows_recommend(self.W1, self.b1, self.ld2, _lib.DRX_REC_BIAS, uid, n, excl,
-                                    lambda lo, u: self._hidden_rows(u, bef[lo:lo + int(u.numel())].contiguous()), out_idx, out_val, chunk_users)
-
-    def rank_items(self, uids, before, items, exclude=None, chunk_rows=None):
-        """(rank int32 [P], score float32 [P]) device tensors for the parallel (user, last L items) rows / items: the position of
-        items[p] in the list recommend(uids[p], before[p], n = unbounded, exclude) would give — whatever the item's own exclusion —,
-        and its logit; -1 / -inf for an item outside the catalogue.  One row per pair (a user with T items costs T rows, its hidden
-        row computed T times: the rows are cheap beside the catalogue walk)."""
-        uid, target, excl = self._rank_request(uids, items, exclude)
-        P = int(uid.numel())
-        if P == 0:
-            return torch.empty(0, dtype=torch.int32, device=self.device), torch.empty(0, dtype=torch.float32, device=self.device)
-        bef = self._dev_i32(before).reshape(P, self.L)
-        return self._rows_rank_items(self.W1, self.b1, self.ld2, _lib.DRX_REC_BIAS, uid, target, excl,
-                                     lambda lo, u: self._hidden_rows(u, bef[lo:lo + int(u.numel())].contiguous()), chunk_rows)
-
-    def pair_scores(self, uids, before, items, chunk_pairs=None):
-        """float32 [P] device tensor: the logit of items[p] for the (user, last L items) row (uids[p], before[p]) and nothing else, the
-        values rank_items reports; -inf for an item outside the catalogue.  One hidden row per pair, as rank_items: a pair is its
-        own query row (the shared launcher is given the pairs' positions as the rows' names)."""
-        uid, item = self._pair_request(uids, items)
-        P = int(uid.numel())
-        bef = self._dev_i32(before).reshape(P, self.L)
-        if P == 0:
-            return torch.empty(0, dtype=torch.float32, device=self.device)
-        pos = torch.arange(P, dtype=torch.int32, device=self.device)
-
-        def rows_of(d):                                                # (a chunk's distinct positions are the chunk: a slice, no gather)
-            lo = int(d[0])
-            return self._hidden_rows(uid[lo:lo + int(d.numel())], bef[lo:lo + int(d.numel())].contiguous())
-        return self._rows_pair_scores(self.W1, self.b1, self.ld2, _lib.DRX_REC_BIAS, pos, item, rows_of, chunk_pairs)
+    # what the four calls of RowsRecommender score against: the logit hidden row . W1 row + b1 — the values scores_all / _rank give.
+    # A hidden row belongs to the request row (user, last L items): ONE per row, from one drx_caser_hidden per chunk (a user with T
+    # rows has its hidden row computed T times: cheap beside the catalogue walk).  The calls take `before` [R, L] behind the users.
+    # Outside the fused domain (n > 128): DrxError — Caser._recommend_batch asks recommend_is_fused first.
+    EPILOGUE = _lib.DRX_REC_BIAS
+    QUERY_BY_ROW = True
 
     def rank_ld(self):
         return self.ld2
 
-    def rank_lists(self, uids, before, indptr, items, exclude=None, chunk_rows=None):
-        """rank_items for rows that own several items: row r = (user uids[r], last L items before[r]) with the ASCENDING
-        items[indptr[r]:indptr[r + 1]] (CSR offsets [R + 1]).  (rank int32 [P], logit float32 [P]) device tensors parallel to `items`,
-        bit for bit what rank_items gives for the pairs, at one catalogue walk and ONE hidden row per rank_lists_group(ld2) items of
-        a row."""
-        uid, ip, d_ip, targets, excl = self._rank_lists_request(uids, indptr, items, exclude)
-        if int(targets.numel()) == 0:
-            return torch.empty(0, dtype=torch.int32, device=self.device), torch.empty(0, dtype=torch.float32, device=self.device)
-        bef = self._dev_i32(before).reshape(int(uid.numel()), self.L)
-        return self._rows_rank_lists(self.W1, self.b1, self.ld2, _lib.DRX_REC_BIAS, uid, (ip, d_ip), targets, excl,
-                                     lambda lo, u: self._hidden_rows(u, bef[lo:lo + int(u.numel())].contiguous()), chunk_rows)
+    def _score_table(self, items=None):
+        return self.W1, self.b1
+
+    def _query_rows(self, uid, bef):
+        return self._hidden_rows(uid, bef.reshape(int(uid.numel()), self.L))

@@ -5,7 +5,7 @@ import numpy as np
 import torch
 
 from . import _lib
-from .engine import ADAM_B1, ADAM_B2, ADAM_EPS, RowsRecommender
+from .engine_rows import ADAM_B1, ADAM_B2, ADAM_EPS, RowsRecommender
 
 
 def aligned_offsets(nbytes):

@@ -21,8 +21,8 @@ import torch
 from . import _lib
 from ._lib import AdamSegments, DmfArgs, DmfDims, DmfK0Update, check, lib, ptr, stream_ptr
 from ._staging import StagedUpload
-from .engine import _round_up
 from .engine_dense import DenseEngine, aligned_offsets
+from .engine_rows import _round_up
 
 
 class DmfEngine(DenseEngine):
@@ -564,58 +564,18 @@ class DmfEngine(DenseEngine):
         check(lib().drx_dmf_predict(C.byref(self.D), C.byref(A), stream_ptr(self.device)), 'drx_dmf_predict')
         return rep
 
-    def recommend(self, uids, n, exclude=None, chunk_users=None):
-        """(idx int32 [R, n], val float32 [R, n]) device tensors: the n best items of every user by (max(1e-6, cosine), item) descending
-        — WITHOUT a bound prediction scale —, -1 / -inf behind the last eligible one.  exclude as CdaeEngine.recommend.  The item
-        tower runs ONCE per call over the catalogue (nothing is cached across calls: the parameters may have moved), the user tower
-        once per requested user; scores and selection come from the fused scorer-selector.  Outside its domain (n > 128): DrxError —
-        DMF._recommend_batch asks recommend_is_fused first and ranks per user instead."""
-        uid, n, excl, out_idx, out_val = self._recommend_request(uids, n, exclude)
-        if int(uid.numel()) == 0:
-            return out_idx, out_val
-        items = self._representations(1, torch.arange(self.N, dtype=torch.int32, device=self.device))
-        return self._rows_recommend(items, None, self.W, _lib.DRX_REC_CLIP, uid, n, excl, lambda lo, u: self._representations(0, u),
-                                    out_idx, out_val, chunk_users)
-
-    def rank_items(self, uids, items, exclude=None, chunk_rows=None):
-        """(rank int32 [P], score float32 [P]) device tensors for the parallel users / items: the position of items[p] in the list
-        recommend(uids[p], n = unbounded, exclude) would give — whatever the item's own exclusion —, and its score max(1e-6, cosine);
-        -1 / -inf for an item outside the catalogue.  One row per pair: a user with T items costs T rows.  The item tower runs ONCE per
-        call, the user tower once per distinct user of a chunk."""
-        uid, target, excl = self._rank_request(uids, items, exclude)
-        if int(uid.numel()) == 0:
-            return torch.empty(0, dtype=torch.int32, device=self.device), torch.empty(0, dtype=torch.float32, device=self.device)
-        table = self._representations(1, torch.arange(self.N, dtype=torch.int32, device=self.device))
-        return self._rows_rank_items(table, None, self.W, _lib.DRX_REC_CLIP, uid, target, excl,
-                                     lambda lo, u: self._rows_per_distinct(u, lambda d: self._representations(0, d)), chunk_rows)
-
-    def pair_scores(self, uids, items, chunk_pairs=None):
-        """float32 [P] device tensor: max(1e-6, cosine) of every (uids[p], items[p]) — WITHOUT a bound prediction scale —, the values
-        rank_items reports; -inf for an item outside the catalogue.  The item tower runs ONCE over the DISTINCT items of the call (never
-        over the catalogue): their representations are the table, a pair's row its item's position among them; the user tower once
-        per distinct user of a chunk."""
-        uid, item = self._pair_request(uids, items)
-        if int(uid.numel()) == 0:
-            return torch.empty(0, dtype=torch.float32, device=self.device)
-        inside = (item >= 0) & (item < self.N)
-        distinct, t_row = torch.unique(torch.where(inside, item, torch.full_like(item, -1)), return_inverse=True)   # ascending: -1 first
-        outside = int(distinct[0].item() < 0)
-        distinct, t_row = distinct[outside:], (t_row - outside).to(torch.int32).contiguous()                        # (-1: no row)
-        if int(distinct.numel()) == 0:
-            return torch.full((int(uid.numel()),), float('-inf'), dtype=torch.float32, device=self.device)
-        table = self._representations(1, distinct.to(torch.int32).contiguous())
-        return self._rows_pair_scores(table, None, self.W, _lib.DRX_REC_CLIP, uid, t_row, lambda d: self._representations(0, d), chunk_pairs)
+    # what the four calls of RowsRecommender score against: max(1e-6, cosine) of the towers' outputs — WITHOUT a bound prediction
+    # scale.  The item tower is the table: computed when a call asks (nothing is cached across calls: the parameters may have moved),
+    # once per call — over the catalogue, in pair_scores over the request's distinct items only; the user tower once per distinct user
+    # of a chunk.  Outside the fused domain (n > 128): DrxError — DMF._recommend_batch asks recommend_is_fused first.
+    EPILOGUE = _lib.DRX_REC_CLIP
+    TABLE_IS_COMPUTED = True
 
     def rank_ld(self):
         return self.W
 
-    def rank_lists(self, uids, indptr, items, exclude=None, chunk_rows=None):
-        """rank_items for rows that own several items: row r = user uids[r] with the ASCENDING items[indptr[r]:indptr[r + 1]] (CSR
-        offsets [R + 1]).  (rank int32 [P], score float32 [P]) device tensors parallel to `items`, bit for bit what rank_items gives
-        for the pairs, at one catalogue walk per rank_lists_group(W) items of a row.  Towers as in rank_items."""
-        uid, ip, d_ip, targets, excl = self._rank_lists_request(uids, indptr, items, exclude)
-        if int(targets.numel()) == 0:
-            return torch.empty(0, dtype=torch.int32, device=self.device), torch.empty(0, dtype=torch.float32, device=self.device)
-        table = self._representations(1, torch.arange(self.N, dtype=torch.int32, device=self.device))
-        return self._rows_rank_lists(table, None, self.W, _lib.DRX_REC_CLIP, uid, (ip, d_ip), targets, excl,
-                                     lambda lo, u: self._rows_per_distinct(u, lambda d: self._representations(0, d)), chunk_rows)
+    def _score_table(self, items=None):
+        return self._representations(1, torch.arange(self.N, dtype=torch.int32, device=self.device) if items is None else items), None
+
+    def _query_rows(self, uid):
+        return self._representations(0, uid)

@@ -8,7 +8,7 @@ import torch
 
 from . import _lib
 from ._lib import check, lib, ptr, stream_ptr
-from .engine import RowsRecommender, pack_mask_bits
+from .engine_rows import RowsRecommender, pack_mask_bits
 
 
 class KnnEngine(RowsRecommender):
@@ -129,13 +129,6 @@ class KnnEngine(RowsRecommender):
     def _fallback(self, use_averages):
         return self.user_mean if use_averages and self.kind == 'item' else None
 
-    def _fused_scratch(self, need):
-        sc = getattr(self, '_fused_sc', None)
-        if need and (sc is None or sc.numel() < need):
-            self._fused_sc = None
-            sc = self._fused_sc = torch.empty(need, dtype=torch.uint8, device=self.device)
-        return sc if need else None
-
     def recommend(self, uids, n, aggregation, use_averages=False, exclude=None, chunk_bytes=None):
         """(idx int32 [R, n], val float32 [R, n]) on the device: per user the n <= FUSED_MAX_N best items the model has a prediction
         for, drx_topk's order, -1 / -inf behind the last; exclude: without the user's row of set_exclusions().  One launch while a
@@ -147,12 +140,12 @@ class KnnEngine(RowsRecommender):
             raise _lib.DrxError(f'drx_knn_recommend: n = {n} lies outside the fused domain 1..{self.FUSED_MAX_N}')
         per = self._fused_chunk(int(L.drx_knn_recommend_scratch_bytes(self.type, 1, self.n_items, n)), R, chunk_bytes)
         fb = self._fallback(use_averages)
-        for lo in range(0, R, per):
-            r = min(per, R - lo)
+        for lo, hi in self._chunks(R, per):
+            r = hi - lo
             need = int(L.drx_knn_recommend_scratch_bytes(self.type, r, self.n_items, n))
-            sc = self._fused_scratch(need)
-            check(L.drx_knn_recommend(*self._model_args(aggregation), ptr(uid[lo:lo + r]), r, n, ptr(fb), ptr(excl[0]) if excl else None,
-                                      ptr(excl[1]) if excl else None, ptr(out_idx[lo:lo + r]), ptr(out_val[lo:lo + r]), ptr(sc), need,
+            sc = self._rows_scratch(need)
+            check(L.drx_knn_recommend(*self._model_args(aggregation), ptr(uid[lo:lo + r]), r, n, ptr(fb), *self._excl_ptrs(excl),
+                                      ptr(out_idx[lo:lo + r]), ptr(out_val[lo:lo + r]), ptr(sc), need,
                                       stream_ptr(self.device)), 'drx_knn_recommend')
         return out_idx, out_val
 
@@ -168,18 +161,17 @@ class KnnEngine(RowsRecommender):
         for a target outside the catalogue or without a prediction.  A target's own exclusion is ignored."""
         uid, ip, d_ip, tg, excl = self._rank_lists_request(uids, indptr, targets, exclude)
         R, P = int(uid.numel()), int(tg.numel())
-        out_rank = torch.empty(P, dtype=torch.int32, device=self.device)
-        out_score = torch.empty(P, dtype=torch.float32, device=self.device)
+        out_rank, out_score = self._outputs(P)
         if R == 0 or P == 0:
             return out_rank, out_score
         L = lib()
         per = self._fused_chunk(int(L.drx_knn_rank_lists_scratch_bytes(self.type, 1, P, self.n_items)), R, chunk_bytes)
         fb = self._fallback(use_averages)
-        for lo in range(0, R, per):
-            r = min(per, R - lo)
+        for lo, hi in self._chunks(R, per):
+            r = hi - lo
             need = int(L.drx_knn_rank_lists_scratch_bytes(self.type, r, P, self.n_items))
-            sc = self._fused_scratch(need)
+            sc = self._rows_scratch(need)
             check(L.drx_knn_rank_lists(*self._model_args(aggregation), ptr(uid[lo:lo + r]), r, ptr(d_ip[lo:]), ptr(tg), P, ptr(fb),
-                                       ptr(excl[0]) if excl else None, ptr(excl[1]) if excl else None, ptr(out_rank), ptr(out_score),
+                                       *self._excl_ptrs(excl), ptr(out_rank), ptr(out_score),
                                        ptr(sc), need, stream_ptr(self.device)), 'drx_knn_rank_lists')
         return out_rank, out_score

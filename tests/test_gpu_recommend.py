@@ -189,7 +189,7 @@ def test_long_catalogue_and_scratch_is_not_a_score_matrix():
     assert int(_lib.lib().drx_cdae_recommend_scratch_bytes(R, 2_000_000_000, 128, n)) < R * N // 4     # ... and does not grow with n_items
     eng = _engine(p, indptr, indices, (indptr, indices))
     idx, val = eng.recommend(uids, n)
-    assert eng._rec_scratch.numel() < R * N // 4
+    assert eng._rows_sc.numel() < R * N // 4
     s64 = _oracle_scores(p, indptr, indices, uids)
     _check(idx.cpu().numpy(), val.cpu().numpy(), s64, _rows(indptr, indices, uids), n, min_separated=0.80)
 

@@ -349,7 +349,7 @@ def test_long_catalogue_and_scratch_is_not_a_score_matrix():
     assert int(_lib.lib().drx_rows_recommend_scratch_bytes(R, 2_000_000_000, 2 * d, n)) < R * N // 4
     prob = _caser_problem(U=U, N=N, R=R, L=L, d=d, seed=11)
     idx, val = prob.rec(n)
-    assert prob.eng._rec_scratch.numel() < R * N // 4
+    assert prob.eng._rows_sc.numel() < R * N // 4
     prob.check(idx, val, n, min_separated=0.80)
     _CACHE.clear()
 

@@ -38,8 +38,8 @@ def test_the_engines_share_one_launcher():
     from drecpy_amd.engine_caser import CaserEngine
     from drecpy_amd.engine_dmf import DmfEngine
     for cls in (CdaeEngine, DmfEngine, CaserEngine):
-        assert cls._rows_pair_scores is RowsRecommender._rows_pair_scores
-        assert 'pair_scores' in vars(cls)
+        assert cls.pair_scores is RowsRecommender.pair_scores
+        assert 'pair_scores' in vars(RowsRecommender) and 'pair_scores' not in vars(cls)
 
 
 def test_the_evaluation_package_exports_the_process_and_its_metrics():

@@ -30,5 +30,5 @@ def test_the_engines_share_one_launcher():
     from drecpy_amd.engine_caser import CaserEngine
     from drecpy_amd.engine_dmf import DmfEngine
     for cls in (CdaeEngine, DmfEngine, CaserEngine):
-        assert cls._rows_rank_items is RowsRecommender._rows_rank_items and cls.rank_is_fused is RowsRecommender.rank_is_fused
-        assert 'rank_items' in vars(cls)
+        assert cls.rank_items is RowsRecommender.rank_items and cls.rank_is_fused is RowsRecommender.rank_is_fused
+        assert 'rank_items' in vars(RowsRecommender) and 'rank_items' not in vars(cls)

@@ -1,5 +1,5 @@
 """The C ABI of the list form of the catalogue-rank entry point: include/drx.h declares drx_rows_rank_lists, its scratch size and its
-group size, drecpy_amd/_lib.py binds them with matching argument counts; the engines share one launcher and each has rank_lists.
+group size, drecpy_amd/_lib.py binds them with matching argument counts; the engines share one rank_lists.
 No GPU."""
 import os
 import re
@@ -32,8 +32,8 @@ def test_the_engines_share_one_launcher_and_each_has_rank_lists():
     from drecpy_amd.engine_dmf import DmfEngine
     assert RowsRecommender.RANK_LISTS_MIN_MEAN >= 1.0
     for cls in (CdaeEngine, DmfEngine, CaserEngine):
-        assert cls._rows_rank_lists is RowsRecommender._rows_rank_lists and cls.rank_lists_group is RowsRecommender.rank_lists_group
-        assert 'rank_lists' in vars(cls) and 'rank_items' in vars(cls)
+        assert cls.rank_lists is RowsRecommender.rank_lists and cls.rank_lists_group is RowsRecommender.rank_lists_group
+        assert 'rank_lists' in vars(RowsRecommender) and 'rank_lists' not in vars(cls) and 'rank_ld' in vars(cls)
         assert cls.RANK_LISTS_MIN_MEAN == RowsRecommender.RANK_LISTS_MIN_MEAN
 
 

@@ -32,20 +32,45 @@ def test_header_and_bindings_agree():
 
 
 def test_the_engines_share_one_launcher():
-    """the chunked launch and the exclusion upload live in one place (no GPU needed to see it)"""
+    """the four calls, the chunked launch and the exclusion upload live in one place (no GPU needed to see it)"""
     from drecpy_amd.engine import CdaeEngine, RowsRecommender
     from drecpy_amd.engine_caser import CaserEngine
     from drecpy_amd.engine_dmf import DmfEngine
+    from drecpy_amd.engine_knn import KnnEngine
+    assert RowsRecommender.__module__ == 'drecpy_amd.engine_rows'
+    calls = ('recommend', 'rank_items', 'rank_lists', 'pair_scores')
     for cls in (CdaeEngine, DmfEngine, CaserEngine):
-        assert issubclass(cls, RowsRecommender) and cls._rows_recommend is RowsRecommender._rows_recommend
-        assert cls.set_exclusions is RowsRecommender.set_exclusions and 'recommend' in vars(cls)
+        assert issubclass(cls, RowsRecommender)
+        for name in calls:
+            assert getattr(cls, name) is getattr(RowsRecommender, name) and name in vars(RowsRecommender), (cls, name)
+            assert name not in vars(cls), (cls, name)
+        assert cls.set_exclusions is RowsRecommender.set_exclusions
         # ... and so do the score-matrix route's selection and the upload of host ids
         for name in ('topk', 'masked_topk', '_dev_i32'):
             assert getattr(cls, name) is getattr(RowsRecommender, name) and name in vars(RowsRecommender), (cls, name)
+        # what an engine declares instead: its table, its query rows, the rows' width and the epilogue
+        for name in ('_score_table', '_query_rows', 'rank_ld', 'EPILOGUE'):
+            assert name in vars(cls), (cls, name)
+    # KnnEngine scores with kernels of its own, from the shared scratch keeper and request helpers
+    assert issubclass(KnnEngine, RowsRecommender) and KnnEngine._rows_scratch is RowsRecommender._rows_scratch
+    assert '_fused_scratch' not in vars(KnnEngine) and 'recommend' in vars(KnnEngine)
+    for name in ('_recommend_request', '_rank_lists_request', '_exclusions', '_chunks'):
+        assert getattr(KnnEngine, name) is getattr(RowsRecommender, name), name
     # no engine or model borrows them from the CDAE engine any more
-    from drecpy_amd import engine_dmf
+    from drecpy_amd import engine_dense, engine_dmf, engine_knn
     from drecpy_amd.Recommender import caser
     assert 'CdaeEngine' not in vars(engine_dmf) and 'CdaeEngine' not in vars(caser)
+    assert engine_dense.RowsRecommender is engine_knn.RowsRecommender is RowsRecommender
+
+
+def test_an_engine_without_a_score_table_says_so():
+    from drecpy_amd.engine import RowsRecommender
+
+    class Bare(RowsRecommender):
+        pass
+    for call in (lambda e: e._score_table(), lambda e: e.rank_ld(), lambda e: e._query_rows(None)):
+        with pytest.raises(NotImplementedError, match='Bare'):
+            call(Bare())
 
 
 @pytest.mark.parametrize('n_items', [1, 7, 3706, 1_000_000])
