@@ -173,6 +173,11 @@ SIGNATURES = {
                                         C.c_void_p, C.c_void_p, C.POINTER(C.c_int32), C.c_void_p]),
     'drx_debug_prep_result': (C.c_int, [C.POINTER(CdaeParams), C.c_int32, C.c_int32, C.c_int32, C.c_void_p, C.c_size_t, C.c_void_p,
                                         C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
+    'drx_debug_cdae_reduce': (C.c_int, [C.POINTER(CdaeParams), C.POINTER(Optim), C.POINTER(History), C.POINTER(Batch), C.POINTER(HotHead),
+                                        C.c_void_p, C.c_size_t, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int32, C.c_void_p, C.c_size_t,
+                                        C.c_void_p]),
+    'drx_debug_span_plan': (C.c_int, [C.POINTER(CdaeParams), C.c_int32, C.c_int32, C.c_int32, C.c_void_p, C.c_size_t, C.c_void_p,
+                                      C.c_void_p, C.c_void_p, C.c_void_p]),
     'drx_cdae_step_sparse_hot': (C.c_int, [C.POINTER(CdaeParams), C.POINTER(Optim), C.POINTER(History), C.POINTER(Batch),
                                            C.POINTER(HotHead), C.c_int32, C.c_void_p, C.c_size_t, C.c_void_p, C.c_size_t,
                                            C.c_void_p, C.POINTER(C.c_void_p), C.c_void_p]),

@@ -850,14 +850,18 @@ size_t drx_cdae_scratch_bytes(const DrxCdaeParams *p, int32_t B, int32_t n_touch
   return align_up(c.off, 256) + 256;
 }
 
+// (drx_debug_cdae_reduce: the caller's gradient rows stand in for the forward kernel's; form 1: the planned form where reduce_form()
+// answers Streamed)
+struct GivenGradients { const float *dz1, *g2, *dz2; int32_t form; };
+
 static int step_sparse_impl(const DrxCdaeParams *p, const DrxOptim *opt, const DrxHistory *hist, const DrxBatch *bt,
                             int32_t loss_kind, const void *prepared, size_t prepared_bytes, void *scratch, size_t scratch_bytes,
                             float *loss_out, void *const *events, void *stream, const float *ks_h = nullptr,
-                            const float *ks_dot = nullptr, const DrxHotHead *hot = nullptr) {
+                            const float *ks_dot = nullptr, const DrxHotHead *hot = nullptr, const GivenGradients *given = nullptr) {
   int rc = check_params(p);
   if (rc) return rc;
   rc = check_batch(hist, bt);
-  if (rc || !opt || !scratch || !bt->iid || !bt->y || !bt->keep_off) return DRX_EINVAL;
+  if (rc || !opt || !scratch || !bt->iid || (!bt->y && !given) || !bt->keep_off) return DRX_EINVAL;
   if (opt->kind != DRX_OPT_ADAM && opt->kind != DRX_OPT_ADAGRAD && opt->kind != DRX_OPT_ROWWISE_ADAGRAD) return DRX_EINVAL;
   for (int i = 0; i < 5; ++i)
     if (!opt->s1[i] || (opt->kind == DRX_OPT_ADAM && !opt->s2[i])) return DRX_EINVAL;
@@ -899,19 +903,31 @@ static int step_sparse_impl(const DrxCdaeParams *p, const DrxOptim *opt, const D
   S.worder = share ? R.worder : nullptr;
   S.n_items = share ? R.n_du : nullptr;
   // which variant of each launch (drx_prep.hpp)
-  const ReduceForm form = reduce_form(opt->kind, bt->B, S.T, *p);
+  ReduceForm form = reduce_form(opt->kind, bt->B, S.T, *p);
   const ForwardForm fwd = forward_form(ks_h != nullptr, share, bt->B, bt->n_touch_slots);
   if (H > 0 && !hot_head_fits(form, p->ld, share, ks_h != nullptr)) return DRX_EINVAL;
+  if (given) {
+    if (share || (given->form == 1 && (H > 0 || form == ReduceForm::PlannedLong))) return DRX_EINVAL;
+    if (given->form == 1) form = ReduceForm::PlannedShort;
+  }
   const HotArgs HA{S.dz1, R.hmask, HB.part, HB.any, hot ? hot->item : nullptr, scale, bt->B, H, R.Bw, hot_slices(bt->B), 0, HB.bpart,
                    loss_out ? S.lossb : nullptr};
   // (with a head the hidden bias's partials are the slices' column sums its partial waves leave)
   const BiasArgs BA = H > 0 ? BiasArgs{S.dz1, HB.bpart, S.lossb, loss_out, bt->B, hot_slices(bt->B), kHotSlice}
                             : BiasArgs{S.dz1, S.bpart, S.lossb, loss_out, bt->B, n_bpart, rows_per_block};
   DRX_HIP(phase_event(events, 0, st));
-  (void)dispatch_geom(p->ld, [&](auto g) -> int {
-    launch_forward<decltype(g)::G, decltype(g)::J>(fwd, *p, *opt, *hist, *bt, scale, qthr, loss_kind, S, ks_h, ks_dot, st);
-    return DRX_OK;                                                   // (launch errors: DRX_LAUNCH_CHECK below)
-  });
+  if (given) {
+    const size_t row_bytes = (size_t)bt->B * p->ld * sizeof(float);
+    DRX_HIP(hipMemcpyAsync(S.dz1, given->dz1, row_bytes, hipMemcpyDeviceToDevice, st));
+    DRX_HIP(hipMemcpyAsync(S.g2, given->g2, row_bytes, hipMemcpyDeviceToDevice, st));
+    DRX_HIP(hipMemcpyAsync(S.dz2, given->dz2, (size_t)bt->B * sizeof(float), hipMemcpyDeviceToDevice, st));
+    DRX_HIP(hipMemsetAsync(S.lossb, 0, (size_t)bt->B * sizeof(float), st));
+  } else {
+    (void)dispatch_geom(p->ld, [&](auto g) -> int {
+      launch_forward<decltype(g)::G, decltype(g)::J>(fwd, *p, *opt, *hist, *bt, scale, qthr, loss_kind, S, ks_h, ks_dot, st);
+      return DRX_OK;                                                   // (launch errors: DRX_LAUNCH_CHECK below)
+    });
+  }
   DRX_HIP(phase_event(events, 1, st));
   if (!prepared) {
     rc = prepare_impl(p, hist, bt, R, st, false, TouchPresence{nullptr, WireGeo{1, 0, 1}}, hot ? hot->slot : nullptr,
@@ -1126,6 +1142,32 @@ int drx_debug_prep_result(const DrxCdaeParams *p, int32_t B, int32_t n_touch_slo
   DRX_HIP(hipMemcpyAsync(solo_v_out, R.solo_v, (size_t)B, hipMemcpyDeviceToDevice, st));
   DRX_HIP(hipMemcpyAsync(solo_o_out, R.solo_o, (size_t)B, hipMemcpyDeviceToDevice, st));
   DRX_HIP(hipMemcpyAsync(order_out, R.order, (size_t)B * sizeof(int32_t), hipMemcpyDeviceToDevice, st));
+  return DRX_OK;
+}
+
+// (include/drx.h: the step's reduction and span launches alone, on gradient rows the caller gives)
+int drx_debug_cdae_reduce(const DrxCdaeParams *p, const DrxOptim *opt, const DrxHistory *hist, const DrxBatch *bt, const DrxHotHead *hot,
+                          const void *prepared, size_t prepared_bytes, const float *dz1_in, const float *g2_in, const float *dz2_in,
+                          int32_t form, void *scratch, size_t scratch_bytes, void *stream) {
+  if (!dz1_in || !g2_in || !dz2_in || (form != 0 && form != 1) || (hot && !hot_ok(p, hot))) return DRX_EINVAL;
+  const GivenGradients given{dz1_in, g2_in, dz2_in, form};
+  return step_sparse_impl(p, opt, hist, bt, DRX_LOSS_BCE, prepared, prepared_bytes, scratch, scratch_bytes, nullptr, nullptr, stream,
+                          nullptr, nullptr, hot && hot->H > 0 ? hot : nullptr, &given);
+}
+
+// (include/drx.h: copies of the span plan a finished preparation left — nothing is launched)
+int drx_debug_span_plan(const DrxCdaeParams *p, int32_t B, int32_t n_touch_slots, int32_t H, const void *prepared, size_t prepared_bytes,
+                        uint8_t *ext_out, uint32_t *desc_out, uint32_t *cnt_out, void *stream) {
+  int rc = check_params(p);
+  if (rc) return rc;
+  if (B < 1 || n_touch_slots < 0 || hot_rows(p, H) < 0 || !prepared || !ext_out || !desc_out || !cnt_out) return DRX_EINVAL;
+  Carver cp(const_cast<void *>(prepared), prepared_bytes);
+  const PrepBufs R = prep_layout(cp, *p, B, n_touch_slots, H);
+  if (!cp.ok()) return DRX_ESCRATCH;
+  hipStream_t st = (hipStream_t)stream;
+  DRX_HIP(hipMemcpyAsync(ext_out, R.plan.ext, (size_t)R.n_chunks, hipMemcpyDeviceToDevice, st));
+  DRX_HIP(hipMemcpyAsync(desc_out, R.plan.desc, (size_t)R.n_chunks * sizeof(uint2), hipMemcpyDeviceToDevice, st));
+  DRX_HIP(hipMemcpyAsync(cnt_out, R.plan.cnt, 2 * sizeof(uint32_t), hipMemcpyDeviceToDevice, st));
   return DRX_OK;
 }
 

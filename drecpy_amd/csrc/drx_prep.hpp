@@ -439,9 +439,12 @@ struct BiasArgs {
 
 template <int G, int J, int NT>
 __device__ __forceinline__ void bias_partial_body(int ld, const BiasArgs &A, int block_id, float *lds /* [NT/G, ld] */, float *red) {
-  constexpr int R = NT / G;
+  // the groups that sum: those of a planned launch's workgroup, whatever launch this rides in — which rows a group adds up fixes the
+  // order of a partial's additions, and the hidden bias must not depend on the form of the reduction (the streamed launch has one wave
+  // per chunk: 256 / 512 threads at rows of 128 / 64 floats; its surplus groups only join the barriers)
+  constexpr int R = (NT < kSegBlock ? NT : kSegBlock) / G;
   const int lane = threadIdx.x % G, r = threadIdx.x / G;
-  const int b0 = block_id * A.rows_per_block, b1 = min(A.B, b0 + A.rows_per_block);
+  const int b0 = block_id * A.rows_per_block, b1 = r < R ? min(A.B, b0 + A.rows_per_block) : 0;
   float4 acc[J];
 #pragma unroll
   for (int j = 0; j < J; ++j) acc[j] = f4_zero();
@@ -459,7 +462,7 @@ __device__ __forceinline__ void bias_partial_body(int ld, const BiasArgs &A, int
 #pragma unroll
       for (int j = 0; j < J; ++j) f4_add(acc[j], v[q][j]);
   }
-  store_row<G, J>(lds, (size_t)r, ld, lane, acc);
+  if (r < R) store_row<G, J>(lds, (size_t)r, ld, lane, acc);
   __syncthreads();
   if (r == 0) {
     float4 t[J];
@@ -475,6 +478,7 @@ __device__ __forceinline__ void bias_partial_body(int ld, const BiasArgs &A, int
     store_row<G, J>(A.part, (size_t)block_id, ld, lane, t);
   }
   if (A.loss_out) {                                // this block's slice of the per-sample losses
+    const int b1 = min(A.B, b0 + A.rows_per_block);
     float a = 0.f;
     for (int b = b0 + (int)threadIdx.x; b < b1; b += NT) a += A.lossb[b];
     const float tl = block_sum(a, red);

@@ -286,6 +286,30 @@ int drx_debug_prep_result(const DrxCdaeParams *p, int32_t B, int32_t n_touch_slo
                           uint32_t *keys_s_out, uint32_t *vals_s_out, uint8_t *solo_v_out, uint8_t *solo_o_out, int32_t *order_out,
                           void *stream);
 
+/* DEBUGGING ENTRY (tests): the sampled step's reduction and span launches ALONE, on gradient rows the caller gives.  Everything is the
+ * step's (drx_cdae_step_sparse / _prepared / _hot: the same scratch layout, the same launches in the form the step would choose, the list
+ * built inline where prepared == NULL) except its forward / backward launch: instead, dz1_in [B, ld], g2_in [B, ld] and dz2_in [B] (device
+ * arrays) are copied into the step's gradient buffers and the per-sample losses are zeroed.  So W row n moves by the optimizer's rule on
+ * g = (1/(1-q)) * sum of dz1_in[b] over the list's touches (n, b), W2T row i on sum g2_in[b] (b2[i] on sum dz2_in[b]) over the samples of
+ * item i, V row u on sum dz1_in[b] over the samples of user u, b on the column sums of dz1_in — each + (reg_rate / B) * the row's value.
+ * A V / W2T row whose sole touch a preparation blanked is the forward kernel's to update: here nobody updates it.
+ * hot: NULL, or the head the list was prepared with (inline lists: the head to build).  form: 0 — as the step; 1 — the planned kernel
+ * where the step would run the streamed one (DRX_EINVAL with a head, or on a list of long segments).  bt->y is not read.
+ * scratch: drx_cdae_scratch_bytes(_hot). */
+int drx_debug_cdae_reduce(const DrxCdaeParams *p, const DrxOptim *opt, const DrxHistory *hist, const DrxBatch *bt, const DrxHotHead *hot,
+                          const void *prepared, size_t prepared_bytes, const float *dz1_in, const float *g2_in, const float *dz2_in,
+                          int32_t form, void *scratch, size_t scratch_bytes, void *stream);
+
+/* DEBUGGING ENTRY (tests): device copies of the span plan a finished preparation left in `prepared` (csrc/drx_segreduce.hpp SpanPlan;
+ * the list's chunks are of 32 touches, of 64 where n_touch_slots + 2 B > 8 (2 n_items + n_users)); nothing is launched:
+ *   ext_out  [n_chunks] bytes   chunk g also takes the first ext[g] touches of chunk g + 1
+ *   desc_out [2 n_chunks] words descriptor i = (first chunk g0, chunks wholly inside | has_end << 31): the short spans from the front,
+ *                               the long ones from the back, each group in no particular order
+ *   cnt_out  [2]                short spans, long spans
+ * prepared: the buffer the preparation wrote, same p, B, n_touch_slots and H. */
+int drx_debug_span_plan(const DrxCdaeParams *p, int32_t B, int32_t n_touch_slots, int32_t H, const void *prepared, size_t prepared_bytes,
+                        uint8_t *ext_out, uint32_t *desc_out, uint32_t *cnt_out, void *stream);
+
 /* off[0] = 0, off[b + 1] = sum_{b' <= b} (indptr[ids[b'] + 1] - indptr[ids[b']]) for device ids: the keep_off of a batch of users (DrxBatch)
  * or the touch offsets of a batch of CSR rows.  scratch: drx_point_sample_scratch_bytes(B). */
 int drx_batch_offsets(const int64_t *indptr, const int32_t *ids, int32_t B, int32_t *off, void *scratch, size_t scratch_bytes, void *stream);
