@@ -142,8 +142,15 @@ __device__ __forceinline__ void sampled_finish(const DrxCdaeParams &P, const Drx
                                                float scale, uint32_t qthr, int loss_kind, const SparseBufs &S, int b, int lane,
                                                const float4 (&acc)[J]) {
   float4 h[J], w2[J];
+#ifdef DRX_STAMPS
+  if (acc[0].x == acc[0].x) DRX_STAMP(S.stamps, b, 5, lane);          // (uses acc: behind the gather)
+#endif
   const float d = sampled_hidden<G, J>(P, bt, scale, b, lane, acc, h, w2);
+#ifdef DRX_STAMPS
+  if (d == d) DRX_STAMP(S.stamps, b, 6, lane);                        // (uses d: V[u], b and W2T[i] have landed)
+#endif
   sampled_rest<G, J, KIND>(P, opt, H, bt, scale, qthr, loss_kind, S, b, lane, d, h, w2);
+  DRX_STAMP(S.stamps, b, 7, lane);                                    // (behind the stores of the in-place updates)
 }
 
 // ---- column-sharded ("K-sharded") step: the two halves as kernels of their own, the all-reduce of dot[] between them ----------
@@ -209,22 +216,20 @@ __global__ __launch_bounds__(kBlock) void k_sampled_fwd_bwd(DrxCdaeParams P, Drx
                                                             uint32_t qthr, int loss_kind, SparseBufs S) {
   const int lane = threadIdx.x % G;
   const int slot = blockIdx.x * (kBlock / G) + threadIdx.x / G;
+#ifdef DRX_STAMPS
+  const unsigned long long t_in = wall_clock64();
+#endif
   if (slot >= bt.B) return;
   const int32_t *const ord = S.order;
   const int b = ord ? ord[slot] : slot;            // longest histories first, similar lengths side by side (k_degree_counts)
   float4 acc[J];
   DenseAux none{};
-  gather_bag<G, J, 0>(P, H, bt, qthr, b, lane, acc, none, nullptr, nullptr, 0);
+#ifdef DRX_STAMPS
+  if (lane == 0 && S.stamps && (unsigned)b < 110000u) S.stamps[(size_t)b * 16] = t_in;          // stamp 0: the group's start
+  if (bt.uid[b] >= 0) DRX_STAMP(S.stamps, b, 1, lane);                                           // (uses uid: it has landed)
+#endif
+  gather_bag<G, J, 0>(P, H, bt, qthr, b, lane, acc, none, nullptr, nullptr, 0, 0, 1, S.stamps);
   sampled_finish<G, J, KIND>(P, opt, H, bt, scale, qthr, loss_kind, S, b, lane, acc);
-}
-
-// the lanes of this thread's row group for which f holds (bit i: lane i of the group)
-template <int G>
-__device__ __forceinline__ unsigned long long group_ballot(bool f) {
-  const unsigned long long m = __ballot(f);
-  if (G >= 64) return m;
-  const int sh = ((int)(threadIdx.x & 63) / G) * G;
-  return (m >> sh) & ((1ull << (G & 63)) - 1ull);
 }
 
 // DRX_BATCH_SHARE_USERS: one WORKGROUP per work item — up to kShareTriples (16) triples of ONE user (drx_prep.hpp k_tp_item_*).

@@ -6,6 +6,11 @@
 #ifndef DRX_GATHER_ROWS
 #define DRX_GATHER_ROWS 8
 #endif
+// 1: a round's rows in flight are formed from the history's KEPT entries only (gather_bag, groups of up to 32 lanes); 0 (a variant
+// build): from consecutive entries, a dropped one leaving its place empty
+#ifndef DRX_GATHER_PACKED
+#define DRX_GATHER_PACKED 1
+#endif
 
 namespace drx {
 
@@ -27,6 +32,15 @@ __device__ __forceinline__ void store_row(float *base, size_t row, int ld, int l
     int c = lane + j * G;
     if (4 * c < ld) r[c] = v[j];
   }
+}
+
+// the lanes of this thread's row group for which f holds (bit i: lane i of the group)
+template <int G>
+__device__ __forceinline__ unsigned long long group_ballot(bool f) {
+  const unsigned long long m = __ballot(f);
+  if (G >= 64) return m;
+  const int sh = ((int)(threadIdx.x & 63) / G) * G;
+  return (m >> sh) & ((1ull << (G & 63)) - 1ull);
 }
 
 __device__ __forceinline__ float colmask(int col, int k, float v) { return col < k ? v : 0.0f; }
@@ -107,32 +121,65 @@ __device__ __forceinline__ void gather_bag(const DrxCdaeParams &P, const DrxHist
         }
       }
     }
-    const int n_here = (int)((e - c) < (int64_t)CH ? (e - c) : (int64_t)CH);
     constexpr int NF = J == 1 ? DRX_GATHER_ROWS : 4;       // rows in flight per group
 #ifdef DRX_STAMPS
     if (first_rows && idx[0] >= -1) DRX_STAMP(stamps, b, 3, lane);      // (uses idx: the stamp waits for the indices)
 #endif
-    for (int t = 0; t < n_here; t += NF) {
-      float4 r[NF][J];
+    // the rows in flight of a round are the next NF KEPT entries, in history order: a dropped entry takes no place among them (bit tt of
+    // `left`: entry tt of this fetch is kept and not yet loaded; the same value in every lane of the group).  The kept rows enter acc in
+    // the order they always did, and the all-zero rows that no longer stand between them changed no sum.  (Groups of 64 lanes keep
+    // consecutive entries: a 64-bit mask costs their kernels the eighth wave per SIMD.)
+    if constexpr (DRX_GATHER_PACKED != 0 && CH <= 32) {
+      uint32_t left = 0;
 #pragma unroll
-      for (int q = 0; q < NF; ++q) {
-        const int tt = t + q;
-        int si = idx[0], sk = kf[0];
+      for (int rr = 0; rr < IPL; ++rr) left |= (uint32_t)group_ballot<G>(kf[rr] != 0) << (rr * G);
+      while (left) {
+        float4 r[NF][J];
 #pragma unroll
-        for (int rr = 1; rr < IPL; ++rr) { si = (tt / G == rr) ? idx[rr] : si; sk = (tt / G == rr) ? kf[rr] : sk; }
-        const int iq = __shfl(si, tt % G, G);
-        const int kq = (tt < n_here) ? __shfl(sk, tt % G, G) : 0;
+        for (int q = 0; q < NF; ++q) {
+          const bool on = left != 0;
+          const int tt = on ? __builtin_ctz(left) : 0;
+          left &= left - 1;                                   // (0 stays 0)
+          int si = idx[0];
 #pragma unroll
-        for (int jx = 0; jx < J; ++jx) r[q][jx] = f4_zero();
-        if (kq) load_row<G, J>(P.W, (size_t)iq, P.ld, lane, r[q]);
-      }
+          for (int rr = 1; rr < IPL; ++rr) si = (tt / G == rr) ? idx[rr] : si;
+          const int iq = __shfl(si, tt % G, G);
 #pragma unroll
-      for (int q = 0; q < NF; ++q)
+          for (int jx = 0; jx < J; ++jx) r[q][jx] = f4_zero();
+          if (on) load_row<G, J>(P.W, (size_t)iq, P.ld, lane, r[q]);
+        }
 #pragma unroll
-        for (int jx = 0; jx < J; ++jx) f4_add(acc[jx], r[q][jx]);
+        for (int q = 0; q < NF; ++q)
+#pragma unroll
+          for (int jx = 0; jx < J; ++jx) f4_add(acc[jx], r[q][jx]);
 #ifdef DRX_STAMPS
-      if (first_rows && acc[0].x == acc[0].x) { DRX_STAMP(stamps, b, 4, lane); first_rows = false; }      // (uses acc: after the first rows landed)
+        if (first_rows && acc[0].x == acc[0].x) { DRX_STAMP(stamps, b, 4, lane); first_rows = false; }      // (uses acc: after the first rows landed)
 #endif
+      }
+    } else {
+      const int n_here = (int)((e - c) < (int64_t)CH ? (e - c) : (int64_t)CH);
+      for (int t = 0; t < n_here; t += NF) {
+        float4 r[NF][J];
+#pragma unroll
+        for (int q = 0; q < NF; ++q) {
+          const int tt = t + q;
+          int si = idx[0], sk = kf[0];
+#pragma unroll
+          for (int rr = 1; rr < IPL; ++rr) { si = (tt / G == rr) ? idx[rr] : si; sk = (tt / G == rr) ? kf[rr] : sk; }
+          const int iq = __shfl(si, tt % G, G);
+          const int kq = (tt < n_here) ? __shfl(sk, tt % G, G) : 0;
+#pragma unroll
+          for (int jx = 0; jx < J; ++jx) r[q][jx] = f4_zero();
+          if (kq) load_row<G, J>(P.W, (size_t)iq, P.ld, lane, r[q]);
+        }
+#pragma unroll
+        for (int q = 0; q < NF; ++q)
+#pragma unroll
+          for (int jx = 0; jx < J; ++jx) f4_add(acc[jx], r[q][jx]);
+#ifdef DRX_STAMPS
+        if (first_rows && acc[0].x == acc[0].x) { DRX_STAMP(stamps, b, 4, lane); first_rows = false; }      // (uses acc: after the first rows landed)
+#endif
+      }
     }
   }
 }

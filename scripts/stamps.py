@@ -57,8 +57,11 @@ def main():
         res['alive_units_mean'] = float(np.mean(alive)); res['alive_units_max'] = int(np.max(alive))
         out[name] = res
     if os.environ.get('SHAPE', 'synth-10m') == 'synth-10m':
-      report('k_sampled_fwd_bwd_pf (per triple)', st[:B], [0, 1, 2, 3, 4, 5, 6, 7, 8],
-             ['uid/iid -> LDS-DMA issued', 'indptr', 'indices + mask', 'first rows', 'rest of the gather', 'b, b2, y + DMA landed', 'loss, dz1 stored', 'sole-toucher updates'])
+      # stamps 0 .. 7 of a triple (csrc/drx_cdae.hip k_sampled_fwd_bwd, csrc/drx_rows.hpp gather_bag); triples that keep no history
+      # entry carry no stamps 3 / 4 and are left out
+      report('k_sampled_fwd_bwd (per triple)', st[:B], [0, 1, 2, 3, 4, 5, 6, 7],
+             ['order, uid / iid / y, flags', 'row pointers', 'indices + keep flags', 'first rows', 'rest of the gather',
+              'hidden layer (V[u], b, W2T[i] landed)', 'loss, gradient rows, in-place updates'])
     # (the reduction's kernels carry no stamps since r05: the planned kernel's were taken out of the hot loop, the streamed one never had
     # any — its phases were sized with library variants side by side, scripts/ab_headline.sh)
     print(json.dumps(out, indent=1))
