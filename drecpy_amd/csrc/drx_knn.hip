@@ -6,13 +6,14 @@
 //                 neighbours are sought the B operand of v_mfma_f32_32x32x2_f32, so a lane owns ONE row i (column = lane & 31) and 16
 //                 rows j of a tile.  A wave owns 32 rows I and walks the split's J tiles; per tile the columns in steps of 8 (within
 //                 a step 0, 4, 1, 5, 2, 6, 3, 7), one MFMA per sum the metric reads; M = (X != 0) and X^2 are made in registers.
-//                 The epilogue runs in double, rounds to float32 once and makes the key (ordered bits << 32 | j).  Selection as the
+//                 The epilogue runs in double, rounds to float32 once and makes the key (drx_keys.hpp).  Selection as the
 //                 scorer-selector's: a lane's own list in the scratch, cut back to its k best by the whole wave at capacity.
-// k_knn_merge     one workgroup per row: its 2 x splits lists ordered in LDS (bitonic network on <= 16384 keys), the k largest out.
+// k_lists_merge   (drx_keys.hpp, with the lists' plan and layout) one workgroup per row: its 2 x splits lists ordered in LDS, the k
+//                 largest out, -1 / 0.0 behind them.
 // No [R, R] matrix, no atomic read-modify-write; a sum is the same fmaf chain whatever the split: a function of the inputs alone.
 // k_knn_score_item / k_knn_score_user / k_knn_pair_scores   predictions for whole rows of R users / for given pairs.
 #include <hip/hip_runtime.h>
-#include "drx_common.hpp"
+#include "drx_keys.hpp"
 
 #pragma clang fp contract(off)            // the CPU oracle states the epilogue as single operations: none may fuse here
 
@@ -20,25 +21,12 @@ namespace drx {
 namespace {
 
 typedef float f32x16 __attribute__((ext_vector_type(16)));
-typedef unsigned long long u64;
 
-constexpr int kKnnRows = 128;             // rows I of a workgroup: 32 per wave
+constexpr int kKnnRows = kListRows;       // rows I of a workgroup: 32 per wave
 constexpr int kKnnTile = 32;              // rows J of a tile
 constexpr int kKnnMaxK = 128;
-constexpr int kKnnMaxMerge = 16384;       // keys the merge orders in LDS (128 KiB)
 constexpr int kKnnTargetGroups = 256;     // workgroups a launch aims for: one per CU
 constexpr size_t kKnnLdsBytes = 160 * 1024;
-
-// (as drx_recommend.hip) the key 0 is "empty slot": no finite float orders to 0 bits
-__device__ __forceinline__ uint32_t knn_ordered_bits(float f) {
-  if (f == 0.0f) f = 0.0f;
-  const uint32_t u = __float_as_uint(f);
-  return (u & 0x80000000u) ? ~u : (u | 0x80000000u);
-}
-__device__ __forceinline__ float knn_score_of(u64 key) {
-  const uint32_t o = (uint32_t)(key >> 32);
-  return __uint_as_float((o & 0x80000000u) ? (o ^ 0x80000000u) : ~o);
-}
 
 // the entries [lo, hi) of CSR row r, clamped into [0, nnz): whatever the offsets hold, no access leaves the arrays
 __device__ __forceinline__ void knn_row(const int64_t *indptr, int64_t nnz, int r, int64_t &lo, int64_t &hi) {
@@ -272,7 +260,7 @@ __global__ __launch_bounds__(256) void k_knn_tiles(KnnArgs A) {
       const float s = dump[e * 64 + lane];
       if (s > 0.0f) {
         const unsigned j = (unsigned)(j0 + 8 * (e >> 2) + 4 * hh + (e & 3));
-        const u64 key = ((u64)knn_ordered_bits(s) << 32) | j;
+        const u64 key = make_key(s, j);
         if (key > tkey) { mylist[cnt] = key; ++cnt; }
       }
       u64 full = __ballot(cnt >= A.cap);
@@ -292,100 +280,44 @@ __global__ __launch_bounds__(256) void k_knn_tiles(KnnArgs A) {
   if (ivalid) A.counts[(group * kKnnRows + (size_t)(wave * 32 + col)) * 2 + hh] = cnt;
 }
 
-__global__ __launch_bounds__(kBlock) void k_knn_merge(const u64 *__restrict__ lists, const int *__restrict__ counts, int k, int cap, int splits,
-                                                      int npad, int32_t *__restrict__ out_idx, float *__restrict__ out_sim) {
-  extern __shared__ __align__(16) unsigned long long keys[];
-  const size_t r = blockIdx.x;
-  const size_t tile = r / kKnnRows, ul = r % kKnnRows;
-  for (int i = threadIdx.x; i < npad; i += kBlock) {
-    u64 key = 0ull;
-    const int slot = i / k, j = i - slot * k;
-    if (slot < 2 * splits) {
-      const size_t lid = ((tile * splits + (slot >> 1)) * kKnnRows + ul) * 2 + (slot & 1);
-      if (j < min(counts[lid], k)) key = lists[lid * cap + j];
-    }
-    keys[i] = key;
-  }
-  for (int size = 2; size <= npad; size <<= 1) {
-    for (int stride = size >> 1; stride > 0; stride >>= 1) {
-      __syncthreads();
-      for (int t = threadIdx.x; t < (npad >> 1); t += kBlock) {
-        const int a = 2 * t - (t & (stride - 1));
-        const int b = a + stride;
-        const u64 ka = keys[a], kb = keys[b];
-        const bool desc = (a & size) == 0;
-        if (desc ? (ka < kb) : (ka > kb)) { keys[a] = kb; keys[b] = ka; }
-      }
-    }
-  }
-  __syncthreads();
-  for (int j = threadIdx.x; j < k; j += kBlock) {
-    const u64 key = j < npad ? keys[j] : 0ull;
-    if (key == 0ull) { out_idx[r * k + j] = -1; out_sim[r * k + j] = 0.0f; }
-    else { out_idx[r * k + j] = (int32_t)(key & 0xFFFFFFFFull); out_sim[r * k + j] = knn_score_of(key); }
-  }
-}
-
 struct KnnPlan {
-  int tiles, splits, jps, cap, npad, Rp, Cp;
-  size_t lds_merge;
+  int Rp, Cp;                    // X's padded shape
+  ListPlan L;                    // the lists of k keys, split over the tiles of 32 rows J
+  float *X;                      // set by knn_layout()
+  KnnStats S;
 };
 
 bool knn_plan(int R, int C, int k, int force_splits, KnnPlan &P) {
   if (R < 1 || C < 1 || k < 1 || k > kKnnMaxK || force_splits < 0) return false;
   if ((int64_t)R + kKnnRows > 0x7FFFFFFFll || (int64_t)C + 8 > 0x7FFFFFFFll) return false;
-  P.tiles = (R + kKnnRows - 1) / kKnnRows;
-  P.Rp = P.tiles * kKnnRows;
+  const int tiles = (R + kKnnRows - 1) / kKnnRows;
+  P.Rp = tiles * kKnnRows;
   P.Cp = (C + 7) / 8 * 8;
-  const int jtiles = (R + kKnnTile - 1) / kKnnTile;
-  int64_t want = force_splits > 0 ? force_splits : (kKnnTargetGroups + P.tiles - 1) / P.tiles;
-  if (want > kKnnMaxMerge / (2 * k)) want = kKnnMaxMerge / (2 * k);
-  if (want > jtiles) want = jtiles;
-  if (want > 65535) want = 65535;
-  if (want < 1) want = 1;
-  P.jps = (int)((jtiles + want - 1) / want);
-  P.splits = (jtiles + P.jps - 1) / P.jps;
-  P.cap = 2 * k < 32 ? 32 : 2 * k;
-  P.npad = 2;
-  while (P.npad < 2 * P.splits * k) P.npad <<= 1;
-  P.lds_merge = (size_t)P.npad * sizeof(u64);
+  P.L = list_plan(tiles, (R + kKnnTile - 1) / kKnnTile, k, kKnnTargetGroups, force_splits);
   return true;
 }
 
-struct KnnLayout {
-  float *X;
-  KnnStats S;
-  u64 *lists;
-  int *counts;
-};
-KnnLayout knn_layout(Carver &cv, const KnnPlan &P, int R) {
-  KnnLayout L;
-  L.X = cv.take<float>((size_t)P.Rp * P.Cp);
-  L.S.cnt = cv.take<int32_t>((size_t)R);
-  L.S.mean = cv.take<double>((size_t)R);
-  L.S.norm = cv.take<double>((size_t)R);
-  L.S.cnorm = cv.take<double>((size_t)R);
-  const size_t n_lists = (size_t)P.tiles * P.splits * kKnnRows * 2;
-  L.lists = cv.take<u64>(n_lists * P.cap);
-  L.counts = cv.take<int>(n_lists);
-  return L;
+void knn_layout(Carver &cv, KnnPlan &P, int R) {
+  P.X = cv.take<float>((size_t)P.Rp * P.Cp);
+  P.S.cnt = cv.take<int32_t>((size_t)R);
+  P.S.mean = cv.take<double>((size_t)R);
+  P.S.norm = cv.take<double>((size_t)R);
+  P.S.cnorm = cv.take<double>((size_t)R);
+  P.L.carve(cv);
 }
 
 size_t knn_scratch_bytes(int R, int C, int k, int force_splits) {
   KnnPlan P;
   if (!knn_plan(R, C, k, force_splits, P)) return 0;
   Carver cv(nullptr, 0);
-  (void)knn_layout(cv, P, R);
+  knn_layout(cv, P, R);
   return align_up(cv.off, 256) + 256;
 }
 
 template <int M>
 int knn_launch(const KnnArgs &A, const KnnPlan &P, int32_t *out_idx, float *out_sim, hipStream_t st) {
-  hipLaunchKernelGGL(k_knn_tiles<M>, dim3(P.tiles, P.splits), dim3(256), 0, st, A);
-  DRX_HIP(hipFuncSetAttribute((const void *)k_knn_merge, hipFuncAttributeMaxDynamicSharedMemorySize, (int)P.lds_merge));
-  hipLaunchKernelGGL(k_knn_merge, dim3(A.R), dim3(kBlock), P.lds_merge, st, A.lists, A.counts, A.k, A.cap, A.splits, P.npad, out_idx, out_sim);
-  DRX_LAUNCH_CHECK();
-  return DRX_OK;
+  hipLaunchKernelGGL(k_knn_tiles<M>, dim3(P.L.tiles, P.L.splits), dim3(256), 0, st, A);
+  return lists_merge(P.L, A.R, 0.0f, out_idx, out_sim, st);
 }
 
 int knn_run(const int64_t *indptr, const int32_t *indices, const float *values, int64_t nnz, int R, int C, int metric, int k, int m,
@@ -400,15 +332,15 @@ int knn_run(const int64_t *indptr, const int32_t *indices, const float *values, 
   if (!knn_plan(R, C, k, force_splits, P)) return DRX_EINVAL;
   if (!scratch) return DRX_ESCRATCH;
   Carver cv(scratch, scratch_bytes);
-  const KnnLayout L = knn_layout(cv, P, R);
+  knn_layout(cv, P, R);
   if (!cv.ok()) return DRX_ESCRATCH;
   hipStream_t st = (hipStream_t)stream;
-  DRX_HIP(hipMemsetAsync(L.X, 0, (size_t)P.Rp * P.Cp * sizeof(float), st));
-  hipLaunchKernelGGL(k_knn_scatter, dim3((R + 3) / 4), dim3(kBlock), 0, st, indptr, indices, values, nnz, R, C, P.Cp, L.X);
-  hipLaunchKernelGGL(k_knn_stats, dim3((R + kBlock - 1) / kBlock), dim3(kBlock), 0, st, indptr, indices, values, nnz, R, C, L.S);
+  DRX_HIP(hipMemsetAsync(P.X, 0, (size_t)P.Rp * P.Cp * sizeof(float), st));
+  hipLaunchKernelGGL(k_knn_scatter, dim3((R + 3) / 4), dim3(kBlock), 0, st, indptr, indices, values, nnz, R, C, P.Cp, P.X);
+  hipLaunchKernelGGL(k_knn_stats, dim3((R + kBlock - 1) / kBlock), dim3(kBlock), 0, st, indptr, indices, values, nnz, R, C, P.S);
   KnnArgs A;
-  A.X = L.X; A.S = L.S; A.R = R; A.Cp = P.Cp; A.k = k; A.cap = P.cap; A.m = m; A.shrink = shrinkage < 0.0 ? -1.0 : shrinkage;
-  A.md2 = max_diff * max_diff; A.splits = P.splits; A.jps = P.jps; A.lists = L.lists; A.counts = L.counts;
+  A.X = P.X; A.S = P.S; A.R = R; A.Cp = P.Cp; A.k = k; A.cap = P.L.cap; A.m = m; A.shrink = shrinkage < 0.0 ? -1.0 : shrinkage;
+  A.md2 = max_diff * max_diff; A.splits = P.L.splits; A.jps = P.L.per; A.lists = P.L.lists; A.counts = P.L.counts;
   switch (metric) {
     case DRX_KNN_COSINE: return knn_launch<DRX_KNN_COSINE>(A, P, out_idx, out_sim, st);
     case DRX_KNN_ADJUSTED_COSINE: return knn_launch<DRX_KNN_ADJUSTED_COSINE>(A, P, out_idx, out_sim, st);
@@ -630,7 +562,7 @@ __device__ __forceinline__ uint32_t *knn_row_keys(const KnnModel &Mo, int u, con
     knn_item_ratings(Mo, u, row);
     for (int i = threadIdx.x; i < N; i += kBlock) {
       float pred;
-      keys[i] = knn_item_predict(Mo, row, u, i, fallback, pred) ? knn_ordered_bits(pred) : 0u;
+      keys[i] = knn_item_predict(Mo, row, u, i, fallback, pred) ? ordered_bits(pred) : 0u;
     }
     __syncthreads();
     return keys;
@@ -643,7 +575,7 @@ __device__ __forceinline__ uint32_t *knn_row_keys(const KnnModel &Mo, int u, con
       const int i = base + (int)threadIdx.x;
       uint32_t key = 0u;
       float pred;
-      if (i < N && knn_user_predict(acc, i, pred)) key = knn_ordered_bits(pred);
+      if (i < N && knn_user_predict(acc, i, pred)) key = ordered_bits(pred);
       __syncthreads();
       if (i < N) keys[i] = key;
     }
@@ -715,7 +647,7 @@ __global__ __launch_bounds__(kBlock) void k_knn_recommend(KnnModel Mo, KnnFused 
       for (int t = j + tid; t < n; t += kBlock) { oi[t] = -1; ov[t] = -INFINITY; }
       break;
     }
-    if (tid == 0) { oi[j] = (int32_t)(best & 0xFFFFFFFFull); ov[j] = knn_score_of(best); }
+    if (tid == 0) { oi[j] = (int32_t)(best & 0xFFFFFFFFull); ov[j] = key_score(best); }
     if (cand == best) cand = best_below(best);
   }
 }
@@ -763,7 +695,7 @@ __global__ __launch_bounds__(kBlock) void k_knn_rank_lists(KnnModel Mo, KnnFused
       if (lane == j && g + j < thi) {
         const bool has = tk[j] != ~0ull;
         out_rank[g + j] = has ? cnt[j] : -1;
-        out_score[g + j] = has ? knn_score_of(tk[j]) : -INFINITY;
+        out_score[g + j] = has ? key_score(tk[j]) : -INFINITY;
       }
     }
   }
@@ -780,6 +712,15 @@ int knn_fused_args(const KnnModel &Mo, const int32_t *uid, int R, const double *
   F.rows = need ? (unsigned char *)scratch : nullptr;
   F.row_bytes = knn_fused_row_bytes(Mo.type, Mo.n_items);
   lds = need ? 0 : F.row_bytes;
+  return DRX_OK;
+}
+
+// a kernel of one workgroup per request row whose working row may lie in LDS: the attribute, the launch
+template <class... P, class... A>
+int knn_rows_launch(void (*kernel)(P...), int R, size_t lds, hipStream_t st, A... args) {
+  DRX_HIP(hipFuncSetAttribute((const void *)kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)kKnnLdsBytes));
+  hipLaunchKernelGGL(kernel, dim3(R), dim3(kBlock), lds, st, args...);
+  DRX_LAUNCH_CHECK();
   return DRX_OK;
 }
 
@@ -824,16 +765,9 @@ extern "C" int drx_knn_score_rows(int32_t type, int32_t aggregation, const int64
   if (need && (!scratch || scratch_bytes < need)) return DRX_ESCRATCH;
   const size_t lds = need ? 0 : row;
   hipStream_t st = (hipStream_t)stream;
-  if (type == DRX_KNN_ITEM) {
-    DRX_HIP(hipFuncSetAttribute((const void *)drx::k_knn_score_item, hipFuncAttributeMaxDynamicSharedMemorySize, (int)drx::kKnnLdsBytes));
-    hipLaunchKernelGGL(drx::k_knn_score_item, dim3(R), dim3(drx::kBlock), lds, st, Mo, uid, fallback, out, cand_mask,
-                       need ? (float *)scratch : nullptr);
-  } else {
-    DRX_HIP(hipFuncSetAttribute((const void *)drx::k_knn_score_user, hipFuncAttributeMaxDynamicSharedMemorySize, (int)drx::kKnnLdsBytes));
-    hipLaunchKernelGGL(drx::k_knn_score_user, dim3(R), dim3(drx::kBlock), lds, st, Mo, uid, out, cand_mask, need ? (double *)scratch : nullptr);
-  }
-  DRX_LAUNCH_CHECK();
-  return DRX_OK;
+  void *rows = need ? scratch : nullptr;
+  if (type == DRX_KNN_ITEM) return drx::knn_rows_launch(drx::k_knn_score_item, R, lds, st, Mo, uid, fallback, out, cand_mask, (float *)rows);
+  return drx::knn_rows_launch(drx::k_knn_score_user, R, lds, st, Mo, uid, out, cand_mask, (double *)rows);
 }
 
 extern "C" int drx_knn_pair_scores(int32_t type, int32_t aggregation, const int64_t *indptr, const int32_t *indices, const float *values,
@@ -870,19 +804,8 @@ extern "C" int drx_knn_recommend(int32_t type, int32_t aggregation, const int64_
   size_t lds;
   const int rc = drx::knn_fused_args(Mo, uid, R, fallback, excl_indptr, excl_indices, scratch, scratch_bytes, F, lds);
   if (rc != DRX_OK || R == 0) return rc;
-  hipStream_t st = (hipStream_t)stream;
-  lds += drx::kKnnFusedTail;
-  if (type == DRX_KNN_ITEM) {
-    DRX_HIP(hipFuncSetAttribute((const void *)drx::k_knn_recommend<DRX_KNN_ITEM>, hipFuncAttributeMaxDynamicSharedMemorySize,
-                                (int)drx::kKnnLdsBytes));
-    hipLaunchKernelGGL(drx::k_knn_recommend<DRX_KNN_ITEM>, dim3(R), dim3(drx::kBlock), lds, st, Mo, F, n, out_idx, out_val);
-  } else {
-    DRX_HIP(hipFuncSetAttribute((const void *)drx::k_knn_recommend<DRX_KNN_USER>, hipFuncAttributeMaxDynamicSharedMemorySize,
-                                (int)drx::kKnnLdsBytes));
-    hipLaunchKernelGGL(drx::k_knn_recommend<DRX_KNN_USER>, dim3(R), dim3(drx::kBlock), lds, st, Mo, F, n, out_idx, out_val);
-  }
-  DRX_LAUNCH_CHECK();
-  return DRX_OK;
+  return drx::knn_rows_launch(type == DRX_KNN_ITEM ? drx::k_knn_recommend<DRX_KNN_ITEM> : drx::k_knn_recommend<DRX_KNN_USER>, R,
+                              lds + drx::kKnnFusedTail, (hipStream_t)stream, Mo, F, n, out_idx, out_val);
 }
 
 extern "C" size_t drx_knn_rank_lists_scratch_bytes(int32_t type, int32_t R, int64_t P, int32_t n_items) {
@@ -903,18 +826,6 @@ extern "C" int drx_knn_rank_lists(int32_t type, int32_t aggregation, const int64
   size_t lds;
   const int rc = drx::knn_fused_args(Mo, uid, work ? R : 0, fallback, excl_indptr, excl_indices, scratch, scratch_bytes, F, lds);
   if (rc != DRX_OK || !work) return rc;
-  hipStream_t st = (hipStream_t)stream;
-  if (type == DRX_KNN_ITEM) {
-    DRX_HIP(hipFuncSetAttribute((const void *)drx::k_knn_rank_lists<DRX_KNN_ITEM>, hipFuncAttributeMaxDynamicSharedMemorySize,
-                                (int)drx::kKnnLdsBytes));
-    hipLaunchKernelGGL(drx::k_knn_rank_lists<DRX_KNN_ITEM>, dim3(R), dim3(drx::kBlock), lds, st, Mo, F, target_indptr, targets, P, out_rank,
-                       out_score);
-  } else {
-    DRX_HIP(hipFuncSetAttribute((const void *)drx::k_knn_rank_lists<DRX_KNN_USER>, hipFuncAttributeMaxDynamicSharedMemorySize,
-                                (int)drx::kKnnLdsBytes));
-    hipLaunchKernelGGL(drx::k_knn_rank_lists<DRX_KNN_USER>, dim3(R), dim3(drx::kBlock), lds, st, Mo, F, target_indptr, targets, P, out_rank,
-                       out_score);
-  }
-  DRX_LAUNCH_CHECK();
-  return DRX_OK;
+  return drx::knn_rows_launch(type == DRX_KNN_ITEM ? drx::k_knn_rank_lists<DRX_KNN_ITEM> : drx::k_knn_rank_lists<DRX_KNN_USER>, R, lds,
+                              (hipStream_t)stream, Mo, F, target_indptr, targets, P, out_rank, out_score);
 }

@@ -4,7 +4,7 @@
 // (CDAE: q = hidden rows, T = W2T), the biased sum itself (Caser: q = [dense_0 output | user row], T = W1) or the sum clipped at 1e-6
 // from below, no bias (DMF: q / T = the l2-normalised tower outputs); everything else is shared.  Columns of q and T between the
 // model's width and ld must be ZERO, not merely unused: they are multiplied (0 x NaN would poison a row's scores).  Order = drx_topk's: descending score, ties by LARGER item index (heapq.nlargest over
-// (score, iid), cdae.py:103), carried by the same 64-bit key (monotone score bits << 32 | item).
+// (score, iid), cdae.py:103), carried by the same 64-bit key (drx_keys.hpp).
 //
 // k_recommend   grid (user tiles of 128, item splits).  The products run on the matrix cores in fp32 (v_mfma_f32_32x32x2_f32: bit for
 //               bit a k-ordered fmaf chain; the item's bias is added to the finished sum) with the ITEM rows as the A operand and the
@@ -19,8 +19,8 @@
 //               search in the user's CSR row, one key per lane; then the rank of every key among the list's keys, through LDS),
 //               which also raises the lane's bound.  No atomic read-modify-write: a list has one writer, and what it ends up
 //               holding is the n largest eligible keys its lane saw.
-// k_recommend_merge   one workgroup per user: the 2 x splits lists of the user ordered in LDS (bitonic network on <= 16384 keys),
-//               the n largest written out.
+// k_lists_merge (drx_keys.hpp, with the lists' plan and layout)   one workgroup per user: the 2 x splits lists of the user ordered in
+//               LDS, the n largest written out, -1 / -inf behind them.
 // Every score is the same fmaf chain whatever the tile, the split or the neighbours of its user, and the keys are unique, so the
 // result is a function of the inputs alone (bit-identical between calls, request orders and chunkings).
 //
@@ -28,34 +28,25 @@
 // where in the whole catalogue a GIVEN item stands for a row — a count of larger keys instead of a selection.
 // drx_rows_pair_scores (k_pair_scores, behind them) answers for given (row, item) pairs with the score alone, from the pair's two rows:
 // the same sum as one scalar fmaf chain per pair, no walk.
+//
+// Host side: the walking calls share one request check (request_ok), one walk plan, one RecArgs builder and one dispatch on the
+// epilogue (by_epilogue); the extern "C" functions at the end of the file are the implementations.  The order of refusals is part of
+// the ABI: DRX_EINVAL, then DRX_ENOTIMPL, then DRX_ESCRATCH (tests/test_gpu_rows_refusals.py).
+#include <climits>
 #include <hip/hip_runtime.h>
-#include "drx_common.hpp"
+#include "drx_keys.hpp"
 
 namespace drx {
 namespace {
 
 typedef float f32x16 __attribute__((ext_vector_type(16)));
-typedef unsigned long long u64;
 
-constexpr int kRecUsers = 128;          // users of a workgroup: 32 per wave
+constexpr int kRecUsers = kListRows;    // users of a workgroup: 32 per wave
 constexpr int kRecItems = 128;          // items of a block step: 4 accumulator tiles of 32
 constexpr int kRecKC = 16;              // k columns of a chunk
 constexpr int kRecKT = kRecKC / 8;      // k steps of 8 per chunk: 4 MFMAs per tile each
 constexpr int kRecMaxN = 128, kRecMaxLd = 256;
-constexpr int kRecMaxMerge = 16384;     // keys the merge orders in LDS (128 KiB)
 constexpr int kRecTargetGroups = 256;   // workgroups a launch aims for: one per CU (the kernel's registers and LDS allow no more)
-
-// The key 0 means "empty slot" everywhere (rec_compact, the merge).  No finite float orders to 0 bits (that is -NaN with every payload
-// bit set), so a real key is never 0 whatever the sign of its score.
-__device__ __forceinline__ uint32_t rec_ordered_bits(float f) {
-  if (f == 0.0f) f = 0.0f;              // -0.0 == 0.0 (as drx_topk)
-  const uint32_t u = __float_as_uint(f);
-  return (u & 0x80000000u) ? ~u : (u | 0x80000000u);
-}
-__device__ __forceinline__ float rec_score_of(u64 key) {
-  const uint32_t o = (uint32_t)(key >> 32);
-  return __uint_as_float((o & 0x80000000u) ? (o ^ 0x80000000u) : ~o);
-}
 
 // A logit bound for a score threshold s: every z below it has sigmoidf_(z) < s STRICTLY, whatever the rounding of expf (taken as
 // |computed - true| <= 1e-6 relative; the division and the addition of sigmoidf_ are monotone).  d ln(sigmoid) / dz = 1 - sigmoid:
@@ -208,7 +199,7 @@ __device__ __forceinline__ void rec_compact(const RecArgs &A, u64 *wave_lists, u
   wave_lds_sync();
   const u64 nth = cb[256];
   if (lane == L) {
-    if (alive >= A.n) { tkey = nth; zt = E::bound(rec_score_of(nth)); }    // (fewer: the bound stays where it was)
+    if (alive >= A.n) { tkey = nth; zt = E::bound(key_score(nth)); }    // (fewer: the bound stays where it was)
     cnt = min(alive, A.n);
   }
   wave_lds_sync();
@@ -305,7 +296,7 @@ __global__ __launch_bounds__(256) void k_recommend(RecArgs A) {
             const unsigned item = (unsigned)ibase + 8u * (e >> 2) + (e & 3);
             if (uvalid && item < (unsigned)i_end) {
               const float sc = E::score(dump[e * 64 + lane]);
-              const u64 key = ((u64)rec_ordered_bits(sc) << 32) | item;
+              const u64 key = make_key(sc, item);
               if (key > tkey) { mylist[cnt] = key; ++cnt; }
             }
           }
@@ -331,125 +322,110 @@ __global__ __launch_bounds__(256) void k_recommend(RecArgs A) {
   if (uvalid) A.counts[(group * kRecUsers + ul) * 2 + hh] = cnt;
 }
 
-__global__ __launch_bounds__(kBlock) void k_recommend_merge(const u64 *__restrict__ lists, const int *__restrict__ counts, int n, int cap,
-                                                            int splits, int npad, int32_t *__restrict__ out_idx,
-                                                            float *__restrict__ out_val) {
-  extern __shared__ __align__(16) unsigned long long keys[];
-  const size_t r = blockIdx.x;
-  const size_t tile = r / kRecUsers, ul = r % kRecUsers;
-  for (int i = threadIdx.x; i < npad; i += kBlock) {
-    u64 key = 0ull;
-    const int slot = i / n, j = i - slot * n;
-    if (slot < 2 * splits) {
-      const size_t lid = ((tile * splits + (slot >> 1)) * kRecUsers + ul) * 2 + (slot & 1);
-      if (j < min(counts[lid], n)) key = lists[lid * cap + j];
-    }
-    keys[i] = key;
-  }
-  for (int size = 2; size <= npad; size <<= 1) {
-    for (int stride = size >> 1; stride > 0; stride >>= 1) {
-      __syncthreads();
-      for (int t = threadIdx.x; t < (npad >> 1); t += kBlock) {
-        const int a = 2 * t - (t & (stride - 1));
-        const int b = a + stride;
-        const u64 ka = keys[a], kb = keys[b];
-        const bool desc = (a & size) == 0;
-        if (desc ? (ka < kb) : (ka > kb)) { keys[a] = kb; keys[b] = ka; }
-      }
-    }
-  }
-  __syncthreads();
-  for (int j = threadIdx.x; j < n; j += kBlock) {
-    const u64 key = j < npad ? keys[j] : 0ull;
-    if (key == 0ull) { out_idx[r * n + j] = -1; out_val[r * n + j] = -INFINITY; }
-    else { out_idx[r * n + j] = (int32_t)(key & 0xFFFFFFFFull); out_val[r * n + j] = rec_score_of(key); }
+// ---- the host side every call of this file shares --------------------------------------------------------------------------------------
+// What the three walking calls (recommend, rank_items, rank_lists) are asked, as given.
+struct RecRequest {
+  const float *table, *bias;
+  int n_items, ld, epilogue;
+  const float *q;
+  const int32_t *uid;
+  int R;
+  const int64_t *xptr;          // exclusion CSR (or null)
+  const int32_t *xidx;
+};
+
+bool ld_ok(int ld) { return ld >= 4 && !(ld & 3); }
+// the clip has no bias, the other two need one
+bool epilogue_ok(int epilogue, const float *bias) {
+  if (epilogue != DRX_REC_SIGMOID_BIAS && epilogue != DRX_REC_BIAS && epilogue != DRX_REC_CLIP) return false;
+  return (epilogue == DRX_REC_CLIP) == (bias == nullptr);
+}
+// false: DRX_EINVAL, before anything else is looked at (a call adds its own pointers to it)
+bool request_ok(const RecRequest &Q) {
+  if (!Q.table || !Q.q || Q.R < 1 || Q.n_items < 1 || !ld_ok(Q.ld) || !epilogue_ok(Q.epilogue, Q.bias)) return false;
+  return (Q.xptr != nullptr) == (Q.xidx != nullptr) && (!Q.xptr || Q.uid);
+}
+
+// fn(E{}) for the epilogue struct E of a checked request
+template <class F>
+int by_epilogue(int epilogue, F &&fn) {
+  switch (epilogue) {
+    case DRX_REC_SIGMOID_BIAS: return fn(RecSigmoidBias{});
+    case DRX_REC_BIAS: return fn(RecBias{});
+    case DRX_REC_CLIP: return fn(RecClip{});
+    default: return DRX_EINVAL;
   }
 }
 
-struct RecPlan {
-  int tiles, splits, ips, cap, nch, hs, npad;
-  size_t lds_main, lds_merge;
+// What the walk needs from the shape of a request, before its items are split: false outside the domain (rows wider than 256 floats).
+struct WalkPlan {
+  int tiles, blocks;             // row tiles of kRecUsers, item blocks of kRecItems
+  int nch, hs;
+  size_t lds;                    // the tile's query rows and the per-wave dump
 };
-
-bool rec_plan(int R, int n_items, int ld, int n, RecPlan &P) {
-  if (R < 1 || n_items < 1 || ld < 4 || (ld & 3) || ld > kRecMaxLd || n < 1 || n > kRecMaxN) return false;
-  P.tiles = (R + kRecUsers - 1) / kRecUsers;
-  const int blocks = (int)(((int64_t)n_items + kRecItems - 1) / kRecItems);
-  int64_t want = (kRecTargetGroups + P.tiles - 1) / P.tiles;
-  if (want > kRecMaxMerge / (2 * n)) want = kRecMaxMerge / (2 * n);
-  if (want > blocks) want = blocks;
-  if (want > 65535) want = 65535;
-  if (want < 1) want = 1;
-  const int bps = (int)((blocks + want - 1) / want);                 // item blocks per split
-  P.ips = bps * kRecItems;
-  P.splits = (blocks + bps - 1) / bps;
-  P.cap = 2 * n < 32 ? 32 : 2 * n;
-  P.nch = 2 * ((ld + 2 * kRecKC - 1) / (2 * kRecKC));                // (even: the kernel alternates two fragment buffers)
-  P.hs = P.nch * kRecKC + 4;                                         // + 4: the 32 users of a wave spread over the LDS banks
-  P.npad = 2;
-  while (P.npad < 2 * P.splits * n) P.npad <<= 1;
-  P.lds_main = ((size_t)kRecUsers * P.hs + 4 * 16 * 64) * sizeof(float) + 4 * 258 * sizeof(u64);
-  P.lds_merge = (size_t)P.npad * sizeof(u64);
+bool walk_plan(int R, int n_items, int ld, WalkPlan &W) {
+  if (R < 1 || n_items < 1 || !ld_ok(ld) || ld > kRecMaxLd) return false;
+  W.tiles = (R + kRecUsers - 1) / kRecUsers;
+  W.blocks = (int)(((int64_t)n_items + kRecItems - 1) / kRecItems);
+  W.nch = 2 * ((ld + 2 * kRecKC - 1) / (2 * kRecKC));                // (even: the kernels alternate two fragment buffers)
+  W.hs = W.nch * kRecKC + 4;                                         // + 4: the 32 users of a wave spread over the LDS banks
+  W.lds = ((size_t)kRecUsers * W.hs + 4 * 16 * 64) * sizeof(float);
   return true;
 }
 
-struct RecLayout { u64 *lists; int *counts; };
-RecLayout rec_layout(Carver &cv, const RecPlan &P) {
-  RecLayout L;
-  const size_t n_lists = (size_t)P.tiles * P.splits * kRecUsers * 2;
-  L.lists = cv.take<u64>(n_lists * P.cap);
-  L.counts = cv.take<int>(n_lists);
-  return L;
+// the kernels' view of a request: `splits` splits of `bps` item blocks each; the selector adds its lists
+RecArgs rec_args(const RecRequest &Q, const WalkPlan &W, int splits, int bps) {
+  RecArgs A{};
+  A.table = Q.table; A.bias = Q.bias; A.q = Q.q; A.uid = Q.uid; A.xptr = Q.xptr; A.xidx = Q.xidx;
+  A.R = Q.R; A.N = Q.n_items; A.ld = Q.ld; A.nch = W.nch; A.hs = W.hs; A.splits = splits; A.ips = bps * kRecItems;
+  return A;
+}
+
+// ---- the selector: the walk plus the lists (drx_keys.hpp: the splits capped so that the merge's keys fit LDS) ---------------------------
+struct RecPlan {
+  WalkPlan W;
+  ListPlan L;
+  size_t lds_main;               // W.lds and the compaction's keys: [4 waves][256 keys + the n-th + pad]
+};
+
+bool rec_plan(int R, int n_items, int ld, int n, RecPlan &P) {
+  if (n < 1 || n > kRecMaxN || !walk_plan(R, n_items, ld, P.W)) return false;
+  P.L = list_plan(P.W.tiles, P.W.blocks, n, kRecTargetGroups);
+  P.lds_main = P.W.lds + 4 * 258 * sizeof(u64);
+  return true;
 }
 
 size_t rec_scratch_bytes(int R, int n_items, int ld, int n) {
   RecPlan P;
   if (!rec_plan(R, n_items, ld, n, P)) return 0;
   Carver cv(nullptr, 0);
-  (void)rec_layout(cv, P);
+  P.L.carve(cv);
   return align_up(cv.off, 256) + 256;
 }
 
-template <class E>
-int rec_launch(const RecArgs &A, const RecPlan &P, const RecLayout &L, int32_t *out_idx, float *out_val, hipStream_t st) {
-  DRX_HIP(hipFuncSetAttribute((const void *)k_recommend<E>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)P.lds_main));
-  hipLaunchKernelGGL(k_recommend<E>, dim3(P.tiles, P.splits), dim3(256), P.lds_main, st, A);
-  DRX_HIP(hipFuncSetAttribute((const void *)k_recommend_merge, hipFuncAttributeMaxDynamicSharedMemorySize, (int)P.lds_merge));
-  hipLaunchKernelGGL(k_recommend_merge, dim3(A.R), dim3(kBlock), P.lds_merge, st, L.lists, L.counts, A.n, P.cap, P.splits, P.npad, out_idx,
-                     out_val);
-  DRX_LAUNCH_CHECK();
-  return DRX_OK;
-}
-
 // the one host function behind drx_rows_recommend and drx_cdae_recommend
-int rec_run(const float *table, const float *bias, int n_items, int ld, int epilogue, const float *q, const int32_t *uid, int R, int n,
-            const int64_t *excl_indptr, const int32_t *excl_indices, int32_t *out_idx, float *out_val, void *scratch, size_t scratch_bytes,
-            void *stream) {
-  if (!table || !q || !out_idx || !out_val || R < 1 || n < 1 || n_items < 1 || ld < 4 || (ld & 3)) return DRX_EINVAL;
-  if (epilogue != DRX_REC_SIGMOID_BIAS && epilogue != DRX_REC_BIAS && epilogue != DRX_REC_CLIP) return DRX_EINVAL;
-  if ((epilogue == DRX_REC_CLIP) != (bias == nullptr)) return DRX_EINVAL;      // the clip has no bias, the other two need one
-  if ((excl_indptr != nullptr) != (excl_indices != nullptr) || (excl_indptr && !uid)) return DRX_EINVAL;
+int rec_run(const RecRequest &Q, int n, int32_t *out_idx, float *out_val, void *scratch, size_t scratch_bytes, void *stream) {
+  if (!request_ok(Q) || !out_idx || !out_val || n < 1) return DRX_EINVAL;
   RecPlan P;
-  if (!rec_plan(R, n_items, ld, n, P)) return DRX_ENOTIMPL;      // n > 128 or rows wider than 256 floats: a score matrix + drx_topk
+  if (!rec_plan(Q.R, Q.n_items, Q.ld, n, P)) return DRX_ENOTIMPL;      // n > 128 or rows wider than 256 floats: a score matrix + drx_topk
   if (!scratch) return DRX_ESCRATCH;
   Carver cv(scratch, scratch_bytes);
-  const RecLayout L = rec_layout(cv, P);
+  P.L.carve(cv);
   if (!cv.ok()) return DRX_ESCRATCH;
-  RecArgs A;
-  A.table = table; A.bias = bias; A.q = q; A.uid = uid; A.xptr = excl_indptr; A.xidx = excl_indices;
-  A.R = R; A.N = n_items; A.ld = ld; A.nch = P.nch; A.hs = P.hs; A.n = n; A.cap = P.cap; A.splits = P.splits; A.ips = P.ips;
-  A.lists = L.lists; A.counts = L.counts;
+  RecArgs A = rec_args(Q, P.W, P.L.splits, P.L.per);
+  A.n = n; A.cap = P.L.cap; A.lists = P.L.lists; A.counts = P.L.counts;
   hipStream_t st = (hipStream_t)stream;
-  switch (epilogue) {
-    case DRX_REC_SIGMOID_BIAS: return rec_launch<RecSigmoidBias>(A, P, L, out_idx, out_val, st);
-    case DRX_REC_BIAS: return rec_launch<RecBias>(A, P, L, out_idx, out_val, st);
-    default: return rec_launch<RecClip>(A, P, L, out_idx, out_val, st);
-  }
+  return by_epilogue(Q.epilogue, [&](auto e) -> int {
+    using E = decltype(e);
+    DRX_HIP(hipFuncSetAttribute((const void *)k_recommend<E>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)P.lds_main));
+    hipLaunchKernelGGL(k_recommend<E>, dim3(P.W.tiles, P.L.splits), dim3(256), P.lds_main, st, A);
+    return lists_merge(P.L, Q.R, -INFINITY, out_idx, out_val, st);
+  });
 }
 
 // ---- catalogue ranks of given (row, item) pairs (drx_rows_rank_items) ------------------------------------------------------------------
 // rank[r] = the number of eligible items i != t[r] whose key is larger than the key of the row's target t[r]: the position of t[r] in
-// the list k_recommend + k_recommend_merge would give for an unbounded n.  Counting needs no lists: the same product walk, two compares
+// the list k_recommend + k_lists_merge would give for an unbounded n.  Counting needs no lists: the same product walk, two compares
 // per score.
 // k_rank_keys    grid (user tiles).  The targets' own sums and keys: a wave walks its 32 rows and computes the 128-item block that holds
 //                a row's target (none when it is the block just done), with k_recommend's fragment loads and MFMA order — the same
@@ -567,7 +543,7 @@ __global__ __launch_bounds__(256) void k_rank_keys(RecArgs A, RankArgs K) {
     if (lane == 32 * th + j) {
       const float z = dump[te * 64 + lane];
       K.tz[r] = z;
-      K.tkey[r] = ((u64)rec_ordered_bits(E::score(z)) << 32) | (unsigned)t;
+      K.tkey[r] = make_key(E::score(z), (unsigned)t);
     }
   }
 }
@@ -600,7 +576,7 @@ __global__ __launch_bounds__(256) void k_rank_count(RecArgs A, RankArgs K) {
     tkey = K.tkey[r];
     if (tkey != 0ull) {
       t = (unsigned)tkey;
-      E::band(K.tz[r], rec_score_of(tkey), zlo, zhi);
+      E::band(K.tz[r], key_score(tkey), zlo, zhi);
       if (A.xptr) {
         const int u = A.uid[r];
         int64_t lo = A.xptr[u];
@@ -663,7 +639,7 @@ __global__ __launch_bounds__(256) void k_rank_count(RecArgs A, RankArgs K) {
           const int e = __ffs(mb) - 1;
           mb &= mb - 1;
           const unsigned item = ibase + 8u * (e >> 2) + (e & 3);
-          const u64 key = ((u64)rec_ordered_bits(E::score(dump[e * 64 + lane])) << 32) | item;
+          const u64 key = make_key(E::score(dump[e * 64 + lane]), item);
           cnt += key > tkey ? 1 : 0;
         }
       }
@@ -686,31 +662,18 @@ __global__ __launch_bounds__(kBlock) void k_rank_finish(const int *__restrict__ 
     sum += p[1];
   }
   out_rank[r] = sum;
-  out_score[r] = rec_score_of(key);
+  out_score[r] = key_score(key);
 }
 
+// the walk plan and its splits WITHOUT the merge's cap; S.room = the splits the scratch has room for: what the launch aims at, so that
+// a longer catalogue does not size it
 struct RankPlan {
-  int tiles, splits, ips, nch, hs;
-  int room;                      // splits the scratch has room for: what the launch aims at, so that n_items does not size it
-  size_t lds;
+  WalkPlan W;
+  Splits S;
 };
-
-// as rec_plan without the merge's cap on the splits
 bool rank_plan(int R, int n_items, int ld, RankPlan &P) {
-  if (R < 1 || n_items < 1 || ld < 4 || (ld & 3) || ld > kRecMaxLd) return false;
-  P.tiles = (R + kRecUsers - 1) / kRecUsers;
-  const int blocks = (int)(((int64_t)n_items + kRecItems - 1) / kRecItems);
-  int64_t want = (kRecTargetGroups + P.tiles - 1) / P.tiles;
-  if (want > blocks) want = blocks;
-  if (want > 65535) want = 65535;
-  if (want < 1) want = 1;
-  const int bps = (int)((blocks + want - 1) / want);                 // item blocks per split
-  P.ips = bps * kRecItems;
-  P.splits = (blocks + bps - 1) / bps;
-  P.room = (int)want;                                                // (>= splits)
-  P.nch = 2 * ((ld + 2 * kRecKC - 1) / (2 * kRecKC));
-  P.hs = P.nch * kRecKC + 4;
-  P.lds = ((size_t)kRecUsers * P.hs + 4 * 16 * 64) * sizeof(float);
+  if (!walk_plan(R, n_items, ld, P.W)) return false;
+  P.S = plan_splits(P.W.tiles, P.W.blocks, kRecTargetGroups, 0, INT_MAX);
   return true;
 }
 
@@ -719,54 +682,8 @@ RankArgs rank_layout(Carver &cv, const RankPlan &P, int R) {
   K.target = nullptr;
   K.tz = cv.take<float>((size_t)R);
   K.tkey = cv.take<u64>((size_t)R);
-  K.partial = cv.take<int>((size_t)P.tiles * P.room * kRecUsers * 2);
+  K.partial = cv.take<int>((size_t)P.W.tiles * P.S.room * kRecUsers * 2);
   return K;
-}
-
-size_t rank_scratch_bytes(int R, int n_items, int ld) {
-  RankPlan P;
-  if (!rank_plan(R, n_items, ld, P)) return 0;
-  Carver cv(nullptr, 0);
-  (void)rank_layout(cv, P, R);
-  return align_up(cv.off, 256) + 256;
-}
-
-template <class E>
-int rank_launch(const RecArgs &A, const RankArgs &K, const RankPlan &P, int32_t *out_rank, float *out_score, hipStream_t st) {
-  DRX_HIP(hipFuncSetAttribute((const void *)k_rank_keys<E>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)P.lds));
-  hipLaunchKernelGGL(k_rank_keys<E>, dim3(P.tiles), dim3(256), P.lds, st, A, K);
-  DRX_HIP(hipFuncSetAttribute((const void *)k_rank_count<E>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)P.lds));
-  hipLaunchKernelGGL(k_rank_count<E>, dim3(P.tiles, P.splits), dim3(256), P.lds, st, A, K);
-  hipLaunchKernelGGL(k_rank_finish, dim3((A.R + kBlock - 1) / kBlock), dim3(kBlock), 0, st, K.partial, K.tkey, A.R, P.splits, out_rank,
-                     out_score);
-  DRX_LAUNCH_CHECK();
-  return DRX_OK;
-}
-
-int rank_run(const float *table, const float *bias, int n_items, int ld, int epilogue, const float *q, const int32_t *uid,
-             const int32_t *target, int R, const int64_t *excl_indptr, const int32_t *excl_indices, int32_t *out_rank, float *out_score,
-             void *scratch, size_t scratch_bytes, void *stream) {
-  if (!table || !q || !target || !out_rank || !out_score || R < 1 || n_items < 1 || ld < 4 || (ld & 3)) return DRX_EINVAL;
-  if (epilogue != DRX_REC_SIGMOID_BIAS && epilogue != DRX_REC_BIAS && epilogue != DRX_REC_CLIP) return DRX_EINVAL;
-  if ((epilogue == DRX_REC_CLIP) != (bias == nullptr)) return DRX_EINVAL;
-  if ((excl_indptr != nullptr) != (excl_indices != nullptr) || (excl_indptr && !uid)) return DRX_EINVAL;
-  RankPlan P;
-  if (!rank_plan(R, n_items, ld, P)) return DRX_ENOTIMPL;         // rows wider than 256 floats
-  if (!scratch) return DRX_ESCRATCH;
-  Carver cv(scratch, scratch_bytes);
-  RankArgs K = rank_layout(cv, P, R);
-  if (!cv.ok()) return DRX_ESCRATCH;
-  K.target = target;
-  RecArgs A;
-  A.table = table; A.bias = bias; A.q = q; A.uid = uid; A.xptr = excl_indptr; A.xidx = excl_indices;
-  A.R = R; A.N = n_items; A.ld = ld; A.nch = P.nch; A.hs = P.hs; A.n = 0; A.cap = 0; A.splits = P.splits; A.ips = P.ips;
-  A.lists = nullptr; A.counts = nullptr;
-  hipStream_t st = (hipStream_t)stream;
-  switch (epilogue) {
-    case DRX_REC_SIGMOID_BIAS: return rank_launch<RecSigmoidBias>(A, K, P, out_rank, out_score, st);
-    case DRX_REC_BIAS: return rank_launch<RecBias>(A, K, P, out_rank, out_score, st);
-    default: return rank_launch<RecClip>(A, K, P, out_rank, out_score, st);
-  }
 }
 
 // ---- catalogue ranks of a row's LIST of targets (drx_rows_rank_lists) ------------------------------------------------------------------
@@ -852,7 +769,7 @@ __global__ __launch_bounds__(256) void k_rankl_keys(RecArgs A, RankListArgs K) {
           if (((m >> 2) & 1) == hh) {                                 // element (item t, this column): register te of this half
             const float z = dump[(4 * (m >> 3) + (m & 3)) * 64 + lane];
             K.tz[cur - K.base] = z;
-            K.tkey[cur - K.base] = ((u64)rec_ordered_bits(E::score(z)) << 32) | (unsigned)t;
+            K.tkey[cur - K.base] = make_key(E::score(z), (unsigned)t);
           }
           ++cur;
           if (cur < end) t = K.targets[cur];
@@ -903,7 +820,7 @@ __global__ __launch_bounds__(256) void k_rankl_count(RecArgs A, RankListArgs K) 
       float zlo = INFINITY, zhi = INFINITY;                           // (no target: nothing is counted)
       if (p < end) {
         tkey = K.tkey[p - K.base];
-        if (tkey != 0ull) E::band(K.tz[p - K.base], rec_score_of(tkey), zlo, zhi);
+        if (tkey != 0ull) E::band(K.tz[p - K.base], key_score(tkey), zlo, zhi);
       }
       if (hh == 0) { zlo_s[g * kRecUsers + ul] = zlo; zhi_s[g * kRecUsers + ul] = zhi; key_s[g * kRecUsers + ul] = tkey; }
       cnt_s[(2 * g + hh) * kRecUsers + ul] = 0;
@@ -977,7 +894,7 @@ __global__ __launch_bounds__(256) void k_rankl_count(RecArgs A, RankListArgs K) 
               const int e = __ffs(mb) - 1;
               mb &= mb - 1;
               const unsigned item = ibase + 8u * (e >> 2) + (e & 3);
-              const u64 key = ((u64)rec_ordered_bits(E::score(dump[e * 64 + lane])) << 32) | item;
+              const u64 key = make_key(E::score(dump[e * 64 + lane]), item);
               c += key > tkey ? 1 : 0;
             }
           }
@@ -1003,78 +920,15 @@ __global__ __launch_bounds__(kBlock) void k_rankl_finish(const int *__restrict__
   int sum = 0;
   for (int j = 0; j < 2 * splits; ++j) sum += p[j];
   out_rank[base + pi] = sum;
-  out_score[base + pi] = rec_score_of(key);
-}
-
-// G: what LDS holds beside the tile's query rows and the dump at this ld
-int rankl_group(int ld) {
-  RankPlan P;
-  if (!rank_plan(1, 1, ld, P) || P.lds + kRankListSlot > kRecLdsBytes) return 0;
-  const size_t g = (kRecLdsBytes - P.lds) / kRankListSlot;
-  return g > (size_t)kRankListMaxG ? kRankListMaxG : (int)g;
+  out_score[base + pi] = key_score(key);
 }
 
 RankListArgs rankl_layout(Carver &cv, const RankPlan &P, int64_t n_targets) {
   RankListArgs K{};
   K.tz = cv.take<float>((size_t)n_targets);
   K.tkey = cv.take<u64>((size_t)n_targets);
-  K.partial = cv.take<int>((size_t)n_targets * 2 * P.room);           // (room, not splits: n_items does not size it)
+  K.partial = cv.take<int>((size_t)n_targets * 2 * P.S.room);         // (room, not splits: n_items does not size it)
   return K;
-}
-
-size_t rankl_scratch_bytes(int R, int64_t n_targets, int n_items, int ld) {
-  RankPlan P;
-  if (n_targets < 0 || !rank_plan(R, n_items, ld, P) || rankl_group(ld) < 1) return 0;
-  Carver cv(nullptr, 0);
-  (void)rankl_layout(cv, P, n_targets);
-  return align_up(cv.off, 256) + 256;
-}
-
-template <class E>
-int rankl_launch(const RecArgs &A, const RankListArgs &K, const RankPlan &P, int32_t *out_rank, float *out_score, hipStream_t st) {
-  const size_t lds_count = P.lds + (size_t)K.G * kRankListSlot;
-  DRX_HIP(hipFuncSetAttribute((const void *)k_rankl_keys<E>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)P.lds));
-  hipLaunchKernelGGL(k_rankl_keys<E>, dim3(P.tiles), dim3(256), P.lds, st, A, K);
-  DRX_HIP(hipFuncSetAttribute((const void *)k_rankl_count<E>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_count));
-  hipLaunchKernelGGL(k_rankl_count<E>, dim3(P.tiles, P.splits), dim3(256), lds_count, st, A, K);
-  hipLaunchKernelGGL(k_rankl_finish, dim3((unsigned)((K.P + kBlock - 1) / kBlock)), dim3(kBlock), 0, st, K.partial, K.tkey, K.base, K.P,
-                     P.splits, out_rank, out_score);
-  DRX_LAUNCH_CHECK();
-  return DRX_OK;
-}
-
-int rankl_run(const float *table, const float *bias, int n_items, int ld, int epilogue, const float *q, const int32_t *uid, int R,
-              const int64_t *target_indptr, const int32_t *targets, const int64_t *excl_indptr, const int32_t *excl_indices,
-              int32_t *out_rank, float *out_score, void *scratch, size_t scratch_bytes, void *stream) {
-  if (!table || !q || !target_indptr || !targets || !out_rank || !out_score || R < 1 || n_items < 1 || ld < 4 || (ld & 3)) return DRX_EINVAL;
-  if (epilogue != DRX_REC_SIGMOID_BIAS && epilogue != DRX_REC_BIAS && epilogue != DRX_REC_CLIP) return DRX_EINVAL;
-  if ((epilogue == DRX_REC_CLIP) != (bias == nullptr)) return DRX_EINVAL;
-  if ((excl_indptr != nullptr) != (excl_indices != nullptr) || (excl_indptr && !uid)) return DRX_EINVAL;
-  RankPlan P;
-  const int G = rankl_group(ld);
-  if (!rank_plan(R, n_items, ld, P) || G < 1) return DRX_ENOTIMPL;   // rows wider than 256 floats
-  hipStream_t st = (hipStream_t)stream;
-  int64_t ends[2] = {0, 0};                                           // the offsets are device data: the two that size the call come back
-  DRX_HIP(hipMemcpyAsync(&ends[0], target_indptr, sizeof(int64_t), hipMemcpyDeviceToHost, st));
-  DRX_HIP(hipMemcpyAsync(&ends[1], target_indptr + R, sizeof(int64_t), hipMemcpyDeviceToHost, st));
-  DRX_HIP(hipStreamSynchronize(st));
-  const int64_t n_targets = ends[1] - ends[0];
-  if (ends[0] < 0 || n_targets < 0 || n_targets > ((int64_t)1 << 40)) return DRX_EINVAL;
-  if (n_targets == 0) return DRX_OK;
-  if (!scratch || scratch_bytes < rankl_scratch_bytes(R, n_targets, n_items, ld)) return DRX_ESCRATCH;   // (what the size function says, to the byte)
-  Carver cv(scratch, scratch_bytes);
-  RankListArgs K = rankl_layout(cv, P, n_targets);
-  if (!cv.ok()) return DRX_ESCRATCH;
-  K.tptr = target_indptr; K.targets = targets; K.base = ends[0]; K.P = n_targets; K.G = G;
-  RecArgs A;
-  A.table = table; A.bias = bias; A.q = q; A.uid = uid; A.xptr = excl_indptr; A.xidx = excl_indices;
-  A.R = R; A.N = n_items; A.ld = ld; A.nch = P.nch; A.hs = P.hs; A.n = 0; A.cap = 0; A.splits = P.splits; A.ips = P.ips;
-  A.lists = nullptr; A.counts = nullptr;
-  switch (epilogue) {
-    case DRX_REC_SIGMOID_BIAS: return rankl_launch<RecSigmoidBias>(A, K, P, out_rank, out_score, st);
-    case DRX_REC_BIAS: return rankl_launch<RecBias>(A, K, P, out_rank, out_score, st);
-    default: return rankl_launch<RecClip>(A, K, P, out_rank, out_score, st);
-  }
 }
 
 // ---- scores of given (query row, table row) pairs and nothing else (drx_rows_pair_scores) -------------------------------------------
@@ -1171,83 +1025,134 @@ __global__ __launch_bounds__(kWave) void k_pair_scores(PairArgs A) {
   }
 }
 
-template <class E>
-int pair_launch(const PairArgs &A, hipStream_t st) {
-  const int64_t groups = (A.P + kWave - 1) / kWave;
-  hipLaunchKernelGGL(k_pair_scores<E>, dim3((unsigned)(groups < kPairMaxGroups ? groups : kPairMaxGroups)), dim3(kWave), 0, st, A);
-  DRX_LAUNCH_CHECK();
-  return DRX_OK;
-}
+}  // namespace
+}  // namespace drx
 
-int pair_run(const float *table, const float *bias, int n_rows, int ld, int epilogue, const float *q, int n_q, const int32_t *q_row,
-             const int32_t *t_row, int64_t P, float *out_score, void *stream) {
-  if (epilogue != DRX_REC_SIGMOID_BIAS && epilogue != DRX_REC_BIAS && epilogue != DRX_REC_CLIP) return DRX_EINVAL;
-  if ((epilogue == DRX_REC_CLIP) != (bias == nullptr)) return DRX_EINVAL;      // the clip has no bias, the other two need one
-  if (ld < 4 || (ld & 3) || P < 0) return DRX_EINVAL;
+using namespace drx;
+
+extern "C" int drx_rows_pair_scores(const float *table, const float *bias, int32_t n_rows, int32_t ld, int32_t epilogue, const float *q,
+                                    int32_t n_q, const int32_t *q_row, const int32_t *t_row, int64_t P, float *out_score, void *stream) {
+  if (!epilogue_ok(epilogue, bias) || !ld_ok(ld) || P < 0) return DRX_EINVAL;
   if (P == 0) return DRX_OK;
   if (!table || !q || !q_row || !t_row || !out_score || n_rows < 1 || n_q < 1) return DRX_EINVAL;
   PairArgs A;
   A.table = table; A.bias = bias; A.q = q; A.q_row = q_row; A.t_row = t_row; A.out = out_score;
   A.n_rows = n_rows; A.n_q = n_q; A.ld = ld; A.P = P;
-  hipStream_t st = (hipStream_t)stream;
-  switch (epilogue) {
-    case DRX_REC_SIGMOID_BIAS: return pair_launch<RecSigmoidBias>(A, st);
-    case DRX_REC_BIAS: return pair_launch<RecBias>(A, st);
-    default: return pair_launch<RecClip>(A, st);
-  }
-}
-
-}  // namespace
-}  // namespace drx
-
-extern "C" int drx_rows_pair_scores(const float *table, const float *bias, int32_t n_rows, int32_t ld, int32_t epilogue, const float *q,
-                                    int32_t n_q, const int32_t *q_row, const int32_t *t_row, int64_t P, float *out_score, void *stream) {
-  return drx::pair_run(table, bias, n_rows, ld, epilogue, q, n_q, q_row, t_row, P, out_score, stream);
+  const int64_t groups = (P + kWave - 1) / kWave;
+  return by_epilogue(epilogue, [&](auto e) -> int {
+    hipLaunchKernelGGL(k_pair_scores<decltype(e)>, dim3((unsigned)(groups < kPairMaxGroups ? groups : kPairMaxGroups)), dim3(kWave), 0,
+                       (hipStream_t)stream, A);
+    DRX_LAUNCH_CHECK();
+    return DRX_OK;
+  });
 }
 
 extern "C" size_t drx_rows_recommend_scratch_bytes(int32_t R, int32_t n_items, int32_t ld, int32_t n) {
-  return drx::rec_scratch_bytes(R, n_items, ld, n);
+  return rec_scratch_bytes(R, n_items, ld, n);
 }
 
 extern "C" int drx_rows_recommend(const float *table, const float *bias, int32_t n_items, int32_t ld, int32_t epilogue, const float *q,
                                   const int32_t *uid, int32_t R, int32_t n, const int64_t *excl_indptr, const int32_t *excl_indices,
                                   int32_t *out_idx, float *out_val, void *scratch, size_t scratch_bytes, void *stream) {
-  return drx::rec_run(table, bias, n_items, ld, epilogue, q, uid, R, n, excl_indptr, excl_indices, out_idx, out_val, scratch, scratch_bytes,
-                      stream);
-}
-
-extern "C" size_t drx_rows_rank_items_scratch_bytes(int32_t R, int32_t n_items, int32_t ld) { return drx::rank_scratch_bytes(R, n_items, ld); }
-
-extern "C" int drx_rows_rank_items(const float *table, const float *bias, int32_t n_items, int32_t ld, int32_t epilogue, const float *q,
-                                   const int32_t *uid, const int32_t *target, int32_t R, const int64_t *excl_indptr,
-                                   const int32_t *excl_indices, int32_t *out_rank, float *out_score, void *scratch, size_t scratch_bytes,
-                                   void *stream) {
-  return drx::rank_run(table, bias, n_items, ld, epilogue, q, uid, target, R, excl_indptr, excl_indices, out_rank, out_score, scratch,
-                       scratch_bytes, stream);
-}
-
-extern "C" int32_t drx_rows_rank_lists_group(int32_t ld) { return drx::rankl_group(ld); }
-
-extern "C" size_t drx_rows_rank_lists_scratch_bytes(int32_t R, int64_t P, int32_t n_items, int32_t ld) {
-  return drx::rankl_scratch_bytes(R, P, n_items, ld);
-}
-
-extern "C" int drx_rows_rank_lists(const float *table, const float *bias, int32_t n_items, int32_t ld, int32_t epilogue, const float *q,
-                                   const int32_t *uid, int32_t R, const int64_t *target_indptr, const int32_t *targets,
-                                   const int64_t *excl_indptr, const int32_t *excl_indices, int32_t *out_rank, float *out_score,
-                                   void *scratch, size_t scratch_bytes, void *stream) {
-  return drx::rankl_run(table, bias, n_items, ld, epilogue, q, uid, R, target_indptr, targets, excl_indptr, excl_indices, out_rank,
-                        out_score, scratch, scratch_bytes, stream);
+  return rec_run({table, bias, n_items, ld, epilogue, q, uid, R, excl_indptr, excl_indices}, n, out_idx, out_val, scratch, scratch_bytes, stream);
 }
 
 extern "C" size_t drx_cdae_recommend_scratch_bytes(int32_t R, int32_t n_items, int32_t ld, int32_t n) {
-  return drx::rec_scratch_bytes(R, n_items, ld, n);
+  return rec_scratch_bytes(R, n_items, ld, n);
 }
 
 extern "C" int drx_cdae_recommend(const DrxCdaeParams *p, const float *h, const int32_t *uid, int32_t R, int32_t n,
                                   const int64_t *excl_indptr, const int32_t *excl_indices, int32_t *out_idx, float *out_val,
                                   void *scratch, size_t scratch_bytes, void *stream) {
   if (!p || !p->W2T || !p->b2) return DRX_EINVAL;
-  return drx::rec_run(p->W2T, p->b2, p->n_items, p->ld, DRX_REC_SIGMOID_BIAS, h, uid, R, n, excl_indptr, excl_indices, out_idx, out_val,
-                      scratch, scratch_bytes, stream);
+  return rec_run({p->W2T, p->b2, p->n_items, p->ld, DRX_REC_SIGMOID_BIAS, h, uid, R, excl_indptr, excl_indices}, n, out_idx, out_val, scratch,
+                 scratch_bytes, stream);
+}
+
+extern "C" size_t drx_rows_rank_items_scratch_bytes(int32_t R, int32_t n_items, int32_t ld) {
+  RankPlan P;
+  if (!rank_plan(R, n_items, ld, P)) return 0;
+  Carver cv(nullptr, 0);
+  (void)rank_layout(cv, P, R);
+  return align_up(cv.off, 256) + 256;
+}
+
+extern "C" int drx_rows_rank_items(const float *table, const float *bias, int32_t n_items, int32_t ld, int32_t epilogue, const float *q,
+                                   const int32_t *uid, const int32_t *target, int32_t R, const int64_t *excl_indptr,
+                                   const int32_t *excl_indices, int32_t *out_rank, float *out_score, void *scratch, size_t scratch_bytes,
+                                   void *stream) {
+  const RecRequest Q{table, bias, n_items, ld, epilogue, q, uid, R, excl_indptr, excl_indices};
+  if (!request_ok(Q) || !target || !out_rank || !out_score) return DRX_EINVAL;
+  RankPlan P;
+  if (!rank_plan(R, n_items, ld, P)) return DRX_ENOTIMPL;         // rows wider than 256 floats
+  if (!scratch) return DRX_ESCRATCH;
+  Carver cv(scratch, scratch_bytes);
+  RankArgs K = rank_layout(cv, P, R);
+  if (!cv.ok()) return DRX_ESCRATCH;
+  K.target = target;
+  const RecArgs A = rec_args(Q, P.W, P.S.count, P.S.per);
+  hipStream_t st = (hipStream_t)stream;
+  return by_epilogue(epilogue, [&](auto e) -> int {
+    using E = decltype(e);
+    DRX_HIP(hipFuncSetAttribute((const void *)k_rank_keys<E>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)P.W.lds));
+    hipLaunchKernelGGL(k_rank_keys<E>, dim3(P.W.tiles), dim3(256), P.W.lds, st, A, K);
+    DRX_HIP(hipFuncSetAttribute((const void *)k_rank_count<E>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)P.W.lds));
+    hipLaunchKernelGGL(k_rank_count<E>, dim3(P.W.tiles, P.S.count), dim3(256), P.W.lds, st, A, K);
+    hipLaunchKernelGGL(k_rank_finish, dim3((R + kBlock - 1) / kBlock), dim3(kBlock), 0, st, K.partial, K.tkey, R, P.S.count, out_rank, out_score);
+    DRX_LAUNCH_CHECK();
+    return DRX_OK;
+  });
+}
+
+// G: what LDS holds beside the tile's query rows and the dump at this ld
+extern "C" int32_t drx_rows_rank_lists_group(int32_t ld) {
+  WalkPlan W;
+  if (!walk_plan(1, 1, ld, W) || W.lds + kRankListSlot > kRecLdsBytes) return 0;
+  const size_t g = (kRecLdsBytes - W.lds) / kRankListSlot;
+  return g > (size_t)kRankListMaxG ? kRankListMaxG : (int)g;
+}
+
+extern "C" size_t drx_rows_rank_lists_scratch_bytes(int32_t R, int64_t n_targets, int32_t n_items, int32_t ld) {
+  RankPlan P;
+  if (n_targets < 0 || !rank_plan(R, n_items, ld, P) || drx_rows_rank_lists_group(ld) < 1) return 0;
+  Carver cv(nullptr, 0);
+  (void)rankl_layout(cv, P, n_targets);
+  return align_up(cv.off, 256) + 256;
+}
+
+extern "C" int drx_rows_rank_lists(const float *table, const float *bias, int32_t n_items, int32_t ld, int32_t epilogue, const float *q,
+                                   const int32_t *uid, int32_t R, const int64_t *target_indptr, const int32_t *targets,
+                                   const int64_t *excl_indptr, const int32_t *excl_indices, int32_t *out_rank, float *out_score,
+                                   void *scratch, size_t scratch_bytes, void *stream) {
+  const RecRequest Q{table, bias, n_items, ld, epilogue, q, uid, R, excl_indptr, excl_indices};
+  if (!request_ok(Q) || !target_indptr || !targets || !out_rank || !out_score) return DRX_EINVAL;
+  RankPlan P;
+  const int G = drx_rows_rank_lists_group(ld);
+  if (!rank_plan(R, n_items, ld, P) || G < 1) return DRX_ENOTIMPL;   // rows wider than 256 floats
+  hipStream_t st = (hipStream_t)stream;
+  int64_t ends[2] = {0, 0};                                           // the offsets are device data: the two that size the call come back
+  DRX_HIP(hipMemcpyAsync(&ends[0], target_indptr, sizeof(int64_t), hipMemcpyDeviceToHost, st));
+  DRX_HIP(hipMemcpyAsync(&ends[1], target_indptr + R, sizeof(int64_t), hipMemcpyDeviceToHost, st));
+  DRX_HIP(hipStreamSynchronize(st));
+  const int64_t n_targets = ends[1] - ends[0];
+  if (ends[0] < 0 || n_targets < 0 || n_targets > ((int64_t)1 << 40)) return DRX_EINVAL;
+  if (n_targets == 0) return DRX_OK;
+  if (!scratch || scratch_bytes < drx_rows_rank_lists_scratch_bytes(R, n_targets, n_items, ld)) return DRX_ESCRATCH;   // (to the byte)
+  Carver cv(scratch, scratch_bytes);
+  RankListArgs K = rankl_layout(cv, P, n_targets);
+  if (!cv.ok()) return DRX_ESCRATCH;
+  K.tptr = target_indptr; K.targets = targets; K.base = ends[0]; K.P = n_targets; K.G = G;
+  const RecArgs A = rec_args(Q, P.W, P.S.count, P.S.per);
+  const size_t lds_count = P.W.lds + (size_t)G * kRankListSlot;
+  return by_epilogue(epilogue, [&](auto e) -> int {
+    using E = decltype(e);
+    DRX_HIP(hipFuncSetAttribute((const void *)k_rankl_keys<E>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)P.W.lds));
+    hipLaunchKernelGGL(k_rankl_keys<E>, dim3(P.W.tiles), dim3(256), P.W.lds, st, A, K);
+    DRX_HIP(hipFuncSetAttribute((const void *)k_rankl_count<E>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_count));
+    hipLaunchKernelGGL(k_rankl_count<E>, dim3(P.W.tiles, P.S.count), dim3(256), lds_count, st, A, K);
+    hipLaunchKernelGGL(k_rankl_finish, dim3((unsigned)((n_targets + kBlock - 1) / kBlock)), dim3(kBlock), 0, st, K.partial, K.tkey, K.base,
+                       K.P, P.S.count, out_rank, out_score);
+    DRX_LAUNCH_CHECK();
+    return DRX_OK;
+  });
 }

@@ -1,17 +1,19 @@
 // Per-row masked top-k with the ordering of heapq.nlargest over (score, iid) tuples
 // (DRecPy/Recommender/cdae.py:102-103, recommender_abc.py:460-461): descending score, ties by LARGER index.
-// One workgroup per row; the row's candidates become 64-bit keys (ordered score bits << 32 | index) sorted by a
-// bitonic network in LDS (up to 16384 keys = 128 KiB of the CU's 160 KiB).
+// One workgroup per row; the row's candidates become 64-bit keys sorted by the bitonic network in LDS (up to 16384 keys = 128 KiB of
+// the CU's 160 KiB); key and network: drx_keys.hpp.  Every emitter returns scores[idx] read back from the matrix, NOT key_score(key):
+// the key maps -0.0 to +0.0, the matrix value keeps its sign.
 #include <cstring>
 #include <hip/hip_runtime.h>
-#include "drx_common.hpp"
+#include "drx_keys.hpp"
 
 namespace drx {
 
-__device__ __forceinline__ uint32_t ordered_bits(float f) {
-  if (f == 0.0f) f = 0.0f;   // -0.0 == 0.0 in Python comparisons
-  uint32_t u = __float_as_uint(f);
-  return (u & 0x80000000u) ? ~u : (u | 0x80000000u);
+// the key of candidate i of a row, 0 where the mask leaves it out
+__device__ __forceinline__ unsigned long long topk_key(const float *scores, const uint32_t *mask, size_t row_off, int i) {
+  const size_t bit = row_off + (size_t)i;
+  const bool ok = !mask || ((mask[bit >> 5] >> (bit & 31)) & 1u);
+  return ok ? make_key(scores[bit], (unsigned)i) : 0ull;
 }
 
 __global__ __launch_bounds__(kBlock) void k_topk_lds(const float *__restrict__ scores, const uint32_t *__restrict__ mask,
@@ -21,26 +23,14 @@ __global__ __launch_bounds__(kBlock) void k_topk_lds(const float *__restrict__ s
   const size_t r = blockIdx.x;
   for (int i = threadIdx.x; i < npad; i += kBlock) {
     unsigned long long key = 0ull;
-    if (i < n) {
+    if (i < n) {                                       // (topk_key written out: calling it here costs 4 SGPRs)
       const size_t bit = r * (size_t)n + i;
       const bool ok = !mask || ((mask[bit >> 5] >> (bit & 31)) & 1u);
-      if (ok) key = ((unsigned long long)ordered_bits(scores[bit]) << 32) | (unsigned)i;
+      if (ok) key = make_key(scores[bit], (unsigned)i);
     }
     keys[i] = key;
   }
-  for (int size = 2; size <= npad; size <<= 1) {
-    for (int stride = size >> 1; stride > 0; stride >>= 1) {
-      __syncthreads();
-      for (int t = threadIdx.x; t < (npad >> 1); t += kBlock) {
-        const int a = 2 * t - (t & (stride - 1));
-        const int b = a + stride;
-        const unsigned long long ka = keys[a], kb = keys[b];
-        const bool desc = (a & size) == 0;
-        if (desc ? (ka < kb) : (ka > kb)) { keys[a] = kb; keys[b] = ka; }
-      }
-    }
-  }
-  __syncthreads();
+  order_keys_desc(keys, npad);
   for (int j = threadIdx.x; j < k; j += kBlock) {
     const unsigned long long key = j < npad ? keys[j] : 0ull;
     if (key == 0ull) {
@@ -52,12 +42,6 @@ __global__ __launch_bounds__(kBlock) void k_topk_lds(const float *__restrict__ s
       out_val[r * (size_t)k + j] = scores[r * (size_t)n + idx];
     }
   }
-}
-
-__device__ __forceinline__ unsigned long long topk_key(const float *scores, const uint32_t *mask, size_t row_off, int i) {
-  const size_t bit = row_off + (size_t)i;
-  const bool ok = !mask || ((mask[bit >> 5] >> (bit & 31)) & 1u);
-  return ok ? (((unsigned long long)ordered_bits(scores[bit]) << 32) | (unsigned)i) : 0ull;
 }
 
 // ---- small k of a short row (the ranking protocols: k = 10 of a MovieLens catalogue): SELECTION by one wave, no sort (r06) ----------
@@ -126,7 +110,7 @@ __global__ __launch_bounds__(kBlock) void k_topk_wave(const float *__restrict__ 
 #pragma unroll
     for (int j = 0; j < NPL; ++j) {
       const int i = lane + 64 * j;
-      key[j] = (i < n && (mw[j] & 1u)) ? (((unsigned long long)ordered_bits(v[j]) << 32) | (unsigned)i) : 0ull;
+      key[j] = (i < n && (mw[j] & 1u)) ? make_key(v[j], (unsigned)i) : 0ull;
     }
   }
   // Every lane keeps its TWO best keys not yet handed out (first version: the lane's maximum below the last winner recomputed over all
@@ -170,7 +154,7 @@ __global__ __launch_bounds__(kBlock) void k_topk_wave(const float *__restrict__ 
 // histogram of the digit among the keys that match the prefix found so far, the bin where the count from the top reaches k, next
 // digit (6 passes over the row, which L2 / the Infinity Cache hold after the first).  Keys are unique (the index is part of them),
 // so exactly k keys are >= the k-th one: they are collected (in any order) and a second launch orders those k in LDS with the
-// bitonic network above.  r02 sorted every row in full with rocprim::segmented_radix_sort_keys_desc.
+// same bitonic network.  r02 sorted every row in full with rocprim::segmented_radix_sort_keys_desc.
 constexpr int kWaveTopkMaxK = 64;       // k_topk_wave: one winner per lane.  (Up to 512 winners in 8 registers per lane was built: k = 100 took 214 us
                                         // against the sort's 232 — with more winners than lanes the refills, 1 us each, take over.)
 constexpr int kSelThreads = 1024;
@@ -253,19 +237,7 @@ __global__ __launch_bounds__(kBlock) void k_topk_order(const unsigned long long 
   const size_t r = blockIdx.x;
   const int have = n_cand[r];
   for (int i = threadIdx.x; i < kpad; i += kBlock) keys[i] = i < have ? cand[r * (size_t)ks + i] : 0ull;
-  for (int size = 2; size <= kpad; size <<= 1) {
-    for (int stride = size >> 1; stride > 0; stride >>= 1) {
-      __syncthreads();
-      for (int t = threadIdx.x; t < (kpad >> 1); t += kBlock) {
-        const int a = 2 * t - (t & (stride - 1));
-        const int b = a + stride;
-        const unsigned long long ka = keys[a], kb = keys[b];
-        const bool desc = (a & size) == 0;
-        if (desc ? (ka < kb) : (ka > kb)) { keys[a] = kb; keys[b] = ka; }
-      }
-    }
-  }
-  __syncthreads();
+  order_keys_desc(keys, kpad);
   for (int j = threadIdx.x; j < k; j += kBlock) {
     const unsigned long long key = j < kpad ? keys[j] : 0ull;
     if (key == 0ull) { out_idx[r * (size_t)k + j] = -1; out_val[r * (size_t)k + j] = -INFINITY; }

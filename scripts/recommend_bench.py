@@ -28,7 +28,7 @@ which is what recommend_batch runs before it maps items back to raw ids.  Device
 Catalogue ranks of given (user, item) pairs (rank_items: drx_rows_rank_items, counting instead of selecting) beside recommend (n = 10)
 at the same R from the same run: R = 1 / 64 / 1024 / 16 384 pairs of distinct users at N = 1 M, K = 128, novelty on (CDAE; the engine
 calls with the hidden rows, and the two library calls alone on the same rows: k_rank_keys + k_rank_count + k_rank_finish against
-k_recommend + k_recommend_merge); with --model the hooks _catalogue_ranks / _recommend_batch of the fitted ml-1m-shaped model.
+k_recommend + k_lists_merge); with --model the hooks _catalogue_ranks / _recommend_batch of the fitted ml-1m-shaped model.
 
     python scripts/recommend_bench.py --ranks --targets 1,2,4,10,16 [--model dmf|caser] [--out profiles/rank_lists.json] [--quick]
 
@@ -304,7 +304,7 @@ def ranks_main(a):
     res = {'n_items': N, 'k': K, 'n': n, 'novelty': True, 'mean_history': float(len(ix) / U),
            'timed': 'engine: CdaeEngine.rank_items / recommend (hidden rows included), results copied to the host; kernels: the library call alone '
                     'on the same hidden rows (drx_rows_rank_items: k_rank_keys + k_rank_count + k_rank_finish; drx_rows_recommend: k_recommend + '
-                    'k_recommend_merge), events around it',
+                    'k_lists_merge), events around it',
            'rank_items': {}, 'recommend': {}, 'rank_over_recommend': {}}
     for R in [1, 64, 1024] + ([] if a.quick else [16384]):
         reps = 5 if a.quick else (20 if R >= 16384 else 30)
