@@ -10,11 +10,13 @@ cdae.py:78-79), L2/B over the full W, W_, V (cdae.py:81-82), dense Keras Adam wi
 mode='sampled' is the engine's throughput mode (CDAE paper's negative sampling, which the reference skips, cdae.py:5):
 the sampled (uid, iid, value) triple selects ONE output unit with target 1[value >= threshold]; sparse Adagrad (or lazy
 Adam) touches only the rows involved; corruption comes from a counter-based mask evaluated on the device.
+
+How either mode trains, alone or sharded over several GPUs, and the state that takes, is in cdae_fit.py: _pre_fit picks one trainer.
 """
 import numpy as np
 
+from . import cdae_fit
 from .recommender_abc import RecommenderABC
-from ..Sampler import PointSampler
 
 
 class CDAE(RecommenderABC):
@@ -62,93 +64,43 @@ class CDAE(RecommenderABC):
 
     def fit(self, interaction_dataset, epochs=50, batch_size=32, learning_rate=0.001, neg_ratio=5, reg_rate=0.001,
             copy_dataset=False, **kwds):
-        self._fit_epochs = int(epochs)         # (the row layout's pipeline issues exchanges for the steps to come: it must know the last one)
         out = super().fit(interaction_dataset, epochs=epochs, batch_size=batch_size, learning_rate=learning_rate, neg_ratio=neg_ratio,
                           reg_rate=reg_rate, copy_dataset=copy_dataset, **kwds)
-        if getattr(self, '_dist_model', None) is not None:      # training is over: every rank keeps the whole model
-            from ..engine import CdaeEngine
-            full = self._dist_model.gather_params_global()
-            self._dist_model = self._pipeline = None
-            self._engine = CdaeEngine(self.n_users, self.n_items, self.hidden_factors, device=self.device)
-            self._engine.set_params(**full)
-            self._engine.set_history(self._hist_indptr, self._hist_indices)
+        if isinstance(self._trainer, cdae_fit.ShardedTrainer):      # training is over: every rank keeps the whole model
+            full = self._trainer.full_params()
+            self._close_trainer()
+            self._restore_engine(full)
         return out
 
-    def _pre_fit_rows(self, rank, world, learning_rate, neg_ratio, reg_rate, **kwds):
-        """layout='rows' (recommender_abc.py:97-98 is the surface; north_star's row-wise shard behind it): this rank keeps the V rows,
-        histories and recorded pairs of users [lo, hi) and the item rows of its item range; dist.ShardedCdae + ShardedPipeline train."""
-        import torch.distributed as dist
-        from ..dist import ShardedCdae
-        ds = self.interaction_dataset
-        self._hist_indptr, self._hist_indices = ds.positives_csr(self.interaction_threshold)
-        seed = self.seed if self.seed is not None else 0
-        U = self.n_users
-        lo, hi = U * rank // world, U * (rank + 1) // world
-        ip = np.asarray(self._hist_indptr, np.int64)
-        m = ShardedCdae(U, self.n_items, self.hidden_factors, rank, world, self.device, ip[lo:hi + 1] - ip[lo],
-                        self._hist_indices[ip[lo]:ip[hi]], seed=seed, lr=learning_rate, reg=reg_rate, optimizer=self.sparse_optimizer,
-                        loss=self._loss_name, q=self.corruption_level, cpu_staging=(dist.get_backend() == 'gloo'),
-                        chunks=self.exchange_chunks,
-                        transport='rccl' if (self.exchange_transport == 'rccl' and dist.get_backend() == 'nccl') else None)
-        weights = kwds.get('initial_weights')
-        n_params = (2 * self.n_items + U) * self.hidden_factors
-        if weights is None and n_params <= (1 << 26):                # the single-GPU initialisation, sliced (larger: drawn per shard on the device)
-            weights = self._glorot_like_single_gpu(seed)
-        if weights is not None:
-            m.set_params_global(**weights)
-        self._dist_model, self._engine = m, m.engine
-        self._row_range = (lo, hi)
-        all_ip, all_cols, _ = ds.interaction_csr()                  # (negatives avoid every recorded pair: see _pre_fit)
-        if len(all_cols) != len(self._hist_indices):
-            all_ip = np.asarray(all_ip, np.int64)
-            m.engine.set_recorded_pairs(all_ip[lo:hi + 1] - all_ip[lo], all_cols[all_ip[lo]:all_ip[hi]])
+    # ---- cdae.py:34-45 ---------------------------------------------------------------------------
+    _trainer = None       # how this fit() trains, and all the state of that: one of cdae_fit's three trainers
+
+    def _pre_fit(self, learning_rate, neg_ratio, reg_rate, **kwds):
+        self._close_trainer()                                        # (the previous fit()'s: draws an early stop left in flight included)
+        world = self._world()
+        if world is not None:
+            t = cdae_fit.ShardedTrainer(self, world[0], world[1], learning_rate, neg_ratio, reg_rate, kwds)
+        elif self.mode == 'reference':
+            t = cdae_fit.ReferenceTrainer(self, learning_rate, neg_ratio, reg_rate, kwds)
         else:
-            m.engine.set_recorded_pairs(None, None)
-        self._pipeline = self._pending = None
+            t = cdae_fit.SampledTrainer(self, learning_rate, neg_ratio, reg_rate, kwds)
+        self._trainer, self._engine, self._sampler = t, t.engine, t.sampler
         self._register_tables()
-        self._sampler = PointSampler(ds, neg_ratio, self.interaction_threshold, self.seed)
-        self._mask_seed = int(self.seed if self.seed is not None else 0)
-        self._mask_rng = None
 
-    def _glorot_like_single_gpu(self, seed):
-        rng = np.random.default_rng(seed)
+    @property
+    def _dist_model(self):      # the sharded model while a sharded fit() trains, else None (tests ask whether one was built)
+        return getattr(self._trainer, 'model', None)
 
-        def glorot(shape):
-            fi, fo = (shape[0], shape[0]) if len(shape) == 1 else (shape[0], shape[1])
-            lim = np.sqrt(6.0 / (fi + fo))
-            return rng.uniform(-lim, lim, size=shape).astype(np.float32)
-        k = self.hidden_factors
-        return dict(W=glorot((self.n_items, k)), W_=glorot((k, self.n_items)), V=glorot((self.n_users, k)), b=glorot((k,)),
-                    b_=glorot((self.n_items,)))
+    def _close_trainer(self):
+        t, self._trainer = self._trainer, None
+        if t is not None:
+            t.close()
 
-    def _pre_fit_distributed(self, rank, world, learning_rate, neg_ratio, reg_rate, **kwds):
-        import torch.distributed as dist
-        from ..dist import ColumnShardedCdae
-        if kwds.get('epoch_callback_fn') is not None or kwds.get('early_stopping_rule') is not None:
-            raise Exception('epoch callbacks / early stopping need the whole model at every call: not available while it is sharded')
-        if self.layout == 'rows':
-            return self._pre_fit_rows(rank, world, learning_rate, neg_ratio, reg_rate, **kwds)
-        ds = self.interaction_dataset
-        self._hist_indptr, self._hist_indices = ds.positives_csr(self.interaction_threshold)
-        seed = self.seed if self.seed is not None else 0
-        m = ColumnShardedCdae(self.n_users, self.n_items, self.hidden_factors, rank, world, self.device, self._hist_indptr,
-                              self._hist_indices, seed=seed, lr=learning_rate, reg=reg_rate, optimizer=self.sparse_optimizer,
-                              loss=self._loss_name, q=self.corruption_level, cpu_staging=(dist.get_backend() == 'gloo'),
-                              prepare=kwds.get('prepare', 'turns' if world >= 4 else 'local'))     # who sorts the touch lists: dist.py
-        weights = kwds.get('initial_weights')
-        n_params = (2 * self.n_items + self.n_users) * self.hidden_factors
-        if weights is None and n_params <= (1 << 26):                # the single-GPU initialisation, sliced
-            weights = self._glorot_like_single_gpu(seed)
-        if weights is not None:
-            m.set_params_global(**weights)
-        self._dist_model, self._engine = m, m.engine
-        all_ip, all_cols, _ = ds.interaction_csr()                  # (negatives avoid every recorded pair: see _pre_fit)
-        m.engine.set_recorded_pairs(*((all_ip, all_cols) if len(all_cols) != len(self._hist_indices) else (None, None)))
-        self._pipeline = self._pending = None
-        self._register_tables()
-        self._sampler = PointSampler(ds, neg_ratio, self.interaction_threshold, self.seed)
-        self._mask_seed = int(self.seed if self.seed is not None else 0)
-        self._mask_rng = None
+    def __del__(self):
+        try:
+            self._close_trainer()
+        except Exception:
+            pass
 
     def _register_tables(self):
         """cdae.py:35-43: the five variables, registered in the order W, W_, V, b, b_ (their Adam counters: t = 5*step + j + 1).
@@ -161,102 +113,27 @@ class CDAE(RecommenderABC):
     def _fused_trainables(self):
         return [self.W, self.W_, self.V, self.b, self.b_]
 
+    # ---- the reference's training hooks: methods here because subclasses override them, work in the trainer (cdae_fit.py) --------
     def _configure_optimizer(self):
-        """Reference mode trains with the registered optimizer's dense rule — Keras Adam by default, or an optimizers.Adam / Adagrad /
-        SGD / RMSprop passed as `optimizer=`; sampled mode with the constructor's `sparse_optimizer` unless `optimizer=` forces another
-        of ITS kinds (adagrad / adam / rowwise_adagrad: the sparse step has no SGD or RMSprop)."""
-        from ..optimizers import N_SLOTS
-        o, e = self.optimizer, self._engine
-        kind = getattr(o, 'kind', None)
-        if getattr(self, '_dist_model', None) is not None:
-            if self._optimizer_forced:
-                raise Exception('optimizer= cannot be forced on a sharded fit() (layout="rows" or "columns"): choose the sparse rule with '
-                                'CDAE(sparse_optimizer=...) — adagrad, adam or rowwise_adagrad')
-            return
-        if self.mode == 'reference':
-            if kind not in N_SLOTS or kind == 'rowwise_adagrad':
-                raise Exception(f'CDAE mode="reference" trains with the dense rules adam, adagrad, sgd, rmsprop (got {o!r}); '
-                                f'rowwise_adagrad exists in mode="sampled"')
-        else:
-            if not self._optimizer_forced:
-                return
-            if kind not in ('adam', 'adagrad', 'rowwise_adagrad'):
-                raise Exception(f'CDAE mode="sampled" has no sparse {kind} step (got {o!r}): choose CDAE(sparse_optimizer=...) among '
-                                f"'adagrad', 'adam', 'rowwise_adagrad', or train with mode=\"reference\", whose dense step takes sgd and rmsprop")
-        if kind == 'adam':
-            same = e.s2 is not None and e.opt_kind == 0 and (e.lr, e.beta1, e.beta2, e.opt_eps) == (o.learning_rate, o.beta_1, o.beta_2, o.epsilon)
-            if not same:                                   # (the slots _pre_fit allocated are kept when nothing differs)
-                e.init_optimizer('adam', o.learning_rate, e.reg_rate, o.beta_1, o.beta_2, o.epsilon)
-        elif kind in ('adagrad', 'rowwise_adagrad'):
-            e.init_optimizer(kind, o.learning_rate, e.reg_rate, eps=o.epsilon, initial_accumulator=o.initial_accumulator_value)
-        else:
-            e.init_optimizer(kind, o.learning_rate, e.reg_rate, eps=getattr(o, 'epsilon', None), momentum=o.momentum, rho=getattr(o, 'rho', 0.9))
+        self._trainer.configure_optimizer(self.optimizer, self._optimizer_forced)
 
-    # ---- cdae.py:34-45 ---------------------------------------------------------------------------
-    def _pre_fit(self, learning_rate, neg_ratio, reg_rate, **kwds):
-        from .. import _lib
-        from ..engine import CdaeEngine
-        ds = self.interaction_dataset
-        self._dist_model = None
-        world = self._world()
-        if world is not None:
-            return self._pre_fit_distributed(world[0], world[1], learning_rate, neg_ratio, reg_rate, **kwds)
-        self._engine = CdaeEngine(self.n_users, self.n_items, self.hidden_factors, device=self.device)
-        self._pipeline = None
-        self._close_drawahead()                                      # (draws an early-stopped fit() left in flight included)
-        self._pending = None
-        weights = kwds.get('initial_weights')
-        if weights is not None:                      # injected weights (TF's GlorotUniform stream is not reproducible)
-            self._engine.set_params(**weights)
-        else:
-            seed = self.seed if self.seed is not None else np.random.SeedSequence().entropy % (2 ** 32)
-            n_params = (2 * self.n_items + self.n_users) * self.hidden_factors
-            # large tables are drawn on the device (same distribution, torch's generator instead of numpy's)
-            (self._engine.init_glorot_device if n_params > (1 << 26) else self._engine.init_glorot)(seed)
-        self._hist_indptr, self._hist_indices = ds.positives_csr(self.interaction_threshold)
-        self._max_degree = int(np.diff(self._hist_indptr).max()) if len(self._hist_indptr) > 1 else 0
-        self._engine.set_history(self._hist_indptr, self._hist_indices)
-        # the device PointSampler draws negatives among the pairs ABSENT from the frame (point_sampler.py:56): where the frame records
-        # pairs below the threshold too, it needs the CSR of every recorded pair
-        all_ip, all_cols, _ = ds.interaction_csr()
-        self._engine.set_recorded_pairs(*((all_ip, all_cols) if len(all_cols) != len(self._hist_indices) else (None, None)))
-        if self.mode == 'reference':
-            self._engine.init_optimizer('adam', learning_rate, reg_rate)
-        else:
-            self._engine.init_optimizer(self.sparse_optimizer, learning_rate, reg_rate)
-        self._register_tables()
-        self._sampler = PointSampler(ds, neg_ratio, self.interaction_threshold, self.seed)
-        L = _lib.lib()
-        seed = self.seed if self.seed is not None else self._rng.getrandbits(62)
-        self._mask_rng = L.drx_rng_create(int(seed))    # same MT19937 stream as self._rng = random.Random(seed)
-        # a second generator on the same stream: inside fit() two worker threads draw batches t+1 and t+2 at once, each from
-        # its own generator advanced to where its batch begins (a batch always consumes 2·N·B words: cdae.py:63 draws for
-        # every item of every row), so the stream is still consumed strictly batch by batch
-        self._mask_rngs = [self._mask_rng, L.drx_rng_create(int(seed))]
-        self._mask_at = [0, 0]                          # words each generator has consumed
-        self._mask_pos = 0                              # where the next batch begins
-        self._draw_ticket = 0
-        self._L, self._q_float = L, float(self.corruption_level)
-        # (reference mode only: the draw-ahead workers need the native host sampler, which a device-sampled fit never builds)
-        self._drawahead = None
-        if self.mode == 'reference':
-            self._drawahead = L.drx_drawahead_create(self._sampler._host._h, self._mask_rngs[0], self._mask_rngs[1],
-                                                     self._hist_indptr.ctypes.data, self._hist_indices.ctypes.data, self.n_items)
-        self._mask_seed = int(seed)
+    def _sample_batch(self, batch_size, **kwds):       # cdae.py:47
+        return self._trainer.sample(batch_size, **kwds)
 
-    def _close_drawahead(self):
-        if getattr(self, '_drawahead', None):
-            from .. import _lib
-            self._drain_draws()
-            _lib.lib().drx_drawahead_destroy(self._drawahead)
-        self._drawahead = None
-        self._pending = None
+    def _do_batch(self, batch_samples, step=0, want_loss=False, **kwds):
+        return self._trainer.step(batch_samples, step, want_loss)
 
-    def __del__(self):
-        try:
-            self._close_drawahead()
-        except Exception:
-            pass
+    def _run_steps(self, first_step, n_steps, batch_size, **kwds):
+        """fit()'s quiet path: the trainer's own loop over the remaining epochs (ReferenceTrainer.run_steps: one library call), when these
+        very hooks would have run — a subclass or an instance that replaces _sample_batch or _do_batch gets the per-step loop.
+        Returns the steps done."""
+        if not getattr(self, 'fused_fit', True) or n_steps < 1:
+            return 0
+        for hook in ('_sample_batch', '_do_batch'):
+            if hook in self.__dict__ or getattr(type(self), hook) is not getattr(CDAE, hook):
+                return 0
+        with self._device_lock:
+            return self._trainer.run_steps(first_step, n_steps, batch_size)
 
     def _restore_engine(self, params):
         from ..engine import CdaeEngine
@@ -266,159 +143,13 @@ class CDAE(RecommenderABC):
         self._hist_indptr, self._hist_indices = ip, idx
         self._engine.set_history(ip, idx)
 
-    def _sample_batch(self, batch_size, **kwds):       # cdae.py:47
-        if self.mode == 'sampled' and self.device_sampler:
-            # the device sampler runs two batches ahead of the training stream inside SampledPipeline; this hook only
-            # makes sure the pipeline exists for this batch size and hands _do_batch a token
-            pipe = getattr(self, '_pipeline', None)
-            if pipe is None or pipe.B != batch_size:
-                from ..engine import SampledPipeline
-                first = 0 if pipe is None else pipe.next
-                ms = self._mask_seed
-                seeds = (lambda s: ms * 7919 + first + s + 1, lambda s: ms + 0x9E3779B9 * (first + s + 1))
-                dm = getattr(self, '_dist_model', None)
-                if dm is not None and self.layout == 'rows':
-                    # every rank draws ITS users' triples: the seeds differ by rank (row_seeds below; tests replay them)
-                    from ..dist import ShardedPipeline
-                    from ..engine import DeviceBatchSource
-                    rs = self.row_seeds(ms, dm.rank, dm.world, first)
-                    src = DeviceBatchSource(dm.engine, batch_size, self._sampler.neg_ratio, self.corruption_level, rs[0], rs[1],
-                                            n_items=self.n_items, stream_slot=0)      # (the pipeline's own run-ahead stream: engine.DeviceBatchSource)
-                    pipe = self._pipeline = ShardedPipeline(dm, src, max(1, self._fit_epochs - first))
-                    pipe.B = batch_size
-                elif dm is not None:                                     # the same seeds on every rank: the same batches
-                    pipe = self._pipeline = dm.pipeline(batch_size, self._sampler.neg_ratio, *seeds)
-                else:
-                    pipe = self._pipeline = SampledPipeline(self._engine, batch_size, self._sampler.neg_ratio, self.corruption_level,
-                                                            *seeds, loss=self._loss_name)
-            return ('device-batch', pipe.next)
-        if self.mode == 'sampled' and kwds.get('as_arrays', True):
-            return self._sampler.sample_arrays(batch_size)      # (uid, iid, value, is_negative) numpy arrays
-        if self.mode == 'reference':
-            return self._reference_batch(batch_size, kwds.get('batches_after', 1 if kwds.get('more_to_come', False) else 0))
-        return self._sampler.sample(batch_size)                  # list of (uid, iid, value) like the reference
-
     @staticmethod
     def row_seeds(mask_seed, rank, world, first=0):
         """(sample seed, corruption-mask seed) of step s on rank `rank` of a row-sharded fit"""
         return (lambda s: (mask_seed * 7919 + first + s + 1) * world + rank,
                 lambda s: (mask_seed + 0x9E3779B9 * (first + s + 1)) * world + rank)
 
-    class _Batch:
-        """What _sample_batch hands _do_batch in reference mode: the reference's list of (uid, iid, value) triples — built only
-        if somebody looks at it (len / iteration / indexing) — carrying what the fused step needs: the users and the
-        corruption stream's keep flags, already in a pinned staging slot of the engine."""
-
-        def __init__(self, arrays, val_type):
-            self._arrays, self._val_type, self._list = arrays, val_type, None
-            self.uid = self.keep_off = self.keep = self.slot = None
-
-        def _triples(self):
-            if self._list is None:
-                u, i, v, neg = self._arrays
-                vt = self._val_type
-                self._list = [(a, b, 0) if ng else (a, b, vt(c)) for a, b, c, ng in zip(u.tolist(), i.tolist(), v.tolist(), neg.tolist())]
-            return self._list
-
-        def __len__(self):
-            return len(self._arrays[0])
-
-        def __iter__(self):
-            return iter(self._triples())
-
-        def __getitem__(self, k):
-            return self._triples()[k]
-
-    def _submit_draw(self, batch_size):
-        """Claims the next batch's place in both streams (sampler ticket, corruption words) and its buffers — a pinned staging
-        slot of the engine for users / offsets / keep flags — and hands the job to the native draw-ahead worker of its
-        generator (drx_drawahead_submit).  Returns what _finish_draw needs."""
-        from .. import _lib
-        B = int(batch_size)
-        ticket = self._draw_ticket                      # (the counters move only once the job is really queued: a ticket that
-        gen = ticket % 2                                #  was handed out but never submitted would stall both workers)
-        at = self._mask_pos
-        discard = at - self._mask_at[gen]
-        cap = max(B * self._max_degree, 1)
-        if self._engine.device.type == 'cuda':
-            stage = self._engine.stage_acquire(B, cap)
-            extra = self._engine.stage_extra(stage[0])
-            ptrs = self._engine.stage_pointers(stage[0])
-        else:
-            stage = (None, np.empty(B, np.int32), np.empty(B + 1, np.int32), np.empty(cap, np.uint8))
-            extra = (np.empty(B, np.int32), np.empty(B, np.float64), np.empty(B, np.uint8))
-            ptrs = (stage[1].ctypes.data, extra[0].ctypes.data, extra[1].ctypes.data, extra[2].ctypes.data, stage[2].ctypes.data,
-                    stage[3].ctypes.data, len(stage[3]))
-        job = self._L.drx_drawahead_submit(self._drawahead, gen, ticket, discard, B, self._q_float, *ptrs)
-        if job < 0:
-            _lib.check(int(job), 'drx_drawahead_submit')
-        self._draw_ticket = ticket + 1
-        self._mask_pos = self._mask_at[gen] = at + 2 * self.n_items * B
-        return B, gen, int(job), stage, extra
-
-    def _finish_draw(self, entry):
-        from .. import _lib
-        B, gen, job, stage, extra = entry
-        rc = self._L.drx_drawahead_wait(self._drawahead, gen, job)
-        if rc:
-            _lib.check(rc, 'drx_cdae_reference_draw')
-        slot, uid_v, ko_v, kp_v = stage
-        batch = CDAE._Batch((uid_v,) + extra, self._sampler._val_type)
-        batch.slot, batch.uid, batch.keep_off = slot, uid_v, ko_v
-        batch.keep = kp_v[:max(int(ko_v[B]), 1)]
-        return batch
-
-    def _drain_draws(self):
-        """Waits for (does not consume) the draws in flight: whoever touches the sampler or a generator directly comes after."""
-        from .. import _lib
-        for B, gen, job, _, _ in (getattr(self, '_pending', None) or []):
-            _lib.lib().drx_drawahead_wait(self._drawahead, gen, job)
-
-    _DRAW_AHEAD = 4        # batches in flight: two per worker
-
-    def _reference_batch(self, batch_size, batches_after):
-        """Inside fit() the host work of the next batches (sampler triples, N uniform draws per row) runs on the two native
-        draw-ahead threads of libdrx while batch t trains; the streams are still consumed strictly batch by batch, and nothing
-        is drawn beyond the last epoch."""
-        pending = getattr(self, '_pending', None) or []
-        self._pending = None
-        if pending and pending[0][0] == batch_size:
-            batch = self._finish_draw(pending.pop(0))
-        else:
-            for entry in pending:                                  # (batches of another size were drawn: consumed, like draws)
-                self._finish_draw(entry)
-            pending = []
-            batch = self._finish_draw(self._submit_draw(batch_size))
-        while len(pending) < min(self._DRAW_AHEAD, batches_after):
-            pending.append(self._submit_draw(batch_size))
-        self._pending = pending or None
-        return batch
-
-    def _run_steps(self, first_step, n_steps, batch_size, **kwds):
-        """fit()'s quiet path in reference mode: the whole sample -> step loop of the remaining epochs in one library call
-        (drx_cdae_fit_dense), when these very hooks would have run — a subclass or an instance that replaces _sample_batch or
-        _do_batch gets the per-step loop.  Same streams, same arithmetic, same launches as that loop; returns the steps done."""
-        if (self.mode != 'reference' or getattr(self, '_dist_model', None) is not None or self._engine.device.type != 'cuda'
-                or not getattr(self, 'fused_fit', True) or n_steps < 1 or getattr(self, '_pending', None)):
-            return 0
-        for hook in ('_sample_batch', '_do_batch', '_reference_batch', '_submit_draw', '_finish_draw'):
-            if hook in self.__dict__ or getattr(type(self), hook) is not getattr(CDAE, hook):
-                return 0
-        B = int(batch_size)
-        from ..engine import CdaeEngine
-        if max(B * self._max_degree, 1) * CdaeEngine._FIT_SLOTS > (1 << 30):      # (the loop's pinned staging ring would exceed 1 GB)
-            return 0
-        cursor = np.array([self._draw_ticket, self._mask_pos, self._mask_at[0], self._mask_at[1]], dtype=np.int64)
-        try:
-            with self._device_lock:
-                self._engine.fit_dense(self._drawahead, cursor, B, self.corruption_level, max(B * self._max_degree, 1), first_step,
-                                       n_steps, self._loss_name, self.loss_targets)
-        finally:                                        # (what the call consumed of the streams, also when it raised)
-            self._draw_ticket, self._mask_pos = int(cursor[0]), int(cursor[1])
-            self._mask_at = [int(cursor[2]), int(cursor[3])]
-        return n_steps
-
-    # ---- fused training step (replaces recommender_abc.py:190-204 for this model) ------------------------------------
+    # ---- what the trainers' steps and the compatibility hooks share -----------------------------------------------------
     def _batch_arrays(self, batch_samples):
         if isinstance(batch_samples, tuple) and len(batch_samples) == 4 and hasattr(batch_samples[0], 'dtype'):
             return batch_samples[0], batch_samples[1], batch_samples[2]
@@ -428,59 +159,8 @@ class CDAE(RecommenderABC):
         return u, i, v
 
     def _corruption_keep(self, uid, gen=0, at=None, out=None):
-        """MT19937 corruption stream of cdae.py:63 for the batch rows (C++ host, N draws per row, batch order).  gen / at: which
-        generator draws and the word of the stream where this batch begins (default: the next unclaimed one)."""
-        from .. import _lib
-        B = len(uid)
-        if at is None:                                   # a draw outside fit()'s run-ahead: after whatever is in flight
-            self._drain_draws()
-            at, self._mask_pos = self._mask_pos, self._mask_pos + 2 * self.n_items * B
-        rng = self._mask_rngs[gen]
-        assert at >= self._mask_at[gen], 'corruption stream claimed out of order'
-        if at > self._mask_at[gen]:
-            _lib.lib().drx_rng_discard(rng, at - self._mask_at[gen])
-        self._mask_at[gen] = at + 2 * self.n_items * B
-        uid32 = np.ascontiguousarray(uid, dtype=np.int32)
-        if out is not None:                               # caller's buffers (a pinned staging slot): keep holds B * max degree
-            keep_off, keep = out
-        else:
-            u64 = uid32.astype(np.int64)
-            keep_off = np.zeros(B + 1, dtype=np.int32)
-            keep = np.zeros(max(int((self._hist_indptr[u64 + 1] - self._hist_indptr[u64]).sum()), 1), dtype=np.uint8)
-        _lib.check(_lib.lib().drx_rng_corruption_keep(
-            rng, self._hist_indptr.ctypes.data, self._hist_indices.ctypes.data, self.n_items,
-            uid32.ctypes.data, B, float(self.corruption_level), keep_off.ctypes.data, keep.ctypes.data, len(keep)),
-            'drx_rng_corruption_keep')
-        return keep_off, (keep if out is None else keep[:max(int(keep_off[B]), 1)])
-
-    def _do_batch(self, batch_samples, step=0, want_loss=False, **kwds):
-        eng = self._engine
-        if self.mode == 'sampled' and self.device_sampler:       # batch drawn and indexed ahead of time on the device
-            loss = self._pipeline.run_step(want_loss=want_loss)
-            if not want_loss:
-                return None
-            return float(loss) if isinstance(loss, float) else float(loss[0].item())
-        if self.mode == 'reference' and getattr(batch_samples, 'slot', None) is not None:     # already in pinned memory
-            bt = eng.batch_in_slot(batch_samples.slot, len(batch_samples.uid), int(batch_samples.keep_off[-1]), self.corruption_level)
-            loss = eng.step_dense(step, bt, self._loss_name, self.loss_targets, want_loss=want_loss)
-            eng.stage_release(batch_samples.slot)
-            return float(loss.sum().item()) if want_loss else None
-        if self.mode == 'reference' and getattr(batch_samples, 'keep', None) is not None:
-            uid, keep_off, keep = batch_samples.uid, batch_samples.keep_off, batch_samples.keep      # prepared by _sample_batch
-            bt, alive = eng.make_batch(uid, keep_off=keep_off, keep=keep, q=self.corruption_level, n_touch_slots=int(keep_off[-1]))
-            loss = eng.step_dense(step, bt, self._loss_name, self.loss_targets, want_loss=want_loss)
-            return float(loss.sum().item()) if want_loss else None
-        uid, iid, val = self._batch_arrays(batch_samples)
-        if self.mode == 'reference':
-            keep_off, keep = self._corruption_keep(uid)
-            bt, alive = eng.make_batch(uid, keep_off=keep_off, keep=keep, q=self.corruption_level,
-                                       n_touch_slots=int(keep_off[-1]))
-            loss = eng.step_dense(step, bt, self._loss_name, self.loss_targets, want_loss=want_loss)
-            return float(loss.sum().item()) if want_loss else None
-        y = (val >= self.interaction_threshold).astype(np.float32)
-        bt, alive = eng.make_batch(uid, iid, y, q=self.corruption_level, mask_seed=self._mask_seed + 0x9E3779B9 * (step + 1))
-        loss = eng.step_sparse(step, bt, self._loss_name, want_loss=want_loss)
-        return float(loss[0].item()) if want_loss else None
+        """MT19937 corruption stream of cdae.py:63 for the batch rows: cdae_fit.CorruptionStream.keep"""
+        return self._trainer.stream.keep(uid, gen, at, out)
 
     # ---- hooks kept for API compatibility (cdae.py:50-82) ---------------------------------------------------
     def _predict_batch(self, batch_samples, **kwds):

@@ -39,8 +39,8 @@ from .early_stopping import InvalidEpochValidationResultsException
 from .loss_tracker import LossTracker
 
 _LOG_FORMAT = '[%(asctime)s] (%(levelname)s) %(name)s: %(message)s'
-_UNPICKLED = ('_engine', '_logger', '_file_logger', '_device_lock', '_sampler', '_mask_rng', '_mask_rngs', '_drawahead', '_L', 'epoch_weights', '_pipeline', '_pending',
-              '_host_pool', '_dist_model', 'optimizer', 'trainable_vars', 'trainable_weights', 'trainable_layers', 'trainable_models',
+_UNPICKLED = ('_engine', '_logger', '_file_logger', '_device_lock', '_sampler', '_trainer', 'epoch_weights',
+              '_host_pool', 'optimizer', 'trainable_vars', 'trainable_weights', 'trainable_layers', 'trainable_models',
               '_extra_weight', 'W', 'W_', 'V', 'b', 'b_', 'user_nn', 'item_nn', '_layers',
               '_ahead', '_dev_side', '_dev_next')             # (run-ahead state of fit(device_sampler=True): streams, events, device batches)
 

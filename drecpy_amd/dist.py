@@ -475,6 +475,15 @@ class ShardedCdae:
         b_l = np.zeros(ipr, dt); b_l[:hi - lo] = b_[lo:hi]
         self.ops.set_params(Wl, W_l, np.asarray(V[self.user_lo:self.user_hi], dt), np.asarray(b, dt), b_l)
 
+    def pipeline(self, batch_size, neg_ratio, sample_seed_of, mask_seed_of, n_steps):
+        """ShardedPipeline over this rank for `n_steps` steps of `batch_size` triples of ITS users, drawn on the device from the seeds
+        of step s (they differ by rank) on the pipeline's own run-ahead stream (engine.DeviceBatchSource)."""
+        from .engine import DeviceBatchSource
+        src = DeviceBatchSource(self.engine, batch_size, neg_ratio, self.q, sample_seed_of, mask_seed_of, n_items=self.n_items, stream_slot=0)
+        pipe = ShardedPipeline(self, src, max(1, n_steps))
+        pipe.B = batch_size
+        return pipe
+
     def gather_params_global(self):
         """The whole model on every rank (reference orientation: W [N,K], W_ [K,N], V [U,K], b [K], b_ [N]) — for evaluation or
         export after training; an infrequent host-side gather, not part of a step."""

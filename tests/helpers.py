@@ -130,3 +130,15 @@ def retry_infra(fn):
                   flush=True)
             return fn(*a, **k)
     return wrapper
+
+
+def count_library_calls(monkeypatch, *names):
+    """Wraps the named functions of the loaded libdrx for the test; returns {name: calls so far}."""
+    from drecpy_amd import _lib
+    L, calls = _lib.lib(), {name: 0 for name in names}
+    for name in names:
+        def counted(*args, _fn=getattr(L, name), _name=name):
+            calls[_name] += 1
+            return _fn(*args)
+        monkeypatch.setattr(L, name, counted)
+    return calls

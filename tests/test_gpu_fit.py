@@ -252,7 +252,8 @@ def test_quiet_fit_in_the_library_equals_the_step_by_step_loop(epochs):
         m = CDAE(hidden_factors=24, corruption_level=0.3, seed=21, verbose=False)
         m.fused_fit = fused
         m.fit(ds, epochs=epochs, batch_size=16, learning_rate=2e-3, reg_rate=1e-3, neg_ratio=3, initial_weights=w)
-        state = (m._draw_ticket, m._mask_pos, list(m._mask_at))
+        st = m._trainer.stream
+        state = (st.ticket, st.pos, list(st.at))
         nxt = m._sampler.sample(5)                      # where the sampler stream stands
         keep = m._corruption_keep(np.array([1, 2, 3], np.int32))     # where the corruption stream stands
         e = m._engine
@@ -281,6 +282,36 @@ def test_quiet_fit_is_left_to_python_when_a_hook_is_replaced():
     m._sample_batch = lambda *a, **k: (seen.append('s'), orig(*a, **k))[1]
     m.fit(ds, epochs=2, batch_size=8)
     assert seen[-2:] == ['s', 's']
+
+
+def test_fits_destroy_the_generators_and_draw_ahead_handles_they_create(monkeypatch):
+    """Two reference-mode fit()s on one object, then the object goes: every MT19937 generator and draw-ahead handle the fits created
+    in the library was destroyed (the handle before the generators it points at: cdae_fit.ReferenceTrainer.close)."""
+    import gc
+    from helpers import count_library_calls
+    from drecpy_amd.Dataset import InteractionDataset
+    from drecpy_amd.Recommender import CDAE
+    ds = InteractionDataset.read_df(_frame(), verbose=False)
+    gc.collect()                                    # (models of earlier tests go now, not while this one counts)
+    calls = count_library_calls(monkeypatch, 'drx_rng_create', 'drx_rng_destroy', 'drx_drawahead_create', 'drx_drawahead_destroy')
+    m = CDAE(hidden_factors=8, seed=10, verbose=False)
+    m.fit(ds, epochs=3, batch_size=16)
+    m.fit(ds, epochs=3, batch_size=16)
+    del m
+    gc.collect()
+    assert calls == {'drx_rng_create': 4, 'drx_rng_destroy': 4, 'drx_drawahead_create': 2, 'drx_drawahead_destroy': 2}
+
+
+def test_a_device_sampled_fit_at_another_batch_size_follows_on_the_same_object():
+    import torch
+    from drecpy_amd.Dataset import InteractionDataset
+    from drecpy_amd.Recommender import CDAE
+    ds = InteractionDataset.read_df(_frame(), verbose=False)
+    m = CDAE(hidden_factors=8, mode='sampled', device_sampler=True, seed=3, verbose=False)
+    m.fit(ds, epochs=6, batch_size=64, learning_rate=0.05)
+    m.fit(ds, epochs=6, batch_size=96, learning_rate=0.05)
+    torch.cuda.synchronize()
+    assert all(bool(torch.isfinite(t).all()) for t in m._engine.tables())
 
 
 @pytest.mark.parametrize('implicit', [True, False])

@@ -142,6 +142,46 @@ def test_two_generators_leapfrogging_the_corruption_stream_equal_one():
         L.drx_rng_destroy(r)
 
 
+def test_corruption_stream_class_draws_one_stream_from_two_generators_and_frees_them(monkeypatch):
+    """cdae_fit.CorruptionStream on 5 users x 7 items (histories of 0, 1, 7, 3 and 2 entries): consecutive batches are
+    random.Random(seed) drawn in the reference's order (cdae.py:63) whichever of its two generators draws them, the cursor counts two
+    words per draw, a claim behind a generator's position is refused, and close() destroys what the constructor created."""
+    from helpers import count_library_calls
+    from drecpy_amd.Recommender.cdae_fit import CorruptionStream
+    from oracle import data_oracle as do
+    calls = count_library_calls(monkeypatch, 'drx_rng_create', 'drx_rng_destroy')
+    N, B, q, seed = 7, 4, 0.3, 10
+    rows = [np.asarray(r, np.int64) for r in ([], [3], list(range(7)), [0, 2, 6], [1, 5])]
+    indptr = np.cumsum([0] + [len(r) for r in rows]).astype(np.int64)
+    indices = np.concatenate(rows).astype(np.int32)
+    batches = [np.array(b, np.int32) for b in ([0, 1, 2, 3], [2, 2, 4, 0], [1, 4, 3, 2])]
+    py = random.Random(seed)
+    want = [do.corruption_keep_mask(py, B, N, q) for _ in batches]
+
+    def check(flags, uids, mask):
+        keep_off, keep = flags
+        assert keep_off[0] == 0 and keep_off.tolist()[1:] == np.cumsum([len(rows[u]) for u in uids]).tolist()
+        for b, u in enumerate(uids):
+            assert keep[keep_off[b]:keep_off[b + 1]].astype(bool).tolist() == mask[b, rows[u]].tolist()
+
+    one = CorruptionStream(seed, indptr, indices, N, q)                 # every batch on generator 0
+    for t, u in enumerate(batches):
+        check(one.keep(u), u, want[t])
+        assert one.cursor().tolist() == [0, 2 * N * B * (t + 1), 2 * N * B * (t + 1), 0]
+    two = CorruptionStream(seed, indptr, indices, N, q)                 # as the draw-ahead workers: generator t % 2, place -> draw -> claim
+    for t, u in enumerate(batches):
+        ticket, gen, skip = two.place()
+        assert (ticket, gen, skip) == (t, t % 2, 2 * N * B * (0, 1, 1)[t])      # (each generator skips the other's batch)
+        check(two.keep(u, gen=gen, at=two.pos), u, want[t])
+        two.claim(gen, B)
+    assert two.cursor().tolist() == [3, 2 * N * B * 3, 2 * N * B * 3, 2 * N * B * 2]
+    with pytest.raises(AssertionError, match='out of order'):
+        two.keep(batches[0], gen=1, at=2 * N * B)                       # generator 1 stands behind batch 1 already
+    assert two.cursor().tolist() == [3, 2 * N * B * 3, 2 * N * B * 3, 2 * N * B * 2]
+    one.close(), two.close(), two.close()
+    assert calls == {'drx_rng_create': 4, 'drx_rng_destroy': 4}
+
+
 def test_native_draw_ahead_workers_reproduce_the_sequential_streams():
     """drx_drawahead_*: the two native worker threads of reference-mode fit() (sampler triples in ticket order, each worker's
     corruption generator advanced past the other's batches) against one sampler + one generator drawing batch after batch."""
