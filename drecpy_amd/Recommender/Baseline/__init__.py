@@ -1,5 +1,6 @@
 from .base_knn import BaseKNN
+from .bpr import BPR
 from .item_knn import ItemKNN
 from .user_knn import UserKNN
 
-__all__ = ['BaseKNN', 'ItemKNN', 'UserKNN']
+__all__ = ['BaseKNN', 'BPR', 'ItemKNN', 'UserKNN']

@@ -281,6 +281,12 @@ SIGNATURES = {
                                          C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_float, C.c_float, C.c_float,
                                          C.POINTER(OptRule), C.c_void_p]),
     'drx_rows_csr_opt_multi': (C.c_int, [C.POINTER(CsrAdamTable), C.c_int32, C.POINTER(OptRule), C.c_void_p]),
+    'drx_bpr_sample': (C.c_int, [C.POINTER(History), C.POINTER(History), C.c_void_p, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_uint64,
+                                 C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
+    'drx_bpr_gather_rows': (C.c_int, [C.c_void_p, C.c_int32, C.c_void_p, C.c_int32, C.c_void_p, C.c_void_p]),
+    'drx_bpr_step_scratch_bytes': (C.c_size_t, [C.c_int32, C.c_int32, C.c_int32, C.c_int32]),
+    'drx_bpr_step': (C.c_int, [C.c_void_p] * 9 + [C.c_int32, C.c_int32, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int32,
+                               C.POINTER(OptRule), C.POINTER(C.c_float), C.c_float, C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p]),
     'drx_caser_step_small_opt': (C.c_int, [C.POINTER(CaserDims), C.POINTER(CaserArgs), C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p,
                                            C.POINTER(AdamSegments), C.POINTER(OptRule), C.c_void_p]),
     'drx_dmf_step_small_opt': (C.c_int, [C.POINTER(DmfDims), C.POINTER(DmfArgs), C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p,

@@ -1212,6 +1212,47 @@ int drx_cdae_fit_dense(const DrxCdaeParams *p, const DrxOptim *opt, const DrxHis
                        const float *h_alphas, void *h_slots, size_t slot_bytes, int32_t n_slots, void *d_stage,
                        size_t d_stage_bytes, void *scratch, size_t scratch_bytes, void *stream);
 
+/* ---- BPR-MF (Rendle et al. 2009; csrc/drx_bpr.hip) ----------------------------------------------------
+ * Score x(u, i) = P[u] . Q[i] + bq[i]  (DRX_REC_BIAS of the fused scorer).  P [n_users, ld], Q [n_items, ld], bq [n_items]; ld = K
+ * rounded up to a multiple of 4, 4 <= ld <= 256, the padding columns zero — every call below keeps them zero.
+ *
+ * THE TRIPLE STREAM (counter-based, no retry loop; every index is (h * n) >> 32 in 64-bit integers, h = drx_hash_u32(seed, a, b)).
+ * With r = neg_ratio >= 1, triple t of a batch belongs to pair p = t / r:
+ *     u = eligible[(h(p, 0) * n_eligible) >> 32]
+ *     i = the positive of u at position (h(p, 1) * deg_u) >> 32 of u's row of `hist`
+ *     j = the item at rank (h(t, 2) * (n_items - nrec_u)) >> 32 of the ascending complement of u's row of `recorded`
+ * hist: CSR of the positives (columns ascending); recorded: CSR of every pair the frame holds (NULL = hist), as in
+ * drx_point_sample_recorded.  eligible: the users with at least one positive and fewer than n_items recorded items (built by the caller,
+ * device int32 [n_eligible]); a listed user who is not eligible gets -1 for the id that cannot be drawn.  One thread per triple.
+ * DRX_EINVAL, and nothing launched: a NULL pointer (hist or its arrays, the arrays of a given `recorded`, eligible, uid, pos, neg),
+ * n_eligible < 1, n_items < 1, T < 1, neg_ratio < 1. */
+int drx_bpr_sample(const DrxHistory *hist, const DrxHistory *recorded, const int32_t *eligible, int32_t n_eligible, int32_t n_items,
+                   int32_t T, int32_t neg_ratio, uint64_t seed, int32_t *uid, int32_t *pos, int32_t *neg, void *stream);
+/* out[r, :] = table[ids[r], :] for n device ids in [0, table rows) (not checked on the device): the query rows of the fused scorer */
+int drx_bpr_gather_rows(const float *table, int32_t ld, const int32_t *ids, int32_t n, float *out, void *stream);
+/* ONE TRAINING STEP on T triples (uid, pos, neg: device int32 [T], ids in range — not checked on the device):
+ *     D_t = x(u, i) - x(u, j);   loss = (1 / T) sum_t softplus(-D_t);   g_t = -sigmoid(-D_t) / T
+ *     dP[u] += g_t (Q[i] - Q[j]);  dQ[i] += g_t P[u];  dQ[j] -= g_t P[u];  dbq[i] += g_t;  dbq[j] -= g_t
+ * then EVERY row of P and Q gets reg * row added to its gradient (bq none) and every row and bias is updated by `rule`, a dense rule
+ * (DrxOptRule): the step sweeps both tables like the other dense steps.  alphas: HOST float [3], the step sizes of P, Q and bq (Adam:
+ * the variable's lr_t; the other rules: the learning rate); rule->lr is ignored.  Slots (P_s1 .. bq_s2): those the rule has, shaped
+ * like their parameter; one it lacks may be NULL and is not touched.
+ * k_bpr_fwd_bwd reads the three rows of a triple once (a group of pick_geom(ld) lanes per triple, one float4 per lane) and writes, per
+ * triple, the gradient row of P[u], a copy of P[u] and the scalars (g_t, -g_t); drx_batch_csr_device groups the T user keys and the
+ * 2 T item keys (i_t, j_t interleaved); ONE drx_rows_csr_opt_multi call updates P (plain form) and Q with bq (outer-product form,
+ * group 2: lookup o has the gradient row scale[o] * copy[o / 2] and the bias gradient scale[o]).  No atomics: every sum runs in an
+ * order fixed by the batch, so equal inputs give equal bits.  The rows are read before the update launch writes them (stream order).
+ * loss_out: device double [1] or NULL (then no loss is summed); the workgroups' partial sums (double) are added in a fixed order.
+ * scratch: drx_bpr_step_scratch_bytes (0 = an invalid description).
+ * DRX_EINVAL, and nothing launched: a NULL pointer among P, Q, bq, uid, pos, neg, rule, alphas, scratch; T < 1; n_users or n_items
+ * < 1; ld outside 4..256 or no multiple of 4; no dense rule; a slot the rule has is NULL; a table or slot not 16-byte aligned.
+ * DRX_ESCRATCH: scratch too small. */
+size_t drx_bpr_step_scratch_bytes(int32_t T, int32_t ld, int32_t n_users, int32_t n_items);
+int drx_bpr_step(float *P, float *Q, float *bq, float *P_s1, float *P_s2, float *Q_s1, float *Q_s2, float *bq_s1, float *bq_s2, int32_t ld,
+                 int32_t n_users, int32_t n_items, const int32_t *uid, const int32_t *pos, const int32_t *neg, int32_t T,
+                 const DrxOptRule *rule, const float *alphas, float reg, double *loss_out, void *scratch, size_t scratch_bytes,
+                 void *stream);
+
 #ifdef __cplusplus
 }
 #endif
