@@ -1,6 +1,7 @@
+from .als import ALS
 from .base_knn import BaseKNN
 from .bpr import BPR
 from .item_knn import ItemKNN
 from .user_knn import UserKNN
 
-__all__ = ['BaseKNN', 'BPR', 'ItemKNN', 'UserKNN']
+__all__ = ['ALS', 'BaseKNN', 'BPR', 'ItemKNN', 'UserKNN']

@@ -1253,6 +1253,50 @@ int drx_bpr_step(float *P, float *Q, float *bq, float *P_s1, float *P_s2, float 
                  const DrxOptRule *rule, const float *alphas, float reg, double *loss_out, void *scratch, size_t scratch_bytes,
                  void *stream);
 
+/* ---- ALS / WMF (Hu, Koren, Volinsky 2008; csrc/drx_als.hip) ----------------------------------------------
+ * Score x(u, i) = X[u] . Y[i]  (DRX_REC_BIAS of the fused scorer with a zero bias).  X [n_users, ld], Y [n_items, ld]; ld = K rounded
+ * up to a multiple of 4, 4 <= ld <= 128, the padding columns zero — every call below keeps them zero.  A positive (u, i) has
+ * preference 1 and confidence 1 + w, w >= 0 given per entry of a CSR of the positives (indptr int64, indices int32, weights float;
+ * user-major for the user half, item-major for the item half).  Objective over ALL n_users x n_items cells:
+ *     L = sum_ui c_ui (p_ui - x_u . y_i)^2 + lambda (|X|^2 + |Y|^2)
+ * Nothing below uses an atomic on a float: every sum runs in an order fixed by its inputs, so equal inputs give equal bits.
+ * Every scratch companion returns 0 for a description outside the domain.
+ *
+ * G = T^T T, out_G [ld, ld] row-major, symmetric bit for bit.  Workgroups take strips of at least 64 rows and accumulate the 16 x 16
+ * tiles of the lower triangle with v_mfma_f32_16x16x4_f32 (an element is a row-ordered fmaf chain per strip); a second launch adds
+ * the strips' tiles in ascending order and mirrors the triangle.
+ * DRX_EINVAL, and nothing launched: a NULL pointer (table, out_G, scratch); n_rows < 1; ld outside 4..128 or no multiple of 4; table or
+ * out_G not 16-byte aligned.  DRX_ESCRATCH: scratch smaller than drx_als_gram_scratch_bytes. */
+size_t drx_als_gram_scratch_bytes(int32_t n_rows, int32_t ld);
+int drx_als_gram(const float *table, int32_t n_rows, int32_t ld, float *out_G, void *scratch, size_t scratch_bytes, void *stream);
+/* ONE HALF-SWEEP: for every row r of the CSR, with S_r its entries,
+ *     A_r = G + sum_{j in S_r} w_j y_j y_j^T + lambda I,   b_r = sum_{j in S_r} (1 + w_j) y_j,   out[r] = A_r^-1 b_r
+ * y_j = other[indices[j]], G = other^T other (drx_als_gram).  A row without entries is written as zeros.  One workgroup per row;
+ * order: device int32 [n_rows] or NULL — workgroup g takes row order[g] (the caller's longest-first order), NULL = g; a value outside
+ * [0, n_rows) is skipped.  An index outside [0, n_other) counts as a zero row.  The entries are taken in rounds of 32 in CSR order
+ * (fp32 MFMA for A, k = the entries of a round; fmaf chains for b), the lower triangle of [A; b^T] is factorised in LDS by a
+ * right-looking column Cholesky over the ld columns, then L^T x = L^-1 b, then ONE step of iterative refinement: the residual
+ * r = sum_j [(1 + w_j) - w_j (y_j . x)] y_j - G x - lambda x is summed in double from the definition (the entries read once more), L L^T d = r
+ * is solved in fp32 and x += d — what is left of the error is the rounding of G and of x, not cond(A) x eps of the fp32 A.  With lambda = 0 a zero column of `other` (its padding
+ * included) is a zero pivot.
+ * fail_count: device int32 [1], incremented once per row whose factorisation met a pivot <= 0 or a non-finite one; that row is written
+ * as zeros; the call still returns DRX_OK.  scratch: drx_als_solve_rows_scratch_bytes (this form carves nothing from it).
+ * DRX_EINVAL, and nothing launched: a NULL pointer (all but order); n_rows or n_other < 1; ld outside 4..128 or no multiple of 4;
+ * lambda < 0 or non-finite; out, other or G not 16-byte aligned.  DRX_ESCRATCH: scratch too small. */
+size_t drx_als_solve_rows_scratch_bytes(int32_t n_rows, int32_t n_other, int32_t ld);
+int drx_als_solve_rows(float *out, const float *other, const float *G, const int64_t *indptr, const int32_t *indices, const float *weights,
+                       const int32_t *order, int32_t n_rows, int32_t n_other, int32_t ld, float lambda, int32_t *fail_count, void *scratch,
+                       size_t scratch_bytes, void *stream);
+/* out_loss[0] (device double) = <Gx, Gy>_F + sum over the entries of [(1 + w) (1 - s)^2 - s^2] + lambda (tr Gx + tr Gy), s = X[u] . Y[i]
+ * in fp32, every sum in double; Gx = X^T X and Gy = Y^T Y as drx_als_gram gives them.  indptr / indices / weights: the user-major CSR.
+ * Workgroups take users b, b + grid, ...; their partial sums are added in ascending order.
+ * DRX_EINVAL, and nothing launched: a NULL pointer; n_users or n_items < 1; ld outside 4..128 or no multiple of 4; lambda < 0 or
+ * non-finite; X, Y, Gx or Gy not 16-byte aligned.  DRX_ESCRATCH: scratch smaller than drx_als_loss_scratch_bytes. */
+size_t drx_als_loss_scratch_bytes(int32_t n_users, int32_t ld);
+int drx_als_loss(const float *X, const float *Y, const float *Gx, const float *Gy, const int64_t *indptr, const int32_t *indices,
+                 const float *weights, int32_t n_users, int32_t n_items, int32_t ld, float lambda, double *out_loss, void *scratch,
+                 size_t scratch_bytes, void *stream);
+
 #ifdef __cplusplus
 }
 #endif
