@@ -1,7 +1,8 @@
 from .als import ALS
 from .base_knn import BaseKNN
 from .bpr import BPR
+from .fpmc import FPMC
 from .item_knn import ItemKNN
 from .user_knn import UserKNN
 
-__all__ = ['ALS', 'BaseKNN', 'BPR', 'ItemKNN', 'UserKNN']
+__all__ = ['ALS', 'BaseKNN', 'BPR', 'FPMC', 'ItemKNN', 'UserKNN']

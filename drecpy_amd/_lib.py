@@ -294,6 +294,10 @@ SIGNATURES = {
                                      C.c_void_p]),
     'drx_als_loss_scratch_bytes': (C.c_size_t, [C.c_int32, C.c_int32]),
     'drx_als_loss': (C.c_int, [C.c_void_p] * 7 + [C.c_int32, C.c_int32, C.c_int32, C.c_float, C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p]),
+    'drx_fpmc_step_scratch_bytes': (C.c_size_t, [C.c_int32] * 6),
+    'drx_fpmc_step': (C.c_int, [C.c_void_p] * 12 + [C.c_int32, C.c_int32, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int32, C.c_int32,
+                                C.c_int32, C.POINTER(OptRule), C.POINTER(C.c_float), C.c_float, C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p]),
+    'drx_fpmc_query_rows': (C.c_int, [C.c_void_p, C.c_void_p, C.c_int32, C.c_void_p, C.c_int32, C.c_void_p, C.c_int32, C.c_void_p, C.c_void_p]),
     'drx_caser_step_small_opt': (C.c_int, [C.POINTER(CaserDims), C.POINTER(CaserArgs), C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p,
                                            C.POINTER(AdamSegments), C.POINTER(OptRule), C.c_void_p]),
     'drx_dmf_step_small_opt': (C.c_int, [C.POINTER(DmfDims), C.POINTER(DmfArgs), C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p,

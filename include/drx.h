@@ -1297,6 +1297,46 @@ int drx_als_loss(const float *X, const float *Y, const float *Gx, const float *G
                  const float *weights, int32_t n_users, int32_t n_items, int32_t ld, float lambda, double *out_loss, void *scratch,
                  size_t scratch_bytes, void *stream);
 
+/* ---- FPMC (Rendle, Freudenthaler, Schmidt-Thieme 2010; csrc/drx_fpmc.hip) ---------------------------------
+ * Four factor tables and an item bias: P [n_users, ld] (user), Q (item as target of the user term), M (item as previous item),
+ * N (item as target of the transition term), b [n_items].  ld = K rounded up to a multiple of 4, 4 <= ld <= 128.  The item side is
+ * ONE table QN [n_items, 2 ld] = [Q[i] | N[i]], each half with its own zero padding; M is [n_items, ld].  A window w = (user u, the
+ * ordered L items S before the target, target i, negatives j_1 .. j_r), 1 <= L <= 8, 1 <= r <= 16 (the forward kernel takes the
+ * negatives' rows in at most two rounds of eight):
+ *     c(u, S) = [P[u] | (1 / |S|) sum_{l in S} M[l]]          (2 ld floats; the sum positions ascending in fp32, then ONE multiply)
+ *     x(u, S, i) = c . QN[i] + b[i]                           (DRX_REC_BIAS of the fused scorer at rows of 2 ld floats)
+ *     D_wk = x(u, S, i) - x(u, S, j_k);  loss = (1 / (B r)) sum_w sum_k softplus(-D_wk);  g_wk = -sigmoid(-D_wk) / (B r)
+ *     d_w = sum_k g_wk (QN[i] - QN[j_k]):  dP[u] += first half of d_w;  dM[l] += (1 / L) second half of d_w for every l in S
+ *     dQN[i] += (sum_k g_wk) c;  dQN[j_k] -= g_wk c;  db[i] += sum_k g_wk;  db[j_k] -= g_wk
+ * ONE TRAINING STEP on B windows in the layout drx_list_sample_device returns at n_targets = 1: uid [B], before [B, L],
+ * after [B, 1 + r] (the target first), device int32, ids in range (not checked on the device).  Then EVERY row of P, M and QN gets
+ * reg * row added to its gradient (b none) and every row and bias is updated by `rule`, a dense rule (DrxOptRule).  alphas: HOST
+ * float [4], the step sizes of P, M, QN and b (Adam: the variable's lr_t; the other rules: the learning rate); rule->lr is ignored.
+ * Slots (P_s1 .. b_s2): those the rule has, shaped like their parameter; one it lacks may be NULL and is not touched.
+ * k_fpmc_fwd_bwd gives a window to a group of pick_geom(2 ld) lanes, one float4 of a 2 ld row per lane; it forms c once per window and
+ * writes c, the first half of d_w, L copies of the second half times 1 / L and the 1 + r scales (sum_k g_wk, -g_w1 .. -g_wr);
+ * drx_batch_csr_device groups the B user keys, the B L previous-item keys and the B (1 + r) item keys (uid, before, after as they
+ * are); ONE drx_rows_csr_opt_multi call updates P and M (plain form) and QN with b (outer-product form, group 1 + r, the written c as
+ * its rows).  No atomics: every sum runs in an order fixed by the batch, so equal inputs give equal bits.
+ * loss_out: device double [1] or NULL (then no loss is summed); the workgroups' partial sums (double) are added in a fixed order.
+ * scratch: drx_fpmc_step_scratch_bytes (0 = a description outside the domain).
+ * DRX_EINVAL, and nothing launched: a NULL pointer among P, M, QN, b, uid, before, after, rule, alphas, scratch; B < 1; L outside
+ * 1..8; neg_ratio outside 1..16; n_users or n_items < 1; ld outside 4..128 or no multiple of 4; no dense rule; a slot the rule has is
+ * NULL; a table or slot not 16-byte aligned.  DRX_ESCRATCH: scratch too small. */
+size_t drx_fpmc_step_scratch_bytes(int32_t B, int32_t L, int32_t neg_ratio, int32_t ld, int32_t n_users, int32_t n_items);
+int drx_fpmc_step(float *P, float *M, float *QN, float *b, float *P_s1, float *P_s2, float *M_s1, float *M_s2, float *QN_s1, float *QN_s2,
+                  float *b_s1, float *b_s2, int32_t ld, int32_t n_users, int32_t n_items, const int32_t *uid, const int32_t *before,
+                  const int32_t *after, int32_t B, int32_t L, int32_t neg_ratio, const DrxOptRule *rule, const float *alphas, float reg,
+                  double *loss_out, void *scratch, size_t scratch_bytes, void *stream);
+/* out[q, :] = c(uid[q], the basket of uid[q]) for n device user ids (in range, not checked on the device): the query rows of the fused
+ * scorer, out [n, 2 ld].  baskets: device int32 [n_users, L], -1 = an absent position; the mean runs over the entries present in
+ * position order, an empty basket gives a zero second half.  The same summation function as the step: a full basket gives the bits
+ * of the context row the step forms for that window.
+ * DRX_EINVAL, and nothing launched: a NULL pointer; n < 1; L outside 1..8; ld outside 4..128 or no multiple of 4; P, M or out not
+ * 16-byte aligned. */
+int drx_fpmc_query_rows(const float *P, const float *M, int32_t ld, const int32_t *baskets, int32_t L, const int32_t *uid, int32_t n,
+                        float *out, void *stream);
+
 #ifdef __cplusplus
 }
 #endif
