@@ -3,6 +3,7 @@ from .base_knn import BaseKNN
 from .bpr import BPR
 from .fpmc import FPMC
 from .item_knn import ItemKNN
+from .ncf import NeuMF
 from .user_knn import UserKNN
 
-__all__ = ['ALS', 'BaseKNN', 'BPR', 'FPMC', 'ItemKNN', 'UserKNN']
+__all__ = ['ALS', 'BaseKNN', 'BPR', 'FPMC', 'ItemKNN', 'NeuMF', 'UserKNN']

@@ -101,6 +101,12 @@ class OptRule(C.Structure):                             # include/drx.h DrxOptRu
     _fields_ = [('kind', C.c_int32), ('lr', C.c_float), ('mu', C.c_float), ('mu2', C.c_float), ('eps', C.c_float)]
 
 
+class NcfDims(C.Structure):                             # include/drx.h DrxNcfDims
+    _fields_ = [(n, C.c_int32) for n in ('n_users', 'n_items', 'kg', 'km', 'ldg', 'ldm', 'n_layers')] + \
+               [('f', C.c_int32 * 4), ('off_w', C.c_int32 * 4), ('off_b', C.c_int32 * 4), ('off_h', C.c_int32), ('off_b0', C.c_int32),
+                ('n_small', C.c_int32)]
+
+
 class CsrList(C.Structure):                             # include/drx.h DrxCsrList
     _fields_ = [('keys', C.c_void_p), ('T', C.c_int32), ('n_rows', C.c_int32), ('row_ptr', C.c_void_p), ('order', C.c_void_p)]
 
@@ -298,6 +304,15 @@ SIGNATURES = {
     'drx_fpmc_step': (C.c_int, [C.c_void_p] * 12 + [C.c_int32, C.c_int32, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int32, C.c_int32,
                                 C.c_int32, C.POINTER(OptRule), C.POINTER(C.c_float), C.c_float, C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p]),
     'drx_fpmc_query_rows': (C.c_int, [C.c_void_p, C.c_void_p, C.c_int32, C.c_void_p, C.c_int32, C.c_void_p, C.c_int32, C.c_void_p, C.c_void_p]),
+    'drx_ncf_grid': (C.c_int, [C.c_int32]),
+    'drx_ncf_step_scratch_bytes': (C.c_size_t, [C.POINTER(NcfDims), C.c_int32]),
+    'drx_ncf_step': (C.c_int, [C.POINTER(NcfDims)] + [C.c_void_p] * 12 + [C.c_int32, C.POINTER(OptRule), C.POINTER(C.c_float), C.c_float,
+                               C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p]),
+    'drx_ncf_half_width': (C.c_int32, [C.POINTER(NcfDims)]),
+    'drx_ncf_half_rows': (C.c_int, [C.POINTER(NcfDims), C.c_void_p, C.c_void_p, C.c_void_p, C.c_int32, C.c_int32, C.c_void_p, C.c_void_p]),
+    'drx_ncf_score_rows': (C.c_int, [C.POINTER(NcfDims), C.c_void_p, C.c_void_p, C.c_void_p, C.c_int32, C.c_void_p, C.c_void_p]),
+    'drx_ncf_pair_scores': (C.c_int, [C.POINTER(NcfDims), C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int32, C.c_void_p,
+                                      C.c_void_p]),
     'drx_caser_step_small_opt': (C.c_int, [C.POINTER(CaserDims), C.POINTER(CaserArgs), C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p,
                                            C.POINTER(AdamSegments), C.POINTER(OptRule), C.c_void_p]),
     'drx_dmf_step_small_opt': (C.c_int, [C.POINTER(DmfDims), C.POINTER(DmfArgs), C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p,

@@ -1337,6 +1337,67 @@ int drx_fpmc_step(float *P, float *M, float *QN, float *b, float *P_s1, float *P
 int drx_fpmc_query_rows(const float *P, const float *M, int32_t ld, const int32_t *baskets, int32_t L, const int32_t *uid, int32_t n,
                         float *out, void *stream);
 
+/* ---- NeuMF (He, Liao, Zhang, Nie, Hu, Chua 2017; csrc/drx_ncf.hip) ------------------------------------------
+ * Tables U [n_users, ldg + ldm] = [Pg[u] | Pm[u]] and V [n_items, ldg + ldm] = [Qg[i] | Qm[i]]: the GMF half of kg floats and the MLP
+ * half of km floats, each rounded up to a multiple of 4 with its own ZERO padding.  One flat array sw of small weights, in this order
+ * (all row-major, DrxNcfDims has the offsets, which must be exactly these):
+ *     W_1 [2 km, f_1], b_1 [f_1], W_l [f_{l-1}, f_l], b_l [f_l] (l = 2 .. n), h = [hg (kg) | hm (f_n)], b0
+ *     a_0 = [Pm[u] ; Qm[i]],  a_l = relu(W_l^T a_{l-1} + b_l),  x(u, i) = sum_k hg[k] Pg[u, k] Qg[i, k] + hm . a_n + b0
+ * (relu's derivative at 0 is 0: A > 0 <=> Z > 0).  Domain: 1 <= kg, km <= 64, 1 <= n <= 4 layers, 1 <= f_l <= 64.  Everything is fp32;
+ * no float atomics; every sum runs in an order fixed by the arguments: equal inputs give equal bits.  All launches are plain. */
+#define DRX_NCF_MAX_LAYERS 4
+typedef struct DrxNcfDims {
+  int32_t n_users, n_items;
+  int32_t kg, km, ldg, ldm;
+  int32_t n_layers, f[DRX_NCF_MAX_LAYERS];
+  int32_t off_w[DRX_NCF_MAX_LAYERS], off_b[DRX_NCF_MAX_LAYERS], off_h, off_b0, n_small;
+} DrxNcfDims;
+/* ONE TRAINING STEP on B point samples (uid, iid: device int32 [B], ids in range — not checked on the device; y: device float [B]):
+ *     loss = (1 / B) sum_b [max(x_b, 0) - y_b x_b + log1p(exp(-|x_b|))],   g_b = (sigmoid(x_b) - y_b) / B
+ * then EVERY row of U and V, every entry of the W_l and of h gets reg * itself added to its gradient (the b_l and b0 none) and
+ * everything is updated by `rule`, a dense rule (DrxOptRule).  alphas: HOST float [3], the step sizes of U, V and sw (Adam: the
+ * variable's lr_t; the other rules: the learning rate); rule->lr is ignored.  Slots: those the rule has, shaped like their parameter;
+ * one it lacks may be NULL and is not touched.
+ * k_ncf_tile: workgroups of four waves, drx_ncf_grid of them = min(tiles, 256), walk tiles of 16 samples (tile t to workgroup
+ * t % grid, ascending).  A tile
+ * gathers its rows into LDS, runs every layer forward and backward as v_mfma_f32_16x16x4_f32 products out of LDS (M = the tile, the
+ * waves split the 16-column tiles) and writes one gradient row per sample for U and V ([B, ldg + ldm]: the GMF half g hg (.) the other
+ * side's row, the MLP half the two halves of W_1 dz_1); the workgroup adds its tiles' gradients of sw (dW_l = A_{l-1}^T dZ_l on the
+ * matrix cores) into ITS row of [grid, n_small] and its loss into one double.  One launch adds those rows in workgroup order and
+ * updates sw by segments (drx_opt_segments' arithmetic); drx_batch_csr_device groups the two key lists and ONE
+ * drx_rows_csr_opt_multi call updates U and V (plain form, the written rows as src).
+ * loss_out: device double [1] or NULL.  scratch: drx_ncf_step_scratch_bytes (0 = a description outside the domain).
+ * DRX_EINVAL, and nothing launched: a NULL pointer among D, U, V, sw, uid, iid, y, rule, alphas, scratch; B < 1 (or >= 2^24); a width
+ * outside the domain; ldg / ldm / offsets / n_small that are not the layout above; n_users or n_items < 1; no dense rule; a slot the
+ * rule has is NULL; a table or table slot not 16-byte aligned.  DRX_ESCRATCH: scratch too small. */
+int drx_ncf_grid(int32_t B);
+size_t drx_ncf_step_scratch_bytes(const DrxNcfDims *D, int32_t B);
+int drx_ncf_step(const DrxNcfDims *D, float *U, float *V, float *sw, float *U_s1, float *U_s2, float *V_s1, float *V_s2, float *sw_s1,
+                 float *sw_s2, const int32_t *uid, const int32_t *iid, const float *y, int32_t B, const DrxOptRule *rule,
+                 const float *alphas, float reg, double *loss_out, void *scratch, size_t scratch_bytes, void *stream);
+/* What a pair's logit needs from ONE side, for n device ids (ids NULL: rows 0 .. n - 1 of the table), out [n, hw] with
+ * hw = drx_ncf_half_width(D) = f_1 rounded up to 4, plus ldg; padding ZERO:
+ *     side 0 (users, table = U):  [W_1[:km]^T Pm[u] + b_1 (f_1) | hg (.) Pg[u] (ldg)]
+ *     side 1 (items, table = V):  [W_1[km:]^T Qm[i]       (f_1) | Qg[i]        (ldg)]
+ * The product runs on MFMA tiles of 16 rows, k ascending in steps of 4 (the matrix core's own order inside a step).
+ * DRX_EINVAL, and nothing launched: a NULL pointer among D, table, sw, out; n < 1; side not 0 / 1; dims outside the domain; table or
+ * out not 16-byte aligned. */
+int32_t drx_ncf_half_width(const DrxNcfDims *D);
+int drx_ncf_half_rows(const DrxNcfDims *D, const float *table, const float *sw, const int32_t *ids, int32_t n, int32_t side, float *out,
+                      void *stream);
+/* out[r, i] = x(user of uhalf row r, item i) for R rows of user half rows against the half rows of ALL n_items items (ihalf
+ * [D->n_items, hw]), out [R, n_items]: a workgroup takes a strip of 64 items and a block of users, keeps the strip's half rows and
+ * the kernels of layers 2 .. n in LDS, forms relu(A_u + B_i) for tiles of 16 pairs (one wave each), runs the layers on
+ * v_mfma_f32_16x16x4_f32, reduces with hm and adds the GMF dot and b0.
+ * drx_ncf_pair_scores: out[p] = x(uhalf row urow[p], ihalf row irow[p]) for P pairs (urow, irow: device int32 [P], rows in range —
+ * not checked on the device) through the SAME device function: the order of a pair's sums does not depend on the pair's place in
+ * a tile, so a pair's logit has the same bits from either call.
+ * DRX_EINVAL, and nothing launched: a NULL pointer; R / P < 1; R above 65535 blocks of 32 users (callers chunk the score matrix long
+ * before); dims outside the domain; uhalf, ihalf not 16-byte aligned. */
+int drx_ncf_score_rows(const DrxNcfDims *D, const float *sw, const float *uhalf, const float *ihalf, int32_t R, float *out, void *stream);
+int drx_ncf_pair_scores(const DrxNcfDims *D, const float *sw, const float *uhalf, const float *ihalf, const int32_t *urow,
+                        const int32_t *irow, int32_t P, float *out, void *stream);
+
 #ifdef __cplusplus
 }
 #endif
