@@ -12,14 +12,14 @@ include/drx.h ("ALS / WMF").
 fit() accepts batch_size, learning_rate and neg_ratio and ignores them: a sweep has no batch, no step size and no sampled negatives.
 It refuses optimizer=, a process group, factors outside 1..128, reg_rate <= 0, alpha < 0, a negative weight and a frame without a
 positive.  Prediction and serving run through the fused hooks of RecommenderABC on the engine's DRX_REC_BIAS scorer (zero bias);
-rank() / ranking_evaluation select on a score matrix (drx_rows_dot + drx_topk).  Single GPU only.
+rank() / ranking_evaluation select on a score matrix (drx_rows_dot + drx_topk): FactorServing's (_base.py).  Single GPU only.
 """
 import numpy as np
 
-from ..recommender_abc import RecommenderABC
+from ._base import FactorServing
 
 
-class ALS(RecommenderABC):
+class ALS(FactorServing):
     MAX_FACTORS = 128
 
     def __init__(self, factors=64, alpha=40.0, init_std=0.01, device='cuda:0', **kwds):
@@ -93,44 +93,3 @@ class ALS(RecommenderABC):
 
     def _compute_batch_loss(self, predictions, desired_values, **kwds):
         raise NotImplementedError('ALS has no batch loss: the sweep returns the whole-matrix objective.')
-
-    # ---- prediction and serving ------------------------------------------------------------------------------------------------------
-    def _predict(self, uid, iid, **kwds):
-        if uid is None or iid is None:
-            return None
-        with self._device_lock:
-            return float(self._engine.pair_scores(np.array([uid], dtype=np.int32), np.array([iid], dtype=np.int32)).cpu().numpy()[0])
-
-    def _recorded_items(self, uid):
-        """every item the frame records for the user, whatever its value (what novelty removes)"""
-        indptr, cols = self._exclusion_csr()
-        return np.asarray(cols[indptr[uid]:indptr[uid + 1]], dtype=np.int64)
-
-    def _rank(self, uid, iids, n, novelty):
-        """Top-n of the candidates by (score, iid) — heapq.nlargest order — on the device."""
-        return self._rank_rows([uid], [list(iids)], n, novelty)[0]
-
-    def _rank_rows(self, uids, iid_lists, n, novelty):
-        """_rank for many users in one engine call: row r holds the top-n of the candidates iid_lists[r] for the internal user uids[r]."""
-        cand = self._candidate_rows(iid_lists)
-        if novelty:
-            for r, uid in enumerate(uids):
-                cand[r, self._recorded_items(uid)] = False
-        return self._topk_of_candidates(cand, n, lambda: self._engine.score_matrix(np.asarray(uids, dtype=np.int32)))
-
-    def _recommend_batch(self, uids, n, novelty):
-        """Top-n of the whole catalogue for many users in one engine call (the fused scorer-selector); lists longer than its domain
-        (n > 128): one _recommend per user."""
-        if not self._engine.recommend_is_fused(self._engine.ld, min(int(n), self.n_items)):
-            return super()._recommend_batch(uids, n, novelty)
-        return self._recommend_batch_fused(uids, n, novelty)
-
-    def _catalogue_ranks(self, uids, iids, novelty):
-        if not self._engine.rank_is_fused(self._engine.ld):
-            return super()._catalogue_ranks(uids, iids, novelty)
-        return self._catalogue_ranks_fused(uids, iids, novelty)
-
-    def _predict_pairs(self, uids, iids):
-        if type(self)._predict is not ALS._predict:
-            return super()._predict_pairs(uids, iids)
-        return self._predict_pairs_fused(uids, iids)

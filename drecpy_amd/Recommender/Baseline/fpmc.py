@@ -18,16 +18,16 @@ window of L items instead of over the previous basket; negatives from the items 
 sampler's rule) instead of those outside the target basket; the logged loss is the data term alone.  L = 1 is the first-order chain.
 
 Prediction and serving run through the fused hooks of RecommenderABC (recommend_batch, catalogue_ranks, predict_pairs) on the engine's
-DRX_REC_BIAS scorer at rows of 2 ld floats; rank() / ranking_evaluation select on a score matrix.  Single GPU only.
+DRX_REC_BIAS scorer at rows of 2 ld floats; rank() / ranking_evaluation select on a score matrix: FactorServing's (_base.py), as the
+refusals, the draw seeds and _do_batch are SampledDenseFit's.  Single GPU only.
 """
 import numpy as np
 
-from ..recommender_abc import RecommenderABC
-
-_DENSE_KINDS = ('adam', 'adagrad', 'sgd', 'momentum', 'nesterov', 'rmsprop', 'rmsprop_momentum')
+from ._base import SampledDenseFit
 
 
-class FPMC(RecommenderABC):
+class FPMC(SampledDenseFit):
+    MODEL, NEGATIVES_PER, DENSE_UPDATE_OF = 'FPMC', 'negatives drawn per window', 'every factor table'
     MAX_FACTORS = 128
     MAX_L = 8
     MAX_NEG_RATIO = 16
@@ -67,15 +67,9 @@ class FPMC(RecommenderABC):
         return out
 
     def _pre_fit(self, learning_rate, neg_ratio, reg_rate, **kwds):
-        import torch.distributed as dist
-        if dist.is_available() and dist.is_initialized():
-            raise Exception('FPMC.fit under a torch.distributed process group: FPMC trains on a single GPU only.')
-        if not (isinstance(neg_ratio, (int, np.integer)) and 1 <= neg_ratio <= self.MAX_NEG_RATIO):
-            raise Exception(f'FPMC.fit(neg_ratio={neg_ratio!r}): neg_ratio must be an integer in 1..{self.MAX_NEG_RATIO} (negatives drawn per '
-                            f'window).')
+        self._start_sampled_fit(neg_ratio)
         self._check_shape()
         from ...engine_fpmc import FpmcEngine
-        self._neg_ratio = int(neg_ratio)
         self._sampler = self._list_sampler(self._neg_ratio)
         if getattr(self._sampler, '_native', None) is None:
             raise Exception('FPMC.fit: the dataset holds no sequence to draw windows from (Failed to sample group records).')
@@ -91,7 +85,6 @@ class FPMC(RecommenderABC):
                        'b': np.zeros(self.n_items)}
         self._engine.set_params(weights)
         self._register_trainables(self._fused_trainables())
-        self._draws = 0
 
     def _restore_engine(self, params):
         """RecommenderABC.load: the engine rebuilt from the saved weights, the baskets from the bound dataset (no window is drawn)"""
@@ -104,26 +97,10 @@ class FPMC(RecommenderABC):
         e = self._engine
         return [e.user_emb, e.trans_emb, e.item_emb]
 
-    def _configure_optimizer(self):
-        o = self.optimizer
-        if getattr(o, 'kind', None) not in _DENSE_KINDS:
-            raise Exception(f'FPMC trains with the dense rules adam, adagrad, sgd, rmsprop (dense update of every factor table); got {o!r}')
-        self._engine.set_optimizer(o)
-
-    def _draw_seed(self, k):
-        """the seed of the k-th batch (k = 1, 2, ...) of a fit()"""
-        return (int(self.seed) if self.seed is not None else 0) * 1000003 + int(k)
-
     def _sample_batch(self, batch_size, **kwds):
-        self._draws += 1
+        seed = self._next_draw_seed()
         with self._device_lock:
-            return self._sampler.sample_device(int(batch_size), self._draw_seed(self._draws))
-
-    def _do_batch(self, batch_samples, step=0, want_loss=False, **kwds):
-        e = self._engine
-        # one apply_gradients per registered item, in registration-list order
-        applies = (len(self._apply_order()),) + tuple(self._apply_position(h) for h in self._fused_trainables())
-        return e.step(step, *batch_samples[:3], want_loss=want_loss, applies=applies)
+            return self._sampler.sample_device(int(batch_size), seed)
 
     def _predict_batch(self, batch_samples, **kwds):
         """x(u, S, i) - x(u, S, j) of the batch's windows (numpy float64 [B r]) against the target 1 — the reference's training hook,
@@ -137,48 +114,3 @@ class FPMC(RecommenderABC):
         x = np.einsum('wf,wjf->wj', c, np.concatenate([p['Q'], p['N']], axis=1)[after]) + p['b'][after]
         d = (x[:, :1] - x[:, 1:]).reshape(-1)
         return d, np.ones(len(d))
-
-    def _compute_batch_loss(self, predictions, desired_values, **kwds):
-        d = -np.asarray(predictions, dtype=np.float64)
-        return float(np.mean(np.maximum(d, 0.0) + np.log1p(np.exp(-np.abs(d)))))
-
-    # ---- prediction and serving ------------------------------------------------------------------------------------------------------
-    def _predict(self, uid, iid, **kwds):
-        if uid is None or iid is None:
-            return None
-        with self._device_lock:
-            return float(self._engine.pair_scores(np.array([uid], dtype=np.int32), np.array([iid], dtype=np.int32)).cpu().numpy()[0])
-
-    def _recorded_items(self, uid):
-        """every item the frame records for the user, whatever its value (what novelty removes)"""
-        indptr, cols = self._exclusion_csr()
-        return np.asarray(cols[indptr[uid]:indptr[uid + 1]], dtype=np.int64)
-
-    def _rank(self, uid, iids, n, novelty):
-        """Top-n of the candidates by (score, iid) — heapq.nlargest order — on the device."""
-        return self._rank_rows([uid], [list(iids)], n, novelty)[0]
-
-    def _rank_rows(self, uids, iid_lists, n, novelty):
-        """_rank for many users in one engine call: row r holds the top-n of the candidates iid_lists[r] for the internal user uids[r]."""
-        cand = self._candidate_rows(iid_lists)
-        if novelty:
-            for r, uid in enumerate(uids):
-                cand[r, self._recorded_items(uid)] = False
-        return self._topk_of_candidates(cand, n, lambda: self._engine.score_matrix(np.asarray(uids, dtype=np.int32)))
-
-    def _recommend_batch(self, uids, n, novelty):
-        """Top-n of the whole catalogue for many users in one engine call (the fused scorer-selector); lists longer than its domain
-        (n > 128): one _recommend per user."""
-        if not self._engine.recommend_is_fused(self._engine.rank_ld(), min(int(n), self.n_items)):
-            return super()._recommend_batch(uids, n, novelty)
-        return self._recommend_batch_fused(uids, n, novelty)
-
-    def _catalogue_ranks(self, uids, iids, novelty):
-        if not self._engine.rank_is_fused(self._engine.rank_ld()):
-            return super()._catalogue_ranks(uids, iids, novelty)
-        return self._catalogue_ranks_fused(uids, iids, novelty)
-
-    def _predict_pairs(self, uids, iids):
-        if type(self)._predict is not FPMC._predict:
-            return super()._predict_pairs(uids, iids)
-        return self._predict_pairs_fused(uids, iids)

@@ -17,8 +17,7 @@ Every ranking call goes through the score matrix (drx_ncf_half_rows + drx_ncf_sc
 """
 import numpy as np
 
-from ..recommender_abc import RecommenderABC
-from .bpr import BPR, _DENSE_KINDS
+from ._base import SampledDenseFit
 
 
 def _sigmoid(x):
@@ -28,7 +27,9 @@ def _sigmoid(x):
         return np.where(np.isneginf(x), -np.inf, 1.0 / (1.0 + np.exp(-x)))
 
 
-class NeuMF(RecommenderABC):
+class NeuMF(SampledDenseFit):
+    MODEL, NEGATIVES_PER, DENSE_UPDATE_OF = 'NeuMF', 'negatives drawn per positive, on average', 'both tables and the small weights'
+    _reported_value = staticmethod(_sigmoid)
     MATRIX_BUDGET_BYTES = 1 << 30          # the score matrix of one chunk of recommend_batch / catalogue_ranks
 
     def __init__(self, factors=8, mlp_factors=32, layers=(32, 16, 8), init_std=0.01, device='cuda:0', **kwds):
@@ -47,8 +48,6 @@ class NeuMF(RecommenderABC):
         except Exception as e:
             raise Exception(str(e)) from None
 
-    _frame = BPR._frame
-
     def _init_weights(self, Kg, Km, layers):
         rng = np.random.default_rng(self.seed)
         w = {'Pg': rng.normal(0.0, self.init_std, size=(self.n_users, Kg)), 'Pm': rng.normal(0.0, self.init_std, size=(self.n_users, Km)),
@@ -63,13 +62,9 @@ class NeuMF(RecommenderABC):
         return w
 
     def _pre_fit(self, learning_rate, neg_ratio, reg_rate, **kwds):
-        import torch.distributed as dist
-        if dist.is_available() and dist.is_initialized():
-            raise Exception('NeuMF.fit under a torch.distributed process group: NeuMF trains on a single GPU only.')
-        if not (isinstance(neg_ratio, (int, np.integer)) and neg_ratio >= 1):
-            raise Exception(f'NeuMF.fit(neg_ratio={neg_ratio!r}): neg_ratio must be an integer >= 1 (negatives drawn per positive, on average).')
+        self._start_sampled_fit(neg_ratio)
         Kg, Km, layers = self._check_shape()
-        positives, recorded, eligible = self._frame()
+        positives, recorded, _ = self._positives_frame()
         if len(positives[1]) == 0:
             raise Exception('NeuMF.fit: the dataset has no positive (no interaction >= interaction_threshold).')
         if not (np.diff(self.interaction_dataset.interaction_csr()[0]) < self.n_items).any():
@@ -81,8 +76,6 @@ class NeuMF(RecommenderABC):
         weights = kwds.get('initial_weights')
         self._engine.set_params(weights if weights is not None else self._init_weights(Kg, Km, layers))
         self._register_trainables(self._fused_trainables())
-        self._neg_ratio = int(neg_ratio)
-        self._draws = 0
 
     def _restore_engine(self, params):
         """RecommenderABC.load: the engine rebuilt from the saved weights (serving needs no sampler frame)"""
@@ -94,25 +87,10 @@ class NeuMF(RecommenderABC):
         e = self._engine
         return [e.user_emb, e.item_emb, e.small]
 
-    def _configure_optimizer(self):
-        o = self.optimizer
-        if getattr(o, 'kind', None) not in _DENSE_KINDS:
-            raise Exception(f'NeuMF trains with the dense rules adam, adagrad, sgd, rmsprop (dense update of both tables and the small '
-                            f'weights); got {o!r}')
-        self._engine.set_optimizer(o)
-
-    _draw_seed = BPR._draw_seed
-
     def _sample_batch(self, batch_size, **kwds):
-        self._draws += 1
+        seed = self._next_draw_seed()
         with self._device_lock:
-            return self._engine.sample(batch_size, self._neg_ratio, self._draw_seed(self._draws))
-
-    def _do_batch(self, batch_samples, step=0, want_loss=False, **kwds):
-        e = self._engine
-        # one apply_gradients per registered item, in registration-list order
-        applies = (len(self._apply_order()),) + tuple(self._apply_position(h) for h in (e.user_emb, e.item_emb, e.small))
-        return e.step(step, *batch_samples[:3], want_loss=want_loss, applies=applies)
+            return self._engine.sample(batch_size, self._neg_ratio, seed)
 
     def _predict_batch(self, batch_samples, **kwds):
         """the logits of the batch's pairs (numpy float64 [B]) against their targets — the reference's training hook, kept for
@@ -139,21 +117,6 @@ class NeuMF(RecommenderABC):
         with self._device_lock:
             x = self._engine.pair_scores(np.asarray(uids, dtype=np.int32), np.asarray(iids, dtype=np.int32)).cpu().numpy()
         return _sigmoid(x), np.zeros(len(x), dtype=bool)
-
-    _recorded_items = BPR._recorded_items
-
-    def _rank(self, uid, iids, n, novelty):
-        """Top-n of the candidates by (logit, iid) — heapq.nlargest order — on the device; the values reported are sigmoid(logit)."""
-        return self._rank_rows([uid], [list(iids)], n, novelty)[0]
-
-    def _rank_rows(self, uids, iid_lists, n, novelty):
-        """_rank for many users in one engine call: row r holds the top-n of the candidates iid_lists[r] for the internal user uids[r]."""
-        cand = self._candidate_rows(iid_lists)
-        if novelty:
-            for r, uid in enumerate(uids):
-                cand[r, self._recorded_items(uid)] = False
-        rows = self._topk_of_candidates(cand, n, lambda: self._engine.score_matrix(np.asarray(uids, dtype=np.int32)))
-        return [[(float(_sigmoid(x)), i) for x, i in row] for row in rows]
 
     def _chunk_lists(self, uids, k, novelty):
         """(idx int64 [R, k], logits float32 [R, k]) of the users' full-catalogue order, a chunk of users at a time: score_matrix + topk,

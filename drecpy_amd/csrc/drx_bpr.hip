@@ -7,6 +7,7 @@
 #include "drx_common.hpp"
 #include "drx_rows.hpp"
 #include "drx_opt.hpp"
+#include "drx_step.hpp"
 
 namespace drx {
 
@@ -64,7 +65,6 @@ __global__ __launch_bounds__(kBlock) void k_bpr_fwd_bwd(const float *__restrict_
                                                         float *__restrict__ pu, float *__restrict__ gs, int32_t *__restrict__ ikeys,
                                                         double *__restrict__ loss_part) {
   constexpr int gpb = kBlock / G;
-  __shared__ double part[gpb];
   const int lane = threadIdx.x % G, gid = threadIdx.x / G;
   const int t = blockIdx.x * gpb + gid;
   float loss = 0.f;
@@ -90,23 +90,7 @@ __global__ __launch_bounds__(kBlock) void k_bpr_fwd_bwd(const float *__restrict_
       ikeys[2 * (size_t)t + 1] = j;
     }
   }
-  if (lane == 0) part[gid] = (double)loss;
-  __syncthreads();
-  if (threadIdx.x == 0) {
-    double s = 0.0;
-    for (int k = 0; k < gpb; ++k) s += part[k];
-    loss_part[blockIdx.x] = s;
-  }
-}
-
-// loss_out[0] = (sum of the n partials) / T: lane l adds partials l, l + 64, ... ascending, then a fixed shuffle tree
-__global__ __launch_bounds__(64) void k_bpr_loss(const double *__restrict__ part, int n, int T, double *__restrict__ out) {
-  const int lane = threadIdx.x;
-  double s = 0.0;
-  for (int k = lane; k < n; k += 64) s += part[k];
-#pragma unroll
-  for (int m = 32; m >= 1; m >>= 1) s += __shfl_xor(s, m, 64);
-  if (lane == 0) out[0] = s / (double)T;
+  block_loss_partial<gpb>(lane, gid, (double)loss, loss_part);
 }
 
 struct BprScratch {
@@ -128,8 +112,7 @@ static bool bpr_shape_ok(int64_t T, int ld, int n_users, int n_items) {
   return T >= 1 && T < (1 << 29) && n_users >= 1 && n_items >= 1 && ld >= 4 && ld <= 256 && !(ld & 3) && (int64_t)T * ld < (int64_t)1 << 40;
 }
 
-// carves the step's scratch; false when the description is invalid.  (Sizes only: a Carver over any non-NULL base that is never
-// dereferenced — drx_batch_csr_device_bytes asks whether the lists' arrays are given, not where they are.)
+// carves the step's scratch; false when the description is invalid
 static bool bpr_carve(Carver &cv, int T, int ld, int n_users, int n_items, BprScratch &S) {
   if (!bpr_shape_ok(T, ld, n_users, n_items)) return false;
   const int gpb = kBlock / pick_geom(ld).G;
@@ -183,10 +166,9 @@ int drx_bpr_gather_rows(const float *table, int32_t ld, const int32_t *ids, int3
 
 size_t drx_bpr_step_scratch_bytes(int32_t T, int32_t ld, int32_t n_users, int32_t n_items) {
   using namespace drx;
-  Carver cv(reinterpret_cast<void *>(uintptr_t(256)), 0);
+  Carver cv = step_dry_carver();
   BprScratch S;
-  if (!bpr_carve(cv, T, ld, n_users, n_items, S)) return 0;
-  return align_up(cv.off, 256) + 256;                  // (+ 256: the step aligns the base it is given)
+  return bpr_carve(cv, T, ld, n_users, n_items, S) ? step_scratch_total(cv) : 0;
 }
 
 int drx_bpr_step(float *P, float *Q, float *bq, float *P_s1, float *P_s2, float *Q_s1, float *Q_s2, float *bq_s1, float *bq_s2, int32_t ld,
@@ -195,16 +177,10 @@ int drx_bpr_step(float *P, float *Q, float *bq, float *P_s1, float *P_s2, float 
                  void *stream) {
   using namespace drx;
   if (!P || !Q || !bq || !uid || !pos || !neg || !rule || !alphas || !scratch || !bpr_shape_ok(T, ld, n_users, n_items)) return DRX_EINVAL;
-  const int kind = rule->kind;
-  if (!opt_dense_kind(kind) || !opt_slots_ok(kind, P_s1, P_s2) || !opt_slots_ok(kind, Q_s1, Q_s2) || !opt_slots_ok(kind, bq_s1, bq_s2))
-    return DRX_EINVAL;
-  if (!opt_has_s1(kind)) P_s1 = Q_s1 = bq_s1 = nullptr;
-  if (!opt_has_s2(kind)) P_s2 = Q_s2 = bq_s2 = nullptr;
-  if (((uintptr_t)P | (uintptr_t)Q | (uintptr_t)P_s1 | (uintptr_t)P_s2 | (uintptr_t)Q_s1 | (uintptr_t)Q_s2) & 15) return DRX_EINVAL;
-  char *base = (char *)(((uintptr_t)scratch + 255) & ~uintptr_t(255));
-  const size_t lead = (size_t)(base - (char *)scratch);
-  if (scratch_bytes < lead) return DRX_ESCRATCH;
-  Carver cv(base, scratch_bytes - lead);
+  StepTensor t[3] = {{P, P_s1, P_s2}, {Q, Q_s1, Q_s2}, {bq, bq_s1, bq_s2}};
+  if (!step_tensors_ok(rule->kind, t, 3, 2)) return DRX_EINVAL;
+  Carver cv(nullptr, 0);
+  if (int rc = step_carver(scratch, scratch_bytes, cv)) return rc;
   BprScratch S;
   if (!bpr_carve(cv, T, ld, n_users, n_items, S)) return DRX_EINVAL;
   if (!cv.ok()) return DRX_ESCRATCH;
@@ -217,21 +193,13 @@ int drx_bpr_step(float *P, float *Q, float *bq, float *P_s1, float *P_s2, float 
     return DRX_OK;
   });
   if (rc) return rc;
-  if (loss_out) hipLaunchKernelGGL(k_bpr_loss, dim3(1), dim3(64), 0, st, S.loss_part, S.blocks, T, loss_out);
+  if (loss_out) hipLaunchKernelGGL(k_loss_mean<>, dim3(1), dim3(64), 0, st, S.loss_part, S.blocks, (double)T, loss_out);
   DrxCsrList ls[2];
   bpr_lists(uid, S, T, n_users, n_items, ls);
   rc = drx_batch_csr_device(ls, 2, S.csr, S.csr_bytes, stream);
   if (rc) return rc;
-  DrxCsrAdamTable tabs[2];
-  memset(tabs, 0, sizeof(tabs));
-  tabs[0].row_ptr = S.rp_u; tabs[0].order = S.ord_u; tabs[0].src = S.dP;
-  tabs[0].group = 0; tabs[0].ld = ld; tabs[0].n_rows = n_users;
-  tabs[0].p = P; tabs[0].m = P_s1; tabs[0].v = P_s2;
-  tabs[0].alpha = alphas[0]; tabs[0].l2_coef = reg;
-  tabs[1].row_ptr = S.rp_i; tabs[1].order = S.ord_i; tabs[1].src = S.pu; tabs[1].scale = S.gs;
-  tabs[1].group = 2; tabs[1].ld = ld; tabs[1].n_rows = n_items;
-  tabs[1].p = Q; tabs[1].m = Q_s1; tabs[1].v = Q_s2; tabs[1].p_s = bq; tabs[1].m_s = bq_s1; tabs[1].v_s = bq_s2;
-  tabs[1].alpha = alphas[1]; tabs[1].alpha_s = alphas[2]; tabs[1].l2_coef = reg;
+  const DrxCsrAdamTable tabs[2] = {step_table(S.rp_u, S.ord_u, S.dP, ld, n_users, t[0], alphas[0], reg),
+                                   step_table_outer(S.rp_i, S.ord_i, S.pu, S.gs, 2, ld, n_items, t[1], t[2], alphas[1], alphas[2], reg)};
   return drx_rows_csr_opt_multi(tabs, 2, rule, stream);
 }
 

@@ -9,6 +9,7 @@
 #include "drx_common.hpp"
 #include "drx_rows.hpp"
 #include "drx_opt.hpp"
+#include "drx_step.hpp"
 
 namespace drx {
 
@@ -58,7 +59,6 @@ __global__ __launch_bounds__(kBlock) void k_fpmc_fwd_bwd(const float *__restrict
                                                          int r, float *__restrict__ ctx, float *__restrict__ dP, float *__restrict__ dM,
                                                          float *__restrict__ gs, double *__restrict__ loss_part) {
   constexpr int gpb = kBlock / G;
-  __shared__ double part[gpb];
   const int lane = threadIdx.x % G, gid = threadIdx.x / G;
   const int w = blockIdx.x * gpb + gid;
   const int ld2 = 2 * ld, h = ld >> 2;
@@ -109,23 +109,7 @@ __global__ __launch_bounds__(kBlock) void k_fpmc_fwd_bwd(const float *__restrict
       for (int l = 0; l < L; ++l) reinterpret_cast<float4 *>(dM + ((size_t)w * L + l) * ld)[lane - h] = d;
     }
   }
-  if (lane == 0) part[gid] = loss;
-  __syncthreads();
-  if (threadIdx.x == 0) {
-    double s = 0.0;
-    for (int k = 0; k < gpb; ++k) s += part[k];
-    loss_part[blockIdx.x] = s;
-  }
-}
-
-// loss_out[0] = (sum of the n partials) / denom: lane l adds partials l, l + 64, ... ascending, then a fixed shuffle tree
-__global__ __launch_bounds__(64) void k_fpmc_loss(const double *__restrict__ part, int n, double denom, double *__restrict__ out) {
-  const int lane = threadIdx.x;
-  double s = 0.0;
-  for (int k = lane; k < n; k += 64) s += part[k];
-#pragma unroll
-  for (int m = 32; m >= 1; m >>= 1) s += __shfl_xor(s, m, 64);
-  if (lane == 0) out[0] = s / denom;
+  block_loss_partial<gpb>(lane, gid, loss, loss_part);
 }
 
 template <int G>
@@ -165,7 +149,7 @@ static bool fpmc_shape_ok(int64_t B, int L, int r, int ld, int n_users, int n_it
   return B >= 1 && B < (1 << 24) && L >= 1 && L <= kFpmcMaxL && r >= 1 && r <= kFpmcMaxNeg && n_users >= 1 && n_items >= 1 && fpmc_ld_ok(ld);
 }
 
-// carves the step's scratch; false when the description is invalid.  (Sizes only over a base that is never dereferenced, as bpr_carve.)
+// carves the step's scratch; false when the description is invalid
 static bool fpmc_carve(Carver &cv, int B, int L, int r, int ld, int n_users, int n_items, FpmcScratch &S) {
   if (!fpmc_shape_ok(B, L, r, ld, n_users, n_items)) return false;
   const int gpb = kBlock / pick_geom(2 * ld).G;
@@ -195,10 +179,9 @@ extern "C" {
 
 size_t drx_fpmc_step_scratch_bytes(int32_t B, int32_t L, int32_t neg_ratio, int32_t ld, int32_t n_users, int32_t n_items) {
   using namespace drx;
-  Carver cv(reinterpret_cast<void *>(uintptr_t(256)), 0);
+  Carver cv = step_dry_carver();
   FpmcScratch S;
-  if (!fpmc_carve(cv, B, L, neg_ratio, ld, n_users, n_items, S)) return 0;
-  return align_up(cv.off, 256) + 256;                  // (+ 256: the step aligns the base it is given)
+  return fpmc_carve(cv, B, L, neg_ratio, ld, n_users, n_items, S) ? step_scratch_total(cv) : 0;
 }
 
 int drx_fpmc_step(float *P, float *M, float *QN, float *b, float *P_s1, float *P_s2, float *M_s1, float *M_s2, float *QN_s1, float *QN_s2,
@@ -209,19 +192,10 @@ int drx_fpmc_step(float *P, float *M, float *QN, float *b, float *P_s1, float *P
   const int r = neg_ratio;
   if (!P || !M || !QN || !b || !uid || !before || !after || !rule || !alphas || !scratch || !fpmc_shape_ok(B, L, r, ld, n_users, n_items))
     return DRX_EINVAL;
-  const int kind = rule->kind;
-  if (!opt_dense_kind(kind) || !opt_slots_ok(kind, P_s1, P_s2) || !opt_slots_ok(kind, M_s1, M_s2) || !opt_slots_ok(kind, QN_s1, QN_s2) ||
-      !opt_slots_ok(kind, b_s1, b_s2))
-    return DRX_EINVAL;
-  if (!opt_has_s1(kind)) P_s1 = M_s1 = QN_s1 = b_s1 = nullptr;
-  if (!opt_has_s2(kind)) P_s2 = M_s2 = QN_s2 = b_s2 = nullptr;
-  if (((uintptr_t)P | (uintptr_t)M | (uintptr_t)QN | (uintptr_t)P_s1 | (uintptr_t)P_s2 | (uintptr_t)M_s1 | (uintptr_t)M_s2 | (uintptr_t)QN_s1 |
-       (uintptr_t)QN_s2) & 15)
-    return DRX_EINVAL;
-  char *base = (char *)(((uintptr_t)scratch + 255) & ~uintptr_t(255));
-  const size_t lead = (size_t)(base - (char *)scratch);
-  if (scratch_bytes < lead) return DRX_ESCRATCH;
-  Carver cv(base, scratch_bytes - lead);
+  StepTensor t[4] = {{P, P_s1, P_s2}, {M, M_s1, M_s2}, {QN, QN_s1, QN_s2}, {b, b_s1, b_s2}};
+  if (!step_tensors_ok(rule->kind, t, 4, 3)) return DRX_EINVAL;
+  Carver cv(nullptr, 0);
+  if (int rc = step_carver(scratch, scratch_bytes, cv)) return rc;
   FpmcScratch S;
   if (!fpmc_carve(cv, B, L, r, ld, n_users, n_items, S)) return DRX_EINVAL;
   if (!cv.ok()) return DRX_ESCRATCH;
@@ -234,25 +208,14 @@ int drx_fpmc_step(float *P, float *M, float *QN, float *b, float *P_s1, float *P
     return DRX_OK;
   });
   if (rc) return rc;
-  if (loss_out) hipLaunchKernelGGL(k_fpmc_loss, dim3(1), dim3(64), 0, st, S.loss_part, S.blocks, (double)B * (double)r, loss_out);
+  if (loss_out) hipLaunchKernelGGL(k_loss_mean<>, dim3(1), dim3(64), 0, st, S.loss_part, S.blocks, (double)B * (double)r, loss_out);
   DrxCsrList ls[3];
   fpmc_lists(uid, before, after, S, B, L, r, n_users, n_items, ls);
   rc = drx_batch_csr_device(ls, 3, S.csr, S.csr_bytes, stream);
   if (rc) return rc;
-  DrxCsrAdamTable tabs[3];
-  memset(tabs, 0, sizeof(tabs));
-  tabs[0].row_ptr = S.rp_u; tabs[0].order = S.ord_u; tabs[0].src = S.dP;
-  tabs[0].group = 0; tabs[0].ld = ld; tabs[0].n_rows = n_users;
-  tabs[0].p = P; tabs[0].m = P_s1; tabs[0].v = P_s2;
-  tabs[0].alpha = alphas[0]; tabs[0].l2_coef = reg;
-  tabs[1].row_ptr = S.rp_m; tabs[1].order = S.ord_m; tabs[1].src = S.dM;
-  tabs[1].group = 0; tabs[1].ld = ld; tabs[1].n_rows = n_items;
-  tabs[1].p = M; tabs[1].m = M_s1; tabs[1].v = M_s2;
-  tabs[1].alpha = alphas[1]; tabs[1].l2_coef = reg;
-  tabs[2].row_ptr = S.rp_i; tabs[2].order = S.ord_i; tabs[2].src = S.ctx; tabs[2].scale = S.gs;
-  tabs[2].group = 1 + r; tabs[2].ld = 2 * ld; tabs[2].n_rows = n_items;
-  tabs[2].p = QN; tabs[2].m = QN_s1; tabs[2].v = QN_s2; tabs[2].p_s = b; tabs[2].m_s = b_s1; tabs[2].v_s = b_s2;
-  tabs[2].alpha = alphas[2]; tabs[2].alpha_s = alphas[3]; tabs[2].l2_coef = reg;
+  const DrxCsrAdamTable tabs[3] = {
+      step_table(S.rp_u, S.ord_u, S.dP, ld, n_users, t[0], alphas[0], reg), step_table(S.rp_m, S.ord_m, S.dM, ld, n_items, t[1], alphas[1], reg),
+      step_table_outer(S.rp_i, S.ord_i, S.ctx, S.gs, 1 + r, 2 * ld, n_items, t[2], t[3], alphas[2], alphas[3], reg)};
   return drx_rows_csr_opt_multi(tabs, 3, rule, stream);
 }
 

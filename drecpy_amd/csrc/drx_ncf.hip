@@ -8,6 +8,7 @@
 #include "drx_common.hpp"
 #include "drx_rows.hpp"
 #include "drx_opt.hpp"
+#include "drx_step.hpp"
 
 namespace drx {
 
@@ -455,10 +456,9 @@ int drx_ncf_grid(int32_t B) {
 
 size_t drx_ncf_step_scratch_bytes(const DrxNcfDims *D, int32_t B) {
   using namespace drx;
-  Carver cv(reinterpret_cast<void *>(uintptr_t(256)), 0);
+  Carver cv = step_dry_carver();
   NcfScratch S;
-  if (!ncf_carve(cv, D, B, S)) return 0;
-  return align_up(cv.off, 256) + 256;                  // (+ 256: the step aligns the base it is given)
+  return ncf_carve(cv, D, B, S) ? step_scratch_total(cv) : 0;
 }
 
 int drx_ncf_step(const DrxNcfDims *D, float *U, float *V, float *sw, float *U_s1, float *U_s2, float *V_s1, float *V_s2, float *sw_s1,
@@ -468,15 +468,10 @@ int drx_ncf_step(const DrxNcfDims *D, float *U, float *V, float *sw, float *U_s1
   if (!D || !U || !V || !sw || !uid || !iid || !y || !rule || !alphas || !scratch || !ncf_dims_ok(D) || B < 1 || B >= (1 << 24))
     return DRX_EINVAL;
   const int kind = rule->kind;
-  if (!opt_dense_kind(kind) || !opt_slots_ok(kind, U_s1, U_s2) || !opt_slots_ok(kind, V_s1, V_s2) || !opt_slots_ok(kind, sw_s1, sw_s2))
-    return DRX_EINVAL;
-  if (!opt_has_s1(kind)) U_s1 = V_s1 = sw_s1 = nullptr;
-  if (!opt_has_s2(kind)) U_s2 = V_s2 = sw_s2 = nullptr;
-  if (((uintptr_t)U | (uintptr_t)V | (uintptr_t)U_s1 | (uintptr_t)U_s2 | (uintptr_t)V_s1 | (uintptr_t)V_s2) & 15) return DRX_EINVAL;
-  char *base = (char *)(((uintptr_t)scratch + 255) & ~uintptr_t(255));
-  const size_t lead = (size_t)(base - (char *)scratch);
-  if (scratch_bytes < lead) return DRX_ESCRATCH;
-  Carver cv(base, scratch_bytes - lead);
+  StepTensor t[3] = {{U, U_s1, U_s2}, {V, V_s1, V_s2}, {sw, sw_s1, sw_s2}};
+  if (!step_tensors_ok(kind, t, 3, 2)) return DRX_EINVAL;
+  Carver cv(nullptr, 0);
+  if (int rc = step_carver(scratch, scratch_bytes, cv)) return rc;
   NcfScratch S;
   if (!ncf_carve(cv, D, B, S)) return DRX_EINVAL;
   if (!cv.ok()) return DRX_ESCRATCH;
@@ -497,7 +492,7 @@ int drx_ncf_step(const DrxNcfDims *D, float *U, float *V, float *sw, float *U_s1
   }
   seg(D->off_h, D->off_b0 - D->off_h, reg);
   seg(D->off_b0, 1, 0.f);
-  hipLaunchKernelGGL(k_ncf_small_opt, dim3((D->n_small + 255) / 256), dim3(256), 0, st, S.gsw_part, S.grid, D->n_small, sw, sw_s1, sw_s2,
+  hipLaunchKernelGGL(k_ncf_small_opt, dim3((D->n_small + 255) / 256), dim3(256), 0, st, S.gsw_part, S.grid, D->n_small, sw, t[2].s1, t[2].s2,
                      sg, kind, rule->mu, rule->mu2, rule->eps, S.loss_part, (double)B, loss_out);
   DRX_LAUNCH_CHECK();
   DrxCsrList ls[2];
@@ -505,16 +500,8 @@ int drx_ncf_step(const DrxNcfDims *D, float *U, float *V, float *sw, float *U_s1
   int rc = drx_batch_csr_device(ls, 2, S.csr, S.csr_bytes, stream);
   if (rc) return rc;
   const int ld = D->ldg + D->ldm;
-  DrxCsrAdamTable tabs[2];
-  memset(tabs, 0, sizeof(tabs));
-  tabs[0].row_ptr = S.rp_u; tabs[0].order = S.ord_u; tabs[0].src = S.dU;
-  tabs[0].group = 0; tabs[0].ld = ld; tabs[0].n_rows = D->n_users;
-  tabs[0].p = U; tabs[0].m = U_s1; tabs[0].v = U_s2;
-  tabs[0].alpha = alphas[0]; tabs[0].l2_coef = reg;
-  tabs[1].row_ptr = S.rp_i; tabs[1].order = S.ord_i; tabs[1].src = S.dV;
-  tabs[1].group = 0; tabs[1].ld = ld; tabs[1].n_rows = D->n_items;
-  tabs[1].p = V; tabs[1].m = V_s1; tabs[1].v = V_s2;
-  tabs[1].alpha = alphas[1]; tabs[1].l2_coef = reg;
+  const DrxCsrAdamTable tabs[2] = {step_table(S.rp_u, S.ord_u, S.dU, ld, D->n_users, t[0], alphas[0], reg),
+                                   step_table(S.rp_i, S.ord_i, S.dV, ld, D->n_items, t[1], alphas[1], reg)};
   return drx_rows_csr_opt_multi(tabs, 2, rule, stream);
 }
 

@@ -20,16 +20,13 @@ class AlsEngine(RowsRecommender):
     EPILOGUE = _lib.DRX_REC_BIAS
 
     def __init__(self, n_users, n_items, factors=64, device='cuda:0'):
-        if not torch.cuda.is_available():
-            raise _lib.DrxError('drecpy_amd needs a ROCm GPU (MI355X); there is no CPU fallback.')
+        self._require_gpu()
         if not (isinstance(factors, (int, np.integer)) and 1 <= factors <= MAX_FACTORS):
             raise _lib.DrxError(f'ALS engine: factors must be an integer in 1..{MAX_FACTORS} (a row\'s K x K system lives in one '
                                 f'workgroup\'s LDS), got factors={factors!r}')
-        lib()
-        self.device = torch.device(device)
-        self.n_users, self.n_items, self.K = int(n_users), int(n_items), int(factors)
+        z = self._open(n_users, n_items, device)
+        self.K = int(factors)
         self.ld = _round_up(self.K, 4)
-        z = dict(dtype=torch.float32, device=self.device)
         self.X = torch.zeros(self.n_users, self.ld, **z)
         self.Y = torch.zeros(self.n_items, self.ld, **z)
         self.bias = torch.zeros(self.n_items, **z)                # stays zero: the scorer's epilogue adds it
@@ -40,9 +37,8 @@ class AlsEngine(RowsRecommender):
         self._loss = torch.zeros(1, dtype=torch.float64, device=self.device)
         self._frame = None
         self._als_scratch = torch.empty(self.scratch_need(self.n_users, self.n_items, self.ld), dtype=torch.uint8, device=self.device)
-        from .Recommender.trainables import TrainableModel
-        self.user_emb = TrainableModel('user_factors', lambda: [self.X[:, :self.K]])
-        self.item_emb = TrainableModel('item_factors', lambda: [self.Y[:, :self.K]])
+        self.user_emb = self._handle('user_factors', 'X')
+        self.item_emb = self._handle('item_factors', 'Y')
 
     @staticmethod
     def scratch_need(n_users, n_items, ld):
@@ -56,17 +52,9 @@ class AlsEngine(RowsRecommender):
     def tensors(self):
         return {'X': self.X, 'Y': self.Y}
 
-    def set_params(self, p):
-        """p: {'X': [n_users, K], 'Y': [n_items, K]} (unpadded); the padding columns are zeroed"""
-        t = lambda a, shape: torch.as_tensor(np.asarray(a, dtype=np.float32).reshape(shape)).to(self.device)
-        for x in self.tensors().values():
-            x.zero_()
-        self.X[:, :self.K] = t(p['X'], (self.n_users, self.K))
-        self.Y[:, :self.K] = t(p['Y'], (self.n_items, self.K))
-
-    def get_params(self):
-        c = lambda x: x.detach().cpu().numpy().copy()
-        return {'X': c(self.X[:, :self.K]), 'Y': c(self.Y[:, :self.K])}
+    def views(self):
+        """{'X': [n_users, K], 'Y': [n_items, K]}"""
+        return {'X': self.X[:, :self.K], 'Y': self.Y[:, :self.K]}
 
     def snapshot(self):
         return {'p': {n: t.clone() for n, t in self.tensors().items()}}
@@ -132,25 +120,6 @@ class AlsEngine(RowsRecommender):
         return self.loss() if want_loss else None
 
     # ---- scores ----------------------------------------------------------------------------------------------------------------------
-    def _rows(self, table, ids):
-        """[len(ids), ld] rows of `table` by device id (drx_bpr_gather_rows: a plain row gather)"""
-        n = int(ids.numel())
-        out = torch.empty(n, self.ld, dtype=torch.float32, device=self.device)
-        if n:
-            check(lib().drx_bpr_gather_rows(ptr(table), self.ld, ptr(ids), n, ptr(out), stream_ptr(self.device)), 'drx_bpr_gather_rows')
-        return out
-
-    def score_matrix(self, uids):
-        """[len(uids), n_items] scores of the given users against all items (drx_rows_dot): the score-matrix route of _rank_rows"""
-        uid = self._dev_i32(uids).reshape(-1)
-        B = int(uid.numel())
-        out = torch.empty(B, self.n_items, dtype=torch.float32, device=self.device)
-        if B:
-            q = self._rows(self.X, uid)
-            check(lib().drx_rows_dot(ptr(q), B, ptr(self.Y), self.n_items, self.ld, ptr(self.bias), ptr(out), stream_ptr(self.device)),
-                  'drx_rows_dot')
-        return out
-
     def rank_ld(self):
         return self.ld
 
@@ -158,4 +127,4 @@ class AlsEngine(RowsRecommender):
         return self.Y, self.bias
 
     def _query_rows(self, uid):
-        return self._rows(self.X, uid)
+        return self._gather_rows(self.X, uid)

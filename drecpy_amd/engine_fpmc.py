@@ -23,55 +23,36 @@ MAX_NEG_RATIO = 16
 
 class FpmcEngine(DenseEngine):
     EPILOGUE = _lib.DRX_REC_BIAS
+    ALPHA_OF = (0, 1, 2, 2)                # P, M, then QN and b with the item handle
 
     def __init__(self, n_users, n_items, factors=64, L=1, device='cuda:0'):
-        if not torch.cuda.is_available():
-            raise _lib.DrxError('drecpy_amd needs a ROCm GPU (MI355X); there is no CPU fallback.')
+        self._require_gpu()
         if not (isinstance(factors, (int, np.integer)) and 1 <= factors <= MAX_FACTORS):
             raise _lib.DrxError(f'FPMC engine: factors must be an integer in 1..{MAX_FACTORS} (a row [Q | N] of the fused scorer holds at most '
                                 f'256 floats), got factors={factors!r}')
         if not (isinstance(L, (int, np.integer)) and 1 <= L <= MAX_L):
             raise _lib.DrxError(f'FPMC engine: L must be an integer in 1..{MAX_L}, got L={L!r}')
-        lib()
-        self.device = torch.device(device)
-        self.n_users, self.n_items, self.K, self.L = int(n_users), int(n_items), int(factors), int(L)
+        z = self._open(n_users, n_items, device)
+        self.K, self.L = int(factors), int(L)
         self.ld = _round_up(self.K, 4)
-        z = dict(dtype=torch.float32, device=self.device)
         self.P = torch.zeros(self.n_users, self.ld, **z)
         self.M = torch.zeros(self.n_items, self.ld, **z)
         self.QN = torch.zeros(self.n_items, 2 * self.ld, **z)
         self.b = torch.zeros(self.n_items, **z)
         self.baskets = torch.full((self.n_users, self.L), -1, dtype=torch.int32, device=self.device)
-        self._init_optimizer_state()
-        self.lr, self.reg = 1e-3, 1e-3
-        self._scratch = None
-        self._loss = torch.zeros(1, dtype=torch.float64, device=self.device)
-        from .Recommender.trainables import TrainableModel
-        K, ld = self.K, self.ld
+        self._init_step_state()
         # what FPMC._pre_fit registers, in this order: one apply_gradients per handle and step (the item side with its biases)
-        self.user_emb = TrainableModel('user_factors', lambda: [self.P[:, :K]])
-        self.trans_emb = TrainableModel('transition_factors', lambda: [self.M[:, :K]])
-        self.item_emb = TrainableModel('item_factors', lambda: [self.QN[:, :K], self.QN[:, ld:ld + K], self.b])
+        self.user_emb = self._handle('user_factors', 'P')
+        self.trans_emb = self._handle('transition_factors', 'M')
+        self.item_emb = self._handle('item_factors', 'Q', 'N', 'b')
 
     def tensors(self):
         return {'P': self.P, 'M': self.M, 'QN': self.QN, 'b': self.b}
 
-    def set_params(self, p):
-        """p: {'P': [n_users, K], 'Q', 'M', 'N': [n_items, K], 'b': [n_items]} (unpadded); the padding columns are zeroed"""
-        t = lambda a, shape: torch.as_tensor(np.asarray(a, dtype=np.float32).reshape(shape)).to(self.device)
-        for x in self.tensors().values():
-            x.zero_()
+    def views(self):
+        """{'P': [n_users, K], 'Q', 'M', 'N': [n_items, K], 'b': [n_items]}: Q and N are the two halves of a row of QN"""
         K, ld = self.K, self.ld
-        self.P[:, :K] = t(p['P'], (self.n_users, K))
-        self.M[:, :K] = t(p['M'], (self.n_items, K))
-        self.QN[:, :K] = t(p['Q'], (self.n_items, K))
-        self.QN[:, ld:ld + K] = t(p['N'], (self.n_items, K))
-        self.b.copy_(t(p['b'], (self.n_items,)))
-
-    def get_params(self):
-        c = lambda x: x.detach().cpu().numpy().copy()
-        K, ld = self.K, self.ld
-        return {'P': c(self.P[:, :K]), 'Q': c(self.QN[:, :K]), 'M': c(self.M[:, :K]), 'N': c(self.QN[:, ld:ld + K]), 'b': c(self.b)}
+        return {'P': self.P[:, :K], 'Q': self.QN[:, :K], 'M': self.M[:, :K], 'N': self.QN[:, ld:ld + K], 'b': self.b}
 
     def set_baskets(self, baskets):
         """baskets [n_users, L] int: the items the transition term of serving averages over, in sequence order; -1 = an absent position"""
@@ -81,14 +62,6 @@ class FpmcEngine(DenseEngine):
         self.baskets.copy_(torch.as_tensor(a))
 
     # ---- the step (include/drx.h drx_fpmc_step) ------------------------------------------------------------------------------------
-    def _step_sizes(self, step_idx, applies):
-        """(alpha_P, alpha_M, alpha_QN, alpha_b): Keras Adam's lr_t of each apply's counter; the learning rate under every other rule"""
-        n, positions = applies[0], applies[1:]
-        if self.opt_kind != 'adam':
-            return (self.lr,) * 4
-        a = [self.adam_alpha(self.lr, n * step_idx + j + 1, self.beta1, self.beta2) for j in positions]
-        return a[0], a[1], a[2], a[2]
-
     def step(self, step_idx, uid, before, after, want_loss=False, applies=None):
         """One step on B windows (arrays or device tensors): uid [B], before [B, L], after [B, 1 + r] (the target first).
         applies = (n, j_user, j_transition, j_item): the number of apply_gradients calls per step and the positions of the three
@@ -101,35 +74,17 @@ class FpmcEngine(DenseEngine):
         assert before.shape[1] == self.L, f'a window holds L = {self.L} previous items'
         r = int(after.shape[1]) - 1
         L_ = lib()
-        need = int(L_.drx_fpmc_step_scratch_bytes(B, self.L, r, self.ld, self.n_users, self.n_items))
-        if need == 0:
-            raise _lib.DrxError(f'drx_fpmc_step: a batch of {B} windows of {self.L} + 1 + {r} items at {self.ld} factors is outside its '
-                                f'domain (1..{MAX_NEG_RATIO} negatives per window)')
-        if self._scratch is None or self._scratch.numel() < need:
-            self._scratch = None
-            self._scratch = torch.empty(need, dtype=torch.uint8, device=self.device)
-        alphas = (C.c_float * 4)(*self._step_sizes(step_idx, applies))
-        slots = [s for name in ('P', 'M', 'QN', 'b') for s in self.state[name]]
-        check(L_.drx_fpmc_step(ptr(self.P), ptr(self.M), ptr(self.QN), ptr(self.b), *[ptr(s) for s in slots], self.ld, self.n_users,
-                               self.n_items, ptr(uid), ptr(before), ptr(after), B, self.L, r, C.byref(self._rule()), alphas, float(self.reg),
-                               ptr(self._loss) if want_loss else None, ptr(self._scratch), self._scratch.numel(), stream_ptr(self.device)),
-              'drx_fpmc_step')
-        return float(self._loss.cpu().numpy()[0]) if want_loss else None
+        scratch = self._step_scratch(int(L_.drx_fpmc_step_scratch_bytes(B, self.L, r, self.ld, self.n_users, self.n_items)),
+                                     lambda: f'drx_fpmc_step: a batch of {B} windows of {self.L} + 1 + {r} items at {self.ld} factors is outside its '
+                                     f'domain (1..{MAX_NEG_RATIO} negatives per window)')
+        alphas, slots, loss = self._step_args(step_idx, applies, want_loss)
+        check(L_.drx_fpmc_step(ptr(self.P), ptr(self.M), ptr(self.QN), ptr(self.b), *slots, self.ld, self.n_users, self.n_items, ptr(uid),
+                               ptr(before), ptr(after), B, self.L, r, C.byref(self._rule()), alphas, float(self.reg), loss, ptr(scratch),
+                               scratch.numel(), stream_ptr(self.device)), 'drx_fpmc_step')
+        return self._read_loss(want_loss)
 
-    # ---- scores ----------------------------------------------------------------------------------------------------------------------
-    def score_matrix(self, uids):
-        """[len(uids), n_items] scores of the given users (their baskets) against all items (drx_rows_dot at 2 ld): the score-matrix
-        route of _rank_rows"""
-        uid = self._dev_i32(uids).reshape(-1)
-        B = int(uid.numel())
-        out = torch.empty(B, self.n_items, dtype=torch.float32, device=self.device)
-        if B:
-            q = self._query_rows(uid)
-            check(lib().drx_rows_dot(ptr(q), B, ptr(self.QN), self.n_items, 2 * self.ld, ptr(self.b), ptr(out), stream_ptr(self.device)),
-                  'drx_rows_dot')
-        return out
-
-    # what the four calls of RowsRecommender score against: [Q | N] and b themselves, and the context rows of the users' baskets
+    # what the four calls of RowsRecommender and its score_matrix (at 2 ld) score against: [Q | N] and b themselves, and the context
+    # rows of the users' baskets
     def rank_ld(self):
         return 2 * self.ld
 

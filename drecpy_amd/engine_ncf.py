@@ -13,7 +13,7 @@ import numpy as np
 import torch
 
 from . import _lib
-from ._lib import History, check, lib, ptr, stream_ptr
+from ._lib import check, lib, ptr, stream_ptr
 from .engine_dense import DenseEngine
 from .engine_rows import _round_up
 
@@ -39,13 +39,12 @@ def check_shape(factors, mlp_factors, layers, who='NeuMF engine'):
 
 
 class NcfEngine(DenseEngine):
+    ALPHA_OF = (0, 1, 2)                   # U, V and the small weights, a handle each
+
     def __init__(self, n_users, n_items, factors=8, mlp_factors=32, layers=(32, 16, 8), device='cuda:0'):
-        if not torch.cuda.is_available():
-            raise _lib.DrxError('drecpy_amd needs a ROCm GPU (MI355X); there is no CPU fallback.')
+        self._require_gpu()
         self.Kg, self.Km, self.layers = check_shape(factors, mlp_factors, layers)
-        lib()
-        self.device = torch.device(device)
-        self.n_users, self.n_items = int(n_users), int(n_items)
+        z = self._open(n_users, n_items, device)
         self.ldg, self.ldm = _round_up(self.Kg, 4), _round_up(self.Km, 4)
         self.ld = self.ldg + self.ldm
         # the flat array of small weights: W_1, b_1, ..., W_n, b_n, h = [hg | hm], b0 (include/drx.h DrxNcfDims)
@@ -61,20 +60,14 @@ class NcfEngine(DenseEngine):
         self.slices['hg'], self.slices['hm'], self.slices['b0'] = (off, (self.Kg,)), (off + self.Kg, (fin,)), (off + self.Kg + fin, (1,))
         self.n_small = int(d.n_small)
         self.hw = int(lib().drx_ncf_half_width(C.byref(d)))
-        z = dict(dtype=torch.float32, device=self.device)
         self.U = torch.zeros(self.n_users, self.ld, **z)
         self.V = torch.zeros(self.n_items, self.ld, **z)
         self.sw = torch.zeros(self.n_small, **z)
-        self._init_optimizer_state()
-        self.lr, self.reg = 1e-3, 1e-3
-        self._scratch = None
-        self._loss = torch.zeros(1, dtype=torch.float64, device=self.device)
-        from .Recommender.trainables import TrainableModel
-        Kg, Km, ldg = self.Kg, self.Km, self.ldg
+        self._init_step_state()
         # what NeuMF._pre_fit registers, in this order: one apply_gradients per handle and step
-        self.user_emb = TrainableModel('user_embeddings', lambda: [self.U[:, :Kg], self.U[:, ldg:ldg + Km]])
-        self.item_emb = TrainableModel('item_embeddings', lambda: [self.V[:, :Kg], self.V[:, ldg:ldg + Km]])
-        self.small = TrainableModel('small_weights', lambda: [self._small(n) for n in self.slices])
+        self.user_emb = self._handle('user_embeddings', 'Pg', 'Pm')
+        self.item_emb = self._handle('item_embeddings', 'Qg', 'Qm')
+        self.small = self._handle('small_weights', *self.slices)
 
     def tensors(self):
         return {'U': self.U, 'V': self.V, 'sw': self.sw}
@@ -83,39 +76,23 @@ class NcfEngine(DenseEngine):
         off, shape = self.slices[name]
         return self.sw[off:off + int(np.prod(shape))].view(*shape)
 
+    def views(self):
+        """{'Pg': [n_users, Kg], 'Pm': [n_users, Km], 'Qg', 'Qm', 'W1' [2 Km, f_1], 'b1' [f_1], ..., 'hg' [Kg], 'hm' [f_n], 'b0' [1]}"""
+        Kg, Km, ldg = self.Kg, self.Km, self.ldg
+        v = {'Pg': self.U[:, :Kg], 'Pm': self.U[:, ldg:ldg + Km], 'Qg': self.V[:, :Kg], 'Qm': self.V[:, ldg:ldg + Km]}
+        v.update({name: self._small(name) for name in self.slices})
+        return v
+
     def set_params(self, p):
-        """p: {'Pg': [n_users, Kg], 'Pm': [n_users, Km], 'Qg', 'Qm', 'W1' [2 Km, f_1], 'b1' [f_1], ..., 'hg' [Kg], 'hm' [f_n], 'b0' [1]}
-        (unpadded); the padding columns are zeroed"""
-        t = lambda a, shape: torch.as_tensor(np.asarray(a, dtype=np.float32).reshape(shape)).to(self.device)
         missing = [n for n in ['Pg', 'Pm', 'Qg', 'Qm'] + list(self.slices) if n not in p]
         if missing:
             raise _lib.DrxError(f'NeuMF engine: set_params lacks {missing}')
-        for x in self.tensors().values():
-            x.zero_()
-        Kg, Km, ldg = self.Kg, self.Km, self.ldg
-        self.U[:, :Kg], self.U[:, ldg:ldg + Km] = t(p['Pg'], (self.n_users, Kg)), t(p['Pm'], (self.n_users, Km))
-        self.V[:, :Kg], self.V[:, ldg:ldg + Km] = t(p['Qg'], (self.n_items, Kg)), t(p['Qm'], (self.n_items, Km))
-        for name, (_, shape) in self.slices.items():
-            self._small(name).copy_(t(p[name], shape))
-
-    def get_params(self):
-        c = lambda x: x.detach().cpu().numpy().copy()
-        Kg, Km, ldg = self.Kg, self.Km, self.ldg
-        out = {'Pg': c(self.U[:, :Kg]), 'Pm': c(self.U[:, ldg:ldg + Km]), 'Qg': c(self.V[:, :Kg]), 'Qm': c(self.V[:, ldg:ldg + Km])}
-        out.update({name: c(self._small(name)) for name in self.slices})
-        return out
+        super().set_params(p)
 
     # ---- the point stream (include/drx.h drx_point_sample_recorded) ------------------------------------------------------------------
     def set_sampler_frame(self, positives, recorded):
-        """positives = (indptr, indices) of the pairs with interaction >= threshold; recorded = (indptr, indices) of every pair of the
-        frame, or None where all of them are positives (columns ascending)"""
-        d = self.device
-        up = lambda csr: (torch.as_tensor(np.asarray(csr[0], np.int64)).to(d),
-                          torch.as_tensor(np.asarray(csr[1], np.int32) if len(csr[1]) else np.zeros(1, np.int32)).to(d))
-        self._pos = up(positives)
-        self._rec = up(recorded) if recorded is not None else None
-        self._H = History(ptr(self._pos[0]), ptr(self._pos[1]))
-        self._R = History(ptr(self._rec[0]), ptr(self._rec[1])) if self._rec is not None else None
+        """DenseEngine._upload_frame's (columns ascending)"""
+        self._upload_frame(positives, recorded)
 
     def sample(self, B, neg_ratio, seed):
         """(uid int32, iid int32, y float32) [B] device tensors: the B point samples of `seed` (drx_point_sample_recorded)"""
@@ -132,13 +109,6 @@ class NcfEngine(DenseEngine):
         return uid, iid, y
 
     # ---- the step (include/drx.h drx_ncf_step) -----------------------------------------------------------------------------------------
-    def _step_sizes(self, step_idx, applies):
-        """(alpha_U, alpha_V, alpha_sw): Keras Adam's lr_t of each apply's counter; the learning rate under every other rule"""
-        n, positions = applies[0], applies[1:]
-        if self.opt_kind != 'adam':
-            return (self.lr,) * 3
-        return tuple(self.adam_alpha(self.lr, n * step_idx + j + 1, self.beta1, self.beta2) for j in positions)
-
     def step(self, step_idx, uid, iid, y, want_loss=False, applies=None):
         """One step on B point samples (arrays or device tensors): uid, iid [B] ids, y [B] in {0, 1}.  applies = (n, j_user, j_item,
         j_small): the number of apply_gradients calls per step and the positions of the three handles among them (the registration
@@ -150,18 +120,13 @@ class NcfEngine(DenseEngine):
         B = int(uid.numel())
         assert iid.numel() == B and y.numel() == B, 'step takes parallel users, items and targets'
         L_ = lib()
-        need = int(L_.drx_ncf_step_scratch_bytes(C.byref(self.dims), B))
-        if need == 0:
-            raise _lib.DrxError(f'drx_ncf_step: a batch of {B} samples is outside its domain (1 .. 2^24 - 1)')
-        if self._scratch is None or self._scratch.numel() < need:
-            self._scratch = None
-            self._scratch = torch.empty(need, dtype=torch.uint8, device=self.device)
-        alphas = (C.c_float * 3)(*self._step_sizes(step_idx, applies))
-        slots = [s for name in ('U', 'V', 'sw') for s in self.state[name]]
-        check(L_.drx_ncf_step(C.byref(self.dims), ptr(self.U), ptr(self.V), ptr(self.sw), *[ptr(s) for s in slots], ptr(uid), ptr(iid), ptr(y),
-                              B, C.byref(self._rule()), alphas, float(self.reg), ptr(self._loss) if want_loss else None, ptr(self._scratch),
-                              self._scratch.numel(), stream_ptr(self.device)), 'drx_ncf_step')
-        return float(self._loss.cpu().numpy()[0]) if want_loss else None
+        scratch = self._step_scratch(int(L_.drx_ncf_step_scratch_bytes(C.byref(self.dims), B)),
+                                     lambda: f'drx_ncf_step: a batch of {B} samples is outside its domain (1 .. 2^24 - 1)')
+        alphas, slots, loss = self._step_args(step_idx, applies, want_loss)
+        check(L_.drx_ncf_step(C.byref(self.dims), ptr(self.U), ptr(self.V), ptr(self.sw), *slots, ptr(uid), ptr(iid), ptr(y), B,
+                              C.byref(self._rule()), alphas, float(self.reg), loss, ptr(scratch), scratch.numel(), stream_ptr(self.device)),
+              'drx_ncf_step')
+        return self._read_loss(want_loss)
 
     # ---- logits --------------------------------------------------------------------------------------------------------------------------
     def half_rows(self, side, ids=None):

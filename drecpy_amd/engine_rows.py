@@ -58,7 +58,61 @@ class RowsRecommender:
             return a.to(self.device, torch.int32).contiguous()
         return torch.as_tensor(np.ascontiguousarray(a, dtype=np.int32)).to(self.device)
 
+    # ---- what the constructors of the factor baselines open with, and their parameters by name ----------------------------------------
+    @staticmethod
+    def _require_gpu():
+        if not torch.cuda.is_available():
+            raise _lib.DrxError('drecpy_amd needs a ROCm GPU (MI355X); there is no CPU fallback.')
+
+    def _open(self, n_users, n_items, device):
+        """After the engine's own domain checks: the library, the device and the sizes.  Returns the keywords of a float32 device tensor."""
+        lib()
+        self.device = torch.device(device)
+        self.n_users, self.n_items = int(n_users), int(n_items)
+        return dict(dtype=torch.float32, device=self.device)
+
+    def views(self):
+        """name -> the UNPADDED view of a parameter inside tensors(), in get_params()'s order: what an engine of a factor baseline
+        declares once; set_params, get_params and its TrainableModel handles read it"""
+        raise NotImplementedError(f'{type(self).__name__} names its parameters itself')
+
+    def set_params(self, p):
+        """p: name -> array of the shape of views()[name] (unpadded); the padding columns are zeroed"""
+        for x in self.tensors().values():
+            x.zero_()
+        for name, v in self.views().items():
+            v.copy_(torch.as_tensor(np.asarray(p[name], dtype=np.float32).reshape(tuple(v.shape))).to(self.device))
+
+    def get_params(self):
+        return {name: v.detach().cpu().numpy().copy() for name, v in self.views().items()}
+
+    def _handle(self, name, *params):
+        """the TrainableModel a model registers for the parameters `params` of views(): one apply_gradients per handle and step"""
+        from .Recommender.trainables import TrainableModel
+        return TrainableModel(name, lambda: [self.views()[n] for n in params])
+
+    def _gather_rows(self, table, ids):
+        """[len(ids), ld] rows of `table` [n, ld] by device id (drx_bpr_gather_rows: a plain row gather)"""
+        n, ld = int(ids.numel()), int(table.shape[1])
+        out = torch.empty(n, ld, dtype=torch.float32, device=self.device)
+        if n:
+            check(lib().drx_bpr_gather_rows(ptr(table), ld, ptr(ids), n, ptr(out), stream_ptr(self.device)), 'drx_bpr_gather_rows')
+        return out
+
     # ---- the score-matrix route: rank(), ranking_evaluation and requests outside the fused domain ------------------------------------
+    def score_matrix(self, uids):
+        """[len(uids), n_items] scores of the given users against all items, from what the engine declares below (_query_rows,
+        _score_table, rank_ld) through drx_rows_dot: the score-matrix route of _rank_rows.  An engine whose score is no dot product
+        (NeuMF) or whose table is computed (DMF) has its own."""
+        uid = self._dev_i32(uids).reshape(-1)
+        B = int(uid.numel())
+        out = torch.empty(B, self.n_items, dtype=torch.float32, device=self.device)
+        if B:
+            q, (table, bias) = self._query_rows(uid), self._score_table()
+            check(lib().drx_rows_dot(ptr(q), B, ptr(table), self.n_items, self.rank_ld(), ptr(bias), ptr(out), stream_ptr(self.device)),
+                  'drx_rows_dot')
+        return out
+
     def topk(self, scores, k, cand_mask=None):
         """Row-wise top-k with heapq.nlargest((score, iid)) ordering (cdae.py:103)."""
         scores = scores.contiguous()
