@@ -2,8 +2,9 @@ from .als import ALS
 from .base_knn import BaseKNN
 from .bpr import BPR
 from .fpmc import FPMC
+from .gru4rec import GRU4Rec
 from .item_knn import ItemKNN
 from .ncf import NeuMF
 from .user_knn import UserKNN
 
-__all__ = ['ALS', 'BaseKNN', 'BPR', 'FPMC', 'ItemKNN', 'NeuMF', 'UserKNN']
+__all__ = ['ALS', 'BaseKNN', 'BPR', 'FPMC', 'GRU4Rec', 'ItemKNN', 'NeuMF', 'UserKNN']

@@ -1,8 +1,8 @@
-"""What the factor baselines share (DESIGN.md sections 3.7 - 3.10).  A new baseline starts from these two classes:
+"""What the factor baselines share (DESIGN.md sections 3.7 - 3.11).  A new baseline starts from these two classes:
 
     FactorServing     prediction and serving of a model whose engine is a RowsRecommender: x(u, i) = query row . table row + bias on the
-                      fused scorer (ALS, BPR, FPMC), the candidate ranking of rank() on the engine's score matrix (NeuMF too).
-    SampledDenseFit   the fit() half of a model trained on sampled batches by one fused dense step (BPR, FPMC, NeuMF): the refusals,
+                      fused scorer (ALS, BPR, FPMC, GRU4Rec), the candidate ranking of rank() on the engine's score matrix (NeuMF too).
+    SampledDenseFit   the fit() half of a model trained on sampled batches by one fused dense step (BPR, FPMC, NeuMF, GRU4Rec): the refusals,
                       the seed of every draw, the apply positions of the step and the softplus batch loss.
 
 A model says what differs as class data (MODEL, NEGATIVES_PER, MAX_NEG_RATIO, DENSE_UPDATE_OF) and keeps its own _pre_fit, sampler and
@@ -12,6 +12,19 @@ import numpy as np
 from ..recommender_abc import RecommenderABC
 
 _DENSE_KINDS = ('adam', 'adagrad', 'sgd', 'momentum', 'nesterov', 'rmsprop', 'rmsprop_momentum')
+
+
+def last_items_baskets(sampler, n_users, L):
+    """[n_users, L] int32, left-aligned, -1 = absent: the last min(L, len) ids of every user's sequence as the list sampler orders and
+    thresholds it — the serving baskets of the sequence-aware baselines (FPMC, GRU4Rec)"""
+    out = np.full((int(n_users), int(L)), -1, dtype=np.int32)
+    if getattr(sampler, '_native', None) is None:
+        return out
+    indptr, row_ids, _ = sampler._twin_arrays
+    for g, u in enumerate(np.asarray(sampler._group_values).tolist()):
+        row = row_ids[max(int(indptr[g]), int(indptr[g + 1]) - int(L)):int(indptr[g + 1])]
+        out[int(u), :len(row)] = row
+    return out
 
 
 class FactorServing(RecommenderABC):

@@ -23,7 +23,7 @@ refusals, the draw seeds and _do_batch are SampledDenseFit's.  Single GPU only.
 """
 import numpy as np
 
-from ._base import SampledDenseFit
+from ._base import SampledDenseFit, last_items_baskets
 
 
 class FPMC(SampledDenseFit):
@@ -57,14 +57,7 @@ class FPMC(SampledDenseFit):
 
     def _baskets(self, sampler):
         """[n_users, L] int32, -1 = absent: the last min(L, len) ids of every user's sequence as the sampler orders and thresholds it"""
-        out = np.full((self.n_users, int(self.L)), -1, dtype=np.int32)
-        if getattr(sampler, '_native', None) is None:
-            return out
-        indptr, row_ids, _ = sampler._twin_arrays
-        for g, u in enumerate(np.asarray(sampler._group_values).tolist()):
-            row = row_ids[max(int(indptr[g]), int(indptr[g + 1]) - int(self.L)):int(indptr[g + 1])]
-            out[int(u), :len(row)] = row
-        return out
+        return last_items_baskets(sampler, self.n_users, self.L)
 
     def _pre_fit(self, learning_rate, neg_ratio, reg_rate, **kwds):
         self._start_sampled_fit(neg_ratio)

@@ -1,7 +1,7 @@
 // NeuMF (He et al. 2017; include/drx.h "NeuMF"): the fused GMF + MLP training step, the half rows of serving and
 // the all-item / pair scorer.  Every dense product runs on v_mfma_f32_16x16x4_f32 (fp32 in, fp32 accumulate) out of LDS, M = a tile of 16
 // samples / rows / pairs.  Operand layout (lane l): A[l % 16][l / 16], B[l / 16][l % 16], C register r = C[4 (l / 16) + r][l % 16].
-//   drx_ncf_step        : k_ncf_tile -> k_ncf_small_opt (partials in workgroup order + the rule on sw) -> drx_batch_csr_device (user keys,
+//   drx_ncf_step        : k_ncf_tile -> k_small_opt (drx_small.hpp: partials in workgroup order + the rule on sw) -> drx_batch_csr_device (user keys,
 //                         item keys) -> ONE drx_rows_csr_opt_multi (U plain, V plain).  No atomics.
 //   drx_ncf_half_rows   : [W_1 half^T row + b_1 | hg (.) Pg]  /  [W_1 half^T row | Qg]
 //   drx_ncf_score_rows / drx_ncf_pair_scores : ncf_tile_logit, ONE definition of a pair's sums, for strips of the catalogue and for pairs.
@@ -9,6 +9,7 @@
 #include "drx_rows.hpp"
 #include "drx_opt.hpp"
 #include "drx_step.hpp"
+#include "drx_small.hpp"
 
 namespace drx {
 
@@ -250,33 +251,6 @@ __global__ __launch_bounds__(256) void k_ncf_tile(DrxNcfDims D, const float *__r
   if (threadIdx.x == 0) loss_part[blockIdx.x] = loss;
 }
 
-// sw[j] <- rule(sum of the n_rows partials of j, rows ascending, + l2 of j's segment * sw[j]); one thread per small weight.
-// thread 0 of block 0: loss_out[0] = (sum of the loss partials, ascending) / denom.
-__global__ __launch_bounds__(256) void k_ncf_small_opt(const float *__restrict__ part, int n_rows, int n, float *p, float *m, float *v,
-                                                       DrxAdamSegments sg, int kind, float b1, float b2, float eps,
-                                                       const double *__restrict__ loss_part, double denom, double *loss_out) {
-  const int j = blockIdx.x * 256 + threadIdx.x;
-  if (j == 0 && loss_out) {
-    double s = 0.0;
-    for (int r = 0; r < n_rows; ++r) s += loss_part[r];
-    loss_out[0] = s / denom;
-  }
-  if (j >= n) return;
-  float t = 0.f;
-  for (int r = 0; r < n_rows; ++r) t += part[(size_t)r * n + j];
-  int sgi = -1;
-  for (int k = 0; k < sg.n; ++k)
-    if (j >= sg.start[k] && j < sg.start[k] + sg.len[k]) sgi = k;
-  if (sgi < 0) return;
-  const OptScalars o{kind, sg.alpha[sgi], 0.f, b1, b2, eps, sg.alpha[sgi]};
-  const bool h1 = opt_has_s1(kind), h2 = opt_has_s2(kind);
-  float pp = p[j], mm = h1 ? m[j] : 0.f, vv = h2 ? v[j] : 0.f;
-  opt_update_dense<-1>(o, fmaf(sg.l2_coef[sgi], pp, t), pp, mm, vv);
-  p[j] = pp;
-  if (h1) m[j] = mm;
-  if (h2) v[j] = vv;
-}
-
 struct NcfScratch {
   float *dU, *dV, *gsw_part;
   double *loss_part;
@@ -440,19 +414,11 @@ __global__ __launch_bounds__(256) void k_ncf_pair_scores(DrxNcfDims D, const flo
   if (q4 == 0 && p < P) out[p] = x;
 }
 
-static int ncf_set_lds(const void *kernel, size_t bytes) {
-  if (bytes > 64 * 1024) DRX_HIP(hipFuncSetAttribute(kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)bytes));
-  return DRX_OK;
-}
-
 }  // namespace drx
 
 extern "C" {
 
-int drx_ncf_grid(int32_t B) {
-  const int tiles = B < 1 ? 1 : (B + 15) / 16;
-  return tiles < drx::kNcfMaxGrid ? tiles : drx::kNcfMaxGrid;
-}
+int drx_ncf_grid(int32_t B) { return drx::step_tile_grid(B, drx::kNcfMaxGrid); }
 
 size_t drx_ncf_step_scratch_bytes(const DrxNcfDims *D, int32_t B) {
   using namespace drx;
@@ -477,7 +443,8 @@ int drx_ncf_step(const DrxNcfDims *D, float *U, float *V, float *sw, float *U_s1
   if (!cv.ok()) return DRX_ESCRATCH;
   hipStream_t st = (hipStream_t)stream;
   const size_t lds = ncf_tile_lds(D);
-  if (int rc = ncf_set_lds((const void *)k_ncf_tile, lds)) return rc;
+  static LdsGrant grant;
+  if (int rc = set_dynamic_lds((const void *)k_ncf_tile, lds, grant)) return rc;
   hipLaunchKernelGGL(k_ncf_tile, dim3(S.grid), dim3(256), lds, st, *D, U, V, sw, uid, iid, y, B, S.dU, S.dV, S.gsw_part, S.loss_part);
   DRX_LAUNCH_CHECK();
   DrxAdamSegments sg;
@@ -492,7 +459,7 @@ int drx_ncf_step(const DrxNcfDims *D, float *U, float *V, float *sw, float *U_s1
   }
   seg(D->off_h, D->off_b0 - D->off_h, reg);
   seg(D->off_b0, 1, 0.f);
-  hipLaunchKernelGGL(k_ncf_small_opt, dim3((D->n_small + 255) / 256), dim3(256), 0, st, S.gsw_part, S.grid, D->n_small, sw, t[2].s1, t[2].s2,
+  hipLaunchKernelGGL(k_small_opt<>, dim3((D->n_small + 255) / 256), dim3(256), 0, st, S.gsw_part, S.grid, D->n_small, sw, t[2].s1, t[2].s2,
                      sg, kind, rule->mu, rule->mu2, rule->eps, S.loss_part, (double)B, loss_out);
   DRX_LAUNCH_CHECK();
   DrxCsrList ls[2];
@@ -524,7 +491,8 @@ int drx_ncf_score_rows(const DrxNcfDims *D, const float *sw, const float *uhalf,
   if (!D || !sw || !uhalf || !ihalf || !out || R < 1 || !ncf_dims_ok(D) || (((uintptr_t)uhalf | (uintptr_t)ihalf) & 15)) return DRX_EINVAL;
   const int ub = R < kNcfUserBlock ? R : kNcfUserBlock;
   const size_t lds = ncf_score_lds(D, ub);
-  if (int rc = ncf_set_lds((const void *)k_ncf_score_rows, lds)) return rc;
+  static LdsGrant grant;
+  if (int rc = set_dynamic_lds((const void *)k_ncf_score_rows, lds, grant)) return rc;
   const int strips = (D->n_items + kNcfStrip - 1) / kNcfStrip, blocks = (R + ub - 1) / ub;
   if (blocks > 65535) return DRX_EINVAL;
   hipLaunchKernelGGL(k_ncf_score_rows, dim3(strips, blocks), dim3(256), lds, (hipStream_t)stream, *D, sw, uhalf, ihalf, R, ub, out);
@@ -538,7 +506,8 @@ int drx_ncf_pair_scores(const DrxNcfDims *D, const float *sw, const float *uhalf
   if (!D || !sw || !uhalf || !ihalf || !urow || !irow || !out || P < 1 || !ncf_dims_ok(D) || (((uintptr_t)uhalf | (uintptr_t)ihalf) & 15))
     return DRX_EINVAL;
   const size_t lds = sizeof(float) * (ncf_serve_weights(D) + 8 * 16 * kNcfTS);
-  if (int rc = ncf_set_lds((const void *)k_ncf_pair_scores, lds)) return rc;
+  static LdsGrant grant;
+  if (int rc = set_dynamic_lds((const void *)k_ncf_pair_scores, lds, grant)) return rc;
   hipLaunchKernelGGL(k_ncf_pair_scores, dim3((P + 63) / 64), dim3(256), lds, (hipStream_t)stream, *D, sw, uhalf, ihalf, urow, irow, P, out);
   DRX_LAUNCH_CHECK();
   return DRX_OK;

@@ -1398,6 +1398,60 @@ int drx_ncf_score_rows(const DrxNcfDims *D, const float *sw, const float *uhalf,
 int drx_ncf_pair_scores(const DrxNcfDims *D, const float *sw, const float *uhalf, const float *ihalf, const int32_t *urow,
                         const int32_t *irow, int32_t P, float *out, void *stream);
 
+/* ---- GRU4Rec (Hidasi, Karatzoglou, Baltrunas, Tikk 2016; csrc/drx_gru.hip) ----------------------------------
+ * Tables E [n_items, ldk] (input embeddings, k floats of a row used) and Q [n_items, ldh] (output rows, h floats used), b [n_items];
+ * ldk / ldh = k / h rounded up to a multiple of 4, the padding columns ZERO.  One flat array sw of small weights, in this order, all
+ * row-major and WITHOUT padding (no row, gate block or bias is padded; DrxGruDims has the offsets, which must be exactly these):
+ *     Wx [k, 3 h] at off_wx = 0 | Wh [h, 3 h] at off_wh = 3 k h | bx [3 h] at off_bx = 3 (k + h) h | bhn [h] at off_bhn = off_bx + 3 h
+ *     n_small = off_bhn + h;  the 3 h gate columns are the blocks z | r | n of h columns each (column g h + c = gate g, unit c).
+ * For a window's ordered items s_1 .. s_L, h_0 = 0, x_t = E[s_t]:
+ *     z_t = sigmoid(x_t Wx_z + h_{t-1} Wh_z + bx_z),  r_t = sigmoid(x_t Wx_r + h_{t-1} Wh_r + bx_r)
+ *     n_t = tanh(x_t Wx_n + bx_n + r_t (.) (h_{t-1} Wh_n + bhn)),  h_t = (1 - z_t) (.) n_t + z_t (.) h_{t-1}        (torch's GRU cell)
+ *     x(S, i) = h_L . Q[i] + b[i]                                  (DRX_REC_BIAS of the fused scorer at rows of ldh floats)
+ *     D_wk = x(S, i) - x(S, j_k);  loss = (1 / (B r)) sum_w sum_k softplus(-D_wk);  g_wk = -sigmoid(-D_wk) / (B r)
+ * A position whose id is < 0 is no step: the row keeps its h (serving's short baskets; a step's windows hold L ids >= 0).
+ * Domain: 1 <= k, h <= 64, 1 <= L <= 8, 1 <= neg_ratio <= 16.  Everything is fp32; no float atomics; every sum runs in an order fixed by
+ * the arguments: equal inputs give equal bits.  All launches are plain. */
+typedef struct DrxGruDims {
+  int32_t n_items;
+  int32_t k, h, ldk, ldh;
+  int32_t off_wx, off_wh, off_bx, off_bhn, n_small;
+} DrxGruDims;
+/* ONE TRAINING STEP on B windows in the layout drx_list_sample_device returns at n_targets = 1: before [B, L], after [B, 1 + r] (the
+ * target first), device int32, ids in range (not checked on the device).  Then EVERY row of E and Q and every entry of Wx, Wh gets
+ * reg * itself added to its gradient (bx, bhn, b none) and everything is updated by `rule`, a dense rule (DrxOptRule).  alphas: HOST
+ * float [3], the step sizes of E, sw and Q with b (Adam: the variable's lr_t; the other rules: the learning rate); rule->lr is ignored.
+ * Slots: those the rule has, shaped like their parameter; one it lacks may be NULL and is not touched.
+ * k_gru_tile: workgroups of four waves, drx_gru_grid of them = min(tiles, 256), walk tiles of 16 windows (tile t to workgroup
+ * t % grid, ascending); wave w takes the 16-column tiles w, w + 4, w + 8 of the 3 h gate columns.  A tile gathers x_1 .. x_L into LDS,
+ * runs the L steps forward (x_t Wx and h_{t-1} Wh as v_mfma_f32_16x16x4_f32 products, Wx / Wh read from global memory as the B
+ * operand, every h_t kept in LDS), forms dh_L = sum_k g_wk (Q[i] - Q[j_k]), then runs the L steps backward: a step's gates are
+ * recomputed from x_t and h_{t-1} by the forward's own function, dgates Wx^T gives the gradient row of E for (window, t) ([B L, ldk]),
+ * dgates Wh^T the dh of the step before, and x_t^T dgates, h_{t-1}^T dgates add to the wave's tiles of dWx, dWh, which stay in
+ * registers over all steps and tiles of the workgroup.  It writes h_L [B, ldh] and the 1 + r scales (sum_k g_wk, -g_w1 .. -g_wr) per
+ * window, its gradient of sw into ITS row of [grid, n_small] and its loss into one double.  One launch adds those rows in workgroup
+ * order and updates sw by segments (drx_opt_segments' arithmetic); drx_batch_csr_device groups the B L input keys and the
+ * B (1 + r) item keys; ONE drx_rows_csr_opt_multi call updates E (plain form) and Q with b (outer-product form, group 1 + r, the
+ * written h_L as its rows).
+ * loss_out: device double [1] or NULL.  scratch: drx_gru_step_scratch_bytes (0 = a description outside the domain).
+ * DRX_EINVAL, and nothing launched: a NULL pointer among D, E, sw, Q, b, before, after, rule, alphas, scratch; B < 1 (or >= 2^24); k or h
+ * outside 1..64; L outside 1..8; neg_ratio outside 1..16; n_items < 1; ldk / ldh / offsets / n_small that are not the layout above; no
+ * dense rule; a slot the rule has is NULL; E, Q or a slot of theirs not 16-byte aligned.  DRX_ESCRATCH: scratch too small. */
+int drx_gru_grid(int32_t B);
+size_t drx_gru_step_scratch_bytes(const DrxGruDims *D, int32_t B, int32_t L, int32_t neg_ratio);
+int drx_gru_step(const DrxGruDims *D, float *E, float *sw, float *Q, float *b, float *E_s1, float *E_s2, float *sw_s1, float *sw_s2,
+                 float *Q_s1, float *Q_s2, float *b_s1, float *b_s2, const int32_t *before, const int32_t *after, int32_t B, int32_t L,
+                 int32_t neg_ratio, const DrxOptRule *rule, const float *alphas, float reg, double *loss_out, void *scratch,
+                 size_t scratch_bytes, void *stream);
+/* out[q, :] = h after the cell has run over the basket of uid[q], for n device user ids (in range, not checked on the device): the
+ * query rows of the fused scorer, out [n, ldh], padding zero.  baskets: device int32 [n_users, L], -1 = an absent position (no step);
+ * an empty basket gives a zero row.  Tiles of 16 users through the SAME device function as the step's forward pass; a row's bits
+ * depend neither on its place in a tile nor on the other rows, and a basket of m < L items gives the bits of m steps.
+ * DRX_EINVAL, and nothing launched: a NULL pointer; n < 1; L outside 1..8; dims outside the domain or not the layout above; E or out
+ * not 16-byte aligned. */
+int drx_gru_query_rows(const float *E, const float *sw, const DrxGruDims *D, const int32_t *baskets, int32_t L, const int32_t *uid,
+                       int32_t n, float *out, void *stream);
+
 #ifdef __cplusplus
 }
 #endif
