@@ -5,6 +5,7 @@ from .fpmc import FPMC
 from .gru4rec import GRU4Rec
 from .item_knn import ItemKNN
 from .ncf import NeuMF
+from .sasrec import SASRec
 from .user_knn import UserKNN
 
-__all__ = ['ALS', 'BaseKNN', 'BPR', 'FPMC', 'GRU4Rec', 'ItemKNN', 'NeuMF', 'UserKNN']
+__all__ = ['ALS', 'BaseKNN', 'BPR', 'FPMC', 'GRU4Rec', 'ItemKNN', 'NeuMF', 'SASRec', 'UserKNN']

@@ -1452,6 +1452,68 @@ int drx_gru_step(const DrxGruDims *D, float *E, float *sw, float *Q, float *b, f
 int drx_gru_query_rows(const float *E, const float *sw, const DrxGruDims *D, const int32_t *baskets, int32_t L, const int32_t *uid,
                        int32_t n, float *out, void *stream);
 
+/* ---- SASRec (Kang & McAuley 2018; csrc/drx_sas.hip) -----------------------------------------------------------
+ * Tables E [n_items, ldh] (input embeddings) and Q [n_items, ldh] (output rows), h floats of a row used, b [n_items]; ldh = h rounded
+ * up to a multiple of 4, the padding columns ZERO.  There is no user table.  One flat array sw of small weights, all row-major and
+ * WITHOUT padding, every regularised entry first and every unregularised one behind (DrxSasDims has the offsets, which must be exactly
+ * these):
+ *     Pos [L, h] at off_pos = 0 | block 0: Wq Wk Wv W1 W2 [h, h] each, from off_blk = L h | block 1 the same | ...
+ *     off_vec = off_blk + 5 h h blocks: block 0: b1 b2 ln1_g ln1_b ln2_g ln2_b [h] each | block 1 the same | ...
+ *     off_lnf = off_vec + 6 h blocks: lnf_g lnf_b [h] each;  n_small = off_lnf + 2 h.
+ * A sequence of m <= L items occupies the positions L - m .. L - 1 (the newest item at L - 1); absent positions are never keys and
+ * are not computed as queries.  For position t holding item s, one head:
+ *     X0_t = E[s] + Pos[t];  LN(x) = (x - mean) / sqrt(var + 1e-5) g + beta, the biased variance over the h columns
+ *     per block: A = LN(X; ln1);  q, k, v = A Wq, A Wk, A Wv;  S_tj = q_t . k_j / sqrt(h) for present j <= t;  P = softmax_j(S);
+ *                X' = X + P v;  F = LN(X'; ln2);  X'' = X' + relu(F W1 + b1) W2 + b2
+ *     h(S) = LN(X_{L-1}; lnf) after the last block; an empty sequence: h = 0 exactly
+ *     x(S, i) = h(S) . Q[i] + b[i]                                 (DRX_REC_BIAS of the fused scorer at rows of ldh floats)
+ *     D_wk = x(S, i) - x(S, j_k);  loss = (1 / (B r)) sum_w sum_k softplus(-D_wk);  g_wk = -sigmoid(-D_wk) / (B r)
+ * Domain: 1 <= h <= 64, 1 <= L <= 16, blocks 1 or 2, 1 <= neg_ratio <= 16.  Everything is fp32; no float atomics; every sum runs in an
+ * order fixed by the arguments: equal inputs give equal bits.  All launches are plain. */
+typedef struct DrxSasDims {
+  int32_t n_items;
+  int32_t h, ldh, L, blocks;
+  int32_t off_pos, off_blk, off_vec, off_lnf, n_small;
+} DrxSasDims;
+/* ONE TRAINING STEP on B windows in the layout drx_list_sample_device returns at n_targets = 1: before [B, L] (full windows, ids >= 0),
+ * after [B, 1 + r] (the target first), device int32, ids in range (not checked on the device).  Then EVERY row of E and Q and every
+ * entry of Pos and of the five matrices of every block gets reg * itself added to its gradient (the biases, the LN gains and offsets and
+ * b none) and everything is updated by `rule`, a dense rule (DrxOptRule).  alphas: HOST float [3], the step sizes of E, sw and Q with b
+ * (Adam: the variable's lr_t; the other rules: the learning rate); rule->lr is ignored.  Slots: those the rule has, shaped like their
+ * parameter; one it lacks may be NULL and is not touched.
+ * k_sas_tile: workgroups of four waves, drx_sas_grid of them = min(B, 256), walk the windows (window w to workgroup w % grid,
+ * ascending).  ONE WINDOW IS ONE MFMA TILE whose 16 rows are the positions, so S = q k^T is one 16 x 16 accumulator and the causal and
+ * presence masks are a test on (row, column); wave w takes the 16-column tile w of h.  The projections, q k^T, P v, the two FFN
+ * layers, their transposes in the backward pass and the x^T dY weight gradients are v_mfma_f32_16x16x4_f32 products, the weights read
+ * from global memory as the B operand; LN, the softmax and ReLU run row-wise on the VALU.  Every activation of the window's forward pass
+ * stays in LDS for its backward pass (nothing is recomputed but the LN statistics; nothing goes to scratch).  A wave's tiles of the
+ * five weight gradients of every block stay in registers over all windows of the workgroup; the gradients of Pos and of the vectors
+ * add up in LDS.  The kernel writes the gradient rows of E [B L, ldh], h [B, ldh] and the 1 + r scales (sum_k g_wk, -g_w1 .. -g_wr)
+ * per window, its gradient of sw into ITS row of [grid, n_small] and its loss into one double.  One launch adds those rows in workgroup
+ * order and updates sw by two segments (drx_opt_segments' arithmetic); drx_batch_csr_device groups the B L input keys and the
+ * B (1 + r) item keys; ONE drx_rows_csr_opt_multi call updates E (plain form) and Q with b (outer-product form, group 1 + r, the
+ * written h as its rows).
+ * loss_out: device double [1] or NULL.  scratch: drx_sas_step_scratch_bytes (0 = a description outside the domain).
+ * DRX_EINVAL, and nothing launched or written: a NULL pointer among D, E, sw, Q, b, before, after, rule, alphas, scratch; B < 1 (or
+ * >= 2^24); h outside 1..64; L outside 1..16; blocks outside 1..2; neg_ratio outside 1..16; n_items < 1; ldh / offsets / n_small that
+ * are not the layout above; no dense rule; a slot the rule has is NULL; E, Q or a slot of theirs not 16-byte aligned.  DRX_ESCRATCH:
+ * scratch too small. */
+int drx_sas_grid(int32_t B);
+size_t drx_sas_step_scratch_bytes(const DrxSasDims *D, int32_t B, int32_t neg_ratio);
+int drx_sas_step(const DrxSasDims *D, float *E, float *sw, float *Q, float *b, float *E_s1, float *E_s2, float *sw_s1, float *sw_s2,
+                 float *Q_s1, float *Q_s2, float *b_s1, float *b_s2, const int32_t *before, const int32_t *after, int32_t B,
+                 int32_t neg_ratio, const DrxOptRule *rule, const float *alphas, float reg, double *loss_out, void *scratch,
+                 size_t scratch_bytes, void *stream);
+/* out[q, :] = h of the basket of uid[q], for n device user ids (in range, not checked on the device): the query rows of the fused
+ * scorer, out [n, ldh], padding zero.  baskets: device int32 [n_users, L], LEFT-aligned, -1 = an absent position; the kernel shifts a
+ * basket of m items to the positions L - m .. L - 1.  An empty basket gives a zero row.  One user per tile through the SAME device
+ * function as the step's forward pass: a row's bits depend neither on its place in the request nor on the other rows, and a full
+ * basket gives the bits of the h the step writes for the same window.
+ * DRX_EINVAL, and nothing launched: a NULL pointer; n < 1; dims outside the domain or not the layout above; E or out not 16-byte
+ * aligned. */
+int drx_sas_query_rows(const float *E, const float *sw, const DrxSasDims *D, const int32_t *baskets, const int32_t *uid, int32_t n,
+                       float *out, void *stream);
+
 #ifdef __cplusplus
 }
 #endif
