@@ -4,8 +4,9 @@ from .bpr import BPR
 from .fpmc import FPMC
 from .gru4rec import GRU4Rec
 from .item_knn import ItemKNN
+from .multvae import MultVAE
 from .ncf import NeuMF
 from .sasrec import SASRec
 from .user_knn import UserKNN
 
-__all__ = ['ALS', 'BaseKNN', 'BPR', 'FPMC', 'GRU4Rec', 'ItemKNN', 'NeuMF', 'SASRec', 'UserKNN']
+__all__ = ['ALS', 'BaseKNN', 'BPR', 'FPMC', 'GRU4Rec', 'ItemKNN', 'MultVAE', 'NeuMF', 'SASRec', 'UserKNN']

@@ -111,6 +111,10 @@ class GruDims(C.Structure):                             # include/drx.h DrxGruDi
     _fields_ = [(n, C.c_int32) for n in ('n_items', 'k', 'h', 'ldk', 'ldh', 'off_wx', 'off_wh', 'off_bx', 'off_bhn', 'n_small')]
 
 
+class VaeDims(C.Structure):                             # include/drx.h DrxVaeDims
+    _fields_ = [(n, C.c_int32) for n in ('n_items', 'h', 'ldh', 'latent', 'variational', 'e', 'off_we', 'off_wd', 'off_vec', 'n_small')]
+
+
 class SasDims(C.Structure):                             # include/drx.h DrxSasDims
     _fields_ = [(n, C.c_int32) for n in ('n_items', 'h', 'ldh', 'L', 'blocks', 'off_pos', 'off_blk', 'off_vec', 'off_lnf', 'n_small')]
 
@@ -332,6 +336,14 @@ SIGNATURES = {
     'drx_sas_step': (C.c_int, [C.POINTER(SasDims)] + [C.c_void_p] * 14 + [C.c_int32, C.c_int32, C.POINTER(OptRule), C.POINTER(C.c_float),
                                C.c_float, C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p]),
     'drx_sas_query_rows': (C.c_int, [C.c_void_p, C.c_void_p, C.POINTER(SasDims), C.c_void_p, C.c_void_p, C.c_int32, C.c_void_p,
+                                     C.c_void_p]),
+    'drx_vae_step_scratch_bytes': (C.c_size_t, [C.POINTER(VaeDims), C.c_int32, C.c_int32, C.c_int32]),
+    'drx_vae_step': (C.c_int, [C.POINTER(VaeDims)] + [C.c_void_p] * 12 + [C.POINTER(History), C.c_void_p, C.c_void_p, C.c_int32, C.c_int32,
+                               C.c_int32, C.c_void_p, C.c_void_p, C.c_float, C.c_float, C.POINTER(OptRule), C.POINTER(C.c_float), C.c_float,
+                               C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p]),
+    'drx_vae_noise': (C.c_int, [C.c_uint64, C.c_void_p, C.c_int32, C.c_int32, C.c_int32, C.c_float, C.c_void_p, C.c_void_p, C.c_void_p,
+                                C.c_void_p]),
+    'drx_vae_query_rows': (C.c_int, [C.c_void_p, C.c_void_p, C.POINTER(VaeDims), C.POINTER(History), C.c_void_p, C.c_int32, C.c_void_p,
                                      C.c_void_p]),
     'drx_caser_step_small_opt': (C.c_int, [C.POINTER(CaserDims), C.POINTER(CaserArgs), C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p,
                                            C.POINTER(AdamSegments), C.POINTER(OptRule), C.c_void_p]),

@@ -1514,6 +1514,66 @@ int drx_sas_step(const DrxSasDims *D, float *E, float *sw, float *Q, float *b, f
 int drx_sas_query_rows(const float *E, const float *sw, const DrxSasDims *D, const int32_t *baskets, const int32_t *uid, int32_t n,
                        float *out, void *stream);
 
+/* ---- Mult-VAE / Mult-DAE (Liang, Krishnan, Hoffman, Jebara 2018; csrc/drx_vae.hip) ---------------------------
+ * Tables W_in [n_items, ldh] (the embedding-bag first layer) and W_out [n_items, ldh] (the output rows), h floats of a row used,
+ * b_out [n_items]; ldh = h rounded up to a multiple of 4, the padding columns ZERO.  One flat array sw of small weights, all row-major
+ * and WITHOUT padding, the regularised entries first (DrxVaeDims has the offsets, which must be exactly these; e = 2 latent where
+ * variational, else latent):
+ *     W_e [h, e] at off_we = 0 | W_d [latent, h] at off_wd = h e || off_vec = off_wd + latent h: b_in [h] | b_e [e] | b_d [h];
+ *     n_small = off_vec + 2 h + e.
+ * For batch row b with user u, P_u the user's row of the positives CSR (ascending items), N_u = |P_u|:
+ *     x1 = c_b sum_{kept lookups j} W_in[P_u[j]] + b_in,  c_b = 1 / (sqrt(N_u) (1 - dropout));  h1 = tanh(x1)
+ *     [mu | logvar] = h1 W_e + b_e;  z = mu + eps exp(logvar / 2) (variational and eps given), else z = mu
+ *     h2 = tanh(z W_d + b_d);  logit_i = h2 . W_out[i] + b_out[i] for EVERY item  (DRX_REC_BIAS of the fused scorer at rows of ldh)
+ *     loss_b = -sum_{i in P_u} log softmax(logit)_i + kl_weight KL_b,  KL_b = -1/2 sum (1 + logvar - mu^2 - exp(logvar));
+ *     loss = mean_b loss_b;  dlogit_bi = (N_u softmax_i - [i in P_u]) / B
+ * Domain: 1 <= h <= 128, 1 <= latent <= 64, 1 <= B <= 65536.  Everything is fp32; no float atomics; every sum runs in an order fixed by
+ * the arguments: equal inputs give equal bits.  All launches are plain. */
+typedef struct DrxVaeDims {
+  int32_t n_items;
+  int32_t h, ldh, latent, variational, e;
+  int32_t off_we, off_wd, off_vec, n_small;
+} DrxVaeDims;
+/* ONE TRAINING STEP on the B users uid (device int32, in range: not checked on the device).  Hst: the positives CSR on the device.
+ * boff [B + 1] (device int32): boff[b] = sum of N_u over the rows before b — lookup j of row b is lookup boff[b] + j of the batch;
+ * T = boff[B] >= 1; max_len >= every N_u of the batch (T <= B max_len < 2^31).  eps [B, latent] floats or NULL (z = mu); keep [T]
+ * bytes or NULL (every lookup kept): what drx_vae_noise writes, or explicit arrays.  kl_weight: beta_t of the step.  Then EVERY row of
+ * W_in and W_out and every entry of W_e and W_d gets reg * itself added to its gradient (the biases none) and everything is updated by
+ * `rule`, a dense rule.  alphas: HOST float [3], the step sizes of W_in, sw and W_out with b_out; rule->lr is ignored.
+ * No array of B x n_items floats exists.  k_vae_encode (row tiles of 16): the bag, h1, [mu | logvar], z, h2, the KL partials, the keys
+ * and scales (keep ? c_b : 0) of the W_in update.  k_vae_lse (pass 1): min(item tiles, 128) persistent workgroups walk the item tiles
+ * g, g + grid, ..; the logits of a 16 x 16 tile are one MFMA accumulator; a running (max, sum) per row and workgroup, combined in
+ * workgroup order (k_vae_lse_combine).  k_vae_out (pass 2, same grid): the tile's logits again, dlogit (membership by a binary search
+ * in the user's CSR row), the tile's dW_out / db_out over ALL rows (the four waves' sums added in wave order) and the dense rule on
+ * its rows of W_out, b_out and their slots in place, and the workgroup's slab of dh2 = dlogit W_out.  k_vae_back (row tiles): the
+ * slabs summed in slab order, the backward pass of the small layers, dx1 [B, ldh], the workgroup's row of small-weight partials.  One
+ * k_small_opt launch updates sw; drx_batch_csr_device groups the T lookups by item; ONE drx_rows_csr_opt_multi call updates W_in in
+ * the outer-product form (group max_len, the rows of dx1, the scales).
+ * loss_out: device double [1] or NULL.  scratch: drx_vae_step_scratch_bytes (0 = a description outside the domain).
+ * DRX_EINVAL, and nothing launched or written: a NULL pointer among D, W_in, sw, W_out, b_out, Hst and its arrays, uid, boff, rule,
+ * alphas, scratch; h outside 1..128; latent outside 1..64; B outside 1..65536; T < 1; max_len outside 1..n_items; T > B max_len or
+ * B max_len >= 2^31; dropout outside [0, 1); kl_weight < 0; offsets / ldh / e / n_small that are not the layout above; no dense
+ * rule; a slot the rule has is NULL; W_in, W_out or a slot of theirs not 16-byte aligned.  DRX_ESCRATCH: scratch too small. */
+size_t drx_vae_step_scratch_bytes(const DrxVaeDims *D, int32_t B, int32_t T, int32_t max_len);
+int drx_vae_step(const DrxVaeDims *D, float *W_in, float *sw, float *W_out, float *b_out, float *W_in_s1, float *W_in_s2, float *sw_s1,
+                 float *sw_s2, float *W_out_s1, float *W_out_s2, float *b_out_s1, float *b_out_s2, const DrxHistory *Hst,
+                 const int32_t *uid, const int32_t *boff, int32_t B, int32_t T, int32_t max_len, const float *eps, const uint8_t *keep,
+                 float dropout, float kl_weight, const DrxOptRule *rule, const float *alphas, float reg, double *loss_out, void *scratch,
+                 size_t scratch_bytes, void *stream);
+/* The randomness of a step, a function of `seed` alone: keep[boff[b] + j] = drx_hash_u32(2 seed, b, j) >= q_threshold(dropout);
+ * words[2 (b latent + c)], words[.. + 1] = w1, w2 = drx_hash_u32(2 seed + 1, b, 2 c), (.., 2 c + 1);  eps[b latent + c] =
+ * sqrt(-2 ln u1) cos(2 pi u2) in fp32 with u1 = (w1 + 1) / 2^32, u2 = w2 / 2^32.  eps, keep, words: each may be NULL (not written).
+ * DRX_EINVAL: boff NULL; B outside 1..65536; T < 0; latent outside 1..64; dropout outside [0, 1). */
+int drx_vae_noise(uint64_t seed, const int32_t *boff, int32_t B, int32_t T, int32_t latent, float dropout, float *eps, uint8_t *keep,
+                  uint32_t *words, void *stream);
+/* out[q, :] = h2 of user uid[q] at z = mu, no dropout, every positive kept, for n device user ids (in range, not checked): the query
+ * rows of the fused scorer, out [n, ldh], padding zero; a user without positives gives tanh(b_in) onwards.  Tiles of 16 users through
+ * the SAME device function as the step's forward pass: a row's bits depend neither on its place nor on the other rows.
+ * DRX_EINVAL, and nothing launched: a NULL pointer; n < 1; dims outside the domain or not the layout above; W_in or out not 16-byte
+ * aligned. */
+int drx_vae_query_rows(const float *W_in, const float *sw, const DrxVaeDims *D, const DrxHistory *Hst, const int32_t *uid, int32_t n,
+                       float *out, void *stream);
+
 #ifdef __cplusplus
 }
 #endif
