@@ -115,7 +115,12 @@ class VaeDims(C.Structure):                             # include/drx.h DrxVaeDi
     _fields_ = [(n, C.c_int32) for n in ('n_items', 'h', 'ldh', 'latent', 'variational', 'e', 'off_we', 'off_wd', 'off_vec', 'n_small')]
 
 
-class SasDims(C.Structure):                             # include/drx.h DrxSasDims
+class LgcnGraph(C.Structure):                           # include/drx.h DrxLgcnGraph
+    _fields_ = [(n, C.c_void_p) for n in ('indptr', 'indices', 'w', 'seg_row', 'seg_ptr', 'cut_rows')] + \
+               [(n, C.c_int32) for n in ('N', 'n_seg', 'n_cut')]
+
+
+class SasDims(C.Structure):                            # include/drx.h DrxSasDims
     _fields_ = [(n, C.c_int32) for n in ('n_items', 'h', 'ldh', 'L', 'blocks', 'off_pos', 'off_blk', 'off_vec', 'off_lnf', 'n_small')]
 
 
@@ -345,6 +350,16 @@ SIGNATURES = {
                                 C.c_void_p]),
     'drx_vae_query_rows': (C.c_int, [C.c_void_p, C.c_void_p, C.POINTER(VaeDims), C.POINTER(History), C.c_void_p, C.c_int32, C.c_void_p,
                                      C.c_void_p]),
+    'drx_lgcn_row_split': (C.c_int32, []),
+    'drx_lgcn_part_bytes': (C.c_size_t, [C.POINTER(LgcnGraph), C.c_int32]),
+    'drx_lgcn_propagate': (C.c_int, [C.POINTER(LgcnGraph), C.c_void_p, C.c_void_p, C.c_void_p, C.c_int32, C.c_float, C.c_void_p, C.c_size_t,
+                                     C.c_void_p]),
+    'drx_lgcn_final_scratch_bytes': (C.c_size_t, [C.POINTER(LgcnGraph), C.c_int32]),
+    'drx_lgcn_final': (C.c_int, [C.c_void_p, C.POINTER(LgcnGraph), C.c_int32, C.c_int32, C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p]),
+    'drx_lgcn_step_scratch_bytes': (C.c_size_t, [C.POINTER(LgcnGraph), C.c_int32, C.c_int32, C.c_int32]),
+    'drx_lgcn_step': (C.c_int, [C.c_void_p] * 5 + [C.c_int32, C.c_int32, C.POINTER(LgcnGraph), C.c_void_p, C.c_void_p, C.c_void_p, C.c_int32,
+                                C.c_int32, C.POINTER(OptRule), C.POINTER(C.c_float), C.c_float, C.c_void_p, C.c_void_p, C.c_size_t,
+                                C.c_void_p]),
     'drx_caser_step_small_opt': (C.c_int, [C.POINTER(CaserDims), C.POINTER(CaserArgs), C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p,
                                            C.POINTER(AdamSegments), C.POINTER(OptRule), C.c_void_p]),
     'drx_dmf_step_small_opt': (C.c_int, [C.POINTER(DmfDims), C.POINTER(DmfArgs), C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p,

@@ -1,6 +1,6 @@
-"""What the engines of the dense models (DMF, Caser, BPR, FPMC, NeuMF, GRU4Rec, SASRec, Mult-VAE) share: the update rule of optimizers.py with its slots, the
+"""What the engines of the dense models (DMF, Caser, BPR, FPMC, NeuMF, GRU4Rec, SASRec, Mult-VAE, LightGCN) share: the update rule of optimizers.py with its slots, the
 snapshot of parameters and slots, the layout of several arrays in one buffer and the keep mask of a step as device bytes; for the fused
-steps of the sampled baselines (drx_bpr_step, drx_fpmc_step, drx_ncf_step, drx_gru_step, drx_sas_step, drx_vae_step) also the host frame of a step — scratch, step sizes, slot
+steps of the sampled baselines (drx_bpr_step, drx_fpmc_step, drx_ncf_step, drx_gru_step, drx_sas_step, drx_vae_step, drx_lgcn_step) also the host frame of a step — scratch, step sizes, slot
 pointers, loss — and the sampler's frame on the device.  (KnnEngine has no optimizer and stays a plain RowsRecommender.)"""
 import ctypes as C
 

@@ -1574,6 +1574,70 @@ int drx_vae_noise(uint64_t seed, const int32_t *boff, int32_t B, int32_t T, int3
 int drx_vae_query_rows(const float *W_in, const float *sw, const DrxVaeDims *D, const DrxHistory *Hst, const int32_t *uid, int32_t n,
                        float *out, void *stream);
 
+/* ---- LightGCN (He, Deng, Wang, Li, Zhang, Wang 2020; csrc/drx_lgcn.hip) --------------------------------------
+ * Nodes: the n_users users, then the n_items items, N = n_users + n_items.  E0 = [P ; Q], [N, ld], ld = K rounded up to a multiple of
+ * 4, 4 <= ld <= 256, the padding columns zero — every call below keeps them zero.  A = the symmetric normalised adjacency of the
+ * positives: A[r, c] = w[r] w[c] on every edge, w[v] = deg(v)^(-1/2), 0 for a node without edges.  Final embeddings
+ * Ebar = (1 / (layers + 1)) sum_{l = 0 .. layers} A^l E0; score x(u, i) = Ebar[u] . Ebar[n_users + i] (DRX_REC_BIAS of the fused scorer
+ * with a zero bias).  0 <= layers <= DRX_LGCN_MAX_LAYERS.
+ *
+ * THE GRAPH (built once by the host, arrays on the device): the CSR of the symmetric adjacency — a user row lists n_users + iid
+ * ascending, an item row lists uids ascending —, w, and the cut of long rows: row r is cut into max(1, ceil(len_r / S)) segments of
+ * S = drx_lgcn_row_split() entries (the last one shorter), seg_ptr [N + 1] their prefix sums, seg_row [n_seg] the row of every segment,
+ * cut_rows [n_cut] the rows of more than one segment, ascending (NULL where n_cut == 0).  Indices lie in [0, N) and the segment arrays
+ * fit the CSR (neither is checked on the device). */
+#define DRX_LGCN_MAX_LAYERS 4
+typedef struct DrxLgcnGraph {
+  const int64_t *indptr;     /* [N + 1] */
+  const int32_t *indices;    /* [nnz2] */
+  const float *w;            /* [N] */
+  const int32_t *seg_row;    /* [n_seg] */
+  const int32_t *seg_ptr;    /* [N + 1] */
+  const int32_t *cut_rows;   /* [n_cut] */
+  int32_t N, n_seg, n_cut;
+} DrxLgcnGraph;
+/* S: rows of more than S entries are cut (0 would mean: never) */
+int32_t drx_lgcn_row_split(void);
+/* ONE PROPAGATION   out[r, :] = scale (base[r, :] + w[r] sum_{c in row r, CSR order} w[c] in[c, :])      (base NULL: no base term)
+ * A group of pick_geom(ld) lanes per segment, one float4 per lane, 4 neighbour rows in flight per group; a row of one segment is
+ * finished where it is summed, a cut row leaves one partial row per segment in `part` and a second launch adds them in segment order.
+ * No atomics: the sum of a row runs in an order fixed by the CSR and S alone, so equal inputs give equal bits.  `base` may be `in`;
+ * `out` must be neither.  part: device, drx_lgcn_part_bytes (0 = an invalid description); may be NULL where no row is cut.
+ * DRX_EINVAL, and nothing launched: graph NULL or one of its arrays NULL (cut_rows with n_cut > 0), N < 1, n_seg < N; in or out NULL;
+ * out == in or out == base; ld outside 4..256 or no multiple of 4; base, in, out or part not 16-byte aligned; part NULL with a cut row.
+ * DRX_ESCRATCH: part too small. */
+size_t drx_lgcn_part_bytes(const DrxLgcnGraph *graph, int32_t ld);
+int drx_lgcn_propagate(const DrxLgcnGraph *graph, const float *base, const float *in, float *out, int32_t ld, float scale, void *part,
+                       size_t part_bytes, void *stream);
+/* THE FINAL EMBEDDINGS in Horner form: S <- E0, `layers` times S <- E0 + A S (drx_lgcn_propagate with base = E0), the last one with
+ * scale = 1 / (layers + 1), into out [N, ld]; layers == 0: a copy of E0.  It is the function the step's forward pass calls: out has the
+ * bits the next drx_lgcn_step on the same E0 computes.  scratch: drx_lgcn_final_scratch_bytes (0 = an invalid description).
+ * DRX_EINVAL, and nothing launched: a NULL pointer (E0, out, scratch, graph and its arrays); out == E0; N < 1; ld outside 4..256 or no
+ * multiple of 4; layers outside 0..4; E0 or out not 16-byte aligned.  DRX_ESCRATCH: scratch too small. */
+size_t drx_lgcn_final_scratch_bytes(const DrxLgcnGraph *graph, int32_t ld);
+int drx_lgcn_final(const float *E0, const DrxLgcnGraph *graph, int32_t layers, int32_t ld, float *out, void *scratch, size_t scratch_bytes,
+                   void *stream);
+/* ONE TRAINING STEP on T triples (uid, pos, neg: device int32 [T], user and item ids in range — not checked on the device):
+ *     D_t = x(u, i) - x(u, j);   loss = (1 / T) sum_t softplus(-D_t);   g_t = -sigmoid(-D_t) / T
+ *     G[u] += g_t (Ebar[i'] - Ebar[j']);  G[i'] += g_t Ebar[u];  G[j'] -= g_t Ebar[u]          (i' = n_users + i, j' = n_users + j)
+ *     dE0 = (1 / (layers + 1)) sum_l A^l G   (A is symmetric), by the same Horner recurrence on G
+ * then EVERY row of E0 gets reg * row added to its gradient and is updated by `rule`, a dense rule (DrxOptRule).  alphas: HOST float
+ * [2], the step sizes of P (rows 0 .. n_users) and Q (the rest); rule->lr is ignored.  Slots: those the rule has, shaped like P and Q;
+ * one it lacks may be NULL and is not touched.
+ * One call: the forward recurrence into the scratch; k_lgcn_fwd_bwd (a lane group per triple, the three rows read once, the loss
+ * partials summed in double in workgroup order) leaves three gradient rows per triple; drx_batch_csr_device groups the 3 T node keys;
+ * one kernel over all N rows sums each row's lookups in batch order into the dense G, zeros included; the backward recurrence;
+ * drx_opt_dense on each half.  layers == 0 runs no propagation (matrix factorisation without a bias).  No atomics, equal inputs give
+ * equal bits.  loss_out: device double [1] or NULL.  scratch: drx_lgcn_step_scratch_bytes (0 = an invalid description); for
+ * layers >= 1 the forward's Ebar [N, ld] is left at its first 256-byte boundary.
+ * DRX_EINVAL, and nothing launched or written: a NULL pointer among E0, graph and its arrays, uid, pos, neg, rule, alphas, scratch;
+ * T < 1 (or >= 2^27); N < 1; n_users outside 1..N-1; ld outside 4..256 or no multiple of 4; layers outside 0..4; no dense rule; a slot
+ * the rule has is NULL; E0 or a slot not 16-byte aligned.  DRX_ESCRATCH: scratch too small. */
+size_t drx_lgcn_step_scratch_bytes(const DrxLgcnGraph *graph, int32_t T, int32_t ld, int32_t n_users);
+int drx_lgcn_step(float *E0, float *P_s1, float *P_s2, float *Q_s1, float *Q_s2, int32_t ld, int32_t n_users, const DrxLgcnGraph *graph,
+                  const int32_t *uid, const int32_t *pos, const int32_t *neg, int32_t T, int32_t layers, const DrxOptRule *rule,
+                  const float *alphas, float reg, double *loss_out, void *scratch, size_t scratch_bytes, void *stream);
+
 #ifdef __cplusplus
 }
 #endif
